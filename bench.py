@@ -12,13 +12,20 @@ Workload: bs=64 PER RANK (reference semantics, UADA_ddp.py:158 -> weak scaling),
 BridgeData-shaped frames resident in HBM as u8, random-init weights of the OpenVLA-7B architecture.
 
 OUTPUT. stdout carries exactly ONE line: a COMPACT JSON record (< 4 KB, pure ASCII, strict JSON — non-finite floats become null, no
-free-text notes) with the contract's keys: metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling /
-vs_baseline / dtype / data / config{...} / roofline{...} / roofline_k1{...} / cpu_baseline{...} / hot_path_* / loss_finite / peak_mem_GiB /
-wall_s. Everything else (per-kernel tables, the standalone kernel suite, the K1 / K2 batch sweeps, rank_shapes, per-leg CPU tables, the
-per-rank and per-config step blocks in full, the environment) goes to the FULL record, a JSON file (`--full-out`, default
-gpurun_out/bench_full.json); its path is in the compact line (`full_record`).
+free-text notes). A plain run (no `--full`) sets up, warms up, times the K steps, writes the outputs (`--dump-outputs`) and prints the
+headline keys: metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data /
+config{workload, global_batch, ...} / host_cpu_ms_per_step / peak_mem_GiB / wall_s — nothing else runs. `--full` adds everything below:
+roofline{...} / roofline_k1{...} / cpu_baseline{...} / hot_path_* / loss_finite and the N=1 blocks in `config`; everything else
+(per-kernel tables, the standalone kernel suite, the K1 / K2 batch sweeps, rank_shapes, per-leg CPU tables, the per-rank and per-config
+step blocks in full, the environment) goes to the FULL record, a JSON file (`--full-out`, default bench_out/bench_full.json under the
+repository root); its path is in the compact line (`full_record`).
 
-What is measured:
+`--dump-outputs DIR` (any mode): what the timed path handed its caller in its LAST timed step, written right after the timed region as
+DIR/<name>.npy in float32 (rank 0): `patch` (after the step's update), `patch_grad` (the rank-mean patch gradient the update consumed; the
+data-parallel step only), `adam_m` / `adam_v` (the optimiser moments; AdamW only) and `loss_scalars` (the step's scalar buffer, written on
+the steps that read their loss: 1 of INNER_LOOP in the headline loop). Every input is seeded, so the same arguments give the same inputs.
+
+What is measured (everything after `value` with `--full` only):
   * `value`: W warm-up steps, then exactly K steps between barrier + synchronize, max over ranks; UN-profiled.
   * `roofline` / `roofline_k1`: a short second pass of the same steps with the library's per-dispatch timer armed (vaa_prof_*: every
     hand-written kernel launched through hipExtLaunchKernel with its own start/stop event pair = that dispatch's begin/end timestamps). The
@@ -30,7 +37,7 @@ What is measured:
     `cpu_baseline` (oracle/ref_port.py on the host cores, bounded sample).
   * N>1 (one rank per GPU, RCCL): only the two timed regions — weak (`value`) and strong (the same global batch split over the ranks,
     `config.strong_*`) — with the collective's in-step cost (`config.allreduce_us_per_step`, `config.comm_frac`); the process group is
-    destroyed right after them. `--regions weak|strong|both`.
+    destroyed right after them. `--regions weak|strong|both` (default: weak in a plain run, both with `--full`).
 `--attack uada|tma|upa` (N=1) makes the main timed region one of the other product loops (for rocprofv3 summaries of configs 2 / 4 / 5).
 """
 from __future__ import annotations
@@ -56,8 +63,14 @@ INNER_LOOP = 50    # UADA_wrapper_ddp.py:104 (--innerLoop): one full-vocabulary 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=6)
+    ap.add_argument("--steps", type=int, default=6, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the per-dispatch-profiled pass (roofline*, hot_path_*), the loss-finite check, "
+                         "the staging figure, at N=1 the validation / per-rank / config 2-4-5 blocks, the kernel suite and cpu_baseline, at N>1 the "
+                         "strong region and the collective's figures; writes the FULL record (--full-out)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the timed path computed in its last timed step as DIR/<name>.npy (float32, rank 0)")
     ap.add_argument("--bs", type=int, default=64, help="per-rank batch (UADA_ddp.py:158)")
     ap.add_argument("--patch", type=str, default="3,50,50")
     ap.add_argument("--model", type=str, default="openvla-7b", choices=["openvla-7b", "tiny", "surrogate"])
@@ -72,12 +85,18 @@ def parse():
     ap.add_argument("--no-configs", action="store_true", help="skip the BASELINE config 2 / 4 / 5 step block of the N=1 record")
     ap.add_argument("--no-val", action="store_true", help="skip the validation-pass block of the N=1 record (config.val_ms_per_batch_bs8)")
     ap.add_argument("--cpu-budget", type=float, default=25.0, help="seconds of host CPU work for cpu_baseline")
-    ap.add_argument("--regions", type=str, default="both", choices=["weak", "strong", "both"],
-                    help="N > 1: which timed regions run (weak = bs per rank, the headline; strong = the global batch split over the ranks). "
-                         "`strong` alone is a functional / diagnostic run: `value` is then null")
-    ap.add_argument("--profile-steps", type=int, default=-1, help="steps of the separate per-dispatch-profiled pass (-1: min(steps, 10); 0: none)")
-    ap.add_argument("--full-out", type=str, default=os.path.join("gpurun_out", "bench_full.json"), help="where the FULL record goes (relative to the repo root)")
-    return ap.parse_args()
+    ap.add_argument("--regions", type=str, default=None, choices=["weak", "strong", "both"],
+                    help="N > 1: which timed regions run (weak = bs per rank, the headline; strong = the global batch split over the ranks; "
+                         "default: weak, with --full both). `strong` alone is a functional / diagnostic run: `value` is then null")
+    ap.add_argument("--profile-steps", type=int, default=-1, help="--full: steps of the separate per-dispatch-profiled pass (-1: min(steps, 10); 0: none)")
+    ap.add_argument("--full-out", type=str, default=os.path.join("bench_out", "bench_full.json"),
+                    help="--full: where the FULL record goes (relative to the repository root)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.regions is None:
+        args.regions = "both" if args.full else "weak"
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -503,11 +522,12 @@ def kernel_table(recs, psteps):
     return kern, op_us
 
 
-def self_launch(args):
-    """`python bench.py --gpus N` without a launcher: re-exec under torch.distributed.run, one rank per GPU (the driver's N > 1 form passes
-    the rendezvous itself and never gets here). With fewer visible GPUs than ranks the run falls back to gloo with ranks sharing GPUs —
-    a functional run (tests), flagged in the record, not a scaling measurement."""
+def self_launch(args) -> int:
+    """`python bench.py --gpus N` without a launcher: runs torch.distributed.run as a child process, one rank per GPU, and returns its exit
+    status (the driver's N > 1 form passes the rendezvous itself and never gets here). With fewer visible GPUs than ranks the run falls back
+    to gloo with ranks sharing GPUs — a functional run (tests), flagged in the record, not a scaling measurement."""
     import socket
+    import subprocess
 
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
@@ -520,7 +540,28 @@ def self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execvpe(cmd[0], cmd, env)
+    sys.stderr.flush()
+    return subprocess.call(cmd, env=env)
+
+
+def dump_outputs(runner, out_dir):
+    """What the timed path handed its caller in its last step -> out_dir/<name>.npy (float32): the patch after the update, the rank-mean
+    patch gradient the update consumed (the data-parallel step: the gradient part of the exchanged message), the AdamW moments and the loss
+    scalar buffer. Called right after the timed region, before anything else runs a step."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = runner.patch.numel()
+    arrays = {"patch": runner.patch.detach()}
+    if runner.sync is not None:
+        arrays["patch_grad"] = (runner.sync.buf[:n] * runner.inv_world).view_as(runner.patch)
+    if getattr(runner.opt, "m", None) is not None:
+        arrays["adam_m"], arrays["adam_v"] = runner.opt.m, runner.opt.v
+    arrays["loss_scalars"] = runner.scal
+    written = []
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+        written.append(name)
+    print(f"bench.py: outputs of the last timed step -> {out_dir}: {', '.join(written)}", file=sys.stderr)
+    return written
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -683,7 +724,7 @@ def main():
     t_main = time.perf_counter()
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        self_launch(args)  # does not return
+        sys.exit(self_launch(args))
     # stdout carries ONE line, the JSON record: libraries that print banners to the process's stdout (RCCL / gloo at init, MIOpen, ...)
     # are sent to stderr for the duration of the run; the original stdout is restored for the record
     sys.stdout.flush()
@@ -714,27 +755,32 @@ def main():
     use_rows, tr, R = runner.use_rows, runner.tr, runner.R
     headline = args.attack == "uada_ddp"
 
-    # PCIe leg, outside the timed region: staging the batch's frames (host list of uint8 HWC arrays -> HBM), done once per
-    # OUTER iteration by the attack loops; the reference re-does ToTensor + H2D for every image on every inner step.
-    host_frames = [np.ascontiguousarray(f) for f in runner.batch["pixel_values"]]
-    tr.stage_images(host_frames)
-    torch.cuda.synchronize()
-    t_stage = time.perf_counter()
-    tr._staged_key = None
-    tr.stage_images(host_frames)
-    torch.cuda.synchronize()
-    stage_ms = (time.perf_counter() - t_stage) * 1e3
+    stage_ms = None
+    if args.full:
+        # PCIe leg, outside the timed region: staging the batch's frames (host list of uint8 HWC arrays -> HBM), done once per
+        # OUTER iteration by the attack loops; the reference re-does ToTensor + H2D for every image on every inner step.
+        host_frames = [np.ascontiguousarray(f) for f in runner.batch["pixel_values"]]
+        tr.stage_images(host_frames)
+        torch.cuda.synchronize()
+        t_stage = time.perf_counter()
+        tr._staged_key = None
+        tr.stage_images(host_frames)
+        torch.cuda.synchronize()
+        stage_ms = (time.perf_counter() - t_stage) * 1e3
 
     run_weak = world == 1 or args.regions in ("weak", "both")
     run_strong = world > 1 and args.regions in ("strong", "both")
-    psteps = min(args.steps, 10) if args.profile_steps < 0 else args.profile_steps
+    psteps = (min(args.steps, 10) if args.profile_steps < 0 else args.profile_steps) if args.full else 0
+    dump = args.dump_outputs if rank == 0 else None
 
     # ---- the timed region: weak scaling, bs = args.bs PER RANK (reference semantics, UADA_ddp.py:158). UN-profiled, like the strong region ----
     t_setup = time.perf_counter() - t_main
     dt = host_enqueue = host_cpu = None
     recs, recs_ce, comm_w, finite = [], [], None, True
     if run_weak:
-        dt, host_enqueue, host_cpu, _, crecs = timed_steps(runner, args.steps, args.warmup, world, dev, comm=True)
+        dt, host_enqueue, host_cpu, _, crecs = timed_steps(runner, args.steps, args.warmup, world, dev, comm=args.full)
+        if dump:
+            dump_outputs(runner, dump)
         comm_w = comm_summary(crecs, world, args.steps, dt, dev)
         # ---- the same steps once more, SEPARATELY, with the library's per-dispatch timer armed: the in-step kernel durations, per step KIND
         #      (slice-only steps, then steps that also evaluate the full-vocabulary CE: 1 of INNER_LOOP in the loop) ----
@@ -748,16 +794,17 @@ def main():
                 _, _, _, recs_ce, _ = timed_steps(runner, min(psteps, 4), 1, world, dev, profile=True)
                 runner.force_ce = None
         # the loss scalars of a step that READS them (the loop folds them on the last inner step of an outer iteration only): finite?
-        if hasattr(runner, "force_ce"):
-            runner.force_ce = True
-        runner.step()
-        if hasattr(runner, "force_ce"):
-            runner.force_ce = None
-        torch.cuda.synchronize()
-        finite = bool(torch.isfinite(runner.scal).all()) and bool(torch.isfinite(runner.patch.detach()).all())
+        if args.full:
+            if hasattr(runner, "force_ce"):
+                runner.force_ce = True
+            runner.step()
+            if hasattr(runner, "force_ce"):
+                runner.force_ce = None
+            torch.cuda.synchronize()
+            finite = bool(torch.isfinite(runner.scal).all()) and bool(torch.isfinite(runner.patch.detach()).all())
     t_region = time.perf_counter() - t_main - t_setup
     peak_mem = torch.cuda.max_memory_allocated(dev) / 2**30
-    b2b = allreduce_back_to_back(runner.sync, world) if world > 1 else None
+    b2b = allreduce_back_to_back(runner.sync, world) if (world > 1 and args.full) else None
 
     # ---- strong scaling (BASELINE config 3: "bs=64 over N GPUs"): the same global batch split over the ranks ----
     strong = None
@@ -766,6 +813,8 @@ def main():
         torch.cuda.empty_cache()  # the weak region's cached activation blocks are not needed any more (ranks that share a GPU in test mode are near its capacity)
         r_s = StepRunner(model, dev, bs_s, patch_shape, rank, world, geometry=geometry)
         dt_s, enq_s, cpu_s, _, crecs_s = timed_steps(r_s, args.steps, args.warmup, world, dev, comm=True)
+        if dump and not run_weak:  # `--regions strong`: this is the timed path
+            dump_outputs(r_s, dump)
         comm_s = comm_summary(crecs_s, world, args.steps, dt_s, dev)
         r_s.force_ce = True
         r_s.step()
@@ -793,6 +842,31 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank != 0:
+        return
+
+    workload = {"uada_ddp": f"UADA_wrapper_ddp inner step: bs={B}/rank (global {B * world}), patch {args.patch}, geometry={geometry}, maskidx={maskidx or [0]}",
+                "uada": f"UADA single-GPU inner step (MSE + 1/CE): bs={B}, patch {args.patch}, geometry={geometry}",
+                "tma": f"TMA inner step (CE gradient): bs={B}, patch {args.patch}, geometry={geometry}",
+                "upa": f"UPA inner step: bs={B}, patch {args.patch}, resize_patch={args.resize_patch}, geometry={geometry}"}[args.attack]
+    config = {"workload": f"{workload}; {model_desc}; u8 frames resident in HBM",
+              "global_batch": B * world, "images_per_s": (B * world * args.steps / dt) if run_weak else None, "parallelism": f"dp{world}",
+              "regions": ("weak" if world == 1 else args.regions),
+              "backend": (os.environ.get("VAA_DIST_BACKEND") or "nccl (RCCL)") if world > 1 else None,
+              "visible_gpus": torch.cuda.device_count(), "labelled_rows_per_rank": R, "tunableop_entries_loaded_min_over_ranks": tun_min}
+    metric = "attack-steps/sec (bs=64, 3x50x50 patch, OpenVLA-7B)"
+    head = {"metric": metric, "value": (world * args.steps / dt) if run_weak else None, "unit": "attack-steps/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": (dt / args.steps * 1e3) if run_weak else None,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic"}
+
+    if not args.full:
+        # a plain run: the headline and what was measured on the way to it, nothing else
+        line = dict(head, config=config, host_cpu_ms_per_step=host_cpu * 1e3 if run_weak else None, peak_mem_GiB=peak_mem)
+        if strong:
+            line["strong_scaling"] = {k_: strong[k_] for k_ in ("per_rank_bs", "global_batch", "ms_per_step", "images_per_s", "loss_finite_all_ranks")}
+        if not run_weak:
+            line["diagnostic"] = "regions=strong only: value not measured"
+        line["wall_s"] = time.perf_counter() - t_main
+        _print_line(encode_line(line), stdout_fd)
         return
 
     # ---- N=1 only: the per-rank steps of the strong-scaling configs and the inner steps of BASELINE configs 2 / 4 / 5 ----
@@ -892,19 +966,10 @@ def main():
         cpu_c, cpu_f = cpu_box.get("c"), cpu_box.get("f")
 
     # ---------------------------------------------------------------- the records ----------------------------------------------------------------
-    workload = {"uada_ddp": f"UADA_wrapper_ddp inner step: bs={B}/rank (global {B * world}), patch {args.patch}, geometry={geometry}, maskidx={maskidx or [0]}",
-                "uada": f"UADA single-GPU inner step (MSE + 1/CE): bs={B}, patch {args.patch}, geometry={geometry}",
-                "tma": f"TMA inner step (CE gradient): bs={B}, patch {args.patch}, geometry={geometry}",
-                "upa": f"UPA inner step: bs={B}, patch {args.patch}, resize_patch={args.resize_patch}, geometry={geometry}"}[args.attack]
-    config = {"workload": f"{workload}; {model_desc}; u8 frames resident in HBM",
-              "global_batch": B * world, "images_per_s": (B * world * args.steps / dt) if run_weak else None, "parallelism": f"dp{world}",
-              "regions": ("weak" if world == 1 else args.regions),
-              "backend": (os.environ.get("VAA_DIST_BACKEND") or "nccl (RCCL)") if world > 1 else None,
-              "visible_gpus": torch.cuda.device_count(), "labelled_rows_per_rank": R, "tunableop_entries_loaded_min_over_ranks": tun_min,
-              "lm_head": (("K3s every step + K3h on CE steps" if sname else ("fused K3h" if hname else "GEMM + K3 rows")) if use_rows else "full logits"),
-              "full_ce_every": every, "ce_steps_in_timed_region": ce_timed, "traffic_source": tfile,
-              "h2d_stage_ms_per_outer_iteration": stage_ms,
-              "pcie_inclusive_value_if_restaged_every_step": (world * args.steps / (dt + args.steps * stage_ms * 1e-3)) if run_weak else None}
+    config.update({"lm_head": (("K3s every step + K3h on CE steps" if sname else ("fused K3h" if hname else "GEMM + K3 rows")) if use_rows else "full logits"),
+                   "full_ce_every": every, "ce_steps_in_timed_region": ce_timed, "traffic_source": tfile,
+                   "h2d_stage_ms_per_outer_iteration": stage_ms,
+                   "pcie_inclusive_value_if_restaged_every_step": (world * args.steps / (dt + args.steps * stage_ms * 1e-3)) if run_weak else None})
     if world > 1:  # the collective
         config["allreduce_us_per_step"] = comm_w["mean_us_min_over_ranks"] if comm_w else None
         config["allreduce_us_per_step_max_over_ranks"] = comm_w["mean_us_max_over_ranks"] if comm_w else None
@@ -944,10 +1009,6 @@ def main():
     if copy_bw:
         config["measured_device_copy_GBs"] = copy_bw
 
-    metric = "attack-steps/sec (bs=64, 3x50x50 patch, OpenVLA-7B)"
-    head = {"metric": metric, "value": (world * args.steps / dt) if run_weak else None, "unit": "attack-steps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": (dt / args.steps * 1e3) if run_weak else None,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic"}
     tail = {"hot_path_us_per_step": sum(op_us.values()), "hot_path_launches_per_step": launches_avg,
             "hot_path_us_slice_step": sum(op_us_slice.values()) if every else None, "hot_path_us_ce_step": sum(op_us_ce.values()) if every else None,
             "hot_path_ops_us": op_us, "host_cpu_ms_per_step": host_cpu * 1e3 if run_weak else None,
@@ -993,6 +1054,11 @@ def main():
         mini["config"] = {k: config.get(k) for k in ("workload", "global_batch", "parallelism", "regions", "backend")}
         mini.update({"roofline": roofline, "cpu_baseline": cpu_c, "loss_finite": tail["loss_finite"], "full_record": full_path})
         out = encode_line(mini)
+    _print_line(out, stdout_fd)
+
+
+def _print_line(out, stdout_fd):
+    """the record -> the process's original stdout (saved as `stdout_fd` at start-up)"""
     sys.stdout.flush()
     os.dup2(stdout_fd, 1)
     os.close(stdout_fd)

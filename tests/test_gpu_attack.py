@@ -701,7 +701,7 @@ def test_bench_py_two_ranks_one_gpu(tmp_path):
     for rank in range(2):
         env = dict(os.environ, RANK=str(rank), WORLD_SIZE="2", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), VAA_DIST_BACKEND="gloo")
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--model", "tiny",
-                                       "--bs", "4", "--full-out", full_path], env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+                                       "--bs", "4", "--full", "--full-out", full_path], env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=600) for p in procs]
     assert all(p.returncode == 0 for p in procs), [o[1][-2000:] for o in outs]
     assert not outs[1][0].strip()  # rank 0 prints, exactly once
@@ -733,7 +733,7 @@ def test_bench_py_two_ranks_one_gpu(tmp_path):
 
 
 def test_bench_py_self_launches_its_ranks(tmp_path):
-    """`python3 bench.py --gpus 2` WITHOUT a launcher (the form the driver's N=1 command has) re-executes itself under torch.distributed.run,
+    """`python3 bench.py --gpus 2` WITHOUT a launcher (the form the driver's N=1 command has) runs torch.distributed.run as a child process,
     one rank per GPU; on this 1-GPU box the two ranks share the GPU over gloo (flagged in the record). ONE JSON line, n_gpus = 2."""
     import subprocess
     import sys
@@ -743,7 +743,7 @@ def test_bench_py_self_launches_its_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "VAA_DIST_BACKEND")}
     full_path = str(tmp_path / "full.json")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--model", "tiny", "--bs", "4",
-                          "--full-out", full_path], capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
+                          "--full", "--full-out", full_path], capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     d, full = _bench_records(out.stdout, full_path)
     assert d["n_gpus"] == 2 and d["loss_finite"] and d["config"]["global_batch"] == 8 and full["strong_scaling"]["per_rank_bs"] == 2
@@ -751,7 +751,7 @@ def test_bench_py_self_launches_its_ranks(tmp_path):
         assert d["config"]["backend"] == "gloo"
     # --regions strong: the strong-scaling region alone (what a full-size 8-rank functional run on ONE GPU uses); `value` is then null
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--model", "tiny", "--bs", "8",
-                          "--regions", "strong", "--full-out", full_path], capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
+                          "--regions", "strong", "--full", "--full-out", full_path], capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     d, full = _bench_records(out.stdout, full_path)
     ss = full["strong_scaling"]
@@ -811,7 +811,7 @@ def test_bench_contract_line_tiny(model, extra_env, tmp_path):
     env = dict(os.environ, **extra_env)
     full_path = str(tmp_path / "full.json")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--model", model, "--bs", "8", "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-kernel-suite", "--no-per-rank", "--no-configs", "--full-out", full_path],
+                          "--no-cpu-baseline", "--no-kernel-suite", "--no-per-rank", "--no-configs", "--full", "--full-out", full_path],
                          capture_output=True, text=True, cwd=root, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d, full = _bench_records(out.stdout, full_path)
@@ -852,7 +852,7 @@ def test_bench_contract_line_tiny(model, extra_env, tmp_path):
 
 
 def test_bench_line_with_every_block_is_compact(tmp_path):
-    """The default N=1 form — per-rank block, BASELINE config 2 / 4 / 5 steps (the product loops' own inner_step), kernel suite + sweeps, CPU
+    """The `--full` N=1 form — per-rank block, BASELINE config 2 / 4 / 5 steps (the product loops' own inner_step), kernel suite + sweeps, CPU
     leg — still prints ONE compact line the driver can parse; the blocks' figures are in `config` (cfg{2,4,5}_ms_per_step, k2_sweep_frac, ...)
     and in full in the FULL record. Tiny model; the standalone suite runs at its real shapes."""
     import subprocess
@@ -861,7 +861,7 @@ def test_bench_line_with_every_block_is_compact(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     full_path = str(tmp_path / "full.json")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--model", "tiny", "--bs", "8", "--steps", "2", "--warmup", "1", "--cpu-budget", "6",
-                          "--full-out", full_path], capture_output=True, text=True, cwd=root, timeout=1200)
+                          "--full", "--full-out", full_path], capture_output=True, text=True, cwd=root, timeout=1200)
     assert out.returncode == 0, out.stderr[-3000:]
     d, full = _bench_records(out.stdout, full_path)
     c = d["config"]
@@ -892,7 +892,7 @@ def test_bench_attack_loops_tiny(attack, extra, tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     full_path = str(tmp_path / "full.json")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--model", "tiny", "--attack", attack, "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-kernel-suite", "--full-out", full_path] + extra, capture_output=True, text=True, cwd=root, timeout=600)
+                          "--no-cpu-baseline", "--no-kernel-suite", "--full", "--full-out", full_path] + extra, capture_output=True, text=True, cwd=root, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     d, full = _bench_records(out.stdout, full_path)
     assert d["loss_finite"] and d["value"] > 0 and attack.upper() in d["config"]["workload"] and full["per_rank_step"] is None
@@ -900,6 +900,43 @@ def test_bench_attack_loops_tiny(attack, extra, tmp_path):
     assert "K1" in hot and ("K3" in hot or "K3h" in hot or "K3s" in hot) and (("K0" in hot) == (attack == "upa"))
     if attack == "upa":  # the reverse-direction loop never reads CE nor a full argmax (UPA.py:145-186): the slice-only head alone
         assert "K3s" in hot and "K3h" not in hot and "K3" not in hot
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no `--full`): ONE line with the headline keys and nothing that takes a run of its own (no profiled pass, no blocks beside
+    the headline, no CPU leg, no full record); `--dump-outputs DIR` writes what the last timed step handed its caller as float32 .npy files,
+    and two runs with the same arguments write the same arrays."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for i in range(2):
+        d_out = tmp_path / f"out{i}"
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--model", "tiny", "--bs", "4", "--steps", "3", "--warmup", "1",
+                              "--dump-outputs", str(d_out)], capture_output=True, text=True, cwd=str(tmp_path), timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, out.stdout
+        assert len(lines[0]) < 4096 and lines[0].isascii() and "NaN" not in lines[0] and "Infinity" not in lines[0]
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "dtype", "data", "config", "wall_s"):
+            assert key in d, key
+        assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True and d["dtype"] == "bf16"
+        assert d["unit"] == "attack-steps/s" and d["value"] > 0 and d["value"] * d["ms_per_step"] * 1e-3 == pytest.approx(1.0, rel=1e-4)
+        for key in ("roofline", "roofline_k1", "cpu_baseline", "hot_path_us_per_step", "hot_path_ops_us", "loss_finite", "profiled_pass_steps", "full_record"):
+            assert key not in d, key
+        assert not any(k.startswith(("cfg", "bs4_", "val_", "k2_sweep", "k1_", "lm_head", "h2d_")) for k in d["config"]), d["config"]
+        arrays = {f[:-4]: np.load(str(d_out / f)) for f in sorted(os.listdir(d_out))}
+        assert set(arrays) == {"patch", "patch_grad", "adam_m", "adam_v", "loss_scalars"}, sorted(arrays)
+        assert all(a.dtype == np.float32 for a in arrays.values()) and sum(a.nbytes for a in arrays.values()) <= 64 * 2**20
+        assert arrays["patch"].shape == (3, 50, 50) and arrays["patch_grad"].shape == (3, 50, 50) and arrays["loss_scalars"].shape == (8,)
+        assert np.isfinite(arrays["patch"]).all() and arrays["patch"].min() >= 0 and arrays["patch"].max() <= 1
+        assert np.isfinite(arrays["patch_grad"]).all() and np.abs(arrays["patch_grad"]).max() > 0 and (arrays["adam_v"] >= 0).all()
+        runs.append(arrays)
+    for k in runs[0]:
+        assert np.array_equal(runs[0][k], runs[1][k]), (k, float(np.abs(runs[0][k] - runs[1][k]).max()))
 
 
 def test_ddp_wrapper_cli_under_torchrun_two_ranks(tmp_path):

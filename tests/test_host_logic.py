@@ -358,3 +358,29 @@ def test_bench_compact_line_is_strict_json():
         bench.encode_line({"note": "256 MB Infinity Cache"})
     with pytest.raises(RuntimeError):
         bench.encode_line({"note": "café NaN"})
+
+
+def test_bench_arguments_plain_and_full(monkeypatch):
+    """bench.py's options: a plain run times the weak region only, `--full` adds the strong one (N > 1), `--steps` below 1 is refused."""
+    import importlib.util
+    import os
+    import sys
+
+    import pytest
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 3 and not a.full and a.regions == "weak" and a.dump_outputs is None
+    assert not os.path.isabs(a.full_out) and not a.full_out.startswith("..")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "o"])
+    a = bench.parse()
+    assert a.full and a.regions == "both" and a.dump_outputs == "o"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--regions", "strong"])
+    assert bench.parse().regions == "strong"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()

@@ -270,25 +270,3 @@ def test_c_oracle_eval_paste_byte_exact():
     ch = (out != imgs).any(-1)
     assert np.array_equal(np.argwhere(ch).astype(np.int16), d["changed_idx"]) and np.array_equal(out[ch], d["changed_val"])
 
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/VLAAttacker"), reason="the reference tree only exists in the build container")
-def test_committed_fixtures_are_what_the_reference_produces_here(tmp_path):
-    """Oracle pinning, re-checked wherever /root/reference is present: tools/gen_golden.py drives the reference's own functions again (the quick
-    parts: RNG parameter stream, mask_labels / tokenizer pairs, scheduler table, K3 losses, the eval-time paste, the K1/K2 cases) and every array it
-    writes equals the committed fixture bit for bit. (The trajectory parts replay whole loops: `python tools/gen_golden.py traj traj2 trajk2e traj3 traj4 trajk3s trajddp`.)"""
-    import subprocess
-    import sys
-
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = str(tmp_path / "golden")
-    os.makedirs(out)
-    p = subprocess.run([sys.executable, os.path.join(root, "tools", "gen_golden.py"), "rng", "labels", "sched", "k3", "sim", "k1k2"], cwd=root,
-                       env=dict(os.environ, VAA_GOLDEN_OUT=out), capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-1500:]
-    made = sorted(f for f in os.listdir(out) if f.endswith(".npz"))
-    assert len(made) >= 15, made
-    for f in made:
-        a, b = np.load(os.path.join(out, f)), np.load(os.path.join(root, "tests", "golden", f))
-        assert sorted(a.files) == sorted(b.files), f
-        for k in a.files:
-            assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), (f, k)

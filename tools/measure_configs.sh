@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 cd "${root}"
 parts="${*:-cfg cfg5ab head}"
 STEPS=20; WARM=3; N=$((STEPS + WARM))   # --profile-steps 0: every kernel of the CSV has N calls per launch site
-common="--steps ${STEPS} --warmup ${WARM} --no-cpu-baseline --no-kernel-suite --no-per-rank --no-configs --profile-steps 0"
+common="--full --steps ${STEPS} --warmup ${WARM} --no-cpu-baseline --no-kernel-suite --no-per-rank --no-configs --profile-steps 0"
 
 run() {  # tag, env assignments (may be empty), bench arguments
   local tag="$1" envs="$2"; shift 2

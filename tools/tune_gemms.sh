@@ -12,6 +12,8 @@ export PYTORCH_TUNABLEOP_FILENAME="gpurun_out/tune/all_.csv"
 export PYTORCH_TUNABLEOP_MAX_TUNING_DURATION_MS="${TUNE_MS:-12}" PYTORCH_TUNABLEOP_MAX_WARMUP_DURATION_MS=2
 for bs in "$@"; do
   t0=$(date +%s)
-  python bench.py --bs "${bs}" --steps 1 --warmup 1 --no-cpu-baseline --no-kernel-suite > "gpurun_out/tune/bench_bs${bs}.json" 2> "gpurun_out/tune/bench_bs${bs}.err"
+  # --full: the per-rank, validation and config 2 / 4 / 5 blocks run (and get their GEMM shapes tuned) beside the main step
+  log="$(dirname "${PYTORCH_TUNABLEOP_FILENAME}")"
+  python bench.py --full --bs "${bs}" --steps 1 --warmup 1 --no-cpu-baseline --no-kernel-suite > "${log}/bench_bs${bs}.json" 2> "${log}/bench_bs${bs}.err"
   echo "bs=${bs}: rc=$? $(( $(date +%s) - t0 )) s, $(wc -l < gpurun_out/tune/all_0.csv) lines"
 done

@@ -16,6 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from roboticattack_amd import cli  # noqa: E402
 from roboticattack_amd import dist as vdist  # noqa: E402
+from roboticattack_amd.attack.uada_ddp import parse_maskidx_sweep  # noqa: E402
 from white_patch.UADA_ddp import OpenVLAAttacker  # noqa: E402
 
 
@@ -55,6 +56,8 @@ def main(args):
     }
     if args.attack != "UADA":  # extension: the same data-parallel loop for UPA / TMA (BASELINE configs 4-5)
         instance_params.update(attack_type=args.attack, alpha=args.alpha, belta=args.belta, target_action=args.targetAction)
+    if args.maskidx_sweep:  # extension: one patch per maskidx group in one loop (patches under {path}/<group tag>/)
+        instance_params.update(maskidx_sweep=args.maskidx_sweep)
     OpenVLAAttacker._attack_entry(rank, instance_params, world)
     print("Attack done!")
 
@@ -69,6 +72,8 @@ def arg_parser(argv=None):
     parser.add_argument("--alpha", type=float, default=0.8)
     parser.add_argument("--belta", type=float, default=0.2)
     parser.add_argument("--targetAction", default=0, type=float)
+    # extension: a maskidx sweep, groups separated by ';' ("0;0,1,2"): one patch per group, optimised together; empty = one patch for --maskidx
+    parser.add_argument("--maskidx_sweep", default="", type=parse_maskidx_sweep)
     return parser.parse_args(argv)
 
 

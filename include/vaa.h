@@ -257,6 +257,42 @@ int vaa_step_epilogue_update(const float* partials, int nparts, int n, const voi
                              float beta2, float eps, int step, double* stat_part, void* stream);
 
 /*
+ * maskidx SWEEP — P patch groups optimised in ONE step (BASELINE config 5's maskidx families, the released UADA-dof1 / UADA-dof1~3 pairs): the
+ * batch is P groups of Bp consecutive images, group p with its own labels (its own maskidx) and its own patch; every group sees the same frames
+ * and transform draws. Group p's outputs are those of a standalone step on its Bp images alone.
+ *   vaa_loss_rowmap_build_seg: rowmap dev (>= vaa_loss_rowmap_seg_bytes(B,L,P)) = the ordinary map of all B = P*Bp label rows (header
+ *             {R, #action rows, P, Bp}; the rows exactly vaa_loss_rowmap_build's), a table {first row, rows, action rows, 0} per group and every
+ *             group's own ordinary map (vaa_loss_rowmap_build on its Bp rows). vaa_head_slice_fwd_bwd (K3s) and vaa_head_loss_rows_stats (K3h) accept
+ *             it in VAA_LOSS_UADA_DDP mode: each row's gradient is normalised by ITS GROUP's action-row count, so dhidden / grad_slice / the row
+ *             statistics of group p's rows are bit for bit those of the call on group p's rows alone with the group's ordinary map (an ordinary map
+ *             gives the old bits). Folds inside those calls (scalars != NULL, vaa_head_loss_rows_finish) treat the map as ONE batch: per-group
+ *             scalars come from vaa_step_epilogue_seg. UPA's batch means are not per group: the segmented map serves VAA_LOSS_UADA_DDP only.
+ *   vaa_step_epilogue_seg: ONE launch, vaa_step_epilogue per group: partials [P*nparts][n] (group p's nparts tiles at p*nparts: K2' with one
+ *             partial per image, nparts = Bp) ->
+ *               msg[p*n .. (p+1)*n)  = group p's fixed-order sum: bitwise vaa_step_epilogue over those nparts tiles
+ *               rowmap (segmented, or an ordinary map with P = 1) != NULL: group p folded with its own map into scalars[8p .. 8p+8) and rows
+ *                                    p*Bp .. of pred_tokens / pred_full_tokens [B, L-1] (VAA_LOSS_UADA_DDP; loss_ws as the K3s / K3h call left it)
+ *               msg[P*n + 4p ..)     = group p's {CE, w^2*MSE, UAD, total}; rowmap == NULL (pass-through): ZEROS — a SUM all-reduce of the tail
+ *                                    can never grow stale values by world^steps
+ *   vaa_step_epilogue_seg_update: the same + K4 (HF-AdamW | PGD + clamp, shared lr / step) on every element of patch / m / v [P*n] as it is
+ *             produced (vaa_step_epilogue_update's arithmetic); stat_part dev f64 [P][ceil(n/64)][2] or NULL: group p's per-block {sum |g|, sum g},
+ *             bitwise the stat_part a standalone vaa_step_epilogue_update writes (their sums give the group's logged K4 stats).
+ *   vaa_patch_update_seg: vaa_patch_update on each of P groups of n elements (patch, g, m, v [P*n]) in one launch — every group its own L1 clip
+ *             and statistics, stats dev [P,2] f32 or NULL: bit for bit P separate vaa_patch_update calls (the data-parallel sweep after its all-reduce).
+ */
+size_t vaa_loss_rowmap_seg_bytes(int B, int L, int P);
+int vaa_loss_rowmap_build_seg(const int64_t* labels, int B, int L, int P, void* rowmap, size_t rowmap_bytes, void* stream);
+int vaa_step_epilogue_seg(const float* partials, int nparts, int n, int P, const void* rowmap, int R, int B, int L, int V, int mode,
+                          const float* params, const void* loss_ws, size_t loss_ws_bytes, float* scalars, int32_t* pred_tokens,
+                          int32_t* pred_full_tokens, float* msg, void* stream);
+int vaa_step_epilogue_seg_update(const float* partials, int nparts, int n, int P, const void* rowmap, int R, int B, int L, int V, int mode,
+                                 const float* params, const void* loss_ws, size_t loss_ws_bytes, float* scalars, int32_t* pred_tokens,
+                                 int32_t* pred_full_tokens, float* msg, float* patch, float* m, float* v, int opt_mode, float lr, float beta1,
+                                 float beta2, float eps, int step, double* stat_part, void* stream);
+int vaa_patch_update_seg(float* patch, const float* g, float* m, float* v, int n, int P, int mode, float lr, float beta1, float beta2,
+                         float eps, int step, float l1_clip, float grad_scale, float* stats, void* stream);
+
+/*
  * LM head FUSED with K3's statistics (SURVEY.md section 8f-2 as the survey wrote it; for callers that own the LM-head weight) — replaces
  * `logits = lm_head(hidden)` on the labelled rows (modeling_prismatic.py:404-415 -> HF Llama's bf16 lm_head) followed by vaa_loss_rows_stats:
  * the [R,V] logits are never written. The head weight is streamed from HBM once (full 128-byte lines, global -> LDS by LDS-DMA, into MFMA fragments), every

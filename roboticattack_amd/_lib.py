@@ -64,6 +64,11 @@ EXPORTS = (
     "vaa_head_slice_fwd_bwd",
     "vaa_step_epilogue",
     "vaa_step_epilogue_update",
+    "vaa_loss_rowmap_seg_bytes",
+    "vaa_loss_rowmap_build_seg",
+    "vaa_step_epilogue_seg",
+    "vaa_step_epilogue_seg_update",
+    "vaa_patch_update_seg",
     "vaa_async_error",
     "vaa_prof_start",
     "vaa_prof_stop",
@@ -213,6 +218,17 @@ def lib() -> C.CDLL:
     L.vaa_step_epilogue_update.restype = i32
     L.vaa_step_epilogue_update.argtypes = [vp, i32, i32, vp, i32, i32, i32, i32, i32, C.POINTER(f32), vp, sz, vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32,
                                            i32, vp, vp]
+    L.vaa_loss_rowmap_seg_bytes.restype = sz
+    L.vaa_loss_rowmap_seg_bytes.argtypes = [i32, i32, i32]
+    L.vaa_loss_rowmap_build_seg.restype = i32
+    L.vaa_loss_rowmap_build_seg.argtypes = [vp, i32, i32, i32, vp, sz, vp]
+    L.vaa_step_epilogue_seg.restype = i32
+    L.vaa_step_epilogue_seg.argtypes = [vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, C.POINTER(f32), vp, sz, vp, vp, vp, vp, vp]
+    L.vaa_step_epilogue_seg_update.restype = i32
+    L.vaa_step_epilogue_seg_update.argtypes = [vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, C.POINTER(f32), vp, sz, vp, vp, vp, vp, vp, vp, vp, i32, f32,
+                                               f32, f32, f32, i32, vp, vp]
+    L.vaa_patch_update_seg.restype = i32
+    L.vaa_patch_update_seg.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, i32, f32, f32, vp, vp]
     L.vaa_async_error.restype = i32
     L.vaa_async_error.argtypes = []
     L.vaa_prof_start.restype = i32

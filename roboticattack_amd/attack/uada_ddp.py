@@ -21,7 +21,7 @@ from .. import _lib
 from .. import dist as vdist
 from .. import ops
 from ..labels import mask_labels as _mask_labels
-from ..optim import CosineWarmupSchedule, PatchOptimizer
+from ..optim import CosineWarmupSchedule, PatchOptimizer, SweepPatchOptimizer
 from .engine import AttackBase, ValReadback, to_dev, wandb, wandb_enabled
 
 
@@ -50,15 +50,44 @@ def default_dataset_factory(dataset_name: str, bs: int, rank: int, world: int):
     return (SyntheticLoader(bs, seed=1234 + 1000003 * rank, kind="noise"), SyntheticLoader(bs, seed=99991 + 1000003 * rank, kind="noise"))
 
 
+SWEEP_MAX_ROWS = 128    # labelled rows per rank K3s covers (vaa_head_slice_applies)
+SWEEP_MAX_IMAGES = 512  # images per rank K2' keeps one partial tile each (vaa_patch_grad_partials)
+
+
+def parse_maskidx_sweep(text):
+    """CLI form of a sweep: "0;0,1,2" -> [[0], [0, 1, 2]]; "" / None -> None (no sweep)."""
+    if text is None or not str(text).strip():
+        return None
+    return [[int(v) for v in part.split(",") if v.strip() != ""] for part in str(text).split(";")]
+
+
+def sweep_tag(maskidx) -> str:
+    """Directory / log tag of a sweep group: [0] -> "maskidx0", [0, 1, 2] -> "maskidx0-1-2"."""
+    return "maskidx" + "-".join(str(int(v)) for v in maskidx)
+
+
+def mask_labels_sweep(labels, sweep):
+    """[Bp, L] labels -> [P*Bp, L]: group p's copy masked with maskidx_p (mask_labels, UADA_ddp.py:89-97)."""
+    return torch.cat([_mask_labels(labels.clone(), m) for m in sweep], dim=0)
+
+
+def sweep_rows(bs: int, sweep) -> int:
+    """Labelled rows per rank of a sweep step: every sample keeps |maskidx_p| action tokens + EOS."""
+    return sum(bs * (len(m) + 1) for m in sweep)
+
+
 class OpenVLAAttacker(AttackBase):
     val_batches = 100  # UADA_ddp.py:240
     val_every = 200  # UADA_ddp.py:233
 
     def __init__(self, vla_path, dataset_name, save_dir="", resize_patch=False, patch_size=[3, 50, 50], lr=0.01, bs=1, warmup=20,
                  num_iter=10000, maskidx=[], innerLoop=1, geometry=True, use_wandb=True, MSE_weights=1,
-                 model_factory=None, dataset_factory=None, device=None, attack_type="UADA", alpha=0.8, belta=0.2, target_action=0.0):
+                 model_factory=None, dataset_factory=None, device=None, attack_type="UADA", alpha=0.8, belta=0.2, target_action=0.0, maskidx_sweep=None):
         """`attack_type`, `alpha`, `belta`, `target_action` are EXTENSIONS (the reference ships DDP for UADA only):
-        "UPA" = UPA.py's reverse-direction loss + L1 grad clip, "TMA" = TMA.py's target-token CE, same data-parallel loop."""
+        "UPA" = UPA.py's reverse-direction loss + L1 grad clip, "TMA" = TMA.py's target-token CE, same data-parallel loop.
+        `maskidx_sweep` (EXTENSION): a list of maskidx lists optimises one patch per list in ONE loop — every group sees the same frames, draws and
+        schedule, and group p ends where a standalone run with maskidx = maskidx_sweep[p] and the same seed ends (DESIGN.md §maskidx sweep).
+        None keeps the loop above exactly as it is; `maskidx` is then unused."""
         rank, world, local = vdist.env_rank_world()
         if device is None:
             device = vdist.local_device()
@@ -77,6 +106,33 @@ class OpenVLAAttacker(AttackBase):
         if attack_type not in ("UADA", "UPA", "TMA"):
             raise ValueError(f"attack_type must be UADA, UPA or TMA, got {attack_type!r}")
         self.attack_type, self.alpha, self.belta, self.target_action = attack_type, alpha, belta, target_action
+        self.maskidx_sweep = None
+        if maskidx_sweep is not None:
+            self.maskidx_sweep = self._check_sweep(maskidx_sweep)
+
+    def _check_sweep(self, sweep):
+        """Refuses (ValueError naming the limit) what the batched sweep does not cover."""
+        sweep = [[int(v) for v in m] for m in sweep]
+        if not sweep or any(len(m) == 0 for m in sweep):
+            raise ValueError("maskidx_sweep: needs at least one group, and every group at least one maskidx")
+        if any(v < 0 or v > 6 or len(set(m)) != len(m) for m in sweep for v in m):
+            raise ValueError(f"maskidx_sweep: every maskidx is a distinct DoF index 0..6, got {sweep}")
+        if len({sweep_tag(m) for m in sweep}) != len(sweep):
+            raise ValueError(f"maskidx_sweep: groups must be distinct, got {sweep}")
+        if self.attack_type != "UADA":
+            raise ValueError(f"maskidx_sweep: UADA only (got attack_type={self.attack_type!r}; UPA / TMA sweeps are not implemented)")
+        if self.randomPatchTransform.resize_patch:
+            raise ValueError("maskidx_sweep: resize_patch=True is not supported (one patch size per group only)")
+        if not self.fused_ddp_available():
+            raise ValueError("maskidx_sweep: needs the fused path (a model that exposes its patch-embed weights and hidden rows, VAA_FUSED_EPILOGUE != 0)")
+        if len(sweep) * self.bs > SWEEP_MAX_IMAGES:
+            raise ValueError(f"maskidx_sweep: {len(sweep)} groups x bs {self.bs} = {len(sweep) * self.bs} images per rank exceed the limit of "
+                             f"{SWEEP_MAX_IMAGES} (K2' one partial tile per image)")
+        rows = sweep_rows(self.bs, sweep)
+        if rows > SWEEP_MAX_ROWS:
+            raise ValueError(f"maskidx_sweep: {rows} labelled rows per rank (sum of bs x (|maskidx| + 1)) exceed the limit of {SWEEP_MAX_ROWS} "
+                             f"(K3s covers at most {SWEEP_MAX_ROWS} rows)")
+        return sweep
 
     def setup(self, rank, world_size):
         vdist.init_process_group(device=self.device if self.device.type == "cuda" else None)
@@ -100,6 +156,8 @@ class OpenVLAAttacker(AttackBase):
             self.cleanup()
 
     def _attack(self, rank, world_size):
+        if self.maskidx_sweep is not None:
+            return self._attack_sweep(rank, world_size)
         dev = self.device
         if rank == 0:
             patch = torch.rand(self.patch_size).to(dev)  # UADA_ddp.py:140-141
@@ -182,6 +240,167 @@ class OpenVLAAttacker(AttackBase):
             if i % self.val_every == 0:
                 self.validate(i, patch, rank)
         return patch
+
+    # ---- maskidx sweep: P patches in one loop ----
+    def _attack_sweep(self, rank, world_size):
+        """The loop above for P patch groups at once (UADA, fused path): one [P*bs] step per inner step — K1 tile-major with one patch per group,
+        ONE forward / backward, K3s with the segmented row map, K2' with a partial per image, the segmented epilogue (+ AdamW of every group);
+        at world > 1 ONE all-reduce of [P gradients | P x 4 scalars] and the segmented K4. The RNG streams are consumed as by ONE standalone run:
+        one patch init (every group starts from it), one transform draw per frame and step, shared by the groups."""
+        dev = self.device
+        sweep = self.maskidx_sweep
+        P = len(sweep)
+        self.sweep_tags = [sweep_tag(m) for m in sweep]
+        if rank == 0:
+            p0 = torch.rand(self.patch_size).to(dev)  # UADA_ddp.py:140-141, drawn once: every group's standalone run draws this patch
+        else:
+            p0 = torch.empty(self.patch_size).to(dev)
+        vdist.broadcast_patch(p0, src=0)
+        patches = p0.unsqueeze(0).repeat(P, *([1] * p0.dim())).contiguous().requires_grad_(True)
+        self.patch = patches
+        n = p0.numel()
+        optimizer = SweepPatchOptimizer(patches, self.lr, "adamW")
+        scheduler = CosineWarmupSchedule(optimizer, self.warmup, int(self.num_iter), 0.5)
+        sync = vdist.PatchGradSync(P * n, 4 * P, dev)
+        inv_world = 1.0 / world_size
+        scalars = torch.zeros((P, 8), dtype=torch.float32, device=dev)
+        W = self.vla.lm_head.weight
+        V = int(W.shape[0])
+        w = float(self.MSE_weights)
+        self.MSE_Distance_best = {t: 1000000 for t in self.sweep_tags}
+        self.val_CE_loss = {t: [] for t in self.sweep_tags}
+        self.val_MSE_Distance = {t: [] for t in self.sweep_tags}
+        self.val_UAD = {t: [] for t in self.sweep_tags}
+
+        for i, data in enumerate(self.train_loader):
+            if i == self.num_iter:
+                break
+            pixel_values, labels, attention_mask, input_ids = to_dev(data, dev)
+            # the batch replicated to P groups ONCE per outer iteration (frames, ids, mask), the labels masked per group, ONE segmented row map
+            img = self.randomPatchTransform.stage_images(pixel_values)
+            img_all = img.repeat(P, 1, 1, 1).contiguous()
+            ids_all = input_ids.repeat(P, 1).contiguous()
+            am_all = attention_mask.repeat(P, 1).contiguous() if attention_mask is not None else None
+            labels_all = mask_labels_sweep(labels, sweep)
+            row_index = self.vla.label_row_index(labels_all)
+            R = int(row_index.numel())
+            if R == 0:
+                raise ValueError("maskidx sweep: no labelled position in the batch")
+            if not self._slice_head(R, None, W):
+                raise ValueError(f"maskidx sweep: K3s does not take {R} labelled rows per rank here (limit {SWEEP_MAX_ROWS} rows, bf16 head)")
+            segmap = ops.LossRowMapSeg(labels_all, P)
+            pack = self.vla.make_pack(am_all) if (hasattr(self.vla, "make_pack") and am_all is not None) else None
+            s_sum = sync.buf[sync.n_grad :]
+            device_failure = None
+            for inner_loop in range(self.innerLoop):
+                exchanged = False
+                if device_failure is None:
+                    try:
+                        full_ce = inner_loop == self.innerLoop - 1
+                        upd = optimizer.fused_update_args() if world_size == 1 else None
+                        self.sweep_step(img_all, patches, ids_all, labels_all, row_index, segmap, pack, w, V, sync.buf, scalars, full_ce, upd)
+                        if world_size == 1:
+                            s_sum = sync.buf[sync.n_grad :]
+                            continue
+                        exchanged = True
+                        g_sum, s_sum = sync.allreduce_packed()
+                        optimizer.step(grad=g_sum.view_as(patches), grad_scale=inv_world)
+                    except _lib.VaaError as e:  # as in the loop above: keep the collectives' cadence, decide together below
+                        device_failure = str(e)
+                        try:
+                            ops.async_error_check()
+                        except _lib.VaaError:
+                            pass
+                if device_failure is not None and world_size > 1 and not exchanged:
+                    sync.buf.fill_(float("nan"))
+                    _, s_sum = sync.allreduce_packed()
+            scheduler.step()
+            s = (s_sum * inv_world).cpu().numpy().reshape(P, 4)
+            self.assert_finite_state(patches, optimizer, s, f"UADA maskidx sweep (data parallel) outer iteration {i}", all_ranks=True,
+                                     device_failure=device_failure)
+            stats = optimizer.last_stats.cpu().numpy()
+            lr = optimizer.param_groups[0]["lr"]
+            self.last_train_log = {}
+            for g, tag in enumerate(self.sweep_tags):
+                log = {"TRAIN_attack_loss(CE)": float(s[g, 0]), "TRAIN_patch_gradient": float(stats[g, 1]), "TRAIN_LR": lr,
+                       "TRAIN_attack_loss (MSE_Distance)": float(s[g, 1]), "TRAIN_UAD": float(s[g, 2])}
+                self.last_train_log[tag] = log
+                if rank == 0 and self.use_wandb and wandb is not None:
+                    wandb.log({f"{tag}/{k}": v for k, v in log.items()}, step=i)
+            if i % self.val_every == 0:
+                self.validate_sweep(i, patches, rank)
+        return patches
+
+    def sweep_step(self, img_all, patches, input_ids, labels_all, row_index, segmap, pack, w, V, msg, scalars, full_ce, update=None):
+        """One inner step of the sweep up to the exchange: K1 (one draw per frame, every group) -> body over P*bs images -> K3s (segmented map: each
+        row normalised by its group's count; K3h behind it when `full_ce`) -> K2' (a partial per image) -> ONE segmented epilogue: msg = [P gradients
+        | P x {CE, w^2*MSE, UAD, total}] (zero tail unless `full_ce`), scalars [P,8] folded per group; `update` = AdamW of every group inside it."""
+        sink = {}
+        pe = self.randomPatchTransform.apply_sweep_batch(img_all, patches, self.mean, self.std, self.geometry, sink)
+        h = self.vla.hidden_rows(input_ids, None, row_index, patch_embeds=pe, pack=pack)
+        W = self.vla.lm_head.weight
+        hd = h.detach().contiguous()
+        o = ops.head_slice_fwd_bwd(hd, W, segmap, ops.LOSS_UADA_DDP, w, want_dh=True, want_scalars=False)
+        ws = ops.head_loss_rows_stats(hd, W, segmap, ops.LOSS_UADA_DDP, w) if full_ce else None
+        h.backward(o["dh"])
+        P = int(patches.shape[0])
+        if not full_ce:
+            ops.step_epilogue_seg(sink["partials"], msg, scalars, P, update=update)
+            return None
+        _, pred_full = ops.step_epilogue_seg(sink["partials"], msg, scalars, P, rowmap=segmap, R=int(hd.shape[0]), V=V, mode=ops.LOSS_UADA_DDP, w=w,
+                                             loss_ws=ws, update=update)
+        return pred_full
+
+    def validate_sweep(self, i, patches, rank):
+        """validate() per group: every validation batch is drawn ONCE (the RNG consumption of one standalone pass) and evaluated with each group's
+        patch and labels; per group the averages, the AVG all-reduces, best-patch selection and the files under save_dir/<group tag>/."""
+        P = len(self.maskidx_sweep)
+        sums = np.zeros((P, 3))  # MSE, UAD, CE
+        rbs = [ValReadback(self.val_batches, self.device) for _ in range(P)]
+        last_images = [None] * P
+        ph, pw = int(patches.shape[2]), int(patches.shape[3])
+        with torch.no_grad():
+            for j, data in enumerate(self.val_loader):
+                if j == self.val_batches:
+                    break
+                pixel_values, labels, attention_mask, input_ids = to_dev(data, self.device)
+                img = self.randomPatchTransform.stage_images(pixel_values)
+                draws = self.randomPatchTransform.draw_params(int(img.shape[0]), ph, pw, self.geometry)
+                for g, m in enumerate(self.maskidx_sweep):
+                    modified = self.randomPatchTransform.apply_random_patch_batch(img, patches[g].detach(), mean=self.mean, std=self.std,
+                                                                                   geometry=self.geometry, draws=draws)
+                    lab = self.mask_labels(labels.clone(), m)
+                    _, sc, _ = self.model_loss(input_ids, attention_mask, modified, lab, ops.LOSS_UADA_DDP, w=float(self.MSE_weights), need_grad=False)
+                    rbs[g].add(sc)
+                    last_images[g] = modified
+        self.last_val_log = {}
+        for g, tag in enumerate(self.sweep_tags):
+            host, _ = rbs[g].read()
+            a_mse = a_uad = a_ce = 0.0
+            for s in host:
+                a_mse += float(np.float32(s[2]))
+                a_uad += float(np.float32(s[7]))
+                a_ce += float(np.float32(s[1]))
+            a_mse /= self.val_batches
+            a_uad /= self.val_batches
+            a_ce /= self.val_batches
+            g_MSE = vdist.allreduce_scalar(a_mse, "AVG", self.device)
+            g_UAD = vdist.allreduce_scalar(a_uad, "AVG", self.device)
+            g_CE = vdist.allreduce_scalar(a_ce, "AVG", self.device)
+            self.last_val_log[tag] = {"VAL_MSE_Distance": g_MSE, "VAL_UAD": g_UAD}
+            if rank == 0:
+                if g_MSE < self.MSE_Distance_best[tag]:
+                    self.MSE_Distance_best[tag] = g_MSE
+                    d = self.save_patch(patches[g], os.path.join(tag, str(i)))
+                    _, pil = self.save_val_images(last_images[g], d)
+                    if self.use_wandb and wandb is not None:
+                        wandb.log({f"{tag}/{k}": v for k, v in self.last_val_log[tag].items()}, step=i)
+                        wandb.log({f"{tag}/AdvImg": [wandb.Image(p) for p in pil]})
+                d = self.save_patch(patches[g], os.path.join(tag, "last"))
+                os.makedirs(os.path.join(d, "val_related_data"), exist_ok=True)
+                self.val_CE_loss[tag].append(g_CE)
+                self.val_MSE_Distance[tag].append(g_MSE)
+                self.val_UAD[tag].append(g_UAD)
 
     def _loss_mode(self):
         return {"UADA": ops.LOSS_UADA_DDP, "UPA": ops.LOSS_UPA, "TMA": ops.LOSS_CE}[self.attack_type]

@@ -221,6 +221,7 @@ struct HeadFinishArgs {
     uint16_t* grad_slice;       // [R][256] bf16 or nullptr (UADA_DDP)
     int R, nwg, split, mode;
     float w;
+    int seg_tbl;                // rowmap_seg_table(B, L): where a segmented map keeps its per-group counts
 };
 
 __global__ __launch_bounds__(256) void head_finish_kernel(HeadFinishArgs a) {
@@ -313,7 +314,7 @@ __global__ __launch_bounds__(256) void head_finish_kernel(HeadFinishArgs a) {
     if (a.mode == VAA_LOSS_UADA_DDP && a.grad_slice && own) {  // gradient of w^2 * mean((E / 256 - t)^2): this row and the row COUNT only
         RowMap me = {0, 0, -1, 0};
         if (r < a.rowmap[0]) me = reinterpret_cast<const RowMap*>(a.rowmap + 4)[r];
-        const int nact = a.rowmap[1];
+        const int nact = row_action_count(a.rowmap, a.seg_tbl, me.b);  // a.rowmap[1], or the row's group count on a segmented map
         float kE = 0.0f;
         if (me.lab > 2 && nact > 0) {
             const double rr = (double)E / 256.0, t = (me.lab > 31872) ? 0.0 : 1.0;  // UADA.py:390-394 (A-D10)
@@ -430,7 +431,7 @@ extern "C" int vaa_head_loss_rows_stats(const uint16_t* hidden, const uint16_t* 
     f.part_out = (PartStat*)loss_ws;
     f.slice_out = (SliceStat*)((char*)loss_ws + (size_t)R * 4 * sizeof(PartStat));
     f.grad_slice = (uint16_t*)grad_slice;
-    f.R = R; f.nwg = a.nwg; f.split = rows_split(R, V); f.mode = mode; f.w = params[0];
+    f.R = R; f.nwg = a.nwg; f.split = rows_split(R, V); f.mode = mode; f.w = params[0]; f.seg_tbl = rowmap_seg_table(B, L);
     VAA_LAUNCH(head_finish_kernel, dim3((unsigned)R), dim3(256), 0, st, f);
     return check_launch(who);
 }

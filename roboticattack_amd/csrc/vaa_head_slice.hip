@@ -229,6 +229,7 @@ __global__ __launch_bounds__(kST) __attribute__((amdgpu_waves_per_eu(CT == 8 ? 4
     // what phase 2 will want from global memory is requested now: the row map entry of this half wave's own row and the counts
     const RowMap* rm = reinterpret_cast<const RowMap*>(a.ra.rowmap + 4);
     const int Rdev = a.ra.rowmap[0], Rn = min(R, Rdev), nact = a.ra.rowmap[1];
+    const bool seg = a.ra.rowmap[2] > 0;  // segmented map (vaa_loss_rowmap_build_seg): every row is normalised by its own group's count
     const int own_lr = 2 * wv + hw;  // 8 waves x 2 half waves = the 16 rows of a block; this half wave takes row own_lr of each block of the group
     RowMap me[NRB];
 #pragma unroll
@@ -486,9 +487,10 @@ __global__ __launch_bounds__(kST) __attribute__((amdgpu_waves_per_eu(CT == 8 ? 4
             leave(rg * NRB + u, own_alse[u], own_E[u], pred[u]);
             if (a.ra.mode == VAA_LOSS_UADA_DDP && (a.dh || a.gs)) {  // the gradient needs this row and the row COUNT only: straight from the registers
                 float kE = 0.0f;
-                if (me[u].lab > 2 && nact > 0) {
+                const int nact_u = seg ? row_action_count(a.ra.rowmap, rowmap_seg_table(a.ra.B, a.ra.L), me[u].b) : nact;  // segmented map: the row's group
+                if (me[u].lab > 2 && nact_u > 0) {
                     const double q = (double)own_E[u] / 256.0, t = (me[u].lab > 31872) ? 0.0 : 1.0;  // UADA.py:390-394 (A-D10)
-                    kE = (float)((double)a.ra.w * a.ra.w * 2.0 * (q - t) / nact / 256.0);
+                    kE = (float)((double)a.ra.w * a.ra.w * 2.0 * (q - t) / nact_u / 256.0);
                 }
                 if (own_gave_up) kE = __uint_as_float(0x7fc00000u);  // NaN gradient, never a stale one
                 grad_row(u, xo[u], own_alse[u], own_E[u], kE);

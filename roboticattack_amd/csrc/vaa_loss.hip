@@ -1360,3 +1360,211 @@ extern "C" int vaa_step_epilogue_update(const float* partials, int nparts, int n
     return step_epilogue_impl(who, partials, nparts, n, rowmap, R, B, L, V, mode, params, loss_ws, loss_ws_bytes, scalars, pred_tokens,
                               pred_full_tokens, msg, &u, stat_part, stream);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// maskidx sweep: P groups of Bp consecutive images in one step, group p with its own labels (its own maskidx) and its own patch.
+// The segmented row map (layout: vaa_rows.h) is P ordinary maps — each built by the very kernel vaa_loss_rowmap_build runs, on the group's own
+// Bp label rows — plus the whole batch's map assembled from them and a per-group table. K3s / K3h normalise a row's gradient by its group's
+// count; vaa_step_epilogue_seg folds every group with the group's own map.
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+namespace vaa {
+
+__global__ __launch_bounds__(1024) void loss_rowmap_seg_kernel(int B, int L, int P, int* __restrict__ out) {
+    __shared__ int r0s[513];
+    const int tid = threadIdx.x, Bp = B / P;
+    const int T = rowmap_seg_table(B, L);
+    if (tid == 0) {  // the groups' rows are consecutive in (b,k) row-major order: prefix sums of the group counts, in group order
+        int r = 0, act = 0;
+        for (int g = 0; g < P; ++g) {
+            const int* sub = out + rowmap_seg_sub(B, L, P, g);
+            r0s[g] = r;
+            out[T + 4 * g] = r; out[T + 4 * g + 1] = sub[0]; out[T + 4 * g + 2] = sub[1]; out[T + 4 * g + 3] = 0;
+            r += sub[0];
+            act += sub[1];
+        }
+        r0s[P] = r;
+        out[0] = r; out[1] = act; out[2] = P; out[3] = Bp;
+    }
+    __syncthreads();
+    RowMap* rm = reinterpret_cast<RowMap*>(out + 4);
+    for (int g = 0; g < P; ++g) {
+        const RowMap* sm = reinterpret_cast<const RowMap*>(out + rowmap_seg_sub(B, L, P, g) + 4);
+        const int n = r0s[g + 1] - r0s[g];
+        for (int q = tid; q < n; q += 1024) {
+            RowMap m = sm[q];
+            m.b += g * Bp;
+            rm[r0s[g] + q] = m;
+        }
+    }
+}
+
+// Step epilogue over P groups (vaa_step_epilogue_seg[_update]): workgroup blk < P*nred sums group blk / nred's partial tiles for its block of 64
+// elements (partial_reduce_block over that group's nparts tiles: the standalone epilogue's order and bits) and — fused update — applies K4 to
+// them with the group's patch / m / v; workgroup P*nred + g folds group g with the group's own row map (rows_fold: the standalone fold's bits)
+// and writes the group's tail msg[P*n + 4g ..] (zeros in the pass-through form: a SUM all-reduce of stale scalars would grow them by world^steps).
+struct EpiSegArgs {
+    EpiArgs e;      // partials / msg / n / nparts / nred / fold / fuse_update / upd / stat_part of the WHOLE sweep
+    int P, Bp, L, R;
+};
+
+__global__ __launch_bounds__(256) void step_epilogue_seg_kernel(EpiSegArgs s, RowsArgs a) {
+    __shared__ double sl[16][16][4];
+    const EpiArgs& e = s.e;
+    const int blk = (int)blockIdx.x;
+    if (blk < s.P * e.nred) {
+        const int g = blk / e.nred, lb = blk - g * e.nred;
+        const size_t off = (size_t)g * e.n;
+        int oe = 0;
+        float gv = 0.0f;
+        const bool own = partial_reduce_block(e.partials + (size_t)g * e.nparts * e.n, e.msg + off, e.n, e.nparts, lb, sl, oe, gv);
+        if (!e.fuse_update) return;
+        if (own) {
+            const bool adam = e.upd.mode == VAA_OPT_ADAMW_HF;
+            float m = adam ? e.upd.m[off + oe] : 0.0f, v = adam ? e.upd.v[off + oe] : 0.0f;
+            const float p = update_one(e.upd, gv, e.upd.patch[off + oe], m, v);
+            if (adam) { e.upd.m[off + oe] = m; e.upd.v[off + oe] = v; }
+            e.upd.patch[off + oe] = p;
+        }
+        if (e.stat_part) {
+            double sa = own ? fabs((double)gv) : 0.0, ss = own ? (double)gv : 0.0;
+            if (threadIdx.x < 64) {
+                sa = wave_sum(sa);
+                ss = wave_sum(ss);
+                if (threadIdx.x == 0) { e.stat_part[2 * blk] = sa; e.stat_part[2 * blk + 1] = ss; }
+            }
+        }
+        return;
+    }
+    const int g = blk - s.P * e.nred;
+    float* tail = e.msg + (size_t)s.P * e.n + 4 * g;
+    if (!e.fold) {
+        if (threadIdx.x < 4) tail[threadIdx.x] = 0.0f;
+        return;
+    }
+    // group g's view: its own map, its rows of the statistics, its images of the prediction maps, its scalars
+    const int* map = a.rowmap;
+    const int Pm = map[2];
+    const bool total_ok = map[0] == s.R && (Pm == s.P || (Pm == 0 && s.P == 1));
+    RowsArgs ag = a;
+    int r0 = 0;
+    if (Pm > 0 && g < Pm) {
+        const int T = rowmap_seg_table(a.B, s.L);
+        r0 = map[T + 4 * g];
+        ag.rowmap = map + rowmap_seg_sub(a.B, s.L, Pm, g);
+    }
+    ag.R = total_ok ? ag.rowmap[0] : -1;  // a map of another batch than the caller states: rows_fold publishes NaN and never reads it
+    ag.B = s.Bp;
+    ag.part = a.part + (size_t)r0 * a.split;
+    ag.slice = a.slice + r0;
+    ag.scalars = a.scalars + 8 * g;
+    if (a.pred_tokens) ag.pred_tokens = a.pred_tokens + (size_t)g * s.Bp * (s.L - 1);
+    if (a.pred_full) ag.pred_full = a.pred_full + (size_t)g * s.Bp * (s.L - 1);
+    double (*sh)[7] = reinterpret_cast<double (*)[7]>(&sl[0][0][0]);
+    const FoldOut f = rows_fold<256>(ag, true, sh);
+    if (threadIdx.x == 0) {
+        const bool ok = ag.rowmap[0] == ag.R;
+        tail[0] = (float)f.CE; tail[1] = (float)f.MSE; tail[2] = (float)f.UAD;
+        tail[3] = ok ? (float)f.total : __uint_as_float(0x7fc00000u);
+    }
+}
+
+static int step_epilogue_seg_impl(const char* who, const float* partials, int nparts, int n, int P, const void* rowmap, int R, int B, int L, int V,
+                                  int mode, const float* params, const void* loss_ws, size_t loss_ws_bytes, float* scalars, int32_t* pred_tokens,
+                                  int32_t* pred_full_tokens, float* msg, const UpdArgs* upd, double* stat_part, void* stream) {
+    if (!partials || !msg || nparts <= 0 || n <= 0 || P <= 0 || P > 512) {
+        set_error("%s: bad arguments (nparts=%d n=%d P=%d)", who, nparts, n, P);
+        return VAA_E_INVALID;
+    }
+    if ((long)P * n > (1l << 30)) {
+        set_error("%s: %d groups of %d elements exceed the launch", who, P, n);
+        return VAA_E_UNSUPPORTED;
+    }
+    EpiSegArgs s = {};
+    s.e.partials = partials; s.e.msg = msg; s.e.scalars_in = nullptr; s.e.n = n; s.e.nparts = nparts; s.e.nred = (n + 63) / 64;
+    s.e.fold = rowmap ? 1 : 0; s.e.fuse_update = upd ? 1 : 0;
+    if (upd) s.e.upd = *upd;
+    s.e.stat_part = stat_part;
+    s.P = P; s.L = L; s.R = R;
+    RowsArgs a = {};
+    if (rowmap) {
+        if (!scalars || B <= 0 || B % P != 0) {
+            set_error("%s: the fold needs scalars [P,8] and B (%d) a multiple of P (%d)", who, B, P);
+            return VAA_E_INVALID;
+        }
+        if (mode != VAA_LOSS_UADA_DDP) {
+            set_error("%s: mode %d — a maskidx sweep folds VAA_LOSS_UADA_DDP only", who, mode);
+            return VAA_E_UNSUPPORTED;
+        }
+        int rc = rows_args(who, nullptr, VAA_DTYPE_BF16, rowmap, R, B, L, V, mode, params, scalars, pred_tokens, pred_full_tokens, nullptr, VAA_GRAD_SLICE,
+                           const_cast<void*>(loss_ws), loss_ws_bytes, a);
+        if (rc != VAA_OK) return rc;
+        s.Bp = B / P;
+    }
+    VAA_LAUNCH(step_epilogue_seg_kernel, dim3((unsigned)(P * s.e.nred + P)), dim3(256), 0, (hipStream_t)stream, s, a);
+    return check_launch(who);
+}
+
+}  // namespace vaa
+
+extern "C" size_t vaa_loss_rowmap_seg_bytes(int B, int L, int P) {
+    if (B <= 0 || L <= 1 || P <= 0 || B % P != 0) return 0;
+    return sizeof(int) * ((size_t)vaa::rowmap_seg_sub(B, L, P, P));
+}
+
+extern "C" int vaa_loss_rowmap_build_seg(const int64_t* labels, int B, int L, int P, void* rowmap, size_t rowmap_bytes, void* stream) {
+    using namespace vaa;
+    const char* who = "vaa_loss_rowmap_build_seg";
+    if (!labels || !rowmap || B <= 0 || L <= 1 || P <= 0 || P > 512 || B % P != 0) {
+        set_error("%s: bad arguments (B=%d L=%d P=%d: B must be P groups of equal size, P <= 512)", who, B, L, P);
+        return VAA_E_INVALID;
+    }
+    if ((long)B * (L - 1) * 8 + 16l * P > (1l << 30)) {
+        set_error("%s: %d x %d labels exceed the map's int offsets", who, B, L);
+        return VAA_E_UNSUPPORTED;
+    }
+    if (rowmap_bytes < vaa_loss_rowmap_seg_bytes(B, L, P)) {
+        set_error("%s: buffer %zu B < required %zu B", who, rowmap_bytes, vaa_loss_rowmap_seg_bytes(B, L, P));
+        return VAA_E_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int Bp = B / P;
+    for (int g = 0; g < P; ++g) {  // each group's own map: the ordinary map of its Bp label rows
+        VAA_LAUNCH(loss_rowmap_kernel, dim3(1), dim3(1024), 0, st, labels + (size_t)g * Bp * L, Bp, L, (int*)rowmap + rowmap_seg_sub(B, L, P, g));
+        int rc = check_launch(who);
+        if (rc != VAA_OK) return rc;
+    }
+    VAA_LAUNCH(loss_rowmap_seg_kernel, dim3(1), dim3(1024), 0, st, B, L, P, (int*)rowmap);
+    return check_launch(who);
+}
+
+extern "C" int vaa_step_epilogue_seg(const float* partials, int nparts, int n, int P, const void* rowmap, int R, int B, int L, int V, int mode,
+                                     const float* params, const void* loss_ws, size_t loss_ws_bytes, float* scalars, int32_t* pred_tokens,
+                                     int32_t* pred_full_tokens, float* msg, void* stream) {
+    return vaa::step_epilogue_seg_impl("vaa_step_epilogue_seg", partials, nparts, n, P, rowmap, R, B, L, V, mode, params, loss_ws, loss_ws_bytes, scalars,
+                                       pred_tokens, pred_full_tokens, msg, nullptr, nullptr, stream);
+}
+
+extern "C" int vaa_step_epilogue_seg_update(const float* partials, int nparts, int n, int P, const void* rowmap, int R, int B, int L, int V, int mode,
+                                            const float* params, const void* loss_ws, size_t loss_ws_bytes, float* scalars, int32_t* pred_tokens,
+                                            int32_t* pred_full_tokens, float* msg, float* patch, float* m, float* v, int opt_mode, float lr, float beta1,
+                                            float beta2, float eps, int step, double* stat_part, void* stream) {
+    using namespace vaa;
+    const char* who = "vaa_step_epilogue_seg_update";
+    if (!patch || (opt_mode == VAA_OPT_ADAMW_HF && (!m || !v))) {
+        set_error("%s: null pointer argument", who);
+        return VAA_E_INVALID;
+    }
+    if ((opt_mode != VAA_OPT_ADAMW_HF && opt_mode != VAA_OPT_PGD_SIGN) || (opt_mode == VAA_OPT_ADAMW_HF && step < 1)) {
+        set_error("%s: bad optimiser mode/step (mode=%d step=%d)", who, opt_mode, step);
+        return VAA_E_INVALID;
+    }
+    UpdArgs u = {};
+    u.patch = patch; u.g = nullptr; u.m = m; u.v = v; u.stats = nullptr; u.n = n; u.mode = opt_mode;
+    u.lr = lr; u.b1 = beta1; u.b2 = beta2; u.eps = eps; u.l1_clip = 0.0f; u.grad_scale = 1.0f;
+    const double b1 = (double)beta1, b2 = (double)beta2;  // narrowed exactly like vaa_step_epilogue_update / vaa_patch_update
+    u.one_m_b1 = (float)(1.0 - b1);
+    u.one_m_b2 = (float)(1.0 - b2);
+    u.step_size = (opt_mode == VAA_OPT_ADAMW_HF) ? (float)((double)lr * sqrt(1.0 - pow(b2, (double)step)) / (1.0 - pow(b1, (double)step))) : 0.0f;
+    return step_epilogue_seg_impl(who, partials, nparts, n, P, rowmap, R, B, L, V, mode, params, loss_ws, loss_ws_bytes, scalars, pred_tokens,
+                                  pred_full_tokens, msg, &u, stat_part, stream);
+}

@@ -24,6 +24,24 @@ struct SliceStat {  // one per row
 
 int rows_split(int R, int V);
 
+// SEGMENTED row map (vaa_loss_rowmap_build_seg: P groups of Bp consecutive images, one maskidx sweep group each), int words:
+//   [0, 4)        {R, #action rows of all groups, P, Bp}             (an ordinary map has {R, #action rows, 0, 0})
+//   [4, T)        RowMap[R] of the whole batch, exactly the ordinary map's rows; T = rowmap_seg_table(B, L)
+//   [T, T + 4P)   per group {first row, rows, action rows, 0}
+//   [S_g, ...)    group g's own ordinary map {R_g, nact_g, 0, 0} + RowMap[R_g] (image index within the group): S_g = rowmap_seg_sub(B, L, P, g)
+// The group's own map is what vaa_step_epilogue_seg folds with: bit for bit the fold a standalone run of that group performs.
+inline __host__ __device__ int rowmap_seg_table(int B, int L) { return 4 + 4 * B * (L - 1); }
+inline __host__ __device__ int rowmap_seg_sub(int B, int L, int P, int g) { return rowmap_seg_table(B, L) + 4 * P + g * (4 + 4 * (B / P) * (L - 1)); }
+// the count that normalises row b's gradient (the kE term of UADA_ddp.py:99-124's mean over action rows): its group's on a segmented map
+__device__ __forceinline__ int row_action_count(const int* rowmap, int tbl, int b) {
+    const int P = rowmap[2];
+    if (P <= 0) return rowmap[1];
+    const int Bp = rowmap[3] > 0 ? rowmap[3] : 1;
+    int g = b / Bp;
+    g = g < 0 ? 0 : (g >= P ? P - 1 : g);
+    return rowmap[tbl + 4 * g + 2];
+}
+
 // head workspace of vaa_head_loss_rows_stats: [R][ceil(V / 128)] PartStat, then (256-byte aligned) the action-column logits [R][256] bf16
 constexpr int kHeadCols = 128;  // vocabulary columns per workgroup of head_stats_kernel
 inline size_t head_ws_align(size_t n) { return (n + 255) / 256 * 256; }

@@ -26,11 +26,11 @@ constexpr int kUpdPer = 2;        // elements a thread UPDATES: the update is sp
 //   R = 0: any n, one workgroup, streaming (patches beyond 32,768 elements).
 // All forms add a thread's elements in the same increasing-index order, so statistics, clip coefficient and updates agree bitwise.
 template <int R>
-__global__ __launch_bounds__(1024) void patch_update_kernel(UpdArgs a) {
+__device__ __forceinline__ void patch_update_body(const UpdArgs& a, int bid) {
     __shared__ double sh_abs[16], sh_sum[16];
     __shared__ float coef_sh;
     constexpr int RR = R > 0 ? R : 1, PER = R > 0 ? kUpdPer : 1, G = R > 0 ? R / kUpdPer : 1;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, bid = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const bool adam = a.mode == VAA_OPT_ADAMW_HF;
     float gq[RR], g2[PER], p2[PER], m2[PER], v2[PER];
     double sa = 0.0, ss = 0.0;
@@ -106,7 +106,62 @@ __global__ __launch_bounds__(1024) void patch_update_kernel(UpdArgs a) {
     }
 }
 
+template <int R>
+__global__ __launch_bounds__(1024) void patch_update_kernel(UpdArgs a) {
+    patch_update_body<R>(a, blockIdx.x);
+}
+
+// maskidx sweep (vaa_patch_update_seg): group blockIdx.y is an independent K4 over its own n elements — its statistics, its clip, its stats[2]
+template <int R>
+__global__ __launch_bounds__(1024) void patch_update_seg_kernel(UpdArgs a) {
+    const size_t off = (size_t)blockIdx.y * a.n;
+    a.patch += off; a.g += off;
+    if (a.m) a.m += off;
+    if (a.v) a.v += off;
+    if (a.stats) a.stats += 2 * blockIdx.y;
+    patch_update_body<R>(a, blockIdx.x);
+}
+
+static int patch_update_launch(const char* who, float* patch, const float* g, float* m, float* v, int n, int P, int mode, float lr, float beta1,
+                               float beta2, float eps, int step, float l1_clip, float grad_scale, float* stats, void* stream) {
+    if (!patch || !g || (mode == VAA_OPT_ADAMW_HF && (!m || !v))) {
+        set_error("%s: null pointer argument", who);
+        return VAA_E_INVALID;
+    }
+    if (n <= 0 || P <= 0 || (long)n * P > (1l << 30) || (mode != VAA_OPT_ADAMW_HF && mode != VAA_OPT_PGD_SIGN) || (mode == VAA_OPT_ADAMW_HF && step < 1)) {
+        set_error("%s: bad sizes/mode (n=%d P=%d mode=%d step=%d)", who, n, P, mode, step);
+        return VAA_E_INVALID;
+    }
+    {   // several workgroups read the WHOLE gradient while others already write their elements of patch / m / v: no byte of g may lie inside
+        // one of those buffers (a view into a shared flat buffer overlaps without being pointer-equal)
+        const size_t nb = (size_t)n * P * sizeof(float);
+        const uintptr_t g0 = (uintptr_t)g, g1 = g0 + nb;
+        auto overlaps = [&](const float* p) { const uintptr_t p0 = (uintptr_t)p; return p && g0 < p0 + nb && p0 < g1; };
+        if (overlaps(patch) || (mode == VAA_OPT_ADAMW_HF && (overlaps(m) || overlaps(v)))) {
+            set_error("%s: the gradient must not overlap the patch or a moment buffer", who);
+            return VAA_E_INVALID;
+        }
+    }
+    UpdArgs a;
+    a.patch = patch; a.g = g; a.m = m; a.v = v; a.stats = stats; a.n = n; a.mode = mode;
+    a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.l1_clip = l1_clip; a.grad_scale = grad_scale;
+    const double b1 = (double)beta1, b2 = (double)beta2;
+    a.one_m_b1 = (float)(1.0 - b1);
+    a.one_m_b2 = (float)(1.0 - b2);
+    a.step_size = (mode == VAA_OPT_ADAMW_HF) ? (float)((double)lr * sqrt(1.0 - pow(b2, (double)step)) / (1.0 - pow(b1, (double)step))) : 0.0f;
+    const hipStream_t st = (hipStream_t)stream;
+    if (n <= 1024 * kUpdRegsSmall) VAA_LAUNCH(patch_update_seg_kernel<kUpdRegsSmall>, dim3(kUpdRegsSmall / kUpdPer, P), dim3(1024), 0, st, a);
+    else if (n <= 1024 * kUpdRegsMid) VAA_LAUNCH(patch_update_seg_kernel<kUpdRegsMid>, dim3(kUpdRegsMid / kUpdPer, P), dim3(1024), 0, st, a);
+    else VAA_LAUNCH(patch_update_seg_kernel<0>, dim3(1, P), dim3(1024), 0, st, a);
+    return check_launch(who);
+}
+
 }  // namespace vaa
+
+extern "C" int vaa_patch_update_seg(float* patch, const float* g, float* m, float* v, int n, int P, int mode, float lr, float beta1, float beta2,
+                                    float eps, int step, float l1_clip, float grad_scale, float* stats, void* stream) {
+    return vaa::patch_update_launch("vaa_patch_update_seg", patch, g, m, v, n, P, mode, lr, beta1, beta2, eps, step, l1_clip, grad_scale, stats, stream);
+}
 
 extern "C" int vaa_patch_update(float* patch, const float* g, float* m, float* v, int n, int mode, float lr, float beta1,
                                 float beta2, float eps, int step, float l1_clip, float grad_scale, float* stats, void* stream) {

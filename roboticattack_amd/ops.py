@@ -503,6 +503,45 @@ class PatchApplyEmbed(torch.autograd.Function):
         return (g,) + (None,) * 14
 
 
+def sweep_pdesc(P: int, Bp: int, ph: int, pw: int, device) -> torch.Tensor:
+    """[P*Bp, 4] int32 patch descriptors of a maskidx sweep: image b of group g = b // Bp pastes patch g of the packed [P,3,ph,pw] tensor."""
+    g = torch.arange(P * Bp, dtype=torch.int32) // Bp
+    d = torch.stack([torch.full_like(g, ph), torch.full_like(g, pw), g * (3 * ph * pw), torch.zeros_like(g)], dim=1)
+    return d.contiguous().to(device, non_blocking=True)
+
+
+class PatchApplySweepEmbed(torch.autograd.Function):
+    """PatchApplyEmbed for a maskidx sweep: P groups of Bp images, image b pastes patch b // Bp of `patches` [P,3,ph,pw] (K1 tile-major with a
+    per-image descriptor pointing into the shared read-only patches). The backward is K2' with one partial tile per image (P*Bp < 512): it leaves
+    the [P*Bp, n] partials in sink["partials"], group g's at rows g*Bp .., for ops.step_epilogue_seg; no gradient is returned."""
+
+    @staticmethod
+    def forward(ctx, patches, img_u8, xy, theta, geometry, mask_mode, mean6, std6, w0, b0, wp0, w1, b1, wp1, sink):
+        P, ph, pw = int(patches.shape[0]), int(patches.shape[2]), int(patches.shape[3])
+        B = int(img_u8.shape[0])
+        if B % P != 0:
+            raise _lib.VaaError(f"PatchApplySweepEmbed: {B} images are not {P} equal groups")
+        if _lib.lib().vaa_patch_grad_partials(B) != B:
+            raise _lib.VaaError(f"PatchApplySweepEmbed: {B} images exceed K2''s one-partial-per-image schedule (at most 511)")
+        p = patches.detach().contiguous()
+        pdesc = sweep_pdesc(P, B // P, ph, pw, p.device)
+        t0, t1, keep_t, flags = patch_apply_fwd_tiles(img_u8, p, xy, theta, geometry, mask_mode, mean6=mean6, std6=std6, pdesc=pdesc, max_hw=(ph, pw))
+        e0 = torch.nn.functional.linear(t0, w0, b0)
+        e1 = torch.nn.functional.linear(t1, w1, b1)
+        ctx.save_for_backward(p, xy, theta if geometry else xy, keep_t, flags, wp0, wp1)
+        ctx.geometry, ctx.mask_mode, ctx.std6, ctx.sink = bool(geometry), int(mask_mode), std6, sink
+        return e0, e1
+
+    @staticmethod
+    def backward(ctx, d0, d1):
+        p, xy, theta, keep_t, flags, wp0, wp1 = ctx.saved_tensors
+        d0, d1 = d0.to(torch.bfloat16).contiguous(), d1.to(torch.bfloat16).contiguous()
+        # the keep words are given: K2' never reads patch values, only the [3,ph,pw] shape
+        ctx.sink["partials"] = patch_embed_grad_gather_tiles(d0, d1, wp0, wp1, p[0], xy, theta if ctx.geometry else None, keep_t, flags, ctx.geometry,
+                                                             ctx.mask_mode, std6=ctx.std6, defer_reduce=True)
+        return (None,) * 15
+
+
 class PatchApplyResizedEmbed(torch.autograd.Function):
     """resize_patch=True with the pixel gradient un-materialised: resize (K0) + K1 with per-image patches + both patch-embed GEMMs forward;
     K2' in per-image mode + the resize adjoint backward."""
@@ -613,6 +652,22 @@ class LossRowMap:
         L = _lib.lib()
         self.buf = torch.empty(L.vaa_loss_rowmap_bytes(self.B, self.L), dtype=torch.uint8, device=labels.device)
         _lib.check(L.vaa_loss_rowmap_build(labels.data_ptr(), self.B, self.L, self.buf.data_ptr(), self.buf.numel(), _stream()), "vaa_loss_rowmap_build")
+
+
+class LossRowMapSeg:
+    """Segmented device row map (vaa_loss_rowmap_build_seg) of a maskidx sweep: labels [P*Bp, L] = P groups of Bp rows, each with its own masking.
+    Usable wherever a LossRowMap is for K3s / K3h (UADA_DDP), and by step_epilogue_seg to fold every group with its own map."""
+
+    def __init__(self, labels: torch.Tensor, P: int):
+        _need(labels, torch.int64, "labels")
+        self.B, self.L, self.P = int(labels.shape[0]), int(labels.shape[1]), int(P)
+        L = _lib.lib()
+        nb = L.vaa_loss_rowmap_seg_bytes(self.B, self.L, self.P)
+        if nb == 0:
+            raise _lib.VaaError(f"LossRowMapSeg: {self.B} label rows are not {self.P} equal groups")
+        self.buf = torch.empty(nb, dtype=torch.uint8, device=labels.device)
+        _lib.check(L.vaa_loss_rowmap_build_seg(labels.data_ptr(), self.B, self.L, self.P, self.buf.data_ptr(), self.buf.numel(), _stream()),
+                   "vaa_loss_rowmap_build_seg")
 
 
 def loss_rows_fwd_bwd(logits, rowmap: LossRowMap, mode: int, w: float = 5.0, alpha: float = 0.8, beta: float = 0.2, scale: float = 1.0,
@@ -822,6 +877,48 @@ def step_epilogue(partials, msg, scalars, rowmap: LossRowMap = None, R: int = 0,
     return pred, pred_full
 
 
+def step_epilogue_seg(partials, msg, scalars, P: int, rowmap=None, R: int = 0, V: int = 32064, mode: int = LOSS_UADA_DDP, w: float = 5.0,
+                      alpha: float = 0.8, beta: float = 0.2, scale: float = 1.0, loss_ws=None, want_pred: bool = True, update=None):
+    """vaa_step_epilogue_seg[_update]: step_epilogue for each of P sweep groups in ONE launch. partials [P*nparts, n] (group g's at g*nparts),
+    msg f32 [>= P*n + 4P] = [P gradients | P x {CE, w^2*MSE, UAD, total}] (a ZERO tail in the pass-through form, rowmap=None), scalars f32 [P,8]
+    (the folded groups; untouched when rowmap is None). update = dict as step_epilogue's, patch / m / v [P*n] and stat_part f64 [P*ceil(n/64), 2].
+    Returns (pred_slice, pred_full) [B, L-1] (group g's images at rows g*B/P ..) or (None, None)."""
+    _need(partials, torch.float32, "partials")
+    rows, n = int(partials.shape[0]), int(partials.shape[1])
+    if rows % P != 0:
+        raise _lib.VaaError(f"partials: {rows} tiles are not {P} equal groups")
+    nparts = rows // P
+    _need(msg, torch.float32, "msg")
+    _need(scalars, torch.float32, "scalars", (P, 8))
+    if msg.numel() < P * (n + 4):
+        raise _lib.VaaError(f"msg: needs {P * (n + 4)} floats, has {msg.numel()}")
+    pred = pred_full = None
+    if rowmap is not None and want_pred:
+        pred = torch.empty((rowmap.B, rowmap.L - 1), dtype=torch.int32, device=msg.device)
+        pred_full = torch.empty((rowmap.B, rowmap.L - 1), dtype=torch.int32, device=msg.device)
+    common = (partials.data_ptr(), nparts, n, int(P), rowmap.buf.data_ptr() if rowmap is not None else None, int(R), rowmap.B if rowmap is not None else 0,
+              rowmap.L if rowmap is not None else 0, int(V), int(mode), _lib.f32x([w, alpha, beta, scale]),
+              loss_ws.data_ptr() if loss_ws is not None else None, loss_ws.numel() if loss_ws is not None else 0, scalars.data_ptr(),
+              pred.data_ptr() if pred is not None else None, pred_full.data_ptr() if pred_full is not None else None, msg.data_ptr())
+    with _timed("EPI_step_epilogue_seg", n=n, parts=nparts, P=P):
+        if update is None:
+            rc = _lib.lib().vaa_step_epilogue_seg(*common, _stream())
+        else:
+            u = update
+            _need(u["patch"], torch.float32, "patch")
+            if u["patch"].numel() != P * n:
+                raise _lib.VaaError(f"update: patch has {u['patch'].numel()} elements, the gradients {P} x {n}")
+            sp = u.get("stat_part")
+            if sp is not None:
+                _need(sp, torch.float64, "stat_part", (P * ((n + 63) // 64), 2))
+            rc = _lib.lib().vaa_step_epilogue_seg_update(*common, u["patch"].data_ptr(), u["m"].data_ptr() if u.get("m") is not None else None,
+                                                         u["v"].data_ptr() if u.get("v") is not None else None, int(u["mode"]), float(u["lr"]),
+                                                         float(u.get("beta1", 0.9)), float(u.get("beta2", 0.999)), float(u.get("eps", 1e-6)), int(u["step"]),
+                                                         sp.data_ptr() if sp is not None else None, _stream())
+    _lib.check(rc, "vaa_step_epilogue_seg")
+    return pred, pred_full
+
+
 class DiscrepancyLossRows(torch.autograd.Function):
     """total = loss(logits [R,V], row map); d total / d logits by the same launch sequence (full-row gradient storage)."""
 
@@ -942,6 +1039,27 @@ def patch_update(patch, grad, m, v, mode: int, lr: float, step: int, beta1: floa
             patch.numel(), int(mode), float(lr), float(beta1), float(beta2), float(eps), int(step), float(l1_clip),
             float(grad_scale), stats.data_ptr() if want_stats else None, _stream())
     _lib.check(rc, "vaa_patch_update")
+    return stats
+
+
+def patch_update_seg(patch, grad, m, v, P: int, mode: int, lr: float, step: int, beta1: float = 0.9, beta2: float = 0.999,
+                     eps: float = 1e-6, l1_clip: float = 0.0, grad_scale: float = 1.0, want_stats: bool = True):
+    """K4 on P groups of patch.numel() / P elements in ONE launch (vaa_patch_update_seg): bit for bit P patch_update calls. Returns stats f32 [P,2]."""
+    _need(patch, torch.float32, "patch")
+    _need(grad, torch.float32, "grad")
+    n_all = int(patch.numel())
+    if grad.numel() != n_all or n_all % P != 0:
+        raise _lib.VaaError(f"patch_update_seg: {n_all} patch / {grad.numel()} gradient elements are not {P} equal groups")
+    if mode == OPT_ADAMW_HF:
+        _need(m, torch.float32, "m", patch.shape)
+        _need(v, torch.float32, "v", patch.shape)
+    stats = torch.empty((P, 2), dtype=torch.float32, device=patch.device) if want_stats else None
+    with _timed("K4_patch_update_seg", n=n_all, P=P):
+        rc = _lib.lib().vaa_patch_update_seg(
+            patch.data_ptr(), grad.data_ptr(), m.data_ptr() if m is not None else None, v.data_ptr() if v is not None else None,
+            n_all // P, int(P), int(mode), float(lr), float(beta1), float(beta2), float(eps), int(step), float(l1_clip),
+            float(grad_scale), stats.data_ptr() if want_stats else None, _stream())
+    _lib.check(rc, "vaa_patch_update_seg")
     return stats
 
 

@@ -83,6 +83,54 @@ class PatchOptimizer:
             self.patch.grad.zero_()
 
 
+class SweepPatchOptimizer(PatchOptimizer):
+    """The optimiser of a maskidx sweep: `patch` is [P, ...] = P independent patches sharing lr and the step count; every group is the AdamW /
+    PGD step a standalone PatchOptimizer would take on its own patch (one launch for all: vaa_patch_update_seg / vaa_step_epilogue_seg_update).
+    last_stats is [P,2] = per group [sum|g|, mean g]."""
+
+    def __init__(self, patch: torch.Tensor, lr: float, mode: str = "adamW", betas=(0.9, 0.999), eps: float = 1e-6, l1_clip: float = 0.0):
+        super().__init__(patch, lr, mode, betas, eps, l1_clip)
+        self.P = int(patch.shape[0])
+        self.n = patch.numel() // self.P
+
+    @property
+    def last_stats(self):
+        if self._last_stats is None and self._stat_part is not None:
+            # group g's block sums are exactly the stat_part of a standalone fused step: summed the same way, the same bits
+            sp = self._stat_part.view(self.P, -1, 2)
+            rows = []
+            for g in range(self.P):
+                t = sp[g].sum(dim=0)
+                rows.append(torch.stack([t[0], t[1] / self.n]).to(torch.float32))
+            self._last_stats = torch.stack(rows)
+        return self._last_stats
+
+    @last_stats.setter
+    def last_stats(self, v):
+        self._last_stats = v
+
+    def fused_update_args(self):
+        if self.l1_clip:
+            raise ValueError("the fused update has no L1 clip")
+        self.t += 1
+        grp = self.param_groups[0]
+        if self._stat_part is None:
+            self._stat_part = torch.zeros((self.P * ((self.n + 63) // 64), 2), dtype=torch.float64, device=self.patch.device)
+        self._last_stats = None
+        return dict(patch=self.patch.data, m=self.m, v=self.v, mode=self.mode, lr=grp["lr"], step=self.t, beta1=grp["betas"][0],
+                    beta2=grp["betas"][1], eps=grp["eps"], stat_part=self._stat_part)
+
+    def step(self, grad: torch.Tensor | None = None, grad_scale: float = 1.0):
+        g = grad if grad is not None else self.patch.grad
+        if g is None:
+            return None
+        self.t += 1
+        grp = self.param_groups[0]
+        self._last_stats = ops.patch_update_seg(self.patch.data, g.contiguous(), self.m, self.v, self.P, self.mode, grp["lr"], self.t,
+                                                grp["betas"][0], grp["betas"][1], grp["eps"], self.l1_clip, grad_scale)
+        return self._last_stats
+
+
 class CosineWarmupSchedule:
     """LambdaLR semantics: lr = initial_lr * lambda(epoch); constructed at epoch 0, `.step()` advances by one."""
 

@@ -132,11 +132,12 @@ class RandomPatchTransform:
         return d[: 2 * B].view(B, 2), d[2 * B :].view(torch.float32).view(B, 6)
 
     # ---- the operators ----
-    def apply_random_patch_batch(self, images, patch, mean, std, geometry, colorjitter=False, out_dtype=torch.bfloat16, grad_sink=None):
+    def apply_random_patch_batch(self, images, patch, mean, std, geometry, colorjitter=False, out_dtype=torch.bfloat16, grad_sink=None, draws=None):
         """Paste `patch` at a random position of every image, optionally warp it by a random rotation+shear, composite
         where the warped canvas is >= -20, normalise twice and stack to 6 channels (:104-136). Differentiable w.r.t. patch.
         grad_sink (dict, one patch for the batch): the backward leaves K2's (or K2''s) partial tiles in grad_sink["partials"] instead of a
-        patch gradient — the caller adds them with ops.step_epilogue (into the DDP message and / or straight through the optimiser)."""
+        patch gradient — the caller adds them with ops.step_epilogue (into the DDP message and / or straight through the optimiser).
+        draws: (xy, theta) host arrays from `draw_params` to use instead of drawing (a maskidx sweep hands every group the same draws)."""
         mean6, std6 = _six(mean, std)
         img = self.stage_images(images)
         B = img.shape[0]
@@ -145,12 +146,31 @@ class RandomPatchTransform:
                 raise ValueError("grad_sink is not available with resize_patch=True (per-image gradients go through the resize adjoint)")
             return self._apply_resized(img, patch, mean6, std6, geometry, out_dtype)
         ph, pw = int(patch.shape[1]), int(patch.shape[2])
-        xy, theta = self._to_dev(*self._draw(B, ph, pw, geometry))
+        xy, theta = self._to_dev(*(draws if draws is not None else self._draw(B, ph, pw, geometry)))
         emb = self._embed_params(patch, out_dtype)
         if emb is not None:
             return ops.PatchEmbeds(ops.PatchApplyEmbed.apply(patch, img, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6, *emb, grad_sink))
         out = ops.PatchApply.apply(patch, img, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6, grad_sink)
         return out if out_dtype == torch.bfloat16 else out.to(out_dtype)
+
+    def draw_params(self, batch, ph, pw, geometry):
+        """The host draws of one apply_random_patch_batch call on `batch` frames (the same RNG consumption), for `draws=` / apply_sweep_batch."""
+        return self._draw(batch, ph, pw, geometry)
+
+    def apply_sweep_batch(self, images, patches, mean, std, geometry, grad_sink, draws=None):
+        """maskidx sweep (training step): `images` uint8 [P*Bp,224,224,3] = the same Bp frames replicated P times, `patches` [P,3,ph,pw]; image b
+        gets patch b // Bp and the draws of frame b % Bp — ONE draw per frame, exactly what a standalone call on the Bp frames consumes, shared by
+        every group. Returns the patch-embed outputs (ops.PatchEmbeds); the backward leaves the per-image partial tiles in grad_sink["partials"]."""
+        mean6, std6 = _six(mean, std)
+        img = self.stage_images(images)
+        P, ph, pw = int(patches.shape[0]), int(patches.shape[2]), int(patches.shape[3])
+        Bp = int(img.shape[0]) // P
+        if self.embed_with is None:
+            raise ValueError("apply_sweep_batch needs a model that exposes its patch-embed weights")
+        xy_n, th_n = draws if draws is not None else self._draw(Bp, ph, pw, geometry)
+        xy, theta = self._to_dev(np.tile(xy_n, (P, 1)), np.tile(th_n, (P, 1)))
+        emb = self.embed_with.patch_embed_params()
+        return ops.PatchEmbeds(ops.PatchApplySweepEmbed.apply(patches, img, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6, *emb, grad_sink))
 
     def _embed_params(self, patch, out_dtype):
         """Patch-embed weights for the path that never materialises the pixel gradient — only for differentiable bf16 calls."""

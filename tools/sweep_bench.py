@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""Measures the maskidx sweep step against P standalone steps (one GPU, world size 1, the fused data-parallel UADA step with AdamW inside the
+epilogue): OpenVLA-7B shapes with random weights by default.
+
+    python tools/sweep_bench.py --configs 2x8,8x4,8x8 --steps 10 --warmup 3 [--vla random:openvla-7b] [--out file.json]
+
+For each (P, Bp): ms per standalone step at bs = Bp (maskidx [0]), ms per sweep step over P groups x Bp images (one DoF per group), their ratio, and the library's own kernels per step (vaa_prof per-dispatch timer: the hand-written microseconds of one step).
+Every step runs with full_ce on its last inner step only, as the loop does (innerLoop = `--inner`)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def _groups(P):
+    """One DoF per group ({0}, {1}, ..., {6}, then {0} again): two labelled rows per sample like the standalone maskidx [0] step, so (8, 8) stays
+    within K3s's 128 rows (a sweep that keeps more DoFs per group needs a smaller P x Bp)."""
+    return [[q % 7] for q in range(P)]
+
+
+def measure(att, P, Bp, steps, warmup, inner, sweep):
+    from roboticattack_amd import ops, synthetic
+    from roboticattack_amd.attack.uada_ddp import mask_labels_sweep
+    from roboticattack_amd.optim import PatchOptimizer, SweepPatchOptimizer
+
+    dev = att.device
+    batch = synthetic.synth_batch(1234, Bp, "noise")
+    pv = att.randomPatchTransform.stage_images(batch["pixel_values"])
+    labels = batch["labels"].to(dev)
+    ids, am = batch["input_ids"].to(dev), batch["attention_mask"].to(dev)
+    n = 3 * 50 * 50
+    if sweep:
+        groups = _groups(P)
+        patches = torch.rand(P, 3, 50, 50, device=dev, requires_grad=True)
+        opt = SweepPatchOptimizer(patches, 1e-3)
+        img = pv.repeat(P, 1, 1, 1).contiguous()
+        ids_all, am_all = ids.repeat(P, 1).contiguous(), am.repeat(P, 1).contiguous()
+        lab = mask_labels_sweep(labels, groups)
+        row_index = att.vla.label_row_index(lab)
+        segmap = ops.LossRowMapSeg(lab, P)
+        pack = att.vla.make_pack(am_all) if hasattr(att.vla, "make_pack") else None
+        msg = torch.zeros(P * (n + 4), device=dev)
+        sc = torch.zeros((P, 8), device=dev)
+        W = att.vla.lm_head.weight
+
+        def step(k):
+            att.sweep_step(img, patches, ids_all, lab, row_index, segmap, pack, 5.0, int(W.shape[0]), msg, sc, k % inner == inner - 1,
+                           opt.fused_update_args())
+    else:
+        patch = torch.rand(3, 50, 50, device=dev, requires_grad=True)
+        opt = PatchOptimizer(patch, 1e-3)
+        lab = att.mask_labels(labels.clone(), [0])
+        msg = torch.zeros(n + 4, device=dev)
+        sc = torch.zeros(8, device=dev)
+
+        def step(k):
+            att.fused_ddp_step(pv, patch, ids, am, lab, True, 5.0, msg, sc, optimizer=opt, full_ce=k % inner == inner - 1)
+
+    for k in range(warmup):
+        step(k)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for k in range(steps):
+        step(k)
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) * 1e3 / steps
+    ops.prof_start(4096)
+    for k in range(inner):
+        step(k)
+    torch.cuda.synchronize()
+    recs = ops.prof_collect()
+    hand = sum(us for _, us in recs) / inner
+    per = {}
+    for nm, us in recs:
+        per[nm] = per.get(nm, 0.0) + us / inner
+    return ms, hand, per
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", default="2x8,8x4,8x8")
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--inner", type=int, default=50)
+    ap.add_argument("--vla", default="random:openvla-7b")
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    os.environ.setdefault("RANK", "0")
+    os.environ.setdefault("WORLD_SIZE", "1")
+    os.environ.setdefault("LOCAL_RANK", "0")
+    from roboticattack_amd.attack import uada_ddp
+
+    torch.manual_seed(0)
+    np.random.seed(0)
+    att = uada_ddp.OpenVLAAttacker(vla_path=a.vla, dataset_name="synthetic", bs=8, use_wandb=False, maskidx=[0],
+                                   dataset_factory=lambda *x: (None, None))
+    assert att.fused_ddp_available()
+    out = []
+    solo = {}
+    for cfg in a.configs.split(","):
+        P, Bp = (int(v) for v in cfg.split("x"))
+        if Bp not in solo:
+            solo[Bp] = measure(att, 1, Bp, a.steps, a.warmup, a.inner, sweep=False)
+        sw = measure(att, P, Bp, a.steps, a.warmup, a.inner, sweep=True)
+        rec = dict(P=P, Bp=Bp, images=P * Bp, standalone_ms=round(solo[Bp][0], 2), P_standalone_ms=round(P * solo[Bp][0], 2),
+                   sweep_ms=round(sw[0], 2), ratio=round(sw[0] / (P * solo[Bp][0]), 3), standalone_hand_us=round(solo[Bp][1], 1),
+                   sweep_hand_us=round(sw[1], 1), sweep_hand_kernels_us={k: round(v, 1) for k, v in sorted(sw[2].items())})
+        print(json.dumps(rec), flush=True)
+        out.append(rec)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

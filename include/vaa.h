@@ -267,8 +267,8 @@ int vaa_step_epilogue_update(const float* partials, int nparts, int n, const voi
  *             statistics of group p's rows are bit for bit those of the call on group p's rows alone with the group's ordinary map (an ordinary map
  *             gives the old bits). Folds inside those calls (scalars != NULL, vaa_head_loss_rows_finish) treat the map as ONE batch: per-group
  *             scalars come from vaa_step_epilogue_seg. UPA's batch means are not per group: the segmented map serves VAA_LOSS_UADA_DDP only.
- *   vaa_step_epilogue_seg: ONE launch, vaa_step_epilogue per group: partials [P*nparts][n] (group p's nparts tiles at p*nparts: K2' with one
- *             partial per image, nparts = Bp) ->
+ *   vaa_step_epilogue_seg: ONE launch, vaa_step_epilogue per group (the same kernel: vaa_step_epilogue is its one-group case): partials
+ *             [P*nparts][n] (group p's nparts tiles at p*nparts: K2' with one partial per image, nparts = Bp) ->
  *               msg[p*n .. (p+1)*n)  = group p's fixed-order sum: bitwise vaa_step_epilogue over those nparts tiles
  *               rowmap (segmented, or an ordinary map with P = 1) != NULL: group p folded with its own map into scalars[8p .. 8p+8) and rows
  *                                    p*Bp .. of pred_tokens / pred_full_tokens [B, L-1] (VAA_LOSS_UADA_DDP; loss_ws as the K3s / K3h call left it)
@@ -278,7 +278,8 @@ int vaa_step_epilogue_update(const float* partials, int nparts, int n, const voi
  *             produced (vaa_step_epilogue_update's arithmetic); stat_part dev f64 [P][ceil(n/64)][2] or NULL: group p's per-block {sum |g|, sum g},
  *             bitwise the stat_part a standalone vaa_step_epilogue_update writes (their sums give the group's logged K4 stats).
  *   vaa_patch_update_seg: vaa_patch_update on each of P groups of n elements (patch, g, m, v [P*n]) in one launch — every group its own L1 clip
- *             and statistics, stats dev [P,2] f32 or NULL: bit for bit P separate vaa_patch_update calls (the data-parallel sweep after its all-reduce).
+ *             and statistics, stats dev [P,2] f32 or NULL: bit for bit P separate vaa_patch_update calls (the data-parallel sweep after its all-reduce;
+ *             the same kernel: vaa_patch_update is its one-group case).
  */
 size_t vaa_loss_rowmap_seg_bytes(int B, int L, int P);
 int vaa_loss_rowmap_build_seg(const int64_t* labels, int B, int L, int P, void* rowmap, size_t rowmap_bytes, void* stream);

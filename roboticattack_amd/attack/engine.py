@@ -225,21 +225,8 @@ class AttackBase:
         W = self.vla.lm_head.weight
         R = int(h.shape[0])
         if self._slice_head(R, h, W):
-            # K3s: slice logits -> statistics -> gradient slice -> d total / d hidden in ONE launch (2.1 MB of head weights); the full-vocabulary
-            # stream (K3h, 263 MB) runs behind it only on the steps whose CE / full argmax is read (`full_ce`: UADA_ddp.py:214-221)
-            hd = h.detach().contiguous()
-            o = ops.head_slice_fwd_bwd(hd, W, self._row_map, ops.LOSS_UADA_DDP, w, want_dh=True, want_scalars=False)
-            ws = ops.head_loss_rows_stats(hd, W, self._row_map, ops.LOSS_UADA_DDP, w) if full_ce else o["ws"]
-            h.backward(o["dh"])
-            upd = optimizer.fused_update_args() if optimizer is not None else None
-            if not full_ce:
-                # nobody reads this step's loss scalars (the loop reads those of the LAST inner step of an outer iteration: UADA_ddp.py:214-221):
-                # the epilogue in its pass-through form — K2's final sum (+ K4), no fold; `scalars` / the message tail keep the last read step's values
-                ops.step_epilogue(sink["partials"], msg, scalars, update=upd)
-                return None
-            _, pred_full = ops.step_epilogue(sink["partials"], msg, scalars, rowmap=self._row_map, R=R, V=int(W.shape[0]),
-                                             mode=ops.LOSS_UADA_DDP, w=w, loss_ws=ws, update=upd)
-            return pred_full
+            return self.slice_step_tail(h, self._row_map, w, int(W.shape[0]), sink, msg, scalars, full_ce,
+                                        optimizer.fused_update_args() if optimizer is not None else None)
         gsl = torch.empty((R, ops.N_ACTION), dtype=h.dtype, device=h.device)
         if self._fused_head(R, h, W):
             # SURVEY.md 8f-2 as the survey wrote it: LM head + K3 statistics in ONE weight-streaming kernel — the [R,V] logits are never written
@@ -251,6 +238,28 @@ class AttackBase:
         _, pred_full = ops.step_epilogue(sink["partials"], msg, scalars, rowmap=self._row_map, R=R, V=int(W.shape[0]),
                                          mode=ops.LOSS_UADA_DDP, w=w, loss_ws=ws,
                                          update=optimizer.fused_update_args() if optimizer is not None else None)
+        return pred_full
+
+    def slice_step_tail(self, h, rowmap, w, V, sink, msg, scalars, full_ce, update, P=None):
+        """The data-parallel UADA step after the model forward, on the K3s head: shared by fused_ddp_step (P None: vaa_step_epilogue) and the
+        maskidx sweep's sweep_step (P groups, a segmented `rowmap`: vaa_step_epilogue_seg). K3s: slice logits -> statistics -> gradient slice ->
+        d total / d hidden in ONE launch (2.1 MB of head weights); the full-vocabulary stream (K3h, 263 MB) runs behind it only on the steps whose
+        CE / full argmax is read (`full_ce`: UADA_ddp.py:214-221); the backward, which leaves K2''s partial tiles in `sink`; then ONE epilogue launch
+        (+ K4 when `update` is given)."""
+        W = self.vla.lm_head.weight
+        hd = h.detach().contiguous()
+        o = ops.head_slice_fwd_bwd(hd, W, rowmap, ops.LOSS_UADA_DDP, w, want_dh=True, want_scalars=False)
+        ws = ops.head_loss_rows_stats(hd, W, rowmap, ops.LOSS_UADA_DDP, w) if full_ce else None
+        h.backward(o["dh"])
+        partials = sink["partials"]
+        epilogue, groups = (ops.step_epilogue, ()) if P is None else (ops.step_epilogue_seg, (P,))
+        if not full_ce:
+            # nobody reads this step's loss scalars (the loop reads those of the LAST inner step of an outer iteration: UADA_ddp.py:214-221):
+            # the epilogue in its pass-through form — K2's final sum (+ K4), no fold; `scalars` keep the last read step's values
+            epilogue(partials, msg, scalars, *groups, update=update)
+            return None
+        _, pred_full = epilogue(partials, msg, scalars, *groups, rowmap=rowmap, R=int(hd.shape[0]), V=V, mode=ops.LOSS_UADA_DDP, w=w, loss_ws=ws,
+                                update=update)
         return pred_full
 
     # ---- single-GPU loops: K2's final sum + K4 as one launch after the backward ----

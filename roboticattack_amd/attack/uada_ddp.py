@@ -174,7 +174,6 @@ class OpenVLAAttacker(AttackBase):
             self._tma_target = tma_target_tokens(float(self.target_action) * torch.ones(7).numpy(), self.maskidx, self.action_tokenizer).to(dev)
         sync = vdist.PatchGradSync(patch.numel(), 4, dev)
         pick = torch.tensor([1, 2, 7, 0], dtype=torch.int64, device=dev)  # CE, w^2*MSE, UAD, total of K3's scalars
-        inv_world = 1.0 / world_size
         # UADA on a model that exposes its patch-embed weights: K2's final sum, K3's fold and the message packing are ONE launch
         fused = self.attack_type == "UADA" and self.fused_ddp_available()
         scalars = torch.zeros(8, dtype=torch.float32, device=dev)
@@ -184,61 +183,23 @@ class OpenVLAAttacker(AttackBase):
                 break
             pixel_values, labels, attention_mask, input_ids = to_dev(data, dev)
             labels = self._prepare_labels(labels)
-            s_sum = sync.buf[sync.n_grad :]
-            device_failure = None  # a library call of THIS rank reported a device-side failure (the sticky word, e.g. a hand-over that timed out)
-            for inner_loop in range(self.innerLoop):
-                exchanged = False
-                if device_failure is None:
-                    try:
-                        optimizer.zero_grad()
-                        # the loop reads the loss scalars of the LAST inner step only (UADA_ddp.py:214-221, below): the full-vocabulary CE is evaluated there
-                        full_ce = inner_loop == self.innerLoop - 1 or os.environ.get("VAA_FULL_CE_EVERY_STEP", "0") == "1"  # (=1: K3h behind K3s on every step; same patch bits)
-                        if fused and world_size == 1:  # nothing to exchange: K4 runs inside the epilogue launch (five launches per step)
-                            self.fused_ddp_step(pixel_values, patch, input_ids, attention_mask, labels, self.geometry, float(self.MSE_weights),
-                                                sync.buf, scalars, optimizer=optimizer, full_ce=full_ce)
-                            s_sum = sync.buf[sync.n_grad :]
-                            continue
-                        if fused:
-                            self.fused_ddp_step(pixel_values, patch, input_ids, attention_mask, labels, self.geometry, float(self.MSE_weights),
-                                                sync.buf, scalars, full_ce=full_ce)
-                            exchanged = True
-                            g_sum, s_sum = sync.allreduce_packed()  # C3 + C4 in one message: [grad | CE, MSE, UAD, total]
-                        else:
-                            pix = self.randomPatchTransform.apply_random_patch_batch(pixel_values, patch, mean=self.mean, std=self.std,
-                                                                                      geometry=self.geometry)
-                            total, scalars, pred = self.model_loss(input_ids, attention_mask, pix, labels, self._loss_mode(), w=float(self.MSE_weights),
-                                                                   alpha=self.alpha, beta=self.belta, full_ce=full_ce, read_scalars=full_ce)
-                            total.backward()  # K2 inside
-                            exchanged = True
-                            g_sum, s_sum = sync.allreduce_step(patch.grad, scalars, pick)
-                        optimizer.step(grad=g_sum.view_as(patch), grad_scale=inv_world)  # K4, DDP mean folded in
-                    except _lib.VaaError as e:
-                        # The failure word is sticky: every library call of this rank fails until it is polled. Raising here would leave the OTHER
-                        # ranks waiting in this step's all-reduce until the RCCL timeout: poll it now (the poll clears it), keep the
-                        # collective's cadence with a NaN message for the rest of the outer iteration, and let the all-reduced verdict below
-                        # take every rank out of the loop together.
-                        device_failure = str(e)
-                        try:
-                            ops.async_error_check()
-                        except _lib.VaaError:
-                            pass
-                if device_failure is not None and world_size > 1 and not exchanged:
-                    sync.buf.fill_(float("nan"))
-                    _, s_sum = sync.allreduce_packed()
-            scheduler.step()
-            s = (s_sum * inv_world).cpu().numpy()
-            self.assert_finite_state(patch, optimizer, s, f"{self.attack_type} (data parallel) outer iteration {i}", all_ranks=True, device_failure=device_failure)
-            # UADA_ddp.py:207,216-217: `patch.grad.mean()` AFTER DistributedDataParallel averaged the gradient, i.e. the mean of the averaged
-            # gradient (identical on every rank, so the reference's MAX all-reduce of it is the value itself): K4 reports it
-            log_patch_grad = float(optimizer.last_stats[1].item())
-            train_logdata = {"TRAIN_attack_loss(CE)": float(s[0]), "TRAIN_patch_gradient": log_patch_grad,
-                             "TRAIN_LR": optimizer.param_groups[0]["lr"], "TRAIN_attack_loss (MSE_Distance)": float(s[1]),
-                             "TRAIN_UAD": float(s[2])}
-            self.last_train_log = train_logdata
-            if rank == 0 and self.use_wandb and wandb is not None:
-                wandb.log(train_logdata, step=i)
-            if i % self.val_every == 0:
-                self.validate(i, patch, rank)
+
+            def step(inner_loop):
+                optimizer.zero_grad()
+                # the loop reads the loss scalars of the LAST inner step only (UADA_ddp.py:214-221, below): the full-vocabulary CE is evaluated there
+                full_ce = inner_loop == self.innerLoop - 1 or os.environ.get("VAA_FULL_CE_EVERY_STEP", "0") == "1"  # (=1: K3h behind K3s on every step; same patch bits)
+                if fused:  # world 1: nothing to exchange, K4 runs inside the epilogue launch (five launches per step)
+                    self.fused_ddp_step(pixel_values, patch, input_ids, attention_mask, labels, self.geometry, float(self.MSE_weights),
+                                        sync.buf, scalars, optimizer=optimizer if world_size == 1 else None, full_ce=full_ce)
+                    return None if world_size == 1 else sync.allreduce_packed  # C3 + C4 in one message: [grad | CE, MSE, UAD, total]
+                pix = self.randomPatchTransform.apply_random_patch_batch(pixel_values, patch, mean=self.mean, std=self.std, geometry=self.geometry)
+                total, sc, _ = self.model_loss(input_ids, attention_mask, pix, labels, self._loss_mode(), w=float(self.MSE_weights),
+                                               alpha=self.alpha, beta=self.belta, full_ce=full_ce, read_scalars=full_ce)
+                total.backward()  # K2 inside
+                return lambda: sync.allreduce_step(patch.grad, sc, pick)
+
+            s_sum, device_failure = self._inner_loop(optimizer, sync, world_size, step)
+            self._end_outer(i, rank, world_size, scheduler, optimizer, s_sum, device_failure, f"{self.attack_type} (data parallel) outer iteration {i}")
         return patch
 
     # ---- maskidx sweep: P patches in one loop ----
@@ -258,11 +219,9 @@ class OpenVLAAttacker(AttackBase):
         vdist.broadcast_patch(p0, src=0)
         patches = p0.unsqueeze(0).repeat(P, *([1] * p0.dim())).contiguous().requires_grad_(True)
         self.patch = patches
-        n = p0.numel()
         optimizer = SweepPatchOptimizer(patches, self.lr, "adamW")
         scheduler = CosineWarmupSchedule(optimizer, self.warmup, int(self.num_iter), 0.5)
-        sync = vdist.PatchGradSync(P * n, 4 * P, dev)
-        inv_world = 1.0 / world_size
+        sync = vdist.PatchGradSync(patches.numel(), 4 * P, dev)
         scalars = torch.zeros((P, 8), dtype=torch.float32, device=dev)
         W = self.vla.lm_head.weight
         V = int(W.shape[0])
@@ -290,46 +249,75 @@ class OpenVLAAttacker(AttackBase):
                 raise ValueError(f"maskidx sweep: K3s does not take {R} labelled rows per rank here (limit {SWEEP_MAX_ROWS} rows, bf16 head)")
             segmap = ops.LossRowMapSeg(labels_all, P)
             pack = self.vla.make_pack(am_all) if (hasattr(self.vla, "make_pack") and am_all is not None) else None
-            s_sum = sync.buf[sync.n_grad :]
-            device_failure = None
-            for inner_loop in range(self.innerLoop):
-                exchanged = False
-                if device_failure is None:
+
+            def step(inner_loop):
+                upd = optimizer.fused_update_args() if world_size == 1 else None
+                self.sweep_step(img_all, patches, ids_all, labels_all, row_index, segmap, pack, w, V, sync.buf, scalars, inner_loop == self.innerLoop - 1, upd)
+                return None if world_size == 1 else sync.allreduce_packed
+
+            s_sum, device_failure = self._inner_loop(optimizer, sync, world_size, step)
+            self._end_outer(i, rank, world_size, scheduler, optimizer, s_sum, device_failure,
+                            f"UADA maskidx sweep (data parallel) outer iteration {i}", tags=self.sweep_tags)
+        return patches
+
+    def _inner_loop(self, optimizer, sync, world_size, step):
+        """The inner steps of one outer iteration (both loops above). `step(inner_loop)` runs this rank's step up to the exchange and returns the
+        all-reduce of its message (-> gradient sum, scalar sums), or None when there is nothing to exchange (world 1: K4 ran inside the epilogue);
+        K4 then takes the rank-mean gradient (DDP's mean folded into grad_scale). Returns (the scalar sums of the last step, device_failure)."""
+        s_sum = sync.buf[sync.n_grad :]
+        inv_world = 1.0 / world_size
+        device_failure = None  # a library call of THIS rank reported a device-side failure (the sticky word, e.g. a hand-over that timed out)
+        for inner_loop in range(self.innerLoop):
+            exchanged = False
+            if device_failure is None:
+                try:
+                    exchange = step(inner_loop)
+                    if exchange is None:
+                        s_sum = sync.buf[sync.n_grad :]
+                        continue
+                    exchanged = True
+                    g_sum, s_sum = exchange()
+                    optimizer.step(grad=g_sum.view_as(optimizer.patch), grad_scale=inv_world)  # K4, DDP mean folded in
+                except _lib.VaaError as e:
+                    # The failure word is sticky: every library call of this rank fails until it is polled. Raising here would leave the OTHER
+                    # ranks waiting in this step's all-reduce until the RCCL timeout (ADVICE r5): poll it now (the poll clears it), keep the
+                    # collective's cadence with a NaN message for the rest of the outer iteration, and let the all-reduced verdict of
+                    # assert_finite_state take every rank out of the loop together.
+                    device_failure = str(e)
                     try:
-                        full_ce = inner_loop == self.innerLoop - 1
-                        upd = optimizer.fused_update_args() if world_size == 1 else None
-                        self.sweep_step(img_all, patches, ids_all, labels_all, row_index, segmap, pack, w, V, sync.buf, scalars, full_ce, upd)
-                        if world_size == 1:
-                            s_sum = sync.buf[sync.n_grad :]
-                            continue
-                        exchanged = True
-                        g_sum, s_sum = sync.allreduce_packed()
-                        optimizer.step(grad=g_sum.view_as(patches), grad_scale=inv_world)
-                    except _lib.VaaError as e:  # as in the loop above: keep the collectives' cadence, decide together below
-                        device_failure = str(e)
-                        try:
-                            ops.async_error_check()
-                        except _lib.VaaError:
-                            pass
-                if device_failure is not None and world_size > 1 and not exchanged:
-                    sync.buf.fill_(float("nan"))
-                    _, s_sum = sync.allreduce_packed()
-            scheduler.step()
-            s = (s_sum * inv_world).cpu().numpy().reshape(P, 4)
-            self.assert_finite_state(patches, optimizer, s, f"UADA maskidx sweep (data parallel) outer iteration {i}", all_ranks=True,
-                                     device_failure=device_failure)
-            stats = optimizer.last_stats.cpu().numpy()
-            lr = optimizer.param_groups[0]["lr"]
-            self.last_train_log = {}
-            for g, tag in enumerate(self.sweep_tags):
-                log = {"TRAIN_attack_loss(CE)": float(s[g, 0]), "TRAIN_patch_gradient": float(stats[g, 1]), "TRAIN_LR": lr,
-                       "TRAIN_attack_loss (MSE_Distance)": float(s[g, 1]), "TRAIN_UAD": float(s[g, 2])}
-                self.last_train_log[tag] = log
+                        ops.async_error_check()
+                    except _lib.VaaError:
+                        pass
+            if device_failure is not None and world_size > 1 and not exchanged:
+                sync.buf.fill_(float("nan"))
+                _, s_sum = sync.allreduce_packed()
+        return s_sum, device_failure
+
+    def _end_outer(self, i, rank, world_size, scheduler, optimizer, s_sum, device_failure, where, tags=None):
+        """The end of an outer iteration (both loops): schedule, the one read-back, the all-ranks finiteness verdict, the train log (one flat dict;
+        per group tag for a sweep) and the validation cadence."""
+        scheduler.step()
+        s = (s_sum * (1.0 / world_size)).cpu().numpy()
+        if tags is not None:
+            s = s.reshape(len(tags), 4)
+        self.assert_finite_state(optimizer.patch, optimizer, s, where, all_ranks=True, device_failure=device_failure)
+        # UADA_ddp.py:207,216-217: `patch.grad.mean()` AFTER DistributedDataParallel averaged the gradient, i.e. the mean of the averaged
+        # gradient (identical on every rank, so the reference's MAX all-reduce of it is the value itself): K4 reports it
+        stats = optimizer.last_stats.cpu().numpy().reshape(-1, 2)
+        lr = optimizer.param_groups[0]["lr"]
+        logs = [{"TRAIN_attack_loss(CE)": float(sg[0]), "TRAIN_patch_gradient": float(st[1]), "TRAIN_LR": lr,
+                 "TRAIN_attack_loss (MSE_Distance)": float(sg[1]), "TRAIN_UAD": float(sg[2])} for sg, st in zip(s.reshape(-1, 4), stats)]
+        if tags is None:
+            self.last_train_log = logs[0]
+            if rank == 0 and self.use_wandb and wandb is not None:
+                wandb.log(logs[0], step=i)
+        else:
+            self.last_train_log = dict(zip(tags, logs))
+            for tag, log in self.last_train_log.items():
                 if rank == 0 and self.use_wandb and wandb is not None:
                     wandb.log({f"{tag}/{k}": v for k, v in log.items()}, step=i)
-            if i % self.val_every == 0:
-                self.validate_sweep(i, patches, rank)
-        return patches
+        if i % self.val_every == 0:
+            (self.validate if tags is None else self.validate_sweep)(i, optimizer.patch, rank)
 
     def sweep_step(self, img_all, patches, input_ids, labels_all, row_index, segmap, pack, w, V, msg, scalars, full_ce, update=None):
         """One inner step of the sweep up to the exchange: K1 (one draw per frame, every group) -> body over P*bs images -> K3s (segmented map: each
@@ -338,26 +326,13 @@ class OpenVLAAttacker(AttackBase):
         sink = {}
         pe = self.randomPatchTransform.apply_sweep_batch(img_all, patches, self.mean, self.std, self.geometry, sink)
         h = self.vla.hidden_rows(input_ids, None, row_index, patch_embeds=pe, pack=pack)
-        W = self.vla.lm_head.weight
-        hd = h.detach().contiguous()
-        o = ops.head_slice_fwd_bwd(hd, W, segmap, ops.LOSS_UADA_DDP, w, want_dh=True, want_scalars=False)
-        ws = ops.head_loss_rows_stats(hd, W, segmap, ops.LOSS_UADA_DDP, w) if full_ce else None
-        h.backward(o["dh"])
-        P = int(patches.shape[0])
-        if not full_ce:
-            ops.step_epilogue_seg(sink["partials"], msg, scalars, P, update=update)
-            return None
-        _, pred_full = ops.step_epilogue_seg(sink["partials"], msg, scalars, P, rowmap=segmap, R=int(hd.shape[0]), V=V, mode=ops.LOSS_UADA_DDP, w=w,
-                                             loss_ws=ws, update=update)
-        return pred_full
+        return self.slice_step_tail(h, segmap, w, V, sink, msg, scalars, full_ce, update, P=int(patches.shape[0]))
 
     def validate_sweep(self, i, patches, rank):
         """validate() per group: every validation batch is drawn ONCE (the RNG consumption of one standalone pass) and evaluated with each group's
         patch and labels; per group the averages, the AVG all-reduces, best-patch selection and the files under save_dir/<group tag>/."""
-        P = len(self.maskidx_sweep)
-        sums = np.zeros((P, 3))  # MSE, UAD, CE
-        rbs = [ValReadback(self.val_batches, self.device) for _ in range(P)]
-        last_images = [None] * P
+        rbs = [ValReadback(self.val_batches, self.device) for _ in self.maskidx_sweep]
+        last_images = [None] * len(rbs)
         ph, pw = int(patches.shape[2]), int(patches.shape[3])
         with torch.no_grad():
             for j, data in enumerate(self.val_loader):
@@ -375,32 +350,7 @@ class OpenVLAAttacker(AttackBase):
                     last_images[g] = modified
         self.last_val_log = {}
         for g, tag in enumerate(self.sweep_tags):
-            host, _ = rbs[g].read()
-            a_mse = a_uad = a_ce = 0.0
-            for s in host:
-                a_mse += float(np.float32(s[2]))
-                a_uad += float(np.float32(s[7]))
-                a_ce += float(np.float32(s[1]))
-            a_mse /= self.val_batches
-            a_uad /= self.val_batches
-            a_ce /= self.val_batches
-            g_MSE = vdist.allreduce_scalar(a_mse, "AVG", self.device)
-            g_UAD = vdist.allreduce_scalar(a_uad, "AVG", self.device)
-            g_CE = vdist.allreduce_scalar(a_ce, "AVG", self.device)
-            self.last_val_log[tag] = {"VAL_MSE_Distance": g_MSE, "VAL_UAD": g_UAD}
-            if rank == 0:
-                if g_MSE < self.MSE_Distance_best[tag]:
-                    self.MSE_Distance_best[tag] = g_MSE
-                    d = self.save_patch(patches[g], os.path.join(tag, str(i)))
-                    _, pil = self.save_val_images(last_images[g], d)
-                    if self.use_wandb and wandb is not None:
-                        wandb.log({f"{tag}/{k}": v for k, v in self.last_val_log[tag].items()}, step=i)
-                        wandb.log({f"{tag}/AdvImg": [wandb.Image(p) for p in pil]})
-                d = self.save_patch(patches[g], os.path.join(tag, "last"))
-                os.makedirs(os.path.join(d, "val_related_data"), exist_ok=True)
-                self.val_CE_loss[tag].append(g_CE)
-                self.val_MSE_Distance[tag].append(g_MSE)
-                self.val_UAD[tag].append(g_UAD)
+            self.last_val_log[tag] = self._val_record(i, rank, rbs[g].read()[0], 2, patches[g], last_images[g], tag)
 
     def _loss_mode(self):
         return {"UADA": ops.LOSS_UADA_DDP, "UPA": ops.LOSS_UPA, "TMA": ops.LOSS_CE}[self.attack_type]
@@ -416,7 +366,6 @@ class OpenVLAAttacker(AttackBase):
 
     def validate(self, i, patch, rank):
         """UADA_ddp.py:233-324: 100 local val batches, 3 scalar all-reduces (C5), rank 0 writes the files."""
-        avg_CE = avg_MSE = avg_UAD = 0.0
         modified_images = None
         rb = ValReadback(self.val_batches, self.device)  # one read-back behind the last batch instead of one per batch
         with torch.no_grad():
@@ -430,9 +379,16 @@ class OpenVLAAttacker(AttackBase):
                 _, scalars, _ = self.model_loss(input_ids, attention_mask, modified_images, labels, self._loss_mode(),
                                                 w=float(self.MSE_weights), alpha=self.alpha, beta=self.belta, need_grad=False)
                 rb.add(scalars)
-        host, _ = rb.read()
+        # selection metric: MSE distance (UADA) or the attack loss
+        self.last_val_log = self._val_record(i, rank, rb.read()[0], 2 if self.attack_type == "UADA" else 0, patch, modified_images)
+
+    def _val_record(self, i, rank, host, metric, patch, images, tag=None):
+        """What validate() does with the scalars of its batches — the run's or, with a sweep group's `tag`, that group's (containers keyed by
+        the tag, files under save_dir/<tag>/): the averages, the 3 AVG all-reduces, best-patch selection, the saved patches and the lists.
+        `metric`: the scalar the selection averages. Returns the validation log."""
+        avg_CE = avg_MSE = avg_UAD = 0.0
         for s in host:
-            avg_MSE += float(np.float32(s[2] if self.attack_type == "UADA" else s[0]))  # selection metric: MSE distance (UADA) or the attack loss
+            avg_MSE += float(np.float32(s[metric]))
             avg_UAD += float(np.float32(s[7]))
             avg_CE += float(np.float32(s[1]))
         avg_MSE /= self.val_batches
@@ -441,20 +397,25 @@ class OpenVLAAttacker(AttackBase):
         g_MSE = vdist.allreduce_scalar(avg_MSE, "AVG", self.device)
         g_UAD = vdist.allreduce_scalar(avg_UAD, "AVG", self.device)
         g_CE = vdist.allreduce_scalar(avg_CE, "AVG", self.device)
-        self.last_val_log = {"VAL_MSE_Distance": g_MSE, "VAL_UAD": g_UAD}
+        log = {"VAL_MSE_Distance": g_MSE, "VAL_UAD": g_UAD}
         if rank == 0:
-            if g_MSE < self.MSE_Distance_best:
-                self.MSE_Distance_best = g_MSE
-                d = self.save_patch(patch, f"{str(i)}")
-                _, pil = self.save_val_images(modified_images, d)
+            pre = "" if tag is None else f"{tag}/"
+            best = self.MSE_Distance_best if tag is None else self.MSE_Distance_best[tag]
+            if g_MSE < best:
+                if tag is None:
+                    self.MSE_Distance_best = g_MSE
+                else:
+                    self.MSE_Distance_best[tag] = g_MSE
+                d = self.save_patch(patch, pre + str(i))
+                _, pil = self.save_val_images(images, d)
                 if self.use_wandb and wandb is not None:
-                    wandb.log(self.last_val_log, step=i)
-                    wandb.log({"AdvImg": [wandb.Image(p) for p in pil]})
-            d = self.save_patch(patch, "last")
+                    wandb.log({pre + k: v for k, v in log.items()}, step=i)
+                    wandb.log({pre + "AdvImg": [wandb.Image(p) for p in pil]})
+            d = self.save_patch(patch, pre + "last")
             os.makedirs(os.path.join(d, "val_related_data"), exist_ok=True)
-            self.val_CE_loss.append(g_CE)
-            self.val_MSE_Distance.append(g_MSE)
-            self.val_UAD.append(g_UAD)
+            for lst, v in ((self.val_CE_loss, g_CE), (self.val_MSE_Distance, g_MSE), (self.val_UAD, g_UAD)):
+                (lst if tag is None else lst[tag]).append(v)
+        return log
 
     @classmethod
     def run(cls, **instance_params):

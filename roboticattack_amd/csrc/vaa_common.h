@@ -8,6 +8,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
@@ -175,6 +176,19 @@ struct UpdArgs {
     int n, mode;
     float lr, b1, b2, eps, step_size, one_m_b1, one_m_b2, l1_clip, grad_scale;
 };
+
+// The scalar part of UpdArgs (the caller sets the pointers and n): the reference optimiser's python-side doubles, narrowed to f32 exactly where
+// torch narrows them. The one builder of every K4 entry point (vaa_patch_update[_seg], vaa_step_epilogue[_seg]_update): one source, same bits.
+inline UpdArgs upd_args(int mode, float lr, float beta1, float beta2, float eps, int step, float l1_clip, float grad_scale) {
+    UpdArgs a = {};
+    a.mode = mode;
+    a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.l1_clip = l1_clip; a.grad_scale = grad_scale;
+    const double b1 = (double)beta1, b2 = (double)beta2;
+    a.one_m_b1 = (float)(1.0 - b1);
+    a.one_m_b2 = (float)(1.0 - b2);
+    a.step_size = (mode == VAA_OPT_ADAMW_HF) ? (float)((double)lr * sqrt(1.0 - pow(b2, (double)step)) / (1.0 - pow(b1, (double)step))) : 0.0f;
+    return a;
+}
 
 __device__ __forceinline__ float update_one(const UpdArgs& a, float g, float p, float& m, float& v) {
     if (a.mode == VAA_OPT_ADAMW_HF) {

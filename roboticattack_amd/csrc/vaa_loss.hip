@@ -865,55 +865,86 @@ __global__ __launch_bounds__(kRowsT) void rows_finish_kernel(RowsArgs a, int gsp
     }
 }
 
-// Step epilogue (vaa_step_epilogue): ONE launch between the backward and the gradient exchange.
-//   workgroups 0 .. nred-1 : msg[e] = sum over K2's partial tiles, the fixed order of patch_grad_reduce_kernel (bitwise the same result)
-//   workgroup  nred        : K3's statistics folded into scalars[8] + the prediction maps (what rows_finish_kernel does in the slice modes
-//                            whose gradient does not wait for it), then the tail of the sync message msg[n..n+4) = {CE, w^2*MSE, UAD, total}
+// Step epilogue (vaa_step_epilogue[_seg]): ONE launch between the backward and the gradient exchange, over P gradients of n elements (the
+// standalone step is P = 1; a maskidx sweep has one group per patch).
+//   workgroup blk < P*nred : msg[g*n + e] = sum over group g = blk / nred's partial tiles for its block of 64 elements, the fixed order of
+//                            patch_grad_reduce_kernel (bitwise the same result), and — fused update — K4 on them with the group's patch / m / v
+//   workgroup P*nred + g   : K3's statistics of group g folded into scalars[8g..] + the prediction maps (what rows_finish_kernel does in the
+//                            slice modes whose gradient does not wait for it), then the group's message tail msg[P*n + 4g ..] = {CE, w^2*MSE,
+//                            UAD, total}. Pass-through form (no row map): the tail is scalars_in[1,2,7,0] of an earlier fold, or zeros when
+//                            scalars_in is null (a sweep: a SUM all-reduce of stale scalars would grow them by world^steps).
 struct EpiArgs {
     const float* partials;
     float* msg;
-    const float* scalars_in;  // fold == 0: final scalars of an earlier vaa_loss_rows_fwd_bwd, only copied into the message
-    int n, nparts, nred, fold;
+    const float* scalars_in;  // pass-through form: final scalars copied into the tail (nullptr: zero tail)
+    int n, nparts, nred, P, fold;
+    int seg;                  // the fold reads the row map's header for its groups (vaa_step_epilogue_seg); 0: the map is folded as is, R rows
     int fuse_update;          // single-GPU step: K4's per-element update applied right where the gradient element is produced
     UpdArgs upd;
-    double* stat_part;        // fuse_update: [nred][2] = {sum |g|, sum g} over the block's 64 elements (the caller adds them for the log)
+    double* stat_part;        // fuse_update: [P*nred][2] = {sum |g|, sum g} over the block's 64 elements (the caller adds them for the log)
 };
 
 __global__ __launch_bounds__(256) void step_epilogue_kernel(EpiArgs e, RowsArgs a) {
     __shared__ double sl[16][16][4];
-    if ((int)blockIdx.x < e.nred) {
+    const int blk = (int)blockIdx.x;
+    if (blk < e.P * e.nred) {
+        const int g = blk / e.nred, lb = blk - g * e.nred;
+        const size_t off = (size_t)g * e.n;
         int oe = 0;
-        float g = 0.0f;
-        const bool own = partial_reduce_block(e.partials, e.msg, e.n, e.nparts, blockIdx.x, sl, oe, g);
+        float gv = 0.0f;
+        const bool own = partial_reduce_block(e.partials + (size_t)g * e.nparts * e.n, e.msg + off, e.n, e.nparts, lb, sl, oe, gv);
         if (!e.fuse_update) return;
         // K4 on the element this thread just produced (grad_scale = 1, no L1 clip: vaa_step_epilogue_update checks): same arithmetic, same bits
         if (own) {
-            float m = e.upd.mode == VAA_OPT_ADAMW_HF ? e.upd.m[oe] : 0.0f, v = e.upd.mode == VAA_OPT_ADAMW_HF ? e.upd.v[oe] : 0.0f;
-            const float p = update_one(e.upd, g, e.upd.patch[oe], m, v);
-            if (e.upd.mode == VAA_OPT_ADAMW_HF) { e.upd.m[oe] = m; e.upd.v[oe] = v; }
-            e.upd.patch[oe] = p;
+            const bool adam = e.upd.mode == VAA_OPT_ADAMW_HF;
+            float m = adam ? e.upd.m[off + oe] : 0.0f, v = adam ? e.upd.v[off + oe] : 0.0f;
+            const float p = update_one(e.upd, gv, e.upd.patch[off + oe], m, v);
+            if (adam) { e.upd.m[off + oe] = m; e.upd.v[off + oe] = v; }
+            e.upd.patch[off + oe] = p;
         }
         if (e.stat_part) {  // the owners are threads 0..63 (slices 0..3 x 16 quads) = wave 0
-            double sa = own ? fabs((double)g) : 0.0, ss = own ? (double)g : 0.0;
+            double sa = own ? fabs((double)gv) : 0.0, ss = own ? (double)gv : 0.0;
             if (threadIdx.x < 64) {
                 sa = wave_sum(sa);
                 ss = wave_sum(ss);
-                if (threadIdx.x == 0) { e.stat_part[2 * blockIdx.x] = sa; e.stat_part[2 * blockIdx.x + 1] = ss; }
+                if (threadIdx.x == 0) { e.stat_part[2 * blk] = sa; e.stat_part[2 * blk + 1] = ss; }
             }
         }
         return;
     }
-    float* tail = e.msg + e.n;
-    if (e.fold) {
-        double (*sh)[7] = reinterpret_cast<double (*)[7]>(&sl[0][0][0]);
-        const FoldOut f = rows_fold<256>(a, true, sh);
-        if (threadIdx.x == 0) {
-            const bool ok = a.rowmap[0] == a.R;
-            tail[0] = (float)f.CE; tail[1] = (float)f.MSE; tail[2] = (float)f.UAD;
-            tail[3] = ok ? (float)f.total : __uint_as_float(0x7fc00000u);
+    const int g = blk - e.P * e.nred;
+    float* tail = e.msg + (size_t)e.P * e.n + 4 * g;
+    if (!e.fold) {
+        if (threadIdx.x < 4) {
+            const int src = threadIdx.x == 3 ? 0 : (threadIdx.x == 2 ? 7 : (int)threadIdx.x + 1);  // CE, w^2*MSE, UAD, total
+            tail[threadIdx.x] = e.scalars_in ? e.scalars_in[src] : 0.0f;
         }
-    } else if (threadIdx.x == 0) {
-        tail[0] = e.scalars_in[1]; tail[1] = e.scalars_in[2]; tail[2] = e.scalars_in[7]; tail[3] = e.scalars_in[0];
+        return;
+    }
+    RowsArgs ag = a;
+    if (e.seg) {  // group g's view: its own map, its rows of the statistics, its images of the prediction maps, its scalars
+        const int* map = a.rowmap;
+        const int Pm = map[2], Bp = a.B / e.P;
+        const bool total_ok = map[0] == a.R && (Pm == e.P || (Pm == 0 && e.P == 1));
+        int r0 = 0;
+        if (Pm > 0 && g < Pm) {
+            r0 = map[rowmap_seg_table(a.B, a.L) + 4 * g];
+            ag.rowmap = map + rowmap_seg_sub(a.B, a.L, Pm, g);
+        }
+        ag.R = total_ok ? ag.rowmap[0] : -1;  // a map of another batch than the caller states: rows_fold publishes NaN and never reads it
+        ag.B = Bp;
+        ag.part = a.part + (size_t)r0 * a.split;
+        ag.slice = a.slice + r0;
+        ag.scalars = a.scalars + 8 * g;
+        if (a.pred_tokens) ag.pred_tokens = a.pred_tokens + (size_t)g * Bp * (a.L - 1);
+        if (a.pred_full) ag.pred_full = a.pred_full + (size_t)g * Bp * (a.L - 1);
+    }
+    double (*sh)[7] = reinterpret_cast<double (*)[7]>(&sl[0][0][0]);
+    const FoldOut f = rows_fold<256>(ag, true, sh);
+    if (threadIdx.x == 0) {
+        const bool ok = ag.rowmap[0] == ag.R;
+        tail[0] = (float)f.CE; tail[1] = (float)f.MSE; tail[2] = (float)f.UAD;
+        tail[3] = ok ? (float)f.total : __uint_as_float(0x7fc00000u);
     }
 }
 
@@ -1302,46 +1333,49 @@ extern "C" int vaa_loss_rows_stats(const void* logits, int dtype, const void* ro
 
 namespace vaa {
 
-static int step_epilogue_impl(const char* who, const float* partials, int nparts, int n, const void* rowmap, int R, int B, int L, int V, int mode,
-                              const float* params, const void* loss_ws, size_t loss_ws_bytes, float* scalars, int32_t* pred_tokens,
+// vaa_step_epilogue[_update] (seg = 0: P = 1, the row map folded as is, any loss mode; the pass-through tail copies `scalars`) and
+// vaa_step_epilogue_seg[_update] (seg = 1: P groups, each folded with its own part of a segmented map, VAA_LOSS_UADA_DDP; a zero pass-through tail)
+static int step_epilogue_impl(const char* who, bool seg, const float* partials, int nparts, int n, int P, const void* rowmap, int R, int B, int L,
+                              int V, int mode, const float* params, const void* loss_ws, size_t loss_ws_bytes, float* scalars, int32_t* pred_tokens,
                               int32_t* pred_full_tokens, float* msg, const UpdArgs* upd, double* stat_part, void* stream) {
-    if (!partials || !msg || !scalars || nparts <= 0 || n <= 0) {
-        set_error("%s: bad arguments (nparts=%d n=%d)", who, nparts, n);
+    if (!partials || !msg || (!seg && !scalars) || nparts <= 0 || n <= 0 || P <= 0 || P > 512) {
+        set_error("%s: bad arguments (nparts=%d n=%d P=%d)", who, nparts, n, P);
         return VAA_E_INVALID;
     }
+    if ((long)P * n > (1l << 30)) {
+        set_error("%s: %d groups of %d elements exceed the launch", who, P, n);
+        return VAA_E_UNSUPPORTED;
+    }
     EpiArgs e = {};
-    e.partials = partials; e.msg = msg; e.scalars_in = scalars; e.n = n; e.nparts = nparts; e.nred = (n + 63) / 64; e.fold = rowmap ? 1 : 0;
-    e.fuse_update = upd ? 1 : 0;
+    e.partials = partials; e.msg = msg; e.scalars_in = seg ? nullptr : scalars; e.n = n; e.nparts = nparts; e.nred = (n + 63) / 64; e.P = P;
+    e.fold = rowmap ? 1 : 0; e.seg = seg ? 1 : 0; e.fuse_update = upd ? 1 : 0;
     if (upd) e.upd = *upd;
     e.stat_part = stat_part;
     RowsArgs a = {};
     if (rowmap) {
+        if (seg && (!scalars || B <= 0 || B % P != 0)) {
+            set_error("%s: the fold needs scalars [P,8] and B (%d) a multiple of P (%d)", who, B, P);
+            return VAA_E_INVALID;
+        }
+        if (seg && mode != VAA_LOSS_UADA_DDP) {
+            set_error("%s: mode %d — a maskidx sweep folds VAA_LOSS_UADA_DDP only", who, mode);
+            return VAA_E_UNSUPPORTED;
+        }
         int rc = rows_args(who, nullptr, VAA_DTYPE_BF16, rowmap, R, B, L, V, mode, params, scalars, pred_tokens, pred_full_tokens, nullptr, VAA_GRAD_SLICE,
                            const_cast<void*>(loss_ws), loss_ws_bytes, a);
         if (rc != VAA_OK) return rc;
     }
-    VAA_LAUNCH(step_epilogue_kernel, dim3((unsigned)(e.nred + 1)), dim3(256), 0, (hipStream_t)stream, e, a);
+    VAA_LAUNCH(step_epilogue_kernel, dim3((unsigned)(P * e.nred + P)), dim3(256), 0, (hipStream_t)stream, e, a);
     return check_launch(who);
-}
-
-}  // namespace vaa
-
-extern "C" int vaa_step_epilogue(const float* partials, int nparts, int n, const void* rowmap, int R, int B, int L, int V, int mode,
-                                 const float* params, const void* loss_ws, size_t loss_ws_bytes, float* scalars, int32_t* pred_tokens,
-                                 int32_t* pred_full_tokens, float* msg, void* stream) {
-    return vaa::step_epilogue_impl("vaa_step_epilogue", partials, nparts, n, rowmap, R, B, L, V, mode, params, loss_ws, loss_ws_bytes, scalars, pred_tokens,
-                                   pred_full_tokens, msg, nullptr, nullptr, stream);
 }
 
 // The single-GPU step has no exchange between the gradient and the update: K4 (vaa_patch_update without L1 clip, grad_scale = 1) is applied by
 // the epilogue on every gradient element as it is produced — same per-element arithmetic, same bits in patch / m / v. The logged statistics come
-// back as per-block partial sums stat_part [ceil(n/64)][2] = {sum |g|, sum g} (fp64) for the caller to add.
-extern "C" int vaa_step_epilogue_update(const float* partials, int nparts, int n, const void* rowmap, int R, int B, int L, int V, int mode,
-                                        const float* params, const void* loss_ws, size_t loss_ws_bytes, float* scalars, int32_t* pred_tokens,
-                                        int32_t* pred_full_tokens, float* msg, float* patch, float* m, float* v, int opt_mode, float lr, float beta1,
-                                        float beta2, float eps, int step, double* stat_part, void* stream) {
-    using namespace vaa;
-    const char* who = "vaa_step_epilogue_update";
+// back as per-block partial sums stat_part [P*ceil(n/64)][2] = {sum |g|, sum g} (fp64) for the caller to add.
+static int step_epilogue_update(const char* who, bool seg, const float* partials, int nparts, int n, int P, const void* rowmap, int R, int B, int L,
+                                int V, int mode, const float* params, const void* loss_ws, size_t loss_ws_bytes, float* scalars, int32_t* pred_tokens,
+                                int32_t* pred_full_tokens, float* msg, float* patch, float* m, float* v, int opt_mode, float lr, float beta1,
+                                float beta2, float eps, int step, double* stat_part, void* stream) {
     if (!patch || (opt_mode == VAA_OPT_ADAMW_HF && (!m || !v))) {
         set_error("%s: null pointer argument", who);
         return VAA_E_INVALID;
@@ -1350,15 +1384,27 @@ extern "C" int vaa_step_epilogue_update(const float* partials, int nparts, int n
         set_error("%s: bad optimiser mode/step (mode=%d step=%d)", who, opt_mode, step);
         return VAA_E_INVALID;
     }
-    UpdArgs u = {};
-    u.patch = patch; u.g = nullptr; u.m = m; u.v = v; u.stats = nullptr; u.n = n; u.mode = opt_mode;
-    u.lr = lr; u.b1 = beta1; u.b2 = beta2; u.eps = eps; u.l1_clip = 0.0f; u.grad_scale = 1.0f;
-    const double b1 = (double)beta1, b2 = (double)beta2;  // python-side doubles of the reference optimiser, narrowed exactly like vaa_patch_update
-    u.one_m_b1 = (float)(1.0 - b1);
-    u.one_m_b2 = (float)(1.0 - b2);
-    u.step_size = (opt_mode == VAA_OPT_ADAMW_HF) ? (float)((double)lr * sqrt(1.0 - pow(b2, (double)step)) / (1.0 - pow(b1, (double)step))) : 0.0f;
-    return step_epilogue_impl(who, partials, nparts, n, rowmap, R, B, L, V, mode, params, loss_ws, loss_ws_bytes, scalars, pred_tokens,
+    UpdArgs u = upd_args(opt_mode, lr, beta1, beta2, eps, step, 0.0f, 1.0f);
+    u.patch = patch; u.m = m; u.v = v; u.n = n;
+    return step_epilogue_impl(who, seg, partials, nparts, n, P, rowmap, R, B, L, V, mode, params, loss_ws, loss_ws_bytes, scalars, pred_tokens,
                               pred_full_tokens, msg, &u, stat_part, stream);
+}
+
+}  // namespace vaa
+
+extern "C" int vaa_step_epilogue(const float* partials, int nparts, int n, const void* rowmap, int R, int B, int L, int V, int mode,
+                                 const float* params, const void* loss_ws, size_t loss_ws_bytes, float* scalars, int32_t* pred_tokens,
+                                 int32_t* pred_full_tokens, float* msg, void* stream) {
+    return vaa::step_epilogue_impl("vaa_step_epilogue", false, partials, nparts, n, 1, rowmap, R, B, L, V, mode, params, loss_ws, loss_ws_bytes, scalars,
+                                   pred_tokens, pred_full_tokens, msg, nullptr, nullptr, stream);
+}
+
+extern "C" int vaa_step_epilogue_update(const float* partials, int nparts, int n, const void* rowmap, int R, int B, int L, int V, int mode,
+                                        const float* params, const void* loss_ws, size_t loss_ws_bytes, float* scalars, int32_t* pred_tokens,
+                                        int32_t* pred_full_tokens, float* msg, float* patch, float* m, float* v, int opt_mode, float lr, float beta1,
+                                        float beta2, float eps, int step, double* stat_part, void* stream) {
+    return vaa::step_epilogue_update("vaa_step_epilogue_update", false, partials, nparts, n, 1, rowmap, R, B, L, V, mode, params, loss_ws, loss_ws_bytes,
+                                     scalars, pred_tokens, pred_full_tokens, msg, patch, m, v, opt_mode, lr, beta1, beta2, eps, step, stat_part, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -1398,112 +1444,6 @@ __global__ __launch_bounds__(1024) void loss_rowmap_seg_kernel(int B, int L, int
     }
 }
 
-// Step epilogue over P groups (vaa_step_epilogue_seg[_update]): workgroup blk < P*nred sums group blk / nred's partial tiles for its block of 64
-// elements (partial_reduce_block over that group's nparts tiles: the standalone epilogue's order and bits) and — fused update — applies K4 to
-// them with the group's patch / m / v; workgroup P*nred + g folds group g with the group's own row map (rows_fold: the standalone fold's bits)
-// and writes the group's tail msg[P*n + 4g ..] (zeros in the pass-through form: a SUM all-reduce of stale scalars would grow them by world^steps).
-struct EpiSegArgs {
-    EpiArgs e;      // partials / msg / n / nparts / nred / fold / fuse_update / upd / stat_part of the WHOLE sweep
-    int P, Bp, L, R;
-};
-
-__global__ __launch_bounds__(256) void step_epilogue_seg_kernel(EpiSegArgs s, RowsArgs a) {
-    __shared__ double sl[16][16][4];
-    const EpiArgs& e = s.e;
-    const int blk = (int)blockIdx.x;
-    if (blk < s.P * e.nred) {
-        const int g = blk / e.nred, lb = blk - g * e.nred;
-        const size_t off = (size_t)g * e.n;
-        int oe = 0;
-        float gv = 0.0f;
-        const bool own = partial_reduce_block(e.partials + (size_t)g * e.nparts * e.n, e.msg + off, e.n, e.nparts, lb, sl, oe, gv);
-        if (!e.fuse_update) return;
-        if (own) {
-            const bool adam = e.upd.mode == VAA_OPT_ADAMW_HF;
-            float m = adam ? e.upd.m[off + oe] : 0.0f, v = adam ? e.upd.v[off + oe] : 0.0f;
-            const float p = update_one(e.upd, gv, e.upd.patch[off + oe], m, v);
-            if (adam) { e.upd.m[off + oe] = m; e.upd.v[off + oe] = v; }
-            e.upd.patch[off + oe] = p;
-        }
-        if (e.stat_part) {
-            double sa = own ? fabs((double)gv) : 0.0, ss = own ? (double)gv : 0.0;
-            if (threadIdx.x < 64) {
-                sa = wave_sum(sa);
-                ss = wave_sum(ss);
-                if (threadIdx.x == 0) { e.stat_part[2 * blk] = sa; e.stat_part[2 * blk + 1] = ss; }
-            }
-        }
-        return;
-    }
-    const int g = blk - s.P * e.nred;
-    float* tail = e.msg + (size_t)s.P * e.n + 4 * g;
-    if (!e.fold) {
-        if (threadIdx.x < 4) tail[threadIdx.x] = 0.0f;
-        return;
-    }
-    // group g's view: its own map, its rows of the statistics, its images of the prediction maps, its scalars
-    const int* map = a.rowmap;
-    const int Pm = map[2];
-    const bool total_ok = map[0] == s.R && (Pm == s.P || (Pm == 0 && s.P == 1));
-    RowsArgs ag = a;
-    int r0 = 0;
-    if (Pm > 0 && g < Pm) {
-        const int T = rowmap_seg_table(a.B, s.L);
-        r0 = map[T + 4 * g];
-        ag.rowmap = map + rowmap_seg_sub(a.B, s.L, Pm, g);
-    }
-    ag.R = total_ok ? ag.rowmap[0] : -1;  // a map of another batch than the caller states: rows_fold publishes NaN and never reads it
-    ag.B = s.Bp;
-    ag.part = a.part + (size_t)r0 * a.split;
-    ag.slice = a.slice + r0;
-    ag.scalars = a.scalars + 8 * g;
-    if (a.pred_tokens) ag.pred_tokens = a.pred_tokens + (size_t)g * s.Bp * (s.L - 1);
-    if (a.pred_full) ag.pred_full = a.pred_full + (size_t)g * s.Bp * (s.L - 1);
-    double (*sh)[7] = reinterpret_cast<double (*)[7]>(&sl[0][0][0]);
-    const FoldOut f = rows_fold<256>(ag, true, sh);
-    if (threadIdx.x == 0) {
-        const bool ok = ag.rowmap[0] == ag.R;
-        tail[0] = (float)f.CE; tail[1] = (float)f.MSE; tail[2] = (float)f.UAD;
-        tail[3] = ok ? (float)f.total : __uint_as_float(0x7fc00000u);
-    }
-}
-
-static int step_epilogue_seg_impl(const char* who, const float* partials, int nparts, int n, int P, const void* rowmap, int R, int B, int L, int V,
-                                  int mode, const float* params, const void* loss_ws, size_t loss_ws_bytes, float* scalars, int32_t* pred_tokens,
-                                  int32_t* pred_full_tokens, float* msg, const UpdArgs* upd, double* stat_part, void* stream) {
-    if (!partials || !msg || nparts <= 0 || n <= 0 || P <= 0 || P > 512) {
-        set_error("%s: bad arguments (nparts=%d n=%d P=%d)", who, nparts, n, P);
-        return VAA_E_INVALID;
-    }
-    if ((long)P * n > (1l << 30)) {
-        set_error("%s: %d groups of %d elements exceed the launch", who, P, n);
-        return VAA_E_UNSUPPORTED;
-    }
-    EpiSegArgs s = {};
-    s.e.partials = partials; s.e.msg = msg; s.e.scalars_in = nullptr; s.e.n = n; s.e.nparts = nparts; s.e.nred = (n + 63) / 64;
-    s.e.fold = rowmap ? 1 : 0; s.e.fuse_update = upd ? 1 : 0;
-    if (upd) s.e.upd = *upd;
-    s.e.stat_part = stat_part;
-    s.P = P; s.L = L; s.R = R;
-    RowsArgs a = {};
-    if (rowmap) {
-        if (!scalars || B <= 0 || B % P != 0) {
-            set_error("%s: the fold needs scalars [P,8] and B (%d) a multiple of P (%d)", who, B, P);
-            return VAA_E_INVALID;
-        }
-        if (mode != VAA_LOSS_UADA_DDP) {
-            set_error("%s: mode %d — a maskidx sweep folds VAA_LOSS_UADA_DDP only", who, mode);
-            return VAA_E_UNSUPPORTED;
-        }
-        int rc = rows_args(who, nullptr, VAA_DTYPE_BF16, rowmap, R, B, L, V, mode, params, scalars, pred_tokens, pred_full_tokens, nullptr, VAA_GRAD_SLICE,
-                           const_cast<void*>(loss_ws), loss_ws_bytes, a);
-        if (rc != VAA_OK) return rc;
-        s.Bp = B / P;
-    }
-    VAA_LAUNCH(step_epilogue_seg_kernel, dim3((unsigned)(P * s.e.nred + P)), dim3(256), 0, (hipStream_t)stream, s, a);
-    return check_launch(who);
-}
-
 }  // namespace vaa
 
 extern "C" size_t vaa_loss_rowmap_seg_bytes(int B, int L, int P) {
@@ -1540,31 +1480,15 @@ extern "C" int vaa_loss_rowmap_build_seg(const int64_t* labels, int B, int L, in
 extern "C" int vaa_step_epilogue_seg(const float* partials, int nparts, int n, int P, const void* rowmap, int R, int B, int L, int V, int mode,
                                      const float* params, const void* loss_ws, size_t loss_ws_bytes, float* scalars, int32_t* pred_tokens,
                                      int32_t* pred_full_tokens, float* msg, void* stream) {
-    return vaa::step_epilogue_seg_impl("vaa_step_epilogue_seg", partials, nparts, n, P, rowmap, R, B, L, V, mode, params, loss_ws, loss_ws_bytes, scalars,
-                                       pred_tokens, pred_full_tokens, msg, nullptr, nullptr, stream);
+    return vaa::step_epilogue_impl("vaa_step_epilogue_seg", true, partials, nparts, n, P, rowmap, R, B, L, V, mode, params, loss_ws, loss_ws_bytes, scalars,
+                                   pred_tokens, pred_full_tokens, msg, nullptr, nullptr, stream);
 }
 
 extern "C" int vaa_step_epilogue_seg_update(const float* partials, int nparts, int n, int P, const void* rowmap, int R, int B, int L, int V, int mode,
                                             const float* params, const void* loss_ws, size_t loss_ws_bytes, float* scalars, int32_t* pred_tokens,
                                             int32_t* pred_full_tokens, float* msg, float* patch, float* m, float* v, int opt_mode, float lr, float beta1,
                                             float beta2, float eps, int step, double* stat_part, void* stream) {
-    using namespace vaa;
-    const char* who = "vaa_step_epilogue_seg_update";
-    if (!patch || (opt_mode == VAA_OPT_ADAMW_HF && (!m || !v))) {
-        set_error("%s: null pointer argument", who);
-        return VAA_E_INVALID;
-    }
-    if ((opt_mode != VAA_OPT_ADAMW_HF && opt_mode != VAA_OPT_PGD_SIGN) || (opt_mode == VAA_OPT_ADAMW_HF && step < 1)) {
-        set_error("%s: bad optimiser mode/step (mode=%d step=%d)", who, opt_mode, step);
-        return VAA_E_INVALID;
-    }
-    UpdArgs u = {};
-    u.patch = patch; u.g = nullptr; u.m = m; u.v = v; u.stats = nullptr; u.n = n; u.mode = opt_mode;
-    u.lr = lr; u.b1 = beta1; u.b2 = beta2; u.eps = eps; u.l1_clip = 0.0f; u.grad_scale = 1.0f;
-    const double b1 = (double)beta1, b2 = (double)beta2;  // narrowed exactly like vaa_step_epilogue_update / vaa_patch_update
-    u.one_m_b1 = (float)(1.0 - b1);
-    u.one_m_b2 = (float)(1.0 - b2);
-    u.step_size = (opt_mode == VAA_OPT_ADAMW_HF) ? (float)((double)lr * sqrt(1.0 - pow(b2, (double)step)) / (1.0 - pow(b1, (double)step))) : 0.0f;
-    return step_epilogue_seg_impl(who, partials, nparts, n, P, rowmap, R, B, L, V, mode, params, loss_ws, loss_ws_bytes, scalars, pred_tokens,
-                                  pred_full_tokens, msg, &u, stat_part, stream);
+    return vaa::step_epilogue_update("vaa_step_epilogue_seg_update", true, partials, nparts, n, P, rowmap, R, B, L, V, mode, params, loss_ws,
+                                     loss_ws_bytes, scalars, pred_tokens, pred_full_tokens, msg, patch, m, v, opt_mode, lr, beta1, beta2, eps, step,
+                                     stat_part, stream);
 }

@@ -106,14 +106,9 @@ __device__ __forceinline__ void patch_update_body(const UpdArgs& a, int bid) {
     }
 }
 
+// group blockIdx.y is an independent K4 over its own n elements — its statistics, its clip, its stats[2] (vaa_patch_update: one group)
 template <int R>
 __global__ __launch_bounds__(1024) void patch_update_kernel(UpdArgs a) {
-    patch_update_body<R>(a, blockIdx.x);
-}
-
-// maskidx sweep (vaa_patch_update_seg): group blockIdx.y is an independent K4 over its own n elements — its statistics, its clip, its stats[2]
-template <int R>
-__global__ __launch_bounds__(1024) void patch_update_seg_kernel(UpdArgs a) {
     const size_t off = (size_t)blockIdx.y * a.n;
     a.patch += off; a.g += off;
     if (a.m) a.m += off;
@@ -142,17 +137,12 @@ static int patch_update_launch(const char* who, float* patch, const float* g, fl
             return VAA_E_INVALID;
         }
     }
-    UpdArgs a;
-    a.patch = patch; a.g = g; a.m = m; a.v = v; a.stats = stats; a.n = n; a.mode = mode;
-    a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.l1_clip = l1_clip; a.grad_scale = grad_scale;
-    const double b1 = (double)beta1, b2 = (double)beta2;
-    a.one_m_b1 = (float)(1.0 - b1);
-    a.one_m_b2 = (float)(1.0 - b2);
-    a.step_size = (mode == VAA_OPT_ADAMW_HF) ? (float)((double)lr * sqrt(1.0 - pow(b2, (double)step)) / (1.0 - pow(b1, (double)step))) : 0.0f;
+    UpdArgs a = upd_args(mode, lr, beta1, beta2, eps, step, l1_clip, grad_scale);
+    a.patch = patch; a.g = g; a.m = m; a.v = v; a.stats = stats; a.n = n;
     const hipStream_t st = (hipStream_t)stream;
-    if (n <= 1024 * kUpdRegsSmall) VAA_LAUNCH(patch_update_seg_kernel<kUpdRegsSmall>, dim3(kUpdRegsSmall / kUpdPer, P), dim3(1024), 0, st, a);
-    else if (n <= 1024 * kUpdRegsMid) VAA_LAUNCH(patch_update_seg_kernel<kUpdRegsMid>, dim3(kUpdRegsMid / kUpdPer, P), dim3(1024), 0, st, a);
-    else VAA_LAUNCH(patch_update_seg_kernel<0>, dim3(1, P), dim3(1024), 0, st, a);
+    if (n <= 1024 * kUpdRegsSmall) VAA_LAUNCH(patch_update_kernel<kUpdRegsSmall>, dim3(kUpdRegsSmall / kUpdPer, P), dim3(1024), 0, st, a);
+    else if (n <= 1024 * kUpdRegsMid) VAA_LAUNCH(patch_update_kernel<kUpdRegsMid>, dim3(kUpdRegsMid / kUpdPer, P), dim3(1024), 0, st, a);
+    else VAA_LAUNCH(patch_update_kernel<0>, dim3(1, P), dim3(1024), 0, st, a);
     return check_launch(who);
 }
 
@@ -165,35 +155,5 @@ extern "C" int vaa_patch_update_seg(float* patch, const float* g, float* m, floa
 
 extern "C" int vaa_patch_update(float* patch, const float* g, float* m, float* v, int n, int mode, float lr, float beta1,
                                 float beta2, float eps, int step, float l1_clip, float grad_scale, float* stats, void* stream) {
-    using namespace vaa;
-    if (!patch || !g || (mode == VAA_OPT_ADAMW_HF && (!m || !v))) {
-        set_error("vaa_patch_update: null pointer argument");
-        return VAA_E_INVALID;
-    }
-    if (n <= 0 || (mode != VAA_OPT_ADAMW_HF && mode != VAA_OPT_PGD_SIGN) || (mode == VAA_OPT_ADAMW_HF && step < 1)) {
-        set_error("vaa_patch_update: bad sizes/mode (n=%d mode=%d step=%d)", n, mode, step);
-        return VAA_E_INVALID;
-    }
-    {   // several workgroups read the WHOLE gradient while others already write their elements of patch / m / v: no byte of g may lie inside
-        // one of those buffers (a view into a shared flat buffer overlaps without being pointer-equal)
-        const uintptr_t g0 = (uintptr_t)g, g1 = g0 + (size_t)n * sizeof(float);
-        auto overlaps = [&](const float* p) { const uintptr_t p0 = (uintptr_t)p; return p && g0 < p0 + (size_t)n * sizeof(float) && p0 < g1; };
-        if (overlaps(patch) || (mode == VAA_OPT_ADAMW_HF && (overlaps(m) || overlaps(v)))) {
-            set_error("vaa_patch_update: the gradient must not overlap the patch or a moment buffer");
-            return VAA_E_INVALID;
-        }
-    }
-    UpdArgs a;
-    a.patch = patch; a.g = g; a.m = m; a.v = v; a.stats = stats; a.n = n; a.mode = mode;
-    a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.l1_clip = l1_clip; a.grad_scale = grad_scale;
-    // python-side doubles of the reference optimiser, narrowed to f32 exactly where torch narrows them
-    const double b1 = (double)beta1, b2 = (double)beta2;
-    a.one_m_b1 = (float)(1.0 - b1);
-    a.one_m_b2 = (float)(1.0 - b2);
-    a.step_size = (mode == VAA_OPT_ADAMW_HF) ? (float)((double)lr * sqrt(1.0 - pow(b2, (double)step)) / (1.0 - pow(b1, (double)step))) : 0.0f;
-    // (the gradient must not alias the patch or the moments: a workgroup reads the whole gradient while others already write their rows)
-    if (n <= 1024 * kUpdRegsSmall) VAA_LAUNCH(patch_update_kernel<kUpdRegsSmall>, dim3(kUpdRegsSmall / kUpdPer), dim3(1024), 0, (hipStream_t)stream, a);
-    else if (n <= 1024 * kUpdRegsMid) VAA_LAUNCH(patch_update_kernel<kUpdRegsMid>, dim3(kUpdRegsMid / kUpdPer), dim3(1024), 0, (hipStream_t)stream, a);
-    else VAA_LAUNCH(patch_update_kernel<0>, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
-    return check_launch("vaa_patch_update");
+    return vaa::patch_update_launch("vaa_patch_update", patch, g, m, v, n, 1, mode, lr, beta1, beta2, eps, step, l1_clip, grad_scale, stats, stream);
 }

@@ -844,37 +844,7 @@ def step_epilogue(partials, msg, scalars, rowmap: LossRowMap = None, R: int = 0,
     K3's statistics are folded into `scalars` (f32[8], output) and the prediction maps; msg[n..n+4) = {CE, w^2*MSE, UAD, total}.
     update = dict(patch=, m=, v=, mode=, lr=, step=, beta1=, beta2=, eps=, stat_part= f64 [ceil(n/64), 2]) fuses K4 (single-GPU step:
     vaa_step_epilogue_update). Returns (pred_slice, pred_full) or (None, None)."""
-    _need(partials, torch.float32, "partials")
-    parts, n = int(partials.shape[0]), int(partials.shape[1])
-    _need(msg, torch.float32, "msg")
-    _need(scalars, torch.float32, "scalars", (8,))
-    if msg.numel() < n + 4:
-        raise _lib.VaaError(f"msg: needs {n + 4} floats, has {msg.numel()}")
-    pred = pred_full = None
-    if rowmap is not None and want_pred:
-        pred = torch.empty((rowmap.B, rowmap.L - 1), dtype=torch.int32, device=msg.device)
-        pred_full = torch.empty((rowmap.B, rowmap.L - 1), dtype=torch.int32, device=msg.device)
-    common = (partials.data_ptr(), parts, n, rowmap.buf.data_ptr() if rowmap is not None else None, int(R), rowmap.B if rowmap is not None else 0,
-              rowmap.L if rowmap is not None else 0, int(V), int(mode), _lib.f32x([w, alpha, beta, scale]),
-              loss_ws.data_ptr() if loss_ws is not None else None, loss_ws.numel() if loss_ws is not None else 0, scalars.data_ptr(),
-              pred.data_ptr() if pred is not None else None, pred_full.data_ptr() if pred_full is not None else None, msg.data_ptr())
-    with _timed("EPI_step_epilogue", n=n, parts=parts):
-        if update is None:
-            rc = _lib.lib().vaa_step_epilogue(*common, _stream())
-        else:
-            u = update
-            _need(u["patch"], torch.float32, "patch")
-            if u["patch"].numel() != n:
-                raise _lib.VaaError(f"update: patch has {u['patch'].numel()} elements, the gradient {n}")
-            sp = u.get("stat_part")
-            if sp is not None:
-                _need(sp, torch.float64, "stat_part", ((n + 63) // 64, 2))
-            rc = _lib.lib().vaa_step_epilogue_update(*common, u["patch"].data_ptr(), u["m"].data_ptr() if u.get("m") is not None else None,
-                                                     u["v"].data_ptr() if u.get("v") is not None else None, int(u["mode"]), float(u["lr"]),
-                                                     float(u.get("beta1", 0.9)), float(u.get("beta2", 0.999)), float(u.get("eps", 1e-6)), int(u["step"]),
-                                                     sp.data_ptr() if sp is not None else None, _stream())
-    _lib.check(rc, "vaa_step_epilogue")
-    return pred, pred_full
+    return _step_epilogue(None, partials, msg, scalars, rowmap, R, V, mode, w, alpha, beta, scale, loss_ws, want_pred, update)
 
 
 def step_epilogue_seg(partials, msg, scalars, P: int, rowmap=None, R: int = 0, V: int = 32064, mode: int = LOSS_UADA_DDP, w: float = 5.0,
@@ -883,26 +853,34 @@ def step_epilogue_seg(partials, msg, scalars, P: int, rowmap=None, R: int = 0, V
     msg f32 [>= P*n + 4P] = [P gradients | P x {CE, w^2*MSE, UAD, total}] (a ZERO tail in the pass-through form, rowmap=None), scalars f32 [P,8]
     (the folded groups; untouched when rowmap is None). update = dict as step_epilogue's, patch / m / v [P*n] and stat_part f64 [P*ceil(n/64), 2].
     Returns (pred_slice, pred_full) [B, L-1] (group g's images at rows g*B/P ..) or (None, None)."""
+    return _step_epilogue(int(P), partials, msg, scalars, rowmap, R, V, mode, w, alpha, beta, scale, loss_ws, want_pred, update)
+
+
+def _step_epilogue(P, partials, msg, scalars, rowmap, R, V, mode, w, alpha, beta, scale, loss_ws, want_pred, update):
+    """The body of step_epilogue (P None: one group, scalars f32[8], vaa_step_epilogue[_update]) and step_epilogue_seg (vaa_step_epilogue_seg[_update])."""
+    seg, P = P is not None, P or 1
+    name = "vaa_step_epilogue_seg" if seg else "vaa_step_epilogue"
     _need(partials, torch.float32, "partials")
     rows, n = int(partials.shape[0]), int(partials.shape[1])
     if rows % P != 0:
         raise _lib.VaaError(f"partials: {rows} tiles are not {P} equal groups")
     nparts = rows // P
     _need(msg, torch.float32, "msg")
-    _need(scalars, torch.float32, "scalars", (P, 8))
+    _need(scalars, torch.float32, "scalars", (P, 8) if seg else (8,))
     if msg.numel() < P * (n + 4):
         raise _lib.VaaError(f"msg: needs {P * (n + 4)} floats, has {msg.numel()}")
     pred = pred_full = None
     if rowmap is not None and want_pred:
         pred = torch.empty((rowmap.B, rowmap.L - 1), dtype=torch.int32, device=msg.device)
         pred_full = torch.empty((rowmap.B, rowmap.L - 1), dtype=torch.int32, device=msg.device)
-    common = (partials.data_ptr(), nparts, n, int(P), rowmap.buf.data_ptr() if rowmap is not None else None, int(R), rowmap.B if rowmap is not None else 0,
-              rowmap.L if rowmap is not None else 0, int(V), int(mode), _lib.f32x([w, alpha, beta, scale]),
-              loss_ws.data_ptr() if loss_ws is not None else None, loss_ws.numel() if loss_ws is not None else 0, scalars.data_ptr(),
-              pred.data_ptr() if pred is not None else None, pred_full.data_ptr() if pred_full is not None else None, msg.data_ptr())
-    with _timed("EPI_step_epilogue_seg", n=n, parts=nparts, P=P):
+    common = ((partials.data_ptr(), nparts, n) + ((P,) if seg else ())
+              + (rowmap.buf.data_ptr() if rowmap is not None else None, int(R), rowmap.B if rowmap is not None else 0,
+                 rowmap.L if rowmap is not None else 0, int(V), int(mode), _lib.f32x([w, alpha, beta, scale]),
+                 loss_ws.data_ptr() if loss_ws is not None else None, loss_ws.numel() if loss_ws is not None else 0, scalars.data_ptr(),
+                 pred.data_ptr() if pred is not None else None, pred_full.data_ptr() if pred_full is not None else None, msg.data_ptr()))
+    with _timed("EPI_" + name[4:], n=n, parts=nparts, **({"P": P} if seg else {})):
         if update is None:
-            rc = _lib.lib().vaa_step_epilogue_seg(*common, _stream())
+            rc = getattr(_lib.lib(), name)(*common, _stream())
         else:
             u = update
             _need(u["patch"], torch.float32, "patch")
@@ -911,11 +889,11 @@ def step_epilogue_seg(partials, msg, scalars, P: int, rowmap=None, R: int = 0, V
             sp = u.get("stat_part")
             if sp is not None:
                 _need(sp, torch.float64, "stat_part", (P * ((n + 63) // 64), 2))
-            rc = _lib.lib().vaa_step_epilogue_seg_update(*common, u["patch"].data_ptr(), u["m"].data_ptr() if u.get("m") is not None else None,
-                                                         u["v"].data_ptr() if u.get("v") is not None else None, int(u["mode"]), float(u["lr"]),
-                                                         float(u.get("beta1", 0.9)), float(u.get("beta2", 0.999)), float(u.get("eps", 1e-6)), int(u["step"]),
-                                                         sp.data_ptr() if sp is not None else None, _stream())
-    _lib.check(rc, "vaa_step_epilogue_seg")
+            rc = getattr(_lib.lib(), name + "_update")(*common, u["patch"].data_ptr(), u["m"].data_ptr() if u.get("m") is not None else None,
+                                                       u["v"].data_ptr() if u.get("v") is not None else None, int(u["mode"]), float(u["lr"]),
+                                                       float(u.get("beta1", 0.9)), float(u.get("beta2", 0.999)), float(u.get("eps", 1e-6)),
+                                                       int(u["step"]), sp.data_ptr() if sp is not None else None, _stream())
+    _lib.check(rc, name)
     return pred, pred_full
 
 
@@ -1027,39 +1005,34 @@ class HeadSliceLoss(torch.autograd.Function):
 def patch_update(patch, grad, m, v, mode: int, lr: float, step: int, beta1: float = 0.9, beta2: float = 0.999,
                  eps: float = 1e-6, l1_clip: float = 0.0, grad_scale: float = 1.0, want_stats: bool = True):
     """K4 (in place on patch/m/v). Returns stats f32[2] = [sum|g|, mean g] (device) or None."""
-    _need(patch, torch.float32, "patch")
-    _need(grad, torch.float32, "grad", patch.shape)
-    if mode == OPT_ADAMW_HF:
-        _need(m, torch.float32, "m", patch.shape)
-        _need(v, torch.float32, "v", patch.shape)
-    stats = torch.empty(2, dtype=torch.float32, device=patch.device) if want_stats else None
-    with _timed("K4_patch_update", n=int(patch.numel())):
-        rc = _lib.lib().vaa_patch_update(
-            patch.data_ptr(), grad.data_ptr(), m.data_ptr() if m is not None else None, v.data_ptr() if v is not None else None,
-            patch.numel(), int(mode), float(lr), float(beta1), float(beta2), float(eps), int(step), float(l1_clip),
-            float(grad_scale), stats.data_ptr() if want_stats else None, _stream())
-    _lib.check(rc, "vaa_patch_update")
-    return stats
+    return _patch_update(None, patch, grad, m, v, mode, lr, step, beta1, beta2, eps, l1_clip, grad_scale, want_stats)
 
 
 def patch_update_seg(patch, grad, m, v, P: int, mode: int, lr: float, step: int, beta1: float = 0.9, beta2: float = 0.999,
                      eps: float = 1e-6, l1_clip: float = 0.0, grad_scale: float = 1.0, want_stats: bool = True):
     """K4 on P groups of patch.numel() / P elements in ONE launch (vaa_patch_update_seg): bit for bit P patch_update calls. Returns stats f32 [P,2]."""
+    return _patch_update(int(P), patch, grad, m, v, mode, lr, step, beta1, beta2, eps, l1_clip, grad_scale, want_stats)
+
+
+def _patch_update(P, patch, grad, m, v, mode, lr, step, beta1, beta2, eps, l1_clip, grad_scale, want_stats):
+    """The body of patch_update (P None: one group, grad of the patch's shape, stats [2]) and patch_update_seg (stats [P,2])."""
+    seg, P = P is not None, P or 1
+    name = "vaa_patch_update_seg" if seg else "vaa_patch_update"
     _need(patch, torch.float32, "patch")
-    _need(grad, torch.float32, "grad")
+    _need(grad, torch.float32, "grad", None if seg else patch.shape)
     n_all = int(patch.numel())
     if grad.numel() != n_all or n_all % P != 0:
         raise _lib.VaaError(f"patch_update_seg: {n_all} patch / {grad.numel()} gradient elements are not {P} equal groups")
     if mode == OPT_ADAMW_HF:
         _need(m, torch.float32, "m", patch.shape)
         _need(v, torch.float32, "v", patch.shape)
-    stats = torch.empty((P, 2), dtype=torch.float32, device=patch.device) if want_stats else None
-    with _timed("K4_patch_update_seg", n=n_all, P=P):
-        rc = _lib.lib().vaa_patch_update_seg(
+    stats = torch.empty((P, 2) if seg else 2, dtype=torch.float32, device=patch.device) if want_stats else None
+    with _timed("K4_" + name[4:], n=n_all, **({"P": P} if seg else {})):
+        rc = getattr(_lib.lib(), name)(
             patch.data_ptr(), grad.data_ptr(), m.data_ptr() if m is not None else None, v.data_ptr() if v is not None else None,
-            n_all // P, int(P), int(mode), float(lr), float(beta1), float(beta2), float(eps), int(step), float(l1_clip),
+            n_all // P, *((P,) if seg else ()), int(mode), float(lr), float(beta1), float(beta2), float(eps), int(step), float(l1_clip),
             float(grad_scale), stats.data_ptr() if want_stats else None, _stream())
-    _lib.check(rc, "vaa_patch_update_seg")
+    _lib.check(rc, name)
     return stats
 
 

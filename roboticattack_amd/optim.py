@@ -25,28 +25,33 @@ def cosine_with_warmup_lambda(step: int, num_warmup_steps: int, num_training_ste
 
 
 class PatchOptimizer:
-    """Owns m, v and the step count of ONE patch tensor; `step()` = K4 (scale, clip, AdamW|PGD, clamp to [0,1])."""
+    """Owns m, v and the step count of ONE patch tensor; `step()` = K4 (scale, clip, AdamW|PGD, clamp to [0,1]).
+    `groups` = P > 1 (a maskidx sweep): `patch` is [P, ...] = P independent patches sharing lr and the step count; every group takes the step a
+    standalone PatchOptimizer would take on its own patch (one launch for all: vaa_patch_update_seg / vaa_step_epilogue_seg_update)."""
 
     def __init__(self, patch: torch.Tensor, lr: float, mode: str = "adamW", betas=(0.9, 0.999), eps: float = 1e-6,
-                 l1_clip: float = 0.0, clamp: bool = True):
+                 l1_clip: float = 0.0, clamp: bool = True, groups: int = 1):
         if mode not in ("adamW", "pgd"):
             raise ValueError(f"unknown optimizer {mode!r}")
         self.patch = patch
+        self.groups = int(groups)
+        self.n = patch.numel() // self.groups  # elements per group
         self.mode = ops.OPT_ADAMW_HF if mode == "adamW" else ops.OPT_PGD_SIGN
         self.param_groups = [dict(params=[patch], lr=lr, initial_lr=lr, betas=betas, eps=eps)]
         self.l1_clip = l1_clip
         self.t = 0
         self.m = torch.zeros_like(patch, requires_grad=False) if self.mode == ops.OPT_ADAMW_HF else None
         self.v = torch.zeros_like(patch, requires_grad=False) if self.mode == ops.OPT_ADAMW_HF else None
-        self._last_stats = None  # device f32[2]: [sum|g|, mean g] of the most recent step
-        self._stat_part = None   # fused steps (vaa_step_epilogue_update): per-block {sum|g|, sum g}, folded on demand
+        self._last_stats = None  # device f32[2] ([groups, 2] when groups > 1): [sum|g|, mean g] of the most recent step
+        self._stat_part = None   # fused steps (vaa_step_epilogue[_seg]_update): per-block {sum|g|, sum g}, folded on demand
 
     @property
     def last_stats(self):
-        """device f32[2] = [sum|g|, mean g] of the most recent step (what K4 logs; after a fused step folded here from its block sums)."""
+        """device f32[2] = [sum|g|, mean g] of the most recent step, [groups, 2] when groups > 1 (what K4 logs; after a fused step folded here
+        from its block sums — group g's are exactly the stat_part of a standalone fused step, summed the same way: the same bits)."""
         if self._last_stats is None and self._stat_part is not None:
-            t = self._stat_part.sum(dim=0)
-            self._last_stats = torch.stack([t[0], t[1] / self.patch.numel()]).to(torch.float32)
+            rows = [torch.stack([t[0], t[1] / self.n]).to(torch.float32) for t in (sp.sum(dim=0) for sp in self._stat_part.view(self.groups, -1, 2))]
+            self._last_stats = rows[0] if self.groups == 1 else torch.stack(rows)
         return self._last_stats
 
     @last_stats.setter
@@ -61,7 +66,7 @@ class PatchOptimizer:
         self.t += 1
         grp = self.param_groups[0]
         if self._stat_part is None:
-            self._stat_part = torch.zeros(((self.patch.numel() + 63) // 64, 2), dtype=torch.float64, device=self.patch.device)
+            self._stat_part = torch.zeros((self.groups * ((self.n + 63) // 64), 2), dtype=torch.float64, device=self.patch.device)
         self._last_stats = None
         return dict(patch=self.patch.data, m=self.m, v=self.v, mode=self.mode, lr=grp["lr"], step=self.t, beta1=grp["betas"][0],
                     beta2=grp["betas"][1], eps=grp["eps"], stat_part=self._stat_part)
@@ -72,8 +77,11 @@ class PatchOptimizer:
             return None
         self.t += 1
         grp = self.param_groups[0]
-        self._last_stats = ops.patch_update(self.patch.data, g.contiguous(), self.m, self.v, self.mode, grp["lr"], self.t,
-                                            grp["betas"][0], grp["betas"][1], grp["eps"], self.l1_clip, grad_scale)
+        hyper = (self.mode, grp["lr"], self.t, grp["betas"][0], grp["betas"][1], grp["eps"], self.l1_clip, grad_scale)
+        if self.groups == 1:
+            self._last_stats = ops.patch_update(self.patch.data, g.contiguous(), self.m, self.v, *hyper)
+        else:
+            self._last_stats = ops.patch_update_seg(self.patch.data, g.contiguous(), self.m, self.v, self.groups, *hyper)
         return self._last_stats
 
     def zero_grad(self, set_to_none: bool = True):
@@ -84,51 +92,10 @@ class PatchOptimizer:
 
 
 class SweepPatchOptimizer(PatchOptimizer):
-    """The optimiser of a maskidx sweep: `patch` is [P, ...] = P independent patches sharing lr and the step count; every group is the AdamW /
-    PGD step a standalone PatchOptimizer would take on its own patch (one launch for all: vaa_patch_update_seg / vaa_step_epilogue_seg_update).
-    last_stats is [P,2] = per group [sum|g|, mean g]."""
+    """The optimiser of a maskidx sweep: PatchOptimizer with one group per leading index of `patch` [P, ...]."""
 
     def __init__(self, patch: torch.Tensor, lr: float, mode: str = "adamW", betas=(0.9, 0.999), eps: float = 1e-6, l1_clip: float = 0.0):
-        super().__init__(patch, lr, mode, betas, eps, l1_clip)
-        self.P = int(patch.shape[0])
-        self.n = patch.numel() // self.P
-
-    @property
-    def last_stats(self):
-        if self._last_stats is None and self._stat_part is not None:
-            # group g's block sums are exactly the stat_part of a standalone fused step: summed the same way, the same bits
-            sp = self._stat_part.view(self.P, -1, 2)
-            rows = []
-            for g in range(self.P):
-                t = sp[g].sum(dim=0)
-                rows.append(torch.stack([t[0], t[1] / self.n]).to(torch.float32))
-            self._last_stats = torch.stack(rows)
-        return self._last_stats
-
-    @last_stats.setter
-    def last_stats(self, v):
-        self._last_stats = v
-
-    def fused_update_args(self):
-        if self.l1_clip:
-            raise ValueError("the fused update has no L1 clip")
-        self.t += 1
-        grp = self.param_groups[0]
-        if self._stat_part is None:
-            self._stat_part = torch.zeros((self.P * ((self.n + 63) // 64), 2), dtype=torch.float64, device=self.patch.device)
-        self._last_stats = None
-        return dict(patch=self.patch.data, m=self.m, v=self.v, mode=self.mode, lr=grp["lr"], step=self.t, beta1=grp["betas"][0],
-                    beta2=grp["betas"][1], eps=grp["eps"], stat_part=self._stat_part)
-
-    def step(self, grad: torch.Tensor | None = None, grad_scale: float = 1.0):
-        g = grad if grad is not None else self.patch.grad
-        if g is None:
-            return None
-        self.t += 1
-        grp = self.param_groups[0]
-        self._last_stats = ops.patch_update_seg(self.patch.data, g.contiguous(), self.m, self.v, self.P, self.mode, grp["lr"], self.t,
-                                                grp["betas"][0], grp["betas"][1], grp["eps"], self.l1_clip, grad_scale)
-        return self._last_stats
+        super().__init__(patch, lr, mode, betas, eps, l1_clip, groups=int(patch.shape[0]))
 
 
 class CosineWarmupSchedule:

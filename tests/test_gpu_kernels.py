@@ -1287,6 +1287,10 @@ def test_step_epilogue_equals_separate_launches(ops, B, dtype):
     assert torch.equal(scal, want_s) and torch.equal(pred, want_p) and torch.equal(pred_full, want_pf)
     assert torch.equal(gsl.view(torch.int16) if dtype == torch.bfloat16 else gsl, want_gs.view(torch.int16) if dtype == torch.bfloat16 else want_gs)
     assert torch.equal(msg[n:], want_s[[1, 2, 7, 0]])
+    # a caller's R other than the map's row count: a NaN total in the scalars and the message; the rows both know are folded as ever
+    msg_r, scal_r = torch.zeros(n + 4, device=DEV), torch.zeros(8, device=DEV)
+    ops.step_epilogue(parts, msg_r, scal_r, rowmap=rm, R=R - 1, V=32064, mode=ops.LOSS_UADA_DDP, w=5.0, loss_ws=ws)
+    assert torch.isnan(scal_r[0]) and torch.isnan(msg_r[n + 3]) and float(scal_r[5]) == R - 1 and torch.equal(msg_r[:n], msg[:n])
     # pass-through form: the scalars are final already (modes whose gradient needs them ran vaa_loss_rows_fwd_bwd), only the message is built
     msg2 = torch.zeros(n + 4, device=DEV)
     ops.step_epilogue(parts, msg2, want_s)

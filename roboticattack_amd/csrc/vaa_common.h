@@ -26,6 +26,41 @@ constexpr unsigned VAA_ASYNC_K3_HANDOVER_TIMEOUT = 1u;
 // vaa_patch_grad.hip: gpatch[e] = sum_p partial[p][e] (p < nparts, e < n) in a fixed order with fp64 accumulation
 int launch_partial_reduce(const float* partial, float* gpatch, int n, int nparts, hipStream_t st, const char* who);
 
+// Argument rules every patch entry point shares (host). check_patch_size: the batch / patch sizes and the frame (what vaa_patch_apply_eval,
+// which has no mask mode and takes its geometry per image, checks); check_patch_call adds the mask mode rules of K1 / K2 / K2'.
+inline int check_patch_size(const char* who, int B, int h, int w) {
+    if (B < 0 || h <= 0 || w <= 0) {
+        set_error("%s: bad sizes (B=%d ph=%d pw=%d)", who, B, h, w);
+        return VAA_E_INVALID;
+    }
+    if (h > VAA_IMG || w > VAA_IMG) {
+        set_error("%s: patch %dx%d larger than the %dx%d frame", who, h, w, VAA_IMG, VAA_IMG);
+        return VAA_E_UNSUPPORTED;
+    }
+    return VAA_OK;
+}
+
+inline int check_patch_call(const char* who, int B, int h, int w, int geometry, int mask_mode) {
+    if (mask_mode != VAA_MASK_LT_M20 && mask_mode != VAA_MASK_NE_M100) {
+        set_error("%s: bad mask_mode %d", who, mask_mode);
+        return VAA_E_INVALID;
+    }
+    const int rc = check_patch_size(who, B, h, w);
+    if (rc != VAA_OK) return rc;
+    if (geometry && mask_mode == VAA_MASK_NE_M100) {
+        // the reference pairs `canvas != -100` only with the un-warped paste (paste_patch_fix / random_paste_patch, :138-188); after a
+        // warp the all-background blend -100*(nw+ne+sw+se) is not exactly -100, so the rule would depend on rounding over the whole frame
+        set_error("%s: VAA_MASK_NE_M100 is defined for geometry=0 only (appply_random_transform.py:153,179)", who);
+        return VAA_E_UNSUPPORTED;
+    }
+    return VAA_OK;
+}
+
+// 1/std of the six normalisation channels, rounded from double: the factor K2 / K2' apply to the incoming gradient
+inline void inv_std6(const float* std6, float* istd6) {
+    for (int q = 0; q < 6; ++q) istd6[q] = (float)(1.0 / (double)std6[q]);
+}
+
 // Per-dispatch timing (include/vaa.h: vaa_prof_*): while the profiler is armed every kernel of the library is dispatched through
 // hipExtLaunchKernel with its own start/stop event pair, which the runtime binds to THAT dispatch's begin/end timestamps (the figures
 // rocprofv3 --kernel-trace reports), so a kernel's duration inside a real step is read without bracketing markers.

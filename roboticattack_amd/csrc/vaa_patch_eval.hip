@@ -113,14 +113,8 @@ extern "C" int vaa_patch_apply_eval(const uint8_t* img_u8, const float* patch, c
         set_error("vaa_patch_apply_eval: null pointer argument");
         return VAA_E_INVALID;
     }
-    if (B < 0 || ph <= 0 || pw <= 0) {
-        set_error("vaa_patch_apply_eval: bad sizes (B=%d ph=%d pw=%d)", B, ph, pw);
-        return VAA_E_INVALID;
-    }
-    if (ph > VAA_IMG || pw > VAA_IMG) {
-        set_error("vaa_patch_apply_eval: patch %dx%d larger than the frame", ph, pw);
-        return VAA_E_UNSUPPORTED;
-    }
+    const int rc = check_patch_size("vaa_patch_apply_eval", B, ph, pw);
+    if (rc != VAA_OK) return rc;
     EvalArgs a;
     a.img = img_u8; a.patch = patch; a.xy = xy; a.theta = theta; a.geometry = geometry; a.out = out_u8; a.B = B; a.ph = ph; a.pw = pw;
     const long total = (long)B * kEvItemsPerImg;

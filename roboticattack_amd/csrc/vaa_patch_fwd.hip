@@ -524,32 +524,31 @@ __global__ __launch_bounds__(kFwdThreads) void patch_apply_tiles_kernel(const Fw
 
 namespace vaa {
 
+// The argument rules and the FwdArgs fill of every K1 entry point (a.out / a.keep stay null: the planar form sets them, the tile-major form
+// has its TileOut). outs: the form's own required output pointers are there.
+static int fwd_args(const char* who, FwdArgs& a, const uint8_t* img_u8, const float* patch, const int32_t* pdesc, const int32_t* xy, const float* theta,
+                    int B, int ph, int pw, int geometry, int mask_mode, const float* mean6, const float* std6, bool outs) {
+    if (!img_u8 || !patch || !xy || !outs || !mean6 || !std6 || (geometry && !theta)) {
+        set_error("%s: null pointer argument", who);
+        return VAA_E_INVALID;
+    }
+    const int rc = check_patch_call(who, B, ph, pw, geometry, mask_mode);
+    if (rc != VAA_OK) return rc;
+    a = FwdArgs{};
+    a.img = img_u8; a.patch = patch; a.xy = xy; a.theta = theta; a.pdesc = pdesc;
+    a.B = B; a.ph = ph; a.pw = pw; a.geometry = geometry ? 1 : 0; a.mask_mode = mask_mode;
+    for (int q = 0; q < 6; ++q) { a.nrm.mean[q] = mean6[q]; a.nrm.stdv[q] = std6[q]; }
+    return VAA_OK;
+}
+
 static int launch_patch_apply(const char* who, const uint8_t* img_u8, const float* patch, const int32_t* pdesc, const int32_t* xy,
                               const float* theta, int B, int ph, int pw, int geometry, int mask_mode, const float* mean6,
                               const float* std6, uint16_t* out_bf16, uint8_t* keep_bits, void* stream) {
     if (B == 0) return VAA_OK;  // empty batch: nothing to read or write (pointers may be null)
-    if (!img_u8 || !patch || !xy || !out_bf16 || !mean6 || !std6 || (geometry && !theta)) {
-        set_error("%s: null pointer argument", who);
-        return VAA_E_INVALID;
-    }
-    if (B < 0 || ph <= 0 || pw <= 0 || (mask_mode != VAA_MASK_LT_M20 && mask_mode != VAA_MASK_NE_M100)) {
-        set_error("%s: bad sizes/mode (B=%d ph=%d pw=%d mask_mode=%d)", who, B, ph, pw, mask_mode);
-        return VAA_E_INVALID;
-    }
-    if (ph > VAA_IMG || pw > VAA_IMG) {
-        set_error("%s: patch %dx%d larger than the %dx%d frame", who, ph, pw, VAA_IMG, VAA_IMG);
-        return VAA_E_UNSUPPORTED;
-    }
-    if (geometry && mask_mode == VAA_MASK_NE_M100) {
-        // the reference pairs `canvas != -100` only with the un-warped paste (paste_patch_fix / random_paste_patch, :138-188); after a
-        // warp the all-background blend -100*(nw+ne+sw+se) is not exactly -100, so the rule would depend on rounding over the whole frame
-        set_error("%s: VAA_MASK_NE_M100 is defined for geometry=0 only (appply_random_transform.py:153,179)", who);
-        return VAA_E_UNSUPPORTED;
-    }
     FwdArgs a;
-    a.img = img_u8; a.patch = patch; a.xy = xy; a.theta = theta; a.out = out_bf16; a.keep = keep_bits; a.pdesc = pdesc;
-    a.B = B; a.ph = ph; a.pw = pw; a.geometry = geometry ? 1 : 0; a.mask_mode = mask_mode;
-    for (int q = 0; q < 6; ++q) { a.nrm.mean[q] = mean6[q]; a.nrm.stdv[q] = std6[q]; }
+    const int rc = fwd_args(who, a, img_u8, patch, pdesc, xy, theta, B, ph, pw, geometry, mask_mode, mean6, std6, out_bf16 != nullptr);
+    if (rc != VAA_OK) return rc;
+    a.out = out_bf16; a.keep = keep_bits;
     const long total = (long)B * kItemsPerImg;
     const long n_bg = (total + kFwdThreads - 1) / kFwdThreads;
     int fsplit = 16;  // footprint workgroups per image: ~6,400 pixel-lanes per 50x50 footprint -> 2 slot rounds each
@@ -578,7 +577,7 @@ extern "C" int vaa_patch_apply_fwd_multi(const uint8_t* img_u8, const float* pac
                                          const float* theta, int B, int max_h, int max_w, int geometry, int mask_mode,
                                          const float* mean6, const float* std6, uint16_t* out_bf16, uint8_t* keep_bits, void* stream) {
     if (B > 0 && !pdesc) {
-        vaa::set_error("vaa_patch_apply_fwd_multi: null pdesc");
+        vaa::set_error("%s: null pointer argument (pdesc)", "vaa_patch_apply_fwd_multi");
         return VAA_E_INVALID;
     }
     return vaa::launch_patch_apply("vaa_patch_apply_fwd_multi", img_u8, packed, pdesc, xy, theta, B, max_h, max_w, geometry, mask_mode, mean6,
@@ -586,31 +585,15 @@ extern "C" int vaa_patch_apply_fwd_multi(const uint8_t* img_u8, const float* pac
 }
 
 // K1 in tile-major form (see patch_apply_tiles_kernel): the operands of the two ViT patch-embed GEMMs + tile-major keep words + tile flags.
-namespace vaa {
-static int patch_apply_tiles_impl(const char* who, const uint8_t* img_u8, const float* patch, const int32_t* pdesc, const int32_t* xy, const float* theta,
-                                  int B, int ph, int pw, int geometry, int mask_mode, const float* mean6, const float* std6, uint16_t* out0,
-                                  uint16_t* out1, uint16_t* keep_tiles, uint32_t* tile_flags, void* stream) {
+extern "C" int vaa_patch_apply_fwd_tiles(const uint8_t* img_u8, const float* patch, const int32_t* pdesc, const int32_t* xy, const float* theta,
+                                         int B, int ph, int pw, int geometry, int mask_mode, const float* mean6, const float* std6,
+                                         uint16_t* out0, uint16_t* out1, uint16_t* keep_tiles, uint32_t* tile_flags, void* stream) {
+    using namespace vaa;
+    const char* who = "vaa_patch_apply_fwd_tiles";
     if (B == 0) return VAA_OK;
-    if (!img_u8 || !patch || !xy || !out0 || !out1 || !mean6 || !std6 || (geometry && !theta)) {
-        set_error("%s: null pointer argument", who);
-        return VAA_E_INVALID;
-    }
-    if (B < 0 || ph <= 0 || pw <= 0 || (mask_mode != VAA_MASK_LT_M20 && mask_mode != VAA_MASK_NE_M100)) {
-        set_error("%s: bad sizes/mode (B=%d ph=%d pw=%d mask_mode=%d)", who, B, ph, pw, mask_mode);
-        return VAA_E_INVALID;
-    }
-    if (ph > VAA_IMG || pw > VAA_IMG) {
-        set_error("%s: patch %dx%d larger than the %dx%d frame", who, ph, pw, VAA_IMG, VAA_IMG);
-        return VAA_E_UNSUPPORTED;
-    }
-    if (geometry && mask_mode == VAA_MASK_NE_M100) {
-        set_error("%s: VAA_MASK_NE_M100 is defined for geometry=0 only (appply_random_transform.py:153,179)", who);
-        return VAA_E_UNSUPPORTED;
-    }
     FwdArgs a;
-    a.img = img_u8; a.patch = patch; a.xy = xy; a.theta = theta; a.out = nullptr; a.keep = nullptr; a.pdesc = pdesc;
-    a.B = B; a.ph = ph; a.pw = pw; a.geometry = geometry ? 1 : 0; a.mask_mode = mask_mode;
-    for (int q = 0; q < 6; ++q) { a.nrm.mean[q] = mean6[q]; a.nrm.stdv[q] = std6[q]; }
+    const int rc = fwd_args(who, a, img_u8, patch, pdesc, xy, theta, B, ph, pw, geometry, mask_mode, mean6, std6, out0 && out1);
+    if (rc != VAA_OK) return rc;
     TileOut o;
     o.out0 = out0; o.out1 = out1; o.keep_t = keep_tiles; o.flags = tile_flags;
     // footprint workgroups per image: each pays a ~2 us prologue (LUT, 224 row spans, tile list) before its first tile, so FEWER, longer-lived
@@ -621,12 +604,4 @@ static int patch_apply_tiles_impl(const char* who, const uint8_t* img_u8, const 
     const long n_fp = (long)B * fsplit, n_bg = (long)B * 16;
     VAA_LAUNCH(patch_apply_tiles_kernel, dim3((unsigned)(n_fp + n_bg)), dim3(kFwdThreads), 0, (hipStream_t)stream, a, o, (int)n_fp, fsplit);
     return check_launch(who);
-}
-}  // namespace vaa
-
-extern "C" int vaa_patch_apply_fwd_tiles(const uint8_t* img_u8, const float* patch, const int32_t* pdesc, const int32_t* xy, const float* theta,
-                                         int B, int ph, int pw, int geometry, int mask_mode, const float* mean6, const float* std6,
-                                         uint16_t* out0, uint16_t* out1, uint16_t* keep_tiles, uint32_t* tile_flags, void* stream) {
-    return vaa::patch_apply_tiles_impl("vaa_patch_apply_fwd_tiles", img_u8, patch, pdesc, xy, theta, B, ph, pw, geometry, mask_mode, mean6, std6, out0, out1,
-                                       keep_tiles, tile_flags, stream);
 }

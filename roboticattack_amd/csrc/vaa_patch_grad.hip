@@ -514,63 +514,88 @@ static int band_rows_for(int ph, int pw, int wgs_per_band) {
     return r2 < rows ? r2 : rows;
 }
 
+// f(std::true_type / std::false_type) for a stored keep mask / none: a launch site names the HASK instantiation of its scatter kernel once
+template <typename F>
+static int with_hask(bool hask, F f) {
+    return hask ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// The one fill of GradArgs: the placement, the stored mask and where the gradient goes. The TILED source (geff .. keep_t) stays null: K2' sets
+// it; band_rows is the launcher's.
+static GradArgs grad_args(const uint16_t* g, const float* patch, const int32_t* pdesc, const int32_t* xy, const float* theta, const uint8_t* keep,
+                          float* partial, int B, int ph, int pw, int geometry, int mask_mode, const float* std6) {
+    GradArgs a = {};
+    a.g = g; a.patch = patch; a.xy = xy; a.theta = theta; a.keep = keep; a.partial = partial; a.pdesc = pdesc;
+    a.B = B; a.ph = ph; a.pw = pw; a.geometry = geometry ? 1 : 0; a.mask_mode = mask_mode;
+    inv_std6(std6, a.istd6);
+    return a;
+}
+
+// the sum over no images is zero
+static int zero_gpatch(const char* who, float* gpatch, int ph, int pw, hipStream_t st) {
+    if (hipMemsetAsync(gpatch, 0, (size_t)3 * ph * pw * sizeof(float), st) != hipSuccess) return check_launch(who);
+    return VAA_OK;
+}
+
 template <bool TILED>
-static int launch_scatter_reduce(const GradArgs& a0, float* gpatch, hipStream_t st, const char* who) {
-    GradArgs a = a0;
+static int launch_scatter_reduce(GradArgs a, float* gpatch, hipStream_t st, const char* who) {
     const int B = a.B, ph = a.ph, pw = a.pw, n = 3 * ph * pw;
     const GradSched gs = grad_sched(B);
     const int G = gs.gx;  // workgroups (x) == partial tiles
     const size_t plane = (size_t)ph * pw;
-    hipError_t e = hipSuccess;
+    int rc;
     if (3 * plane * sizeof(long long) <= 64 * 1024) {  // e.g. 50x50: 60,000 B
         // 512 threads: two workgroups per CU (<= 128 VGPRs each, 2 x 68 KB of LDS at one band), so one scatters while the other waits on its
         // loads or its barrier (B = 256 / 1024 / 4096: 41.8 / 76.7 / 183 us with one 1024-thread workgroup per CU -> 33.4 / 64.8 / 173 us)
         a.band_rows = (ph + gs.bands - 1) / gs.bands;
         const int nb = (ph + a.band_rows - 1) / a.band_rows;
         const size_t lds = 3 * (size_t)a.band_rows * pw * sizeof(long long);
-        if (a.keep) VAA_LAUNCH((patch_grad_scatter_kernel<3, TILED, false, true, 512, 3>), dim3(G, 1, nb), dim3(512), lds, st, a, gs.gx);
-        else VAA_LAUNCH((patch_grad_scatter_kernel<3, TILED, false, false, 512, 3>), dim3(G, 1, nb), dim3(512), lds, st, a, gs.gx);
+        rc = with_hask(a.keep != nullptr, [&](auto hask) {
+            VAA_LAUNCH((patch_grad_scatter_kernel<3, TILED, false, decltype(hask)::value, 512, 3>), dim3(G, 1, nb), dim3(512), lds, st, a, gs.gx);
+            return VAA_OK;
+        });
     } else {  // one channel per workgroup (grid.y), row bands (grid.z) when even one plane exceeds the LDS (> 135x135)
         a.band_rows = band_rows_for(ph, pw, 3 * G);
         const int nbands = (ph + a.band_rows - 1) / a.band_rows;
         const size_t bytes = (size_t)a.band_rows * pw * sizeof(long long);
-        const void* fn = a.keep ? (const void*)patch_grad_scatter_kernel<1, TILED, false, true, 1024, 3>
-                                : (const void*)patch_grad_scatter_kernel<1, TILED, false, false, 1024, 3>;
-        if (bytes > 64 * 1024) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e == hipSuccess) {
-            if (a.keep)
-                VAA_LAUNCH((patch_grad_scatter_kernel<1, TILED, false, true, 1024, 3>), dim3(G, 3, nbands), dim3(1024), bytes, st, a, gs.gx);
-            else
-                VAA_LAUNCH((patch_grad_scatter_kernel<1, TILED, false, false, 1024, 3>), dim3(G, 3, nbands), dim3(1024), bytes, st, a, gs.gx);
-        }
+        rc = with_hask(a.keep != nullptr, [&](auto hask) {
+            constexpr bool HASK = decltype(hask)::value;
+            if (bytes > 64 * 1024) {
+                const hipError_t e = hipFuncSetAttribute((const void*)patch_grad_scatter_kernel<1, TILED, false, HASK, 1024, 3>,
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+                if (e != hipSuccess) {
+                    set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
+                    return VAA_E_LAUNCH;
+                }
+            }
+            VAA_LAUNCH((patch_grad_scatter_kernel<1, TILED, false, HASK, 1024, 3>), dim3(G, 3, nbands), dim3(1024), bytes, st, a, gs.gx);
+            return VAA_OK;
+        });
     }
-    if (e != hipSuccess) {
-        set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
-        return VAA_E_LAUNCH;
-    }
-    int rc = check_launch(who);
+    if (rc != VAA_OK) return rc;
+    rc = check_launch(who);
     if (rc != VAA_OK || !gpatch) return rc;  // gpatch == nullptr: the caller's step epilogue adds the partial tiles
     return launch_partial_reduce((const float*)a.partial, gpatch, n, G, st, who);
 }
 
-// one workgroup per (image, channel, row band); every image's own gradient is drained into gpacked
+// one workgroup per (image, channel, row band); every image's own gradient is drained into gpacked (a.ph / a.pw bound the patch sizes)
 template <bool TILED>
-static int launch_scatter_multi(GradArgs a, int max_h, int max_w, hipStream_t st, const char* who) {
+static int launch_scatter_multi(GradArgs a, hipStream_t st, const char* who) {
     const int B = a.B;
-    a.band_rows = band_rows_for(max_h, max_w, 3 * B);
-    const int nbands = (max_h + a.band_rows - 1) / a.band_rows;
-    const size_t bytes = (size_t)a.band_rows * max_w * sizeof(long long);
-    const void* fn = a.keep ? (const void*)patch_grad_scatter_kernel<1, TILED, true, true, 1024, 3>
-                            : (const void*)patch_grad_scatter_kernel<1, TILED, true, false, 1024, 3>;
-    if (bytes > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
-        set_error("%s: hipFuncSetAttribute failed", who);
-        return VAA_E_LAUNCH;
-    }
-    if (a.keep)
-        VAA_LAUNCH((patch_grad_scatter_kernel<1, TILED, true, true, 1024, 3>), dim3(B, 3, nbands), dim3(1024), bytes, st, a, B);
-    else
-        VAA_LAUNCH((patch_grad_scatter_kernel<1, TILED, true, false, 1024, 3>), dim3(B, 3, nbands), dim3(1024), bytes, st, a, B);
-    return check_launch(who);
+    a.band_rows = band_rows_for(a.ph, a.pw, 3 * B);
+    const int nbands = (a.ph + a.band_rows - 1) / a.band_rows;
+    const size_t bytes = (size_t)a.band_rows * a.pw * sizeof(long long);
+    const int rc = with_hask(a.keep != nullptr, [&](auto hask) {
+        constexpr bool HASK = decltype(hask)::value;
+        if (bytes > 64 * 1024 && hipFuncSetAttribute((const void*)patch_grad_scatter_kernel<1, TILED, true, HASK, 1024, 3>,
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+            set_error("%s: hipFuncSetAttribute failed", who);
+            return VAA_E_LAUNCH;
+        }
+        VAA_LAUNCH((patch_grad_scatter_kernel<1, TILED, true, HASK, 1024, 3>), dim3(B, 3, nbands), dim3(1024), bytes, st, a, B);
+        return VAA_OK;
+    });
+    return rc != VAA_OK ? rc : check_launch(who);
 }
 
 }  // namespace vaa
@@ -589,38 +614,21 @@ extern "C" int vaa_patch_grad_gather(const uint16_t* gout_bf16, const float* pat
                                      const uint8_t* keep_bits, int B, int ph, int pw, int geometry, int mask_mode,
                                      const float* std6, float* gpatch, void* ws, size_t ws_bytes, void* stream) {
     using namespace vaa;
-    if (B == 0 && gpatch && ph > 0 && pw > 0) {  // empty batch: the sum over no images is zero
-        if (hipMemsetAsync(gpatch, 0, (size_t)3 * ph * pw * sizeof(float), (hipStream_t)stream) != hipSuccess)
-            return check_launch("vaa_patch_grad_gather(memset)");
-        return VAA_OK;
-    }
-    if (!gout_bf16 || !xy || !std6 || (geometry && !theta) || (!keep_bits && !patch)) {  // gpatch == NULL: the final sum is left to vaa_step_epilogue
-        set_error("vaa_patch_grad_gather: null pointer argument");
-        return VAA_E_INVALID;
-    }
-    if (B < 0 || ph <= 0 || pw <= 0 || (mask_mode != VAA_MASK_LT_M20 && mask_mode != VAA_MASK_NE_M100)) {
-        set_error("vaa_patch_grad_gather: bad sizes/mode (B=%d ph=%d pw=%d mask_mode=%d)", B, ph, pw, mask_mode);
-        return VAA_E_INVALID;
-    }
-    if (ph > VAA_IMG || pw > VAA_IMG) {
-        set_error("vaa_patch_grad_gather: patch %dx%d larger than the frame", ph, pw);
-        return VAA_E_UNSUPPORTED;
-    }
-    if (geometry && mask_mode == VAA_MASK_NE_M100) {
-        set_error("vaa_patch_grad_gather: VAA_MASK_NE_M100 is defined for geometry=0 only");
-        return VAA_E_UNSUPPORTED;
-    }
+    const char* who = "vaa_patch_grad_gather";
     hipStream_t st = (hipStream_t)stream;
+    if (B == 0 && gpatch && ph > 0 && pw > 0) return zero_gpatch(who, gpatch, ph, pw, st);  // empty batch
+    if (!gout_bf16 || !xy || !std6 || (geometry && !theta) || (!keep_bits && !patch)) {  // gpatch == NULL: the final sum is left to vaa_step_epilogue
+        set_error("%s: null pointer argument", who);
+        return VAA_E_INVALID;
+    }
+    const int rc = check_patch_call(who, B, ph, pw, geometry, mask_mode);
+    if (rc != VAA_OK) return rc;
     if (!ws || ws_bytes < vaa_patch_grad_ws_bytes(B, ph, pw)) {
-        set_error("vaa_patch_grad_gather: workspace %zu B < required %zu B", ws_bytes, vaa_patch_grad_ws_bytes(B, ph, pw));
+        set_error("%s: workspace %zu B < required %zu B", who, ws_bytes, vaa_patch_grad_ws_bytes(B, ph, pw));
         return VAA_E_WORKSPACE;
     }
-    GradArgs a;
-    a.g = gout_bf16; a.patch = patch; a.xy = xy; a.theta = theta; a.keep = keep_bits; a.partial = (float*)ws; a.pdesc = nullptr;
-    a.B = B; a.ph = ph; a.pw = pw; a.geometry = geometry ? 1 : 0; a.mask_mode = mask_mode; a.band_rows = ph;
-    for (int q = 0; q < 6; ++q) a.istd6[q] = (float)(1.0 / (double)std6[q]);
-    a.geff = nullptr; a.geff2 = nullptr; a.geff_bf16 = 0; a.keep_t = nullptr;
-    return launch_scatter_reduce<false>(a, gpatch, st, "vaa_patch_grad_gather");
+    return launch_scatter_reduce<false>(grad_args(gout_bf16, patch, nullptr, xy, theta, keep_bits, (float*)ws, B, ph, pw, geometry, mask_mode, std6),
+                                        gpatch, st, who);
 }
 
 // K2 with one patch per image (resize_patch=True, appply_random_transform.py:113-118): image b's patch is packed + offset_b,
@@ -629,29 +637,16 @@ extern "C" int vaa_patch_grad_gather_multi(const uint16_t* gout_bf16, const floa
                                            const float* theta, const uint8_t* keep_bits, int B, int max_h, int max_w, int geometry,
                                            int mask_mode, const float* std6, float* gpacked, void* stream) {
     using namespace vaa;
+    const char* who = "vaa_patch_grad_gather_multi";
     if (B == 0) return VAA_OK;
     if (!gout_bf16 || !pdesc || !xy || !std6 || !gpacked || (geometry && !theta) || (!keep_bits && !packed)) {
-        set_error("vaa_patch_grad_gather_multi: null pointer argument");
+        set_error("%s: null pointer argument", who);
         return VAA_E_INVALID;
     }
-    if (B < 0 || max_h <= 0 || max_w <= 0 || (mask_mode != VAA_MASK_LT_M20 && mask_mode != VAA_MASK_NE_M100)) {
-        set_error("vaa_patch_grad_gather_multi: bad sizes/mode (B=%d max_h=%d max_w=%d mask_mode=%d)", B, max_h, max_w, mask_mode);
-        return VAA_E_INVALID;
-    }
-    if (max_h > VAA_IMG || max_w > VAA_IMG) {
-        set_error("vaa_patch_grad_gather_multi: patch bound %dx%d larger than the frame", max_h, max_w);
-        return VAA_E_UNSUPPORTED;
-    }
-    if (geometry && mask_mode == VAA_MASK_NE_M100) {
-        set_error("vaa_patch_grad_gather_multi: VAA_MASK_NE_M100 is defined for geometry=0 only");
-        return VAA_E_UNSUPPORTED;
-    }
-    GradArgs a;
-    a.g = gout_bf16; a.patch = packed; a.xy = xy; a.theta = theta; a.keep = keep_bits; a.partial = gpacked; a.pdesc = pdesc;
-    a.B = B; a.ph = max_h; a.pw = max_w; a.geometry = geometry ? 1 : 0; a.mask_mode = mask_mode;
-    for (int q = 0; q < 6; ++q) a.istd6[q] = (float)(1.0 / (double)std6[q]);
-    a.geff = nullptr; a.geff2 = nullptr; a.geff_bf16 = 0; a.keep_t = nullptr;
-    return launch_scatter_multi<false>(a, max_h, max_w, (hipStream_t)stream, "vaa_patch_grad_gather_multi");
+    const int rc = check_patch_call(who, B, max_h, max_w, geometry, mask_mode);
+    if (rc != VAA_OK) return rc;
+    return launch_scatter_multi<false>(grad_args(gout_bf16, packed, pdesc, xy, theta, keep_bits, gpacked, B, max_h, max_w, geometry, mask_mode, std6),
+                                       (hipStream_t)stream, who);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -1146,22 +1141,26 @@ static int launch_embed_tiles(EmbedArgs& e, int ph, int pw, hipStream_t st, cons
             nch = eff <= 24 ? 5 : (eff <= 40 ? 3 : 2);
         }
         const int nbmax = ((kNBlocks + nch - 1) / nch + VAA_EMBED_WAVES - 1) / VAA_EMBED_WAVES;  // 1, 2 or 3
-        const void* fn = nullptr;
-        if (e.tower_split) fn = nbmax == 1 ? (const void*)embed_dgrad_tiles_lds_kernel<true, 1> : (nbmax == 2 ? (const void*)embed_dgrad_tiles_lds_kernel<true, 2> : (const void*)embed_dgrad_tiles_lds_kernel<true, 3>);
-        else fn = (const void*)embed_dgrad_tiles_lds_kernel<false, 2>;
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fast) != hipSuccess) {
-            set_error("%s: hipFuncSetAttribute failed", who);
-            return VAA_E_LAUNCH;
-        }
         const long units = (long)B * ny;
         // SPLIT: every XCD takes ceil(units / 4) units of ITS tower; else 8 XCDs share the units
         const long slots = e.tower_split ? (units + 3) / 4 : (units + 7) / 8;
         e.pair_bf16 = (e.tower_split && e.round_bf16 && !getenv("VAA_K2E_F32_PAIRS")) ? 1 : 0;
         const dim3 grid((unsigned)(slots * 8 * nch)), blk(kEmbedFastThreads);
-        if (!e.tower_split) VAA_LAUNCH((embed_dgrad_tiles_lds_kernel<false, 2>), grid, blk, lds_fast, st, e, nch);
-        else if (nbmax == 1) VAA_LAUNCH((embed_dgrad_tiles_lds_kernel<true, 1>), grid, blk, lds_fast, st, e, nch);
-        else if (nbmax == 2) VAA_LAUNCH((embed_dgrad_tiles_lds_kernel<true, 2>), grid, blk, lds_fast, st, e, nch);
-        else VAA_LAUNCH((embed_dgrad_tiles_lds_kernel<true, 3>), grid, blk, lds_fast, st, e, nch);
+        const auto launch = [&](auto split, auto nb) {  // the one launch site of embed_dgrad_tiles_lds_kernel<SPLIT, NB>
+            constexpr bool SPLIT = decltype(split)::value;
+            constexpr int NB = decltype(nb)::value;
+            if (hipFuncSetAttribute((const void*)embed_dgrad_tiles_lds_kernel<SPLIT, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fast) != hipSuccess) {
+                set_error("%s: hipFuncSetAttribute failed", who);
+                return VAA_E_LAUNCH;
+            }
+            VAA_LAUNCH((embed_dgrad_tiles_lds_kernel<SPLIT, NB>), grid, blk, lds_fast, st, e, nch);
+            return VAA_OK;
+        };
+        using std::integral_constant;
+        if (e.tower_split && nbmax == 1) return launch(std::true_type{}, integral_constant<int, 1>{});
+        if (e.tower_split && nbmax == 2) return launch(std::true_type{}, integral_constant<int, 2>{});
+        if (e.tower_split) return launch(std::true_type{}, integral_constant<int, 3>{});
+        return launch(std::false_type{}, integral_constant<int, 2>{});
     } else {  // wide towers: fragments straight from global memory
         const int nch = (kNBlocks + 3) / 4;  // 10 workgroups per image
         VAA_LAUNCH(embed_dgrad_tiles_kernel, dim3((unsigned)((B + 7) / 8 * 8) * nch, ny), dim3(kEmbedThreads), 0, st, e, nch);
@@ -1196,60 +1195,60 @@ extern "C" size_t vaa_patch_embed_grad_ws_bytes(int B, int ph, int pw) {
     return vaa_patch_grad_ws_bytes(B, ph, pw) + 2 * (size_t)B * 256 * vaa::kTileElems * sizeof(float) + 256;  // partial tiles + one tile-gradient buffer per tower
 }
 
+extern "C" size_t vaa_patch_embed_grad_multi_ws_bytes(int B) {
+    if (B <= 0) return 0;
+    return 2 * (size_t)B * 256 * vaa::kTileElems * sizeof(float) + 256;
+}
+
+extern "C" int vaa_patch_grad_partials(int B) { return B > 0 ? vaa::grad_sched(B).gx : 0; }
+
 namespace vaa {
 
-// K2' for one patch per batch. keep_tiles / tile_flags (K1's tile-major outputs) replace keep_bits when given; gpatch == nullptr leaves the
-// fixed-order sum of the partial tiles (ws[0 .. parts*3*ph*pw), parts = vaa_patch_grad_partials(B)) to the caller's vaa_step_epilogue.
-static int embed_grad_gather_impl(const char* who, const uint16_t* dy0, int D0, const uint16_t* dy1, int D1, const uint16_t* wt0, const uint16_t* wt1,
-                                  const float* patch, const int32_t* xy, const float* theta, const uint8_t* keep_bits, const uint16_t* keep_tiles,
-                                  const uint32_t* tile_flags, int B, int ph, int pw, int geometry, int mask_mode, const float* std6,
-                                  int round_bf16, float* gpatch, bool defer_reduce, void* ws, size_t ws_bytes, void* stream) {
+// K2' behind its four entry points. keep_tiles / tile_flags (K1's tile-major outputs) replace keep_bits when given.
+//   !multi (pdesc == nullptr), one patch per batch: the partial tiles sit at the front of the workspace (ws[0 .. parts*3*ph*pw), parts =
+//       vaa_patch_grad_partials(B)), the tile gradients behind them; gout = gpatch, or defer_reduce to leave the fixed-order sum of the partial
+//       tiles to the caller's vaa_step_epilogue.
+//   multi, one patch per image (resize_patch=True; ph / pw bound the sizes): the tile gradients do not depend on the patches and take the
+//       whole workspace; the gather runs in MULTI mode and drains every image's own gradient into gout = gpacked.
+static int embed_grad_gather_impl(const char* who, const uint16_t* dy0, int D0, const uint16_t* dy1, int D1, const uint16_t* wp0, const uint16_t* wp1,
+                                  const float* patch, const int32_t* pdesc, bool multi, const int32_t* xy, const float* theta, const uint8_t* keep_bits,
+                                  const uint16_t* keep_tiles, const uint32_t* tile_flags, int B, int ph, int pw, int geometry, int mask_mode,
+                                  const float* std6, int round_bf16, float* gout, bool defer_reduce, void* ws, size_t ws_bytes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (B == 0 && gpatch && ph > 0 && pw > 0) {
-        if (hipMemsetAsync(gpatch, 0, (size_t)3 * ph * pw * sizeof(float), st) != hipSuccess) return check_launch(who);
-        return VAA_OK;
-    }
-    const bool tiled_keep = keep_tiles != nullptr;
-    if (!dy0 || !dy1 || !wt0 || !wt1 || !xy || !std6 || (!gpatch && !defer_reduce) || (!keep_bits && !tiled_keep) || (tiled_keep && !tile_flags) ||
-        (geometry && !theta)) {
+    if (B == 0 && multi) return VAA_OK;
+    if (B == 0 && gout && ph > 0 && pw > 0) return zero_gpatch(who, gout, ph, pw, st);
+    if (!dy0 || !dy1 || !wp0 || !wp1 || !xy || !std6 || (multi && !pdesc) || (!gout && !defer_reduce) || (!keep_bits && !keep_tiles) ||
+        (keep_tiles && !tile_flags) || (geometry && !theta)) {
         set_error("%s: null pointer argument (the keep mask of K1 is required)", who);
         return VAA_E_INVALID;
     }
-    if (B <= 0 || ph <= 0 || pw <= 0 || D0 <= 0 || D1 <= 0 || (D0 % 64) != 0 || (D1 % 64) != 0 ||
-        (mask_mode != VAA_MASK_LT_M20 && mask_mode != VAA_MASK_NE_M100)) {
-        set_error("%s: bad sizes/mode (B=%d ph=%d pw=%d D0=%d D1=%d; D %% 64 == 0)", who, B, ph, pw, D0, D1);
+    if (B <= 0 || D0 <= 0 || D1 <= 0 || (D0 % 64) != 0 || (D1 % 64) != 0) {
+        set_error("%s: bad sizes (B=%d D0=%d D1=%d; D %% 64 == 0)", who, B, D0, D1);
         return VAA_E_INVALID;
     }
-    if (ph > VAA_IMG || pw > VAA_IMG) {
-        set_error("%s: patch %dx%d larger than the frame", who, ph, pw);
-        return VAA_E_UNSUPPORTED;
-    }
-    if (geometry && mask_mode == VAA_MASK_NE_M100) {
-        set_error("%s: VAA_MASK_NE_M100 is defined for geometry=0 only", who);
-        return VAA_E_UNSUPPORTED;
-    }
-    if (!ws || ws_bytes < vaa_patch_embed_grad_ws_bytes(B, ph, pw)) {
-        set_error("%s: workspace %zu B < required %zu B", who, ws_bytes, vaa_patch_embed_grad_ws_bytes(B, ph, pw));
+    int rc = check_patch_call(who, B, ph, pw, geometry, mask_mode);
+    if (rc != VAA_OK) return rc;
+    const size_t need = multi ? vaa_patch_embed_grad_multi_ws_bytes(B) : vaa_patch_embed_grad_ws_bytes(B, ph, pw);
+    if (!ws || ws_bytes < need) {
+        set_error("%s: workspace %zu B < required %zu B", who, ws_bytes, need);
         return VAA_E_WORKSPACE;
     }
-    char* wsb = reinterpret_cast<char*>(ws);
-    const size_t part_bytes = (vaa_patch_grad_ws_bytes(B, ph, pw) + 255) / 256 * 256;
+    const size_t part_bytes = multi ? 0 : (vaa_patch_grad_ws_bytes(B, ph, pw) + 255) / 256 * 256;
+    // a non-null keep selects the stored-mask instantiation: the tile-major words stand in for the bits
+    GradArgs a = grad_args(nullptr, patch, pdesc, xy, theta, keep_tiles ? reinterpret_cast<const uint8_t*>(keep_tiles) : keep_bits,
+                           multi ? gout : (float*)ws, B, ph, pw, geometry, mask_mode, std6);
     EmbedArgs e;
-    e.dy0 = dy0; e.dy1 = dy1; e.wt0 = wt0; e.wt1 = wt1; e.keep = keep_bits; e.flags = tile_flags;
-    e.geff = reinterpret_cast<float*>(wsb + part_bytes);
+    e.dy0 = dy0; e.dy1 = dy1; e.wt0 = wp0; e.wt1 = wp1; e.keep = keep_bits; e.flags = tile_flags;
+    e.geff = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + part_bytes);
     e.geff2 = e.geff + (size_t)B * 256 * kTileElems;
     e.B = B; e.D0 = D0; e.D1 = D1; e.round_bf16 = round_bf16 ? 1 : 0;
-    for (int q = 0; q < 6; ++q) e.istd6[q] = (float)(1.0 / (double)std6[q]);
+    for (int q = 0; q < 6; ++q) e.istd6[q] = a.istd6[q];
     if (launch_embed_tiles(e, ph, pw, st, who) != VAA_OK) return VAA_E_LAUNCH;
-    int rc = check_launch(who);
+    rc = check_launch(who);
     if (rc != VAA_OK) return rc;
-    GradArgs a;
-    a.g = nullptr; a.patch = patch; a.xy = xy; a.theta = theta; a.keep = keep_bits; a.partial = (float*)ws; a.pdesc = nullptr;
-    a.B = B; a.ph = ph; a.pw = pw; a.geometry = geometry ? 1 : 0; a.mask_mode = mask_mode;
-    for (int q = 0; q < 6; ++q) a.istd6[q] = e.istd6[q];
     a.geff = e.geff; a.geff2 = e.tower_split ? e.geff2 : nullptr; a.geff_bf16 = e.pair_bf16; a.keep_t = keep_tiles;
-    if (keep_tiles) a.keep = reinterpret_cast<const uint8_t*>(keep_tiles);  // non-null selects the stored-mask instantiation
-    return launch_scatter_reduce<true>(a, defer_reduce ? nullptr : gpatch, st, who);
+    if (!multi) return launch_scatter_reduce<true>(a, defer_reduce ? nullptr : gout, st, who);
+    return launch_scatter_multi<true>(a, st, who);
 }
 
 }  // namespace vaa
@@ -1258,80 +1257,24 @@ extern "C" int vaa_patch_embed_grad_gather(const uint16_t* dy0, int D0, const ui
                                            const float* patch, const int32_t* xy, const float* theta, const uint8_t* keep_bits, int B, int ph,
                                            int pw, int geometry, int mask_mode, const float* std6, int round_bf16, float* gpatch, void* ws,
                                            size_t ws_bytes, void* stream) {
-    return vaa::embed_grad_gather_impl("vaa_patch_embed_grad_gather", dy0, D0, dy1, D1, wt0, wt1, patch, xy, theta, keep_bits, nullptr, nullptr, B, ph,
-                                       pw, geometry, mask_mode, std6, round_bf16, gpatch, false, ws, ws_bytes, stream);
+    return vaa::embed_grad_gather_impl("vaa_patch_embed_grad_gather", dy0, D0, dy1, D1, wt0, wt1, patch, nullptr, false, xy, theta, keep_bits, nullptr, nullptr,
+                                       B, ph, pw, geometry, mask_mode, std6, round_bf16, gpatch, false, ws, ws_bytes, stream);
 }
-
-extern "C" int vaa_patch_grad_partials(int B) { return B > 0 ? vaa::grad_sched(B).gx : 0; }
 
 extern "C" int vaa_patch_embed_grad_gather_tiles(const uint16_t* dy0, int D0, const uint16_t* dy1, int D1, const uint16_t* wt0, const uint16_t* wt1,
                                                  const float* patch, const int32_t* xy, const float* theta, const uint16_t* keep_tiles,
                                                  const uint32_t* tile_flags, int B, int ph, int pw, int geometry, int mask_mode, const float* std6,
                                                  int round_bf16, float* gpatch, void* ws, size_t ws_bytes, void* stream) {
-    return vaa::embed_grad_gather_impl("vaa_patch_embed_grad_gather_tiles", dy0, D0, dy1, D1, wt0, wt1, patch, xy, theta, nullptr, keep_tiles, tile_flags,
-                                       B, ph, pw, geometry, mask_mode, std6, round_bf16, gpatch, gpatch == nullptr, ws, ws_bytes, stream);
+    return vaa::embed_grad_gather_impl("vaa_patch_embed_grad_gather_tiles", dy0, D0, dy1, D1, wt0, wt1, patch, nullptr, false, xy, theta, nullptr, keep_tiles,
+                                       tile_flags, B, ph, pw, geometry, mask_mode, std6, round_bf16, gpatch, gpatch == nullptr, ws, ws_bytes, stream);
 }
-
-extern "C" size_t vaa_patch_embed_grad_multi_ws_bytes(int B) {
-    if (B <= 0) return 0;
-    return 2 * (size_t)B * 256 * vaa::kTileElems * sizeof(float) + 256;
-}
-
-namespace vaa {
-
-// K2' with one patch per image (resize_patch=True): the tile gradients do not depend on the patches, the gather runs in MULTI mode.
-static int embed_grad_gather_multi_impl(const char* who, const uint16_t* dy0, int D0, const uint16_t* dy1, int D1, const uint16_t* wp0, const uint16_t* wp1,
-                                        const float* packed, const int32_t* pdesc, const int32_t* xy, const float* theta, const uint8_t* keep_bits,
-                                        const uint16_t* keep_tiles, const uint32_t* tile_flags, int B, int max_h, int max_w, int geometry, int mask_mode,
-                                        const float* std6, int round_bf16, float* gpacked, void* ws, size_t ws_bytes, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (B == 0) return VAA_OK;
-    if (!dy0 || !dy1 || !wp0 || !wp1 || !pdesc || !xy || !std6 || !gpacked || (!keep_bits && !keep_tiles) || (keep_tiles && !tile_flags) || (geometry && !theta)) {
-        set_error("%s: null pointer argument (the keep mask of K1 is required)", who);
-        return VAA_E_INVALID;
-    }
-    if (B < 0 || max_h <= 0 || max_w <= 0 || D0 <= 0 || D1 <= 0 || (D0 % 64) != 0 || (D1 % 64) != 0 ||
-        (mask_mode != VAA_MASK_LT_M20 && mask_mode != VAA_MASK_NE_M100)) {
-        set_error("%s: bad sizes/mode (B=%d max_h=%d max_w=%d D0=%d D1=%d; D %% 64 == 0)", who, B, max_h, max_w, D0, D1);
-        return VAA_E_INVALID;
-    }
-    if (max_h > VAA_IMG || max_w > VAA_IMG) {
-        set_error("%s: patch bound %dx%d larger than the frame", who, max_h, max_w);
-        return VAA_E_UNSUPPORTED;
-    }
-    if (geometry && mask_mode == VAA_MASK_NE_M100) {
-        set_error("%s: VAA_MASK_NE_M100 is defined for geometry=0 only", who);
-        return VAA_E_UNSUPPORTED;
-    }
-    if (!ws || ws_bytes < vaa_patch_embed_grad_multi_ws_bytes(B)) {
-        set_error("%s: workspace %zu B < required %zu B", who, ws_bytes, vaa_patch_embed_grad_multi_ws_bytes(B));
-        return VAA_E_WORKSPACE;
-    }
-    EmbedArgs e;
-    e.dy0 = dy0; e.dy1 = dy1; e.wt0 = wp0; e.wt1 = wp1; e.keep = keep_bits; e.flags = tile_flags; e.geff = reinterpret_cast<float*>(ws);
-    e.geff2 = e.geff + (size_t)B * 256 * kTileElems;
-    e.B = B; e.D0 = D0; e.D1 = D1; e.round_bf16 = round_bf16 ? 1 : 0;
-    for (int q = 0; q < 6; ++q) e.istd6[q] = (float)(1.0 / (double)std6[q]);
-    if (launch_embed_tiles(e, max_h, max_w, st, who) != VAA_OK) return VAA_E_LAUNCH;
-    int rc = check_launch(who);
-    if (rc != VAA_OK) return rc;
-    GradArgs a;
-    a.g = nullptr; a.patch = packed; a.xy = xy; a.theta = theta; a.keep = keep_bits; a.partial = gpacked; a.pdesc = pdesc;
-    a.B = B; a.ph = max_h; a.pw = max_w; a.geometry = geometry ? 1 : 0; a.mask_mode = mask_mode;
-    for (int q = 0; q < 6; ++q) a.istd6[q] = e.istd6[q];
-    a.geff = e.geff; a.geff2 = e.tower_split ? e.geff2 : nullptr; a.geff_bf16 = e.pair_bf16; a.keep_t = keep_tiles;
-    if (keep_tiles) a.keep = reinterpret_cast<const uint8_t*>(keep_tiles);  // non-null selects the stored-mask instantiation
-    return launch_scatter_multi<true>(a, max_h, max_w, st, who);
-}
-
-}  // namespace vaa
 
 extern "C" int vaa_patch_embed_grad_gather_multi(const uint16_t* dy0, int D0, const uint16_t* dy1, int D1, const uint16_t* wp0, const uint16_t* wp1,
                                                  const float* packed, const int32_t* pdesc, const int32_t* xy, const float* theta,
                                                  const uint8_t* keep_bits, int B, int max_h, int max_w, int geometry, int mask_mode,
                                                  const float* std6, int round_bf16, float* gpacked, void* ws, size_t ws_bytes, void* stream) {
-    return vaa::embed_grad_gather_multi_impl("vaa_patch_embed_grad_gather_multi", dy0, D0, dy1, D1, wp0, wp1, packed, pdesc, xy, theta, keep_bits, nullptr, nullptr,
-                                             B, max_h, max_w, geometry, mask_mode, std6, round_bf16, gpacked, ws, ws_bytes, stream);
+    return vaa::embed_grad_gather_impl("vaa_patch_embed_grad_gather_multi", dy0, D0, dy1, D1, wp0, wp1, packed, pdesc, true, xy, theta, keep_bits, nullptr, nullptr,
+                                       B, max_h, max_w, geometry, mask_mode, std6, round_bf16, gpacked, false, ws, ws_bytes, stream);
 }
 
 extern "C" int vaa_patch_embed_grad_gather_multi_tiles(const uint16_t* dy0, int D0, const uint16_t* dy1, int D1, const uint16_t* wp0, const uint16_t* wp1,
@@ -1339,6 +1282,6 @@ extern "C" int vaa_patch_embed_grad_gather_multi_tiles(const uint16_t* dy0, int 
                                                        const uint16_t* keep_tiles, const uint32_t* tile_flags, int B, int max_h, int max_w, int geometry,
                                                        int mask_mode, const float* std6, int round_bf16, float* gpacked, void* ws, size_t ws_bytes,
                                                        void* stream) {
-    return vaa::embed_grad_gather_multi_impl("vaa_patch_embed_grad_gather_multi_tiles", dy0, D0, dy1, D1, wp0, wp1, packed, pdesc, xy, theta, nullptr, keep_tiles,
-                                             tile_flags, B, max_h, max_w, geometry, mask_mode, std6, round_bf16, gpacked, ws, ws_bytes, stream);
+    return vaa::embed_grad_gather_impl("vaa_patch_embed_grad_gather_multi_tiles", dy0, D0, dy1, D1, wp0, wp1, packed, pdesc, true, xy, theta, nullptr, keep_tiles,
+                                       tile_flags, B, max_h, max_w, geometry, mask_mode, std6, round_bf16, gpacked, false, ws, ws_bytes, stream);
 }

@@ -109,86 +109,122 @@ def async_error_check() -> None:
 
 
 # ------------------------------------------------------------------------------------------------------
-# K1 / K2
+# K1 / K2 / K2': one body per kernel family (_k1, _k2, _k2e); the public wrappers below name the variant
 # ------------------------------------------------------------------------------------------------------
-def patch_apply_fwd(img_u8, patch, xy, theta, geometry: bool, mask_mode: int = MASK_LT_M20, want_keep: bool = True,
-                    mean6=None, std6=None):
-    """K1. img_u8 [B,224,224,3] u8, patch [3,ph,pw] f32, xy [B,2] i32, theta [B,6] f32 -> (bf16 [B,6,224,224], keep bits)."""
-    B = img_u8.shape[0]
-    _need(img_u8, torch.uint8, "img_u8", (B, IMG, IMG, 3))
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _placement(B: int, patch, xy, theta, geometry: bool, pdesc, max_hw):
+    """The arguments every K1 / K2 / K2' call shares, checked once: the patch (or, with pdesc / max_hw, the packed per-image patches and their
+    bounds), where it lands (xy) and how it is warped (theta). Returns the C arguments (patch, [pdesc,] xy, theta) and (ph, pw)."""
     _need(patch, torch.float32, "patch")
     _need(xy, torch.int32, "xy", (B, 2))
     if geometry:
         _need(theta, torch.float32, "theta", (B, 6))
-    ph, pw = int(patch.shape[1]), int(patch.shape[2])
-    out = torch.empty((B, 6, IMG, IMG), dtype=torch.bfloat16, device=img_u8.device)
-    keep = torch.empty((B, 3, IMG * IMG // 8), dtype=torch.uint8, device=img_u8.device) if want_keep else None
+    if pdesc is None:
+        return (patch.data_ptr(), xy.data_ptr(), theta.data_ptr() if geometry else None), (int(patch.shape[1]), int(patch.shape[2]))
+    _need(pdesc, torch.int32, "pdesc", (B, 4))
+    return (patch.data_ptr(), pdesc.data_ptr(), xy.data_ptr(), theta.data_ptr() if geometry else None), (int(max_hw[0]), int(max_hw[1]))
+
+
+def _partials_view(ws, B: int, ph: int, pw: int):
+    """The partial tiles [parts, 3*ph*pw] a deferred K2 / K2' left at the front of its workspace, for ops.step_epilogue to add."""
+    parts, n = _lib.lib().vaa_patch_grad_partials(B), 3 * ph * pw
+    return ws[: parts * n * 4].view(torch.float32).view(parts, n)
+
+
+def _k1(img_u8, patch, xy, theta, geometry, mask_mode, mean6, std6, pdesc=None, max_hw=None, tiles=False, want_keep=True):
+    """K1 in every form. Planar: -> (bf16 [B,6,224,224], keep bits or None); tiles: -> (out0, out1, keep_tiles, tile_flags)."""
+    B = img_u8.shape[0]
+    _need(img_u8, torch.uint8, "img_u8", (B, IMG, IMG, 3))
+    place, (ph, pw) = _placement(B, patch, xy, theta, geometry, pdesc, max_hw)
+    dev = img_u8.device
+    if tiles:
+        name = "patch_apply_fwd_tiles"
+        outs = (torch.empty((B, 256, 588), dtype=torch.bfloat16, device=dev), torch.empty((B, 256, 588), dtype=torch.bfloat16, device=dev),
+                torch.empty((B, 3, 256, 14), dtype=torch.int16, device=dev), torch.empty((B, 256), dtype=torch.int32, device=dev))
+        if pdesc is None:  # this entry point takes the descriptor in both cases
+            place = (place[0], None) + place[1:]
+    else:
+        name = "patch_apply_fwd" if pdesc is None else "patch_apply_fwd_multi"
+        outs = (torch.empty((B, 6, IMG, IMG), dtype=torch.bfloat16, device=dev),
+                torch.empty((B, 3, IMG * IMG // 8), dtype=torch.uint8, device=dev) if want_keep else None)
     mean_c = _MEAN if mean6 is None else _lib.f32x(mean6)
     std_c = _STD if std6 is None else _lib.f32x(std6)
-    with _timed("K1_patch_apply_fwd", B=B, ph=ph, pw=pw):
-        rc = _lib.lib().vaa_patch_apply_fwd(
-            img_u8.data_ptr(), patch.data_ptr(), xy.data_ptr(), theta.data_ptr() if geometry else None, B, ph, pw,
-            int(bool(geometry)), int(mask_mode), mean_c, std_c, out.data_ptr(), keep.data_ptr() if want_keep else None, _stream())
-    _lib.check(rc, "vaa_patch_apply_fwd")
-    return out, keep
+    with _timed("K1_" + name, B=B, ph=ph, pw=pw):
+        rc = getattr(_lib.lib(), "vaa_" + name)(img_u8.data_ptr(), *place, B, ph, pw, int(bool(geometry)), int(mask_mode), mean_c, std_c,
+                                                *map(_ptr, outs), _stream())
+    _lib.check(rc, "vaa_" + name)
+    return outs
+
+
+def _grad_call(name, kind, B, lead, patch, xy, theta, mask, geometry, mask_mode, std6, tail, pdesc, max_hw, defer_reduce):
+    """What K2 and K2' share behind their own leading (`lead`: the incoming gradient) and trailing (`tail`) arguments: the placement, the keep
+    mask (`mask`: tensors as the entry point takes them), the output and the workspace. One patch: -> dL/d patch [3,ph,pw], or with defer_reduce
+    the partial tiles (_partials_view). pdesc / max_hw: -> the gradient of every image's own patch, in the layout of the packed `patch`."""
+    place, (ph, pw) = _placement(B, patch, xy, theta, geometry, pdesc, max_hw)
+    L = _lib.lib()
+    ws = ()
+    if pdesc is not None:  # (no partial tiles here: no wrapper offers defer_reduce with per-image patches)
+        out = torch.zeros_like(patch)
+        if kind == "k2e":
+            ws = (_workspace(patch.device, L.vaa_patch_embed_grad_multi_ws_bytes(B), kind),)
+    else:
+        out = None if defer_reduce else torch.empty_like(patch)
+        ws = (_workspace(patch.device, (L.vaa_patch_grad_ws_bytes if kind == "k2" else L.vaa_patch_embed_grad_ws_bytes)(B, ph, pw), kind),)
+    std_c = _STD if std6 is None else _lib.f32x(std6)
+    with _timed("K2_" + name, B=B, ph=ph, pw=pw):
+        rc = getattr(L, "vaa_" + name)(*lead, *place, *map(_ptr, mask), B, ph, pw, int(bool(geometry)), int(mask_mode), std_c, *tail, _ptr(out),
+                                       *(a for w in ws for a in (w.data_ptr(), w.numel())), _stream())
+    _lib.check(rc, "vaa_" + name)
+    return _partials_view(ws[0], B, ph, pw) if defer_reduce else out
+
+
+def _k2(gout_bf16, patch, xy, theta, keep_bits, geometry, mask_mode, std6, pdesc=None, max_hw=None, defer_reduce=False):
+    """K2 in every form: the model's bf16 pixel gradient [B,6,224,224] -> the patch gradient (_grad_call). keep_bits=None: the mask is re-derived."""
+    B = gout_bf16.shape[0]
+    _need(gout_bf16, torch.bfloat16, "gout_bf16", (B, 6, IMG, IMG))
+    if keep_bits is not None:
+        _need(keep_bits, torch.uint8, "keep_bits", (B, 3, IMG * IMG // 8))
+    name = "patch_grad_gather" if pdesc is None else "patch_grad_gather_multi"
+    return _grad_call(name, "k2", B, (gout_bf16.data_ptr(),), patch, xy, theta, (keep_bits,), geometry, mask_mode, std6, (), pdesc, max_hw, defer_reduce)
+
+
+def _k2e(dy0, dy1, wp0, wp1, patch, xy, theta, keep, tile_flags, geometry, mask_mode, std6, round_bf16, pdesc=None, max_hw=None, defer_reduce=False):
+    """K2' in every form: the gradients of the two patch-embed outputs -> the patch gradient (_grad_call). The keep mask is K1's: keep bits
+    (tile_flags=None), or the tile-major keep words with their tile flags."""
+    B = dy0.shape[0]
+    D0, D1 = int(dy0.shape[2]), int(dy1.shape[2])
+    _need(dy0, torch.bfloat16, "dy0", (B, 256, D0))
+    _need(dy1, torch.bfloat16, "dy1", (B, 256, D1))
+    _need(wp0, torch.bfloat16, "wp0", (592 * D0,))
+    _need(wp1, torch.bfloat16, "wp1", (592 * D1,))
+    if tile_flags is None:
+        mask = (_need(keep, torch.uint8, "keep_bits", (B, 3, IMG * IMG // 8)),)
+    else:
+        mask = (_need(keep, torch.int16, "keep_tiles", (B, 3, 256, 14)), _need(tile_flags, torch.int32, "tile_flags", (B, 256)))
+    name = "patch_embed_grad_gather" + ("" if pdesc is None else "_multi") + ("" if tile_flags is None else "_tiles")
+    lead = (dy0.data_ptr(), D0, dy1.data_ptr(), D1, wp0.data_ptr(), wp1.data_ptr())
+    return _grad_call(name, "k2e", B, lead, patch, xy, theta, mask, geometry, mask_mode, std6, (int(bool(round_bf16)),), pdesc, max_hw, defer_reduce)
+
+
+def patch_apply_fwd(img_u8, patch, xy, theta, geometry: bool, mask_mode: int = MASK_LT_M20, want_keep: bool = True,
+                    mean6=None, std6=None):
+    """K1. img_u8 [B,224,224,3] u8, patch [3,ph,pw] f32, xy [B,2] i32, theta [B,6] f32 -> (bf16 [B,6,224,224], keep bits)."""
+    return _k1(img_u8, patch, xy, theta, geometry, mask_mode, mean6, std6, want_keep=want_keep)
 
 
 def patch_apply_fwd_tiles(img_u8, patch, xy, theta, geometry: bool, mask_mode: int = MASK_LT_M20, mean6=None, std6=None, pdesc=None, max_hw=None):
     """K1 in tile-major form (vaa_patch_apply_fwd_tiles): -> (out0, out1 bf16 [B,256,588], keep_tiles u16 [B,3,256,14], tile_flags u32 [B,256]).
     out_k are the operands of the two ViT patch-embed GEMMs (tile t = ty*16 + tx, element c*196 + y*14 + x). pdesc/max_hw: per-image patches."""
-    B = img_u8.shape[0]
-    _need(img_u8, torch.uint8, "img_u8", (B, IMG, IMG, 3))
-    _need(patch, torch.float32, "patch")
-    _need(xy, torch.int32, "xy", (B, 2))
-    if geometry:
-        _need(theta, torch.float32, "theta", (B, 6))
-    if pdesc is not None:
-        _need(pdesc, torch.int32, "pdesc", (B, 4))
-        ph, pw = int(max_hw[0]), int(max_hw[1])
-    else:
-        ph, pw = int(patch.shape[1]), int(patch.shape[2])
-    dev = img_u8.device
-    out0 = torch.empty((B, 256, 588), dtype=torch.bfloat16, device=dev)
-    out1 = torch.empty((B, 256, 588), dtype=torch.bfloat16, device=dev)
-    keep_t = torch.empty((B, 3, 256, 14), dtype=torch.int16, device=dev)
-    flags = torch.empty((B, 256), dtype=torch.int32, device=dev)
-    mean_c = _MEAN if mean6 is None else _lib.f32x(mean6)
-    std_c = _STD if std6 is None else _lib.f32x(std6)
-    with _timed("K1_patch_apply_fwd_tiles", B=B, ph=ph, pw=pw):
-        rc = _lib.lib().vaa_patch_apply_fwd_tiles(
-            img_u8.data_ptr(), patch.data_ptr(), pdesc.data_ptr() if pdesc is not None else None, xy.data_ptr(), theta.data_ptr() if geometry else None,
-            B, ph, pw, int(bool(geometry)), int(mask_mode), mean_c, std_c, out0.data_ptr(), out1.data_ptr(), keep_t.data_ptr(), flags.data_ptr(), _stream())
-    _lib.check(rc, "vaa_patch_apply_fwd_tiles")
-    return out0, out1, keep_t, flags
+    return _k1(img_u8, patch, xy, theta, geometry, mask_mode, mean6, std6, pdesc, max_hw, tiles=True)
 
 
 def patch_grad_gather(gout_bf16, patch, xy, theta, keep_bits, geometry: bool, mask_mode: int = MASK_LT_M20, std6=None, defer_reduce: bool = False):
     """K2. gout_bf16 [B,6,224,224] bf16 -> dL/d patch [3,ph,pw] f32 (sum over the batch). defer_reduce=True returns the partial tiles
     [parts, 3*ph*pw] (a view of the workspace) for ops.step_epilogue to add."""
-    B = gout_bf16.shape[0]
-    _need(gout_bf16, torch.bfloat16, "gout_bf16", (B, 6, IMG, IMG))
-    _need(patch, torch.float32, "patch")
-    _need(xy, torch.int32, "xy", (B, 2))
-    if geometry:
-        _need(theta, torch.float32, "theta", (B, 6))
-    if keep_bits is not None:
-        _need(keep_bits, torch.uint8, "keep_bits", (B, 3, IMG * IMG // 8))
-    ph, pw = int(patch.shape[1]), int(patch.shape[2])
-    L = _lib.lib()
-    nbytes = L.vaa_patch_grad_ws_bytes(B, ph, pw)
-    ws = _workspace(patch.device, nbytes)
-    gpatch = None if defer_reduce else torch.empty_like(patch)
-    std_c = _STD if std6 is None else _lib.f32x(std6)
-    with _timed("K2_patch_grad_gather", B=B, ph=ph, pw=pw):
-        rc = L.vaa_patch_grad_gather(
-            gout_bf16.data_ptr(), patch.data_ptr(), xy.data_ptr(), theta.data_ptr() if geometry else None,
-            keep_bits.data_ptr() if keep_bits is not None else None, B, ph, pw, int(bool(geometry)), int(mask_mode), std_c,
-            gpatch.data_ptr() if gpatch is not None else None, ws.data_ptr(), ws.numel(), _stream())
-    _lib.check(rc, "vaa_patch_grad_gather")
-    if defer_reduce:
-        parts, n = L.vaa_patch_grad_partials(B), 3 * ph * pw
-        return ws[: parts * n * 4].view(torch.float32).view(parts, n)
-    return gpatch
+    return _k2(gout_bf16, patch, xy, theta, keep_bits, geometry, mask_mode, std6, defer_reduce=defer_reduce)
 
 
 def pack_embed_weights(wt):
@@ -210,141 +246,26 @@ def patch_embed_grad_gather(dy0, dy1, wp0, wp1, patch, xy, theta, keep_bits, geo
     """K2' (SURVEY.md 8f-3): dL/d patch from the gradients of the two ViT patch-embed OUTPUTS. dy0 [B,256,D0], dy1 [B,256,D1] bf16
     (tokens in tile order), wp0 / wp1 = pack_embed_weights(W^T [588,D]) of the two towers. Only tiles with kept pixels are
     evaluated (MFMA); the pixel gradient is never materialised."""
-    B = dy0.shape[0]
-    D0, D1 = int(dy0.shape[2]), int(dy1.shape[2])
-    _need(dy0, torch.bfloat16, "dy0", (B, 256, D0))
-    _need(dy1, torch.bfloat16, "dy1", (B, 256, D1))
-    _need(wp0, torch.bfloat16, "wp0", (592 * D0,))
-    _need(wp1, torch.bfloat16, "wp1", (592 * D1,))
-    _need(patch, torch.float32, "patch")
-    _need(xy, torch.int32, "xy", (B, 2))
-    if geometry:
-        _need(theta, torch.float32, "theta", (B, 6))
-    _need(keep_bits, torch.uint8, "keep_bits", (B, 3, IMG * IMG // 8))
-    ph, pw = int(patch.shape[1]), int(patch.shape[2])
-    L = _lib.lib()
-    ws = _workspace(patch.device, L.vaa_patch_embed_grad_ws_bytes(B, ph, pw), "k2e")
-    gpatch = torch.empty_like(patch)
-    std_c = _STD if std6 is None else _lib.f32x(std6)
-    with _timed("K2_patch_embed_grad_gather", B=B, ph=ph, pw=pw):
-        rc = L.vaa_patch_embed_grad_gather(dy0.data_ptr(), D0, dy1.data_ptr(), D1, wp0.data_ptr(), wp1.data_ptr(), patch.data_ptr(), xy.data_ptr(),
-                                           theta.data_ptr() if geometry else None, keep_bits.data_ptr(), B, ph, pw, int(bool(geometry)),
-                                           int(mask_mode), std_c, int(bool(round_bf16)), gpatch.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
-    _lib.check(rc, "vaa_patch_embed_grad_gather")
-    return gpatch
+    return _k2e(dy0, dy1, wp0, wp1, patch, xy, theta, keep_bits, None, geometry, mask_mode, std6, round_bf16)
 
 
 def patch_embed_grad_gather_tiles(dy0, dy1, wp0, wp1, patch, xy, theta, keep_tiles, tile_flags, geometry: bool, mask_mode: int = MASK_LT_M20,
                                   std6=None, round_bf16: bool = True, defer_reduce: bool = False):
     """K2' fed by the tile-major mask of patch_apply_fwd_tiles. defer_reduce=True returns (partials view [parts, 3*ph*pw] of the workspace):
     the fixed-order sum is then left to ops.step_epilogue."""
-    B = dy0.shape[0]
-    D0, D1 = int(dy0.shape[2]), int(dy1.shape[2])
-    _need(dy0, torch.bfloat16, "dy0", (B, 256, D0))
-    _need(dy1, torch.bfloat16, "dy1", (B, 256, D1))
-    _need(wp0, torch.bfloat16, "wp0", (592 * D0,))
-    _need(wp1, torch.bfloat16, "wp1", (592 * D1,))
-    _need(patch, torch.float32, "patch")
-    _need(xy, torch.int32, "xy", (B, 2))
-    if geometry:
-        _need(theta, torch.float32, "theta", (B, 6))
-    _need(keep_tiles, torch.int16, "keep_tiles", (B, 3, 256, 14))
-    _need(tile_flags, torch.int32, "tile_flags", (B, 256))
-    ph, pw = int(patch.shape[1]), int(patch.shape[2])
-    L = _lib.lib()
-    ws = _workspace(patch.device, L.vaa_patch_embed_grad_ws_bytes(B, ph, pw), "k2e")
-    gpatch = None if defer_reduce else torch.empty_like(patch)
-    std_c = _STD if std6 is None else _lib.f32x(std6)
-    with _timed("K2_patch_embed_grad_gather_tiles", B=B, ph=ph, pw=pw):
-        rc = L.vaa_patch_embed_grad_gather_tiles(dy0.data_ptr(), D0, dy1.data_ptr(), D1, wp0.data_ptr(), wp1.data_ptr(), patch.data_ptr(), xy.data_ptr(),
-                                                 theta.data_ptr() if geometry else None, keep_tiles.data_ptr(), tile_flags.data_ptr(), B, ph, pw,
-                                                 int(bool(geometry)), int(mask_mode), std_c, int(bool(round_bf16)),
-                                                 gpatch.data_ptr() if gpatch is not None else None, ws.data_ptr(), ws.numel(), _stream())
-    _lib.check(rc, "vaa_patch_embed_grad_gather_tiles")
-    if defer_reduce:
-        parts, n = L.vaa_patch_grad_partials(B), 3 * ph * pw
-        return ws[: parts * n * 4].view(torch.float32).view(parts, n)
-    return gpatch
+    return _k2e(dy0, dy1, wp0, wp1, patch, xy, theta, keep_tiles, tile_flags, geometry, mask_mode, std6, round_bf16, defer_reduce=defer_reduce)
 
 
 def patch_embed_grad_gather_multi(dy0, dy1, wp0, wp1, packed, pdesc, max_hw, xy, theta, keep_bits, geometry: bool, mask_mode: int = MASK_LT_M20,
                                   std6=None, round_bf16: bool = True):
     """K2' with one patch per image (resize_patch=True): like patch_grad_gather_multi, fed by the patch-embed output gradients."""
-    B = dy0.shape[0]
-    D0, D1 = int(dy0.shape[2]), int(dy1.shape[2])
-    _need(dy0, torch.bfloat16, "dy0", (B, 256, D0))
-    _need(dy1, torch.bfloat16, "dy1", (B, 256, D1))
-    _need(wp0, torch.bfloat16, "wp0", (592 * D0,))
-    _need(wp1, torch.bfloat16, "wp1", (592 * D1,))
-    _need(packed, torch.float32, "packed")
-    _need(pdesc, torch.int32, "pdesc", (B, 4))
-    _need(xy, torch.int32, "xy", (B, 2))
-    if geometry:
-        _need(theta, torch.float32, "theta", (B, 6))
-    _need(keep_bits, torch.uint8, "keep_bits", (B, 3, IMG * IMG // 8))
-    L = _lib.lib()
-    ws = _workspace(packed.device, L.vaa_patch_embed_grad_multi_ws_bytes(B), "k2e")
-    gpacked = torch.zeros_like(packed)
-    std_c = _STD if std6 is None else _lib.f32x(std6)
-    with _timed("K2_patch_embed_grad_gather_multi", B=B):
-        rc = L.vaa_patch_embed_grad_gather_multi(dy0.data_ptr(), D0, dy1.data_ptr(), D1, wp0.data_ptr(), wp1.data_ptr(), packed.data_ptr(), pdesc.data_ptr(),
-                                                 xy.data_ptr(), theta.data_ptr() if geometry else None, keep_bits.data_ptr(), B, int(max_hw[0]), int(max_hw[1]),
-                                                 int(bool(geometry)), int(mask_mode), std_c, int(bool(round_bf16)), gpacked.data_ptr(), ws.data_ptr(),
-                                                 ws.numel(), _stream())
-    _lib.check(rc, "vaa_patch_embed_grad_gather_multi")
-    return gpacked
+    return _k2e(dy0, dy1, wp0, wp1, packed, xy, theta, keep_bits, None, geometry, mask_mode, std6, round_bf16, pdesc, max_hw)
 
 
 def patch_embed_grad_gather_multi_tiles(dy0, dy1, wp0, wp1, packed, pdesc, max_hw, xy, theta, keep_tiles, tile_flags, geometry: bool,
                                         mask_mode: int = MASK_LT_M20, std6=None, round_bf16: bool = True):
     """K2' with one patch per image, fed by the tile-major mask of patch_apply_fwd_tiles(pdesc=...)."""
-    B = dy0.shape[0]
-    D0, D1 = int(dy0.shape[2]), int(dy1.shape[2])
-    _need(dy0, torch.bfloat16, "dy0", (B, 256, D0))
-    _need(dy1, torch.bfloat16, "dy1", (B, 256, D1))
-    _need(wp0, torch.bfloat16, "wp0", (592 * D0,))
-    _need(wp1, torch.bfloat16, "wp1", (592 * D1,))
-    _need(packed, torch.float32, "packed")
-    _need(pdesc, torch.int32, "pdesc", (B, 4))
-    _need(xy, torch.int32, "xy", (B, 2))
-    if geometry:
-        _need(theta, torch.float32, "theta", (B, 6))
-    _need(keep_tiles, torch.int16, "keep_tiles", (B, 3, 256, 14))
-    _need(tile_flags, torch.int32, "tile_flags", (B, 256))
-    L = _lib.lib()
-    ws = _workspace(packed.device, L.vaa_patch_embed_grad_multi_ws_bytes(B), "k2e")
-    gpacked = torch.zeros_like(packed)
-    std_c = _STD if std6 is None else _lib.f32x(std6)
-    with _timed("K2_patch_embed_grad_gather_multi_tiles", B=B):
-        rc = L.vaa_patch_embed_grad_gather_multi_tiles(dy0.data_ptr(), D0, dy1.data_ptr(), D1, wp0.data_ptr(), wp1.data_ptr(), packed.data_ptr(), pdesc.data_ptr(),
-                                                       xy.data_ptr(), theta.data_ptr() if geometry else None, keep_tiles.data_ptr(), tile_flags.data_ptr(), B,
-                                                       int(max_hw[0]), int(max_hw[1]), int(bool(geometry)), int(mask_mode), std_c, int(bool(round_bf16)),
-                                                       gpacked.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
-    _lib.check(rc, "vaa_patch_embed_grad_gather_multi_tiles")
-    return gpacked
-
-
-class PatchApply(torch.autograd.Function):
-    """Differentiable (w.r.t. `patch`) K1: PyTorch-ROCm autograd hands the model's bf16 pixel gradient to K2."""
-
-    @staticmethod
-    def forward(ctx, patch, img_u8, xy, theta, geometry, mask_mode, mean6=None, std6=None, sink=None):
-        """sink (dict, optional): as in PatchApplyEmbed — the backward leaves K2's partial tiles in sink["partials"] and no patch gradient."""
-        p = patch.detach().contiguous()
-        out, keep = patch_apply_fwd(img_u8, p, xy, theta, geometry, mask_mode, want_keep=True, mean6=mean6, std6=std6)
-        ctx.save_for_backward(p, xy, theta if geometry else xy, keep)
-        ctx.geometry, ctx.mask_mode, ctx.std6, ctx.sink = bool(geometry), int(mask_mode), std6, sink
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        patch, xy, theta, keep = ctx.saved_tensors
-        g = patch_grad_gather(gout.to(torch.bfloat16).contiguous(), patch, xy, theta if ctx.geometry else None, keep,
-                              ctx.geometry, ctx.mask_mode, std6=ctx.std6, defer_reduce=ctx.sink is not None)
-        if ctx.sink is not None:
-            ctx.sink["partials"] = g
-            g = None
-        return g, None, None, None, None, None, None, None, None
+    return _k2e(dy0, dy1, wp0, wp1, packed, xy, theta, keep_tiles, tile_flags, geometry, mask_mode, std6, round_bf16, pdesc, max_hw)
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -394,74 +315,17 @@ def patch_resize_bwd(gpacked, pdesc, ph: int, pw: int):
 def patch_apply_fwd_multi(img_u8, packed, pdesc, max_hw, xy, theta, geometry: bool, mask_mode: int = MASK_LT_M20, want_keep: bool = True,
                           mean6=None, std6=None):
     """K1 with one patch per image (packed/pdesc from patch_resize_fwd). max_hw = (max h, max w) over the batch (host ints)."""
-    B = img_u8.shape[0]
-    _need(img_u8, torch.uint8, "img_u8", (B, IMG, IMG, 3))
-    _need(packed, torch.float32, "packed")
-    _need(pdesc, torch.int32, "pdesc", (B, 4))
-    _need(xy, torch.int32, "xy", (B, 2))
-    if geometry:
-        _need(theta, torch.float32, "theta", (B, 6))
-    out = torch.empty((B, 6, IMG, IMG), dtype=torch.bfloat16, device=img_u8.device)
-    keep = torch.empty((B, 3, IMG * IMG // 8), dtype=torch.uint8, device=img_u8.device) if want_keep else None
-    mean_c = _MEAN if mean6 is None else _lib.f32x(mean6)
-    std_c = _STD if std6 is None else _lib.f32x(std6)
-    with _timed("K1_patch_apply_fwd_multi", B=B, ph=int(max_hw[0]), pw=int(max_hw[1])):
-        rc = _lib.lib().vaa_patch_apply_fwd_multi(
-            img_u8.data_ptr(), packed.data_ptr(), pdesc.data_ptr(), xy.data_ptr(), theta.data_ptr() if geometry else None, B,
-            int(max_hw[0]), int(max_hw[1]), int(bool(geometry)), int(mask_mode), mean_c, std_c, out.data_ptr(),
-            keep.data_ptr() if want_keep else None, _stream())
-    _lib.check(rc, "vaa_patch_apply_fwd_multi")
-    return out, keep
+    return _k1(img_u8, packed, xy, theta, geometry, mask_mode, mean6, std6, pdesc, max_hw, want_keep=want_keep)
 
 
 def patch_grad_gather_multi(gout_bf16, packed, pdesc, max_hw, xy, theta, keep_bits, geometry: bool, mask_mode: int = MASK_LT_M20, std6=None):
     """K2 with one patch per image: returns gpacked (layout of `packed`): d L / d (every image's own patch)."""
-    B = gout_bf16.shape[0]
-    _need(gout_bf16, torch.bfloat16, "gout_bf16", (B, 6, IMG, IMG))
-    _need(packed, torch.float32, "packed")
-    _need(pdesc, torch.int32, "pdesc", (B, 4))
-    _need(xy, torch.int32, "xy", (B, 2))
-    if geometry:
-        _need(theta, torch.float32, "theta", (B, 6))
-    if keep_bits is not None:
-        _need(keep_bits, torch.uint8, "keep_bits", (B, 3, IMG * IMG // 8))
-    gpacked = torch.zeros_like(packed)
-    std_c = _STD if std6 is None else _lib.f32x(std6)
-    with _timed("K2_patch_grad_gather_multi", B=B, ph=int(max_hw[0]), pw=int(max_hw[1])):
-        rc = _lib.lib().vaa_patch_grad_gather_multi(
-            gout_bf16.data_ptr(), packed.data_ptr(), pdesc.data_ptr(), xy.data_ptr(), theta.data_ptr() if geometry else None,
-            keep_bits.data_ptr() if keep_bits is not None else None, B, int(max_hw[0]), int(max_hw[1]), int(bool(geometry)), int(mask_mode),
-            std_c, gpacked.data_ptr(), _stream())
-    _lib.check(rc, "vaa_patch_grad_gather_multi")
-    return gpacked
+    return _k2(gout_bf16, packed, xy, theta, keep_bits, geometry, mask_mode, std6, pdesc, max_hw)
 
 
-class PatchApplyResized(torch.autograd.Function):
-    """resize_patch=True: resize (K0) + K1 with per-image patches forward; K2 (per-image gradients) + resize adjoint backward.
-    `sizes` is a host int array [B,2] (h,w); four launches + one fixed-order reduce per step, independent of B."""
-
-    @staticmethod
-    def forward(ctx, patch, img_u8, sizes, xy, theta, geometry, mask_mode, mean6=None, std6=None):
-        p = patch.detach().contiguous()
-        pdesc_np, total = make_pdesc(sizes)
-        pdesc = torch.from_numpy(pdesc_np).to(p.device, non_blocking=True)
-        max_hw = (int(pdesc_np[:, 0].max()), int(pdesc_np[:, 1].max()))
-        packed = patch_resize_fwd(p, pdesc, total)
-        out, keep = patch_apply_fwd_multi(img_u8, packed, pdesc, max_hw, xy, theta, geometry, mask_mode, want_keep=True, mean6=mean6, std6=std6)
-        ctx.save_for_backward(packed, pdesc, xy, theta if geometry else xy, keep)
-        ctx.geometry, ctx.mask_mode, ctx.std6, ctx.max_hw = bool(geometry), int(mask_mode), std6, max_hw
-        ctx.base_hw = (int(p.shape[1]), int(p.shape[2]))
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        packed, pdesc, xy, theta, keep = ctx.saved_tensors
-        gp = patch_grad_gather_multi(gout.to(torch.bfloat16).contiguous(), packed, pdesc, ctx.max_hw, xy, theta if ctx.geometry else None, keep,
-                                     ctx.geometry, ctx.mask_mode, std6=ctx.std6)
-        g = patch_resize_bwd(gp, pdesc, *ctx.base_hw)
-        return g, None, None, None, None, None, None, None, None
-
-
+# ------------------------------------------------------------------------------------------------------
+# autograd: the five Functions share one forward and one backward; each names its variant
+# ------------------------------------------------------------------------------------------------------
 class PatchEmbeds(tuple):
     """(e0, e1): the two ViT patch-embed outputs [B,256,D] of a patched batch, standing in for `pixel_values` on the path that
     keeps the pixel gradient un-materialised (PatchApplyEmbed). `OpenVLAShaped.forward_rows(..., patch_embeds=...)` consumes it."""
@@ -473,6 +337,93 @@ def unfold_tiles(x3: torch.Tensor) -> torch.Tensor:
     return x3.reshape(B, 3, 16, 14, 16, 14).permute(0, 2, 4, 1, 3, 5).reshape(B, 256, 588)
 
 
+def sweep_pdesc(P: int, Bp: int, ph: int, pw: int, device) -> torch.Tensor:
+    """[P*Bp, 4] int32 patch descriptors of a maskidx sweep: image b of group g = b // Bp pastes patch g of the packed [P,3,ph,pw] tensor."""
+    g = torch.arange(P * Bp, dtype=torch.int32) // Bp
+    d = torch.stack([torch.full_like(g, ph), torch.full_like(g, pw), g * (3 * ph * pw), torch.zeros_like(g)], dim=1)
+    return d.contiguous().to(device, non_blocking=True)
+
+
+def _resized_pack(patch, sizes):
+    """The prologue of resize_patch=True: host sizes [B,2] (h,w) -> (every image's own resized patch, packed (K0); pdesc on the device; (max h, max w))."""
+    pdesc_np, total = make_pdesc(sizes)
+    pdesc = torch.from_numpy(pdesc_np).to(patch.device, non_blocking=True)
+    return patch_resize_fwd(patch, pdesc, total), pdesc, (int(pdesc_np[:, 0].max()), int(pdesc_np[:, 1].max()))
+
+
+def _paste_forward(ctx, p, img_u8, xy, theta, geometry, mask_mode, mean6, std6, pdesc=None, max_hw=None, embed=None, sink=None, base=None):
+    """Forward of every PatchApply* Function. p: what K1 pastes — the patch, or with pdesc / max_hw the per-image patches. embed=None: K1 planar
+    -> pixel values; embed=(w0, b0, wp0, w1, b1, wp1): K1 writes the two GEMM operands directly (tile-major: no [B,6,224,224] tensor, no im2col
+    copies) -> the two patch-embed outputs. base: the base patch p was resized from (the backward then ends in the resize adjoint)."""
+    if embed is None:
+        ret, keep = _k1(img_u8, p, xy, theta, geometry, mask_mode, mean6, std6, pdesc, max_hw)
+        mask = (keep,)
+    else:
+        w0, b0, wp0, w1, b1, wp1 = embed
+        t0, t1, keep_t, flags = _k1(img_u8, p, xy, theta, geometry, mask_mode, mean6, std6, pdesc, max_hw, tiles=True)
+        ret = torch.nn.functional.linear(t0, w0, b0), torch.nn.functional.linear(t1, w1, b1)
+        mask = (keep_t, flags, wp0, wp1)
+    ctx.save_for_backward(p, xy, theta if geometry else xy, pdesc if base is not None else xy, *mask)
+    ctx.geometry, ctx.mask_mode, ctx.std6, ctx.sink = bool(geometry), int(mask_mode), std6, sink
+    ctx.max_hw, ctx.base_hw = (max_hw, (int(base.shape[1]), int(base.shape[2]))) if base is not None else (None, None)
+    return ret
+
+
+def _paste_backward(ctx, *grads):
+    """Backward of every PatchApply* Function: K2 on the pixel gradient, or K2' on the gradients of the two patch-embed outputs. With a sink the
+    partial tiles are left in sink["partials"] for the caller's step epilogue and there is no gradient; a resized patch ends in the resize adjoint."""
+    p, xy, theta, pdesc, *mask = ctx.saved_tensors
+    g = [t.to(torch.bfloat16).contiguous() for t in grads]
+    if p.dim() == 4:  # a sweep's patches [P,3,ph,pw]: the keep words are given, K2' never reads patch values, only the [3,ph,pw] shape
+        p = p[0]
+    theta, resized, defer = theta if ctx.geometry else None, ctx.base_hw is not None, ctx.sink is not None
+    rest = (ctx.geometry, ctx.mask_mode, ctx.std6)
+    # through the public wrappers, looked up when called: they are where a caller counts or replaces the K2 / K2' of a step
+    if len(g) == 1:
+        if resized:
+            out = patch_grad_gather_multi(g[0], p, pdesc, ctx.max_hw, xy, theta, mask[0], *rest)
+        else:
+            out = patch_grad_gather(g[0], p, xy, theta, mask[0], *rest, defer_reduce=defer)
+    else:
+        keep_t, flags, wp0, wp1 = mask
+        if resized:
+            out = patch_embed_grad_gather_multi_tiles(g[0], g[1], wp0, wp1, p, pdesc, ctx.max_hw, xy, theta, keep_t, flags, *rest)
+        else:
+            out = patch_embed_grad_gather_tiles(g[0], g[1], wp0, wp1, p, xy, theta, keep_t, flags, *rest, defer_reduce=defer)
+    if defer:
+        ctx.sink["partials"] = out
+        return None
+    return patch_resize_bwd(out, pdesc, *ctx.base_hw) if ctx.base_hw is not None else out
+
+
+class PatchApply(torch.autograd.Function):
+    """Differentiable (w.r.t. `patch`) K1: PyTorch-ROCm autograd hands the model's bf16 pixel gradient to K2."""
+
+    @staticmethod
+    def forward(ctx, patch, img_u8, xy, theta, geometry, mask_mode, mean6=None, std6=None, sink=None):
+        """sink (dict, optional): as in PatchApplyEmbed — the backward leaves K2's partial tiles in sink["partials"] and no patch gradient."""
+        return _paste_forward(ctx, patch.detach().contiguous(), img_u8, xy, theta, geometry, mask_mode, mean6, std6, sink=sink)
+
+    @staticmethod
+    def backward(ctx, gout):
+        return (_paste_backward(ctx, gout),) + (None,) * 8
+
+
+class PatchApplyResized(torch.autograd.Function):
+    """resize_patch=True: resize (K0) + K1 with per-image patches forward; K2 (per-image gradients) + resize adjoint backward.
+    `sizes` is a host int array [B,2] (h,w); four launches + one fixed-order reduce per step, independent of B."""
+
+    @staticmethod
+    def forward(ctx, patch, img_u8, sizes, xy, theta, geometry, mask_mode, mean6=None, std6=None):
+        p = patch.detach().contiguous()
+        packed, pdesc, max_hw = _resized_pack(p, sizes)
+        return _paste_forward(ctx, packed, img_u8, xy, theta, geometry, mask_mode, mean6, std6, pdesc, max_hw, base=p)
+
+    @staticmethod
+    def backward(ctx, gout):
+        return (_paste_backward(ctx, gout),) + (None,) * 8
+
+
 class PatchApplyEmbed(torch.autograd.Function):
     """K1 + both patch-embed GEMMs forward; backward = K2' (SURVEY.md 8f-3): the gradients of the patch-embed OUTPUTS go straight to
     `patch_embed_grad_gather`, which evaluates the patch-embed backward only for the tiles under the patch. w: [D,588], wp: pack_embed_weights(w^T)."""
@@ -481,33 +432,12 @@ class PatchApplyEmbed(torch.autograd.Function):
     def forward(ctx, patch, img_u8, xy, theta, geometry, mask_mode, mean6, std6, w0, b0, wp0, w1, b1, wp1, sink=None):
         """sink (a dict, optional): the backward then leaves K2''s partial tiles in sink["partials"] and returns NO gradient for `patch`
         — the caller's step epilogue (ops.step_epilogue) adds them straight into the DDP message."""
-        ctx.sink = sink
-        p = patch.detach().contiguous()
-        # K1 writes the two GEMM operands directly (tile-major): no [B,6,224,224] tensor, no im2col copies
-        t0, t1, keep_t, flags = patch_apply_fwd_tiles(img_u8, p, xy, theta, geometry, mask_mode, mean6=mean6, std6=std6)
-        e0 = torch.nn.functional.linear(t0, w0, b0)
-        e1 = torch.nn.functional.linear(t1, w1, b1)
-        ctx.save_for_backward(p, xy, theta if geometry else xy, keep_t, flags, wp0, wp1)
-        ctx.geometry, ctx.mask_mode, ctx.std6 = bool(geometry), int(mask_mode), std6
-        return e0, e1
+        return _paste_forward(ctx, patch.detach().contiguous(), img_u8, xy, theta, geometry, mask_mode, mean6, std6,
+                              embed=(w0, b0, wp0, w1, b1, wp1), sink=sink)
 
     @staticmethod
     def backward(ctx, d0, d1):
-        patch, xy, theta, keep_t, flags, wp0, wp1 = ctx.saved_tensors
-        d0, d1 = d0.to(torch.bfloat16).contiguous(), d1.to(torch.bfloat16).contiguous()
-        g = patch_embed_grad_gather_tiles(d0, d1, wp0, wp1, patch, xy, theta if ctx.geometry else None, keep_t, flags, ctx.geometry,
-                                          ctx.mask_mode, std6=ctx.std6, defer_reduce=ctx.sink is not None)
-        if ctx.sink is not None:
-            ctx.sink["partials"] = g
-            g = None
-        return (g,) + (None,) * 14
-
-
-def sweep_pdesc(P: int, Bp: int, ph: int, pw: int, device) -> torch.Tensor:
-    """[P*Bp, 4] int32 patch descriptors of a maskidx sweep: image b of group g = b // Bp pastes patch g of the packed [P,3,ph,pw] tensor."""
-    g = torch.arange(P * Bp, dtype=torch.int32) // Bp
-    d = torch.stack([torch.full_like(g, ph), torch.full_like(g, pw), g * (3 * ph * pw), torch.zeros_like(g)], dim=1)
-    return d.contiguous().to(device, non_blocking=True)
+        return (_paste_backward(ctx, d0, d1),) + (None,) * 14
 
 
 class PatchApplySweepEmbed(torch.autograd.Function):
@@ -523,23 +453,15 @@ class PatchApplySweepEmbed(torch.autograd.Function):
             raise _lib.VaaError(f"PatchApplySweepEmbed: {B} images are not {P} equal groups")
         if _lib.lib().vaa_patch_grad_partials(B) != B:
             raise _lib.VaaError(f"PatchApplySweepEmbed: {B} images exceed K2''s one-partial-per-image schedule (at most 511)")
+        if sink is None:
+            raise _lib.VaaError("PatchApplySweepEmbed: the partial tiles need a sink (there is no gradient for `patches`)")
         p = patches.detach().contiguous()
-        pdesc = sweep_pdesc(P, B // P, ph, pw, p.device)
-        t0, t1, keep_t, flags = patch_apply_fwd_tiles(img_u8, p, xy, theta, geometry, mask_mode, mean6=mean6, std6=std6, pdesc=pdesc, max_hw=(ph, pw))
-        e0 = torch.nn.functional.linear(t0, w0, b0)
-        e1 = torch.nn.functional.linear(t1, w1, b1)
-        ctx.save_for_backward(p, xy, theta if geometry else xy, keep_t, flags, wp0, wp1)
-        ctx.geometry, ctx.mask_mode, ctx.std6, ctx.sink = bool(geometry), int(mask_mode), std6, sink
-        return e0, e1
+        return _paste_forward(ctx, p, img_u8, xy, theta, geometry, mask_mode, mean6, std6, sweep_pdesc(P, B // P, ph, pw, p.device), (ph, pw),
+                              embed=(w0, b0, wp0, w1, b1, wp1), sink=sink)
 
     @staticmethod
     def backward(ctx, d0, d1):
-        p, xy, theta, keep_t, flags, wp0, wp1 = ctx.saved_tensors
-        d0, d1 = d0.to(torch.bfloat16).contiguous(), d1.to(torch.bfloat16).contiguous()
-        # the keep words are given: K2' never reads patch values, only the [3,ph,pw] shape
-        ctx.sink["partials"] = patch_embed_grad_gather_tiles(d0, d1, wp0, wp1, p[0], xy, theta if ctx.geometry else None, keep_t, flags, ctx.geometry,
-                                                             ctx.mask_mode, std6=ctx.std6, defer_reduce=True)
-        return (None,) * 15
+        return (_paste_backward(ctx, d0, d1),) + (None,) * 14
 
 
 class PatchApplyResizedEmbed(torch.autograd.Function):
@@ -549,26 +471,12 @@ class PatchApplyResizedEmbed(torch.autograd.Function):
     @staticmethod
     def forward(ctx, patch, img_u8, sizes, xy, theta, geometry, mask_mode, mean6, std6, w0, b0, wp0, w1, b1, wp1):
         p = patch.detach().contiguous()
-        pdesc_np, total = make_pdesc(sizes)
-        pdesc = torch.from_numpy(pdesc_np).to(p.device, non_blocking=True)
-        max_hw = (int(pdesc_np[:, 0].max()), int(pdesc_np[:, 1].max()))
-        packed = patch_resize_fwd(p, pdesc, total)
-        # K1 with per-image patches, tile-major: the two GEMM operands directly (no [B,6,224,224] tensor, no im2col copies)
-        t0, t1, keep_t, flags = patch_apply_fwd_tiles(img_u8, packed, xy, theta, geometry, mask_mode, mean6=mean6, std6=std6, pdesc=pdesc, max_hw=max_hw)
-        e0 = torch.nn.functional.linear(t0, w0, b0)
-        e1 = torch.nn.functional.linear(t1, w1, b1)
-        ctx.save_for_backward(packed, pdesc, xy, theta if geometry else xy, keep_t, flags, wp0, wp1)
-        ctx.geometry, ctx.mask_mode, ctx.std6, ctx.max_hw = bool(geometry), int(mask_mode), std6, max_hw
-        ctx.base_hw = (int(p.shape[1]), int(p.shape[2]))
-        return e0, e1
+        packed, pdesc, max_hw = _resized_pack(p, sizes)
+        return _paste_forward(ctx, packed, img_u8, xy, theta, geometry, mask_mode, mean6, std6, pdesc, max_hw, embed=(w0, b0, wp0, w1, b1, wp1), base=p)
 
     @staticmethod
     def backward(ctx, d0, d1):
-        packed, pdesc, xy, theta, keep_t, flags, wp0, wp1 = ctx.saved_tensors
-        gp = patch_embed_grad_gather_multi_tiles(d0.to(torch.bfloat16).contiguous(), d1.to(torch.bfloat16).contiguous(), wp0, wp1, packed, pdesc, ctx.max_hw,
-                                                 xy, theta if ctx.geometry else None, keep_t, flags, ctx.geometry, ctx.mask_mode, std6=ctx.std6)
-        g = patch_resize_bwd(gp, pdesc, *ctx.base_hw)
-        return (g,) + (None,) * 14
+        return (_paste_backward(ctx, d0, d1),) + (None,) * 14
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -28,6 +28,7 @@
 
 #include "vaa_common.h"
 #include "vaa_rows.h"
+#include "vaa_rows_fold.h"
 
 namespace vaa {
 
@@ -239,21 +240,8 @@ __global__ __launch_bounds__(256) void head_finish_kernel(HeadFinishArgs a) {
         if (p.m > m || (p.m == m && p.amax < mi)) { m = p.m; mi = p.amax; }
         zl = fmaxf(zl, p.zlab);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float om = __shfl_xor(m, o, 64);
-        const int oi = __shfl_xor(mi, o, 64);
-        if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
-        zl = fmaxf(zl, __shfl_xor(zl, o, 64));
-    }
-    if (lane == 0) { redm[wv] = m; redi[wv] = mi; redz[wv] = zl; }
-    __syncthreads();
-    float M = redm[0], Z = redz[0];
-    int MI = redi[0];
-    for (int q = 1; q < 4; ++q) {
-        if (redm[q] > M || (redm[q] == M && redi[q] < MI)) { M = redm[q]; MI = redi[q]; }
-        Z = fmaxf(Z, redz[q]);
-    }
+    block_argmax<256>(m, mi, redm, redi, &zl, redz);
+    const float M = m;
     for (int q = 0; q < np; ++q) s_acc += psum[q] * expf(pm[q] - M);
     s_acc = wave_sum(s_acc);
     if (lane == 0) reds[wv] = s_acc;
@@ -262,77 +250,34 @@ __global__ __launch_bounds__(256) void head_finish_kernel(HeadFinishArgs a) {
         PartStat o;
         o.m = M;
         o.s = (reds[0] + reds[1]) + (reds[2] + reds[3]);
-        o.zlab = Z;
-        o.amax = MI;
+        o.zlab = zl;
+        o.amax = mi;
         a.part_out[(size_t)r * a.split] = o;
-        PartStat nz;  // neutral element of the fold's combination
-        nz.m = -INFINITY; nz.s = 0.0f; nz.zlab = -INFINITY; nz.amax = 0x7fffffff;
-        for (int q = 1; q < a.split; ++q) a.part_out[(size_t)r * a.split + q] = nz;
+        for (int q = 1; q < a.split; ++q) a.part_out[(size_t)r * a.split + q] = neutral_part();
     }
     if (wv != 0) return;
-    // ---- action slice: the arithmetic of rows_stats_kernel's bf16 instantiation (32 lanes x 8 logits), so that the same logits give the same bits ----
-    constexpr int N = 8, nthr = kNA / N;
+    // ---- action slice: rows_stats_kernel's bf16 form (32 lanes x 8 logits through the same slice_soft_argmax): same logits, same bits ----
+    constexpr int N = Vec<uint16_t>::N, nthr = kNA / N;
     const bool own = lane < nthr;
     float x[N];
 #pragma unroll
     for (int e = 0; e < N; ++e) x[e] = -INFINITY;
-    if (own) {
-        const uint4 v = *reinterpret_cast<const uint4*>(a.slice_logits + (size_t)r * kNA + lane * N);
-        x[0] = bf16_bits_to_f32(v.x & 0xffffu); x[1] = bf16_bits_to_f32(v.x >> 16); x[2] = bf16_bits_to_f32(v.y & 0xffffu); x[3] = bf16_bits_to_f32(v.y >> 16);
-        x[4] = bf16_bits_to_f32(v.z & 0xffffu); x[5] = bf16_bits_to_f32(v.z >> 16); x[6] = bf16_bits_to_f32(v.w & 0xffffu); x[7] = bf16_bits_to_f32(v.w >> 16);
-    }
-    int ai = 0;
-#pragma unroll
-    for (int e = 1; e < N; ++e) if (x[e] > x[ai]) ai = e;
-    float bestv = x[ai], am = x[ai];
-    int besti = lane * N + ai;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bestv, o, 64);
-        const int oi = __shfl_xor(besti, o, 64);
-        if (ov > bestv || (ov == bestv && oi < besti)) { bestv = ov; besti = oi; }
-    }
-    am = wave_max(am);
-    float ex[N], es = 0.0f, ew = 0.0f;
-#pragma unroll
-    for (int e = 0; e < N; ++e) {
-        ex[e] = expf(x[e] - am);
-        es += ex[e];
-        ew += ex[e] * (float)(lane * N + e + 1);
-    }
-    es = wave_sum(es);
-    ew = wave_sum(ew);
-    const float E = ew / es;
-    if (lane == 0) {
-        SliceStat ss;
-        ss.alse = am + logf(es);
-        ss.E = E;
-        ss.pred = kA0 + besti;
-        ss.pad = 0;
-        a.slice_out[r] = ss;
-    }
+    if (own) Vec<uint16_t>::load(a.slice_logits + (size_t)r * kNA + lane * N, x);
+    SliceStat ss;
+    slice_soft_argmax(x, ss.alse, ss.E, ss.pred);
+    ss.pad = 0;
+    if (lane == 0) a.slice_out[r] = ss;
     if (a.mode == VAA_LOSS_UADA_DDP && a.grad_slice && own) {  // gradient of w^2 * mean((E / 256 - t)^2): this row and the row COUNT only
         RowMap me = {0, 0, -1, 0};
         if (r < a.rowmap[0]) me = reinterpret_cast<const RowMap*>(a.rowmap + 4)[r];
         const int nact = row_action_count(a.rowmap, a.seg_tbl, me.b);  // a.rowmap[1], or the row's group count on a segmented map
-        float kE = 0.0f;
-        if (me.lab > 2 && nact > 0) {
-            const double rr = (double)E / 256.0, t = (me.lab > 31872) ? 0.0 : 1.0;  // UADA.py:390-394 (A-D10)
-            kE = (float)((double)a.w * a.w * 2.0 * (rr - t) / nact / 256.0);
-        }
-        const float alse = am + logf(es);
+        const float kE = (me.lab > 2 && nact > 0) ? mse_kE(a.w, ss.E, me.lab, nact) : 0.0f;
         float o[N];
 #pragma unroll
-        for (int e = 0; e < N; ++e) o[e] = kE * expf(x[e] - alse) * ((float)(lane * N + e + 1) - E);
-        uint4 pk;
-        pk.x = f32_to_bf16_bits(o[0]) | (f32_to_bf16_bits(o[1]) << 16);
-        pk.y = f32_to_bf16_bits(o[2]) | (f32_to_bf16_bits(o[3]) << 16);
-        pk.z = f32_to_bf16_bits(o[4]) | (f32_to_bf16_bits(o[5]) << 16);
-        pk.w = f32_to_bf16_bits(o[6]) | (f32_to_bf16_bits(o[7]) << 16);
-        *reinterpret_cast<uint4*>(a.grad_slice + (size_t)r * kNA + lane * N) = pk;
+        for (int e = 0; e < N; ++e) o[e] = slice_grad(x[e], lane * N + e, kE, ss.alse, ss.E);
+        Vec<uint16_t>::store(a.grad_slice + (size_t)r * kNA + lane * N, o);
     }
 }
-
 
 }  // namespace vaa
 

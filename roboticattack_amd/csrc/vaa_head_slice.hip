@@ -389,8 +389,7 @@ __global__ __launch_bounds__(kST) __attribute__((amdgpu_waves_per_eu(CT == 8 ? 4
                 SliceStat ss;
                 ss.alse = alse; ss.E = E; ss.pred = pred; ss.pad = 0;
                 a.ra.slice[rr] = ss;
-                PartStat nz;  // neutral element of the fold: "no full-vocabulary statistics on this step" (rows_fold)
-                nz.m = -INFINITY; nz.s = 0.0f; nz.zlab = -INFINITY; nz.amax = 0x7fffffff;
+                const PartStat nz = neutral_part();  // "no full-vocabulary statistics on this step" (rows_fold)
                 for (int q = 0; q < a.ra.split; ++q) a.ra.part[(size_t)rr * a.ra.split + q] = nz;
             }
         }
@@ -488,10 +487,7 @@ __global__ __launch_bounds__(kST) __attribute__((amdgpu_waves_per_eu(CT == 8 ? 4
             if (a.ra.mode == VAA_LOSS_UADA_DDP && (a.dh || a.gs)) {  // the gradient needs this row and the row COUNT only: straight from the registers
                 float kE = 0.0f;
                 const int nact_u = seg ? row_action_count(a.ra.rowmap, rowmap_seg_table(a.ra.B, a.ra.L), me[u].b) : nact;  // segmented map: the row's group
-                if (me[u].lab > 2 && nact_u > 0) {
-                    const double q = (double)own_E[u] / 256.0, t = (me[u].lab > 31872) ? 0.0 : 1.0;  // UADA.py:390-394 (A-D10)
-                    kE = (float)((double)a.ra.w * a.ra.w * 2.0 * (q - t) / nact_u / 256.0);
-                }
+                if (me[u].lab > 2 && nact_u > 0) kE = mse_kE(a.ra.w, own_E[u], me[u].lab, nact_u);
                 if (own_gave_up) kE = __uint_as_float(0x7fc00000u);  // NaN gradient, never a stale one
                 grad_row(u, xo[u], own_alse[u], own_E[u], kE);
             }

@@ -15,6 +15,8 @@
 
 #include <atomic>
 #include <mutex>
+#include <string>
+#include <type_traits>
 
 #include "vaa_common.h"
 #include "vaa_rows.h"
@@ -23,7 +25,6 @@
 namespace vaa {
 
 constexpr int kRowThreads = 1024;
-
 
 struct LossArgs {
     const void* logits;
@@ -42,40 +43,6 @@ constexpr int kLabLds = 24576;  // label matrices up to this many entries (48 KB
 __device__ __forceinline__ size_t row_offset(const LossArgs& a, int b, int k, int rowidx) {
     return a.layout == VAA_LAYOUT_FULL ? ((size_t)b * a.S + (a.S - a.L + k)) * a.V : (size_t)rowidx * a.V;
 }
-
-template <typename T>
-struct Vec;
-template <>
-struct Vec<float> {
-    static constexpr int N = 4;
-    __device__ static void load(const float* p, float* v) {
-        float4 r = *reinterpret_cast<const float4*>(p);
-        v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
-    }
-    __device__ static void store(float* p, const float* v) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-    __device__ static float get(const float* p) { return *p; }
-};
-template <>
-struct Vec<uint16_t> {  // bf16 bits
-    static constexpr int N = 8;
-    __device__ static void load(const uint16_t* p, float* v) {
-        uint4 r = *reinterpret_cast<const uint4*>(p);
-        const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { v[2 * q] = __uint_as_float(w[q] << 16); v[2 * q + 1] = __uint_as_float(w[q] & 0xffff0000u); }
-    }
-    __device__ static void store(uint16_t* p, const float* v) {
-        uint4 r;
-        r.x = f32_to_bf16_bits(v[0]) | (f32_to_bf16_bits(v[1]) << 16);
-        r.y = f32_to_bf16_bits(v[2]) | (f32_to_bf16_bits(v[3]) << 16);
-        r.z = f32_to_bf16_bits(v[4]) | (f32_to_bf16_bits(v[5]) << 16);
-        r.w = f32_to_bf16_bits(v[6]) | (f32_to_bf16_bits(v[7]) << 16);
-        *reinterpret_cast<uint4*>(p) = r;
-    }
-    __device__ static float get(const uint16_t* p) { return bf16_bits_to_f32(*p); }
-};
-
-
 
 // Label access: the whole [B,L] matrix staged in LDS as int16 (token ids < 32768, -100 stays -100) when it fits, else global.
 struct Labels {
@@ -137,7 +104,6 @@ __device__ __forceinline__ void count_labelled(const Labels& lb, int B, int L, i
     for (int q = 0; q < NT / 64; ++q) { before += shi[q][0]; total += shi[q][1]; }
 }
 
-
 // ---- kernel A: per labelled row: compact rank, logsumexp, label logit, action-slice soft-argmax / argmax ----
 template <typename T>
 __global__ __launch_bounds__(kRowThreads) void loss_stats_kernel(LossArgs a, int J) {
@@ -150,8 +116,6 @@ __global__ __launch_bounds__(kRowThreads) void loss_stats_kernel(LossArgs a, int
     __shared__ float red[16];
     __shared__ int redi[16];
     __shared__ int shi[16][2];
-    __shared__ float bmax;
-    __shared__ int bidx;
     constexpr int N = Vec<T>::N;
     const int nvec = a.V / N;  // V = 32064 is a multiple of 8
     // one streaming pass: this thread's elements stay in registers (8 f32 or 4 bf16 16-byte vectors = 32 logits)
@@ -188,25 +152,9 @@ __global__ __launch_bounds__(kRowThreads) void loss_stats_kernel(LossArgs a, int
         for (int e = 0; e < N; ++e)
             if (t[e] > m) { m = t[e]; mi = q * N + e; }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float om = __shfl_xor(m, o, 64);
-        const int oi = __shfl_xor(mi, o, 64);
-        if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
-    }
-    __syncthreads();
-    if (lane == 0) { red[wv] = m; redi[wv] = mi; }
-    __syncthreads();
-    if (tid == 0) {
-        float mm = red[0];
-        int ii = redi[0];
-        for (int q = 1; q < kRowThreads / 64; ++q)
-            if (red[q] > mm || (red[q] == mm && redi[q] < ii)) { mm = red[q]; ii = redi[q]; }
-        bmax = mm;
-        bidx = ii;
-    }
-    __syncthreads();
-    const float M = bmax;
+    __syncthreads();  // the previous row's readers of red / redi are done
+    block_argmax<kRowThreads>(m, mi, red, redi);
+    const float M = m;
     float s = 0.0f;
 #pragma unroll
     for (int c = 0; c < MAXV; ++c)
@@ -228,37 +176,10 @@ __global__ __launch_bounds__(kRowThreads) void loss_stats_kernel(LossArgs a, int
     float alse = 0.0f, E = 0.0f;
     int pred = 0;
     if (wv == t0 / 64) {
-        const bool own = lane < nthr;
         float x[N];
 #pragma unroll
-        for (int e = 0; e < N; ++e) x[e] = own ? v[cs][e] : -INFINITY;
-        float am = x[0];
-        int ai = 0;
-#pragma unroll
-        for (int e = 1; e < N; ++e) if (x[e] > x[ai]) ai = e;
-        float bestv = x[ai];
-        int besti = lane * N + ai;
-#pragma unroll
-        for (int e = 1; e < N; ++e) am = fmaxf(am, x[e]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {  // argmax with lowest-index tie break (torch.argmax)
-            const float ov = __shfl_xor(bestv, o, 64);
-            const int oi = __shfl_xor(besti, o, 64);
-            if (ov > bestv || (ov == bestv && oi < besti)) { bestv = ov; besti = oi; }
-        }
-        am = wave_max(am);
-        float es = 0.0f, ew = 0.0f;
-#pragma unroll
-        for (int e = 0; e < N; ++e) {
-            const float ex = expf(x[e] - am);
-            es += ex;
-            ew += ex * (float)(lane * N + e + 1);
-        }
-        es = wave_sum(es);
-        ew = wave_sum(ew);
-        alse = am + logf(es);
-        E = ew / es;
-        pred = kA0 + besti;
+        for (int e = 0; e < N; ++e) x[e] = lane < nthr ? v[cs][e] : -INFINITY;
+        slice_soft_argmax(x, alse, E, pred);
     }
     __syncthreads();
     if (tid == t0) {  // first lane of the slice wave
@@ -273,12 +194,11 @@ __global__ __launch_bounds__(kRowThreads) void loss_stats_kernel(LossArgs a, int
         r.pos = b * (a.L - 1) + k;
         r.lab = lab;
         r.ord = jj;
-        r.predf = bidx;
+        r.predf = mi;
         a.st[rowidx] = r;
     }
   }
 }
-
 
 // ---- kernel B: every labelled row folds the compact per-row statistics into the global scalars it needs (fixed order ->
 //      deterministic and identical in all workgroups), then writes its gradient row; rank-0's workgroup (or workgroup 0
@@ -355,10 +275,7 @@ __global__ __launch_bounds__(kGradT) void loss_grad_kernel(LossArgs a, int J) {
         else if (a.mode == VAA_LOSS_UADA_DDP) { total = MSE; }                            // UADA_ddp.py:203-206
         else { total = (double)a.scale * CE; dce = (double)a.scale; }                     // TMA.py:148
         kce = nrow > 0 ? (float)(dce / nrow) : 0.0f;
-        if (a.mode != VAA_LOSS_CE && lab > 2) {
-            const double rr = (double)me.E / 256.0, t = (lab > 31872) ? 0.0 : 1.0;
-            kE = (float)((double)a.w * a.w * 2.0 * (rr - t) / nact / 256.0);
-        }
+        if (a.mode != VAA_LOSS_CE && lab > 2) kE = mse_kE(a.w, me.E, lab, nact);
     }
 
     // publication: scalars by the rank-0 row (or by workgroup 0 when nothing is labelled); predicted tokens likewise
@@ -400,23 +317,15 @@ __global__ __launch_bounds__(kGradT) void loss_grad_kernel(LossArgs a, int J) {
         const bool in_slice = (v0 >= kA0 && v0 < kA0 + kNA);
         float o[N];
 #pragma unroll
-        for (int e = 0; e < N; ++e) {
-            float gv = 0.0f;
-            if (kce != 0.0f) gv = kce * (expf(x[c][e] - me.lse) - ((v0 + e) == lab ? 1.0f : 0.0f));
-            if (in_slice && kE != 0.0f) {
-                const float pa = expf(x[c][e] - me.alse);
-                gv += kE * pa * ((float)(v0 + e - kA0 + 1) - me.E);
-            }
-            o[e] = gv;
-        }
+        for (int e = 0; e < N; ++e) o[e] = logit_grad(x[c][e], v0 + e, lab, kce, me.lse, in_slice, kE, me.alse, me.E);
         Vec<T>::store(g + (size_t)v0, o);
     }
     for (int q = tid + MAXV * kGradT; q < nvec; q += kGradT) {  // generic tail for larger vocabularies
-        float t[N], o[N];
+        float t[N] = {}, o[N];
         const int v0 = q * N;
         if (kce != 0.0f) Vec<T>::load(z + (size_t)v0, t);
 #pragma unroll
-        for (int e = 0; e < N; ++e) o[e] = kce != 0.0f ? kce * (expf(t[e] - me.lse) - ((v0 + e) == lab ? 1.0f : 0.0f)) : 0.0f;
+        for (int e = 0; e < N; ++e) o[e] = logit_grad(t[e], v0 + e, lab, kce, me.lse, false, 0.0f, 0.0f, 0.0f);
         Vec<T>::store(g + (size_t)v0, o);
     }
   }
@@ -441,6 +350,19 @@ __global__ __launch_bounds__(kGradT) void loss_grad_kernel(LossArgs a, int J) {
 // 512 workgroups at R' = 128 — 15.9 -> 14.6 us), else 512
 constexpr int kRowsTMax = 512;
 static int rows_threads(int V) { return V <= 4 * 256 * 32 ? 256 : 512; }
+
+// The one ladder over the row kernels' instantiations {f32, bf16} x {256, 512 threads}: f(element type, threads, "type, threads") with the
+// first two as tag values and the third as they are spelled in a kernel's name; `variant` numbers them 0..3 for per-instantiation tables.
+template <typename F>
+static auto with_rows_inst(int dtype, int nt, F f) {
+    using T256 = std::integral_constant<int, 256>;
+    using T512 = std::integral_constant<int, 512>;
+    if (dtype == VAA_DTYPE_F32) return nt == 256 ? f(float{}, T256{}, "float, 256") : f(float{}, T512{}, "float, 512");
+    return nt == 256 ? f(uint16_t{}, T256{}, "uint16_t, 256") : f(uint16_t{}, T512{}, "uint16_t, 512");
+}
+// the name the per-dispatch profiler records (vaa_prof_get), spelled as VAA_LAUNCH spells a kernel named in full: "(kernel<type, threads, more>)"
+static std::string rows_inst_name(const char* kernel, const char* inst, const char* more) { return std::string("(") + kernel + "<" + inst + more + ">)"; }
+static int rows_inst_variant(int dtype, int nt) { return (nt == 256 ? 0 : 2) + (dtype == VAA_DTYPE_F32 ? 0 : 1); }
 
 __global__ __launch_bounds__(1024) void loss_rowmap_kernel(const int64_t* __restrict__ labels, int B, int L, int* __restrict__ out) {
     // out: int hdr[4] = {R, n_action_rows, 0, 0}, then RowMap[R] in (b,k) row-major order of labels[b,k+1] != -100
@@ -485,7 +407,6 @@ __global__ __launch_bounds__(1024) void loss_rowmap_kernel(const int64_t* __rest
     if (tid == 0) { out[0] = carry[0]; out[1] = carry[1]; out[2] = 0; out[3] = 0; }
 }
 
-
 template <typename T>
 __device__ __forceinline__ void store_slice_or_row(const RowsArgs& a, int r, int col0, const float* o) {  // Vec<T>::N values at column col0
     T* g = reinterpret_cast<T*>(a.grad);
@@ -493,12 +414,29 @@ __device__ __forceinline__ void store_slice_or_row(const RowsArgs& a, int r, int
     else Vec<T>::store(g + (size_t)r * a.V + col0, o);
 }
 
-
-struct SliceStat;
+// d total / d logits of row r, part [v_lo, v_hi), from the logits a thread holds (v[c] = vector v_lo + tid + c * kRowsT): full-row modes
+// (UADA: 1/CE^2 term + the action-slice term, CE).
 template <typename T, int kRowsT>
 __device__ __forceinline__ void rows_full_gradient(const RowsArgs& a, float kce, double nact, int r, int v_lo, int v_hi,
-                                                   const float (&v)[32 / Vec<T>::N][Vec<T>::N], float lse, float alse, float E);
-
+                                                   const float (&v)[32 / Vec<T>::N][Vec<T>::N], float lse, float alse, float E) {
+    constexpr int N = Vec<T>::N;
+    constexpr int MAXV = 32 / N;
+    const int tid = threadIdx.x;
+    const RowMap me = reinterpret_cast<const RowMap*>(a.rowmap + 4)[r];
+    const float kE = (a.mode != VAA_LOSS_CE && me.lab > 2) ? mse_kE(a.w, E, me.lab, nact) : 0.0f;
+    T* g = reinterpret_cast<T*>(a.grad) + (size_t)r * a.V;
+#pragma unroll
+    for (int c = 0; c < MAXV; ++c) {
+        const int q = v_lo + tid + c * kRowsT;
+        if (q >= v_hi) continue;
+        const int v0 = q * N;
+        const bool in_slice = (v0 >= kA0 && v0 < kA0 + kNA);
+        float o[N];
+#pragma unroll
+        for (int e = 0; e < N; ++e) o[e] = logit_grad(v[c][e], v0 + e, me.lab, kce, lse, in_slice, kE, alse, E);
+        Vec<T>::store(g + (size_t)v0, o);
+    }
+}
 
 // ONEPASS (full-row gradients of UADA / CE, whose scale needs the folded scalars): the statistics pass keeps its 32 logits per thread in
 // registers across a grid-wide barrier, folds the statistics and writes the gradient from them — the logits are read ONCE (the two-launch
@@ -514,8 +452,6 @@ __global__ __launch_bounds__(kRowsT) void rows_stats_kernel(RowsArgs a, unsigned
     const T* z = reinterpret_cast<const T*>(a.logits) + (size_t)r * a.V;
     __shared__ float redf[kRowsT / 64];
     __shared__ int redi[kRowsT / 64];
-    __shared__ float bmax;
-    __shared__ int bidx;
     float v[MAXV][N];
 #pragma unroll
     for (int c = 0; c < MAXV; ++c) {
@@ -553,24 +489,8 @@ __global__ __launch_bounds__(kRowsT) void rows_stats_kernel(RowsArgs a, unsigned
         for (int e = 0; e < N; ++e)
             if (v[c][e] > m) { m = v[c][e]; mi = q * N + e; }  // within a thread columns are visited in increasing order
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float om = __shfl_xor(m, o, 64);
-        const int oi = __shfl_xor(mi, o, 64);
-        if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
-    }
-    if (lane == 0) { redf[wv] = m; redi[wv] = mi; }
-    __syncthreads();
-    if (tid == 0) {
-        float mm = redf[0];
-        int ii = redi[0];
-        for (int q = 1; q < kRowsT / 64; ++q)
-            if (redf[q] > mm || (redf[q] == mm && redi[q] < ii)) { mm = redf[q]; ii = redi[q]; }
-        bmax = mm;
-        bidx = ii;
-    }
-    __syncthreads();
-    const float M = bmax;
+    block_argmax<kRowsT>(m, mi, redf, redi);
+    const float M = m;
     float s = 0.0f;
 #pragma unroll
     for (int c = 0; c < MAXV; ++c)
@@ -586,7 +506,7 @@ __global__ __launch_bounds__(kRowsT) void rows_stats_kernel(RowsArgs a, unsigned
         PartStat ps;
         ps.m = M;
         ps.s = tot;
-        ps.amax = bidx;
+        ps.amax = mi;
         ps.zlab = zlab_early;
         stat_store<ONEPASS>(&a.part[(size_t)r * a.split + h], ps);
     }
@@ -598,46 +518,15 @@ __global__ __launch_bounds__(kRowsT) void rows_stats_kernel(RowsArgs a, unsigned
 #pragma unroll
         for (int e = 0; e < N; ++e) x[e] = -INFINITY;
     }
-    int ai = 0;
-#pragma unroll
-    for (int e = 1; e < N; ++e) if (x[e] > x[ai]) ai = e;
-    float bestv = x[ai], am = x[ai];
-    int besti = lane * N + ai;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bestv, o, 64);
-        const int oi = __shfl_xor(besti, o, 64);
-        if (ov > bestv || (ov == bestv && oi < besti)) { bestv = ov; besti = oi; }
-    }
-    am = wave_max(am);
-    float ex[N], es = 0.0f, ew = 0.0f;
-#pragma unroll
-    for (int e = 0; e < N; ++e) {
-        ex[e] = expf(x[e] - am);
-        es += ex[e];
-        ew += ex[e] * (float)(lane * N + e + 1);
-    }
-    es = wave_sum(es);
-    ew = wave_sum(ew);
-    const float E = ew / es;
-    if (lane == 0) {
-        SliceStat ss;
-        ss.alse = am + logf(es);
-        ss.E = E;
-        ss.pred = kA0 + besti;
-        ss.pad = 0;
-        stat_store<ONEPASS>(&a.slice[r], ss);
-    }
+    SliceStat ss;
+    slice_soft_argmax(x, ss.alse, ss.E, ss.pred);
+    ss.pad = 0;
+    if (lane == 0) stat_store<ONEPASS>(&a.slice[r], ss);
     if (a.mode == VAA_LOSS_UADA_DDP && a.grad && own) {  // gradient of w^2*mean((E/256 - t)^2): needs this row and the row COUNT only
+        const float kE = (me.lab > 2 && nact > 0) ? mse_kE(a.w, ss.E, me.lab, nact) : 0.0f;
         float o[N];
-        float kE = 0.0f;
-        if (me.lab > 2 && nact > 0) {
-            const double rr = (double)E / 256.0, t = (me.lab > 31872) ? 0.0 : 1.0;  // UADA.py:390-394 (A-D10)
-            kE = (float)((double)a.w * a.w * 2.0 * (rr - t) / nact / 256.0);
-        }
-        const float alse = am + logf(es);
 #pragma unroll
-        for (int e = 0; e < N; ++e) o[e] = kE * expf(x[e] - alse) * ((float)(lane * N + e + 1) - E);
+        for (int e = 0; e < N; ++e) o[e] = slice_grad(x[e], lane * N + e, kE, ss.alse, ss.E);
         store_slice_or_row<T>(a, r, kA0 + lane * N, o);
     }
     }
@@ -709,41 +598,6 @@ __global__ __launch_bounds__(kRowsT) void rows_stats_kernel(RowsArgs a, unsigned
     if (a.grad && r < Rn) rows_full_gradient<T, kRowsT>(a, kce, (double)nact_all, r, v_lo, v_hi, v, __uint_as_float(hand[11]), __uint_as_float(hand[8]), __uint_as_float(hand[9]));
 }
 
-// d total / d logits of row r, part [v_lo, v_hi), from the logits a thread holds (v[c] = vector v_lo + tid + c * kRowsT): full-row modes
-// (UADA: 1/CE^2 term + the action-slice term, CE).
-template <typename T, int kRowsT>
-__device__ __forceinline__ void rows_full_gradient(const RowsArgs& a, float kce, double nact, int r, int v_lo, int v_hi,
-                                                   const float (&v)[32 / Vec<T>::N][Vec<T>::N], float lse, float alse, float E) {
-    constexpr int N = Vec<T>::N;
-    constexpr int MAXV = 32 / N;
-    const int tid = threadIdx.x;
-    const RowMap me = reinterpret_cast<const RowMap*>(a.rowmap + 4)[r];
-    struct { float alse, E; } ms = {alse, E};
-    float kE = 0.0f;
-    if (a.mode != VAA_LOSS_CE && me.lab > 2) {
-        const double q = (double)ms.E / 256.0, t = (me.lab > 31872) ? 0.0 : 1.0;
-        kE = (float)((double)a.w * a.w * 2.0 * (q - t) / nact / 256.0);
-    }
-    T* g = reinterpret_cast<T*>(a.grad) + (size_t)r * a.V;
-#pragma unroll
-    for (int c = 0; c < MAXV; ++c) {
-        const int q = v_lo + tid + c * kRowsT;
-        if (q >= v_hi) continue;
-        const int v0 = q * N;
-        const bool in_slice = (v0 >= kA0 && v0 < kA0 + kNA);
-        float o[N];
-#pragma unroll
-        for (int e = 0; e < N; ++e) {
-            float gv = 0.0f;
-            if (kce != 0.0f) gv = kce * (expf(v[c][e] - lse) - ((v0 + e) == me.lab ? 1.0f : 0.0f));
-            if (in_slice && kE != 0.0f) gv += kE * expf(v[c][e] - ms.alse) * ((float)(v0 + e - kA0 + 1) - ms.E);
-            o[e] = gv;
-        }
-        Vec<T>::store(g + (size_t)v0, o);
-    }
-}
-
-
 // grid = R x split (full-row gradients) or R (slice / no gradient); every workgroup folds the statistics in the same fixed order.
 // fold_wg >= 0 (VAA_LOSS_CE with a full-row gradient: d total / d z = scale / nrow (softmax - onehot) needs the row's own parts and the row COUNT
 // of the map, nothing of other rows): workgroup fold_wg — one past the gradient workgroups — folds and publishes the scalars, every other
@@ -770,29 +624,6 @@ __global__ __launch_bounds__(kRowsT) void rows_finish_kernel(RowsArgs a, int gsp
             if (q < v_hi) Vec<T>::load(z + (size_t)q * N, v[c]);
         }
     }
-    auto row_lse = [&](int rr, float& zlab, int& amax) {  // combine the parts of row rr
-        float M = -INFINITY;
-        for (int q = 0; q < a.split; ++q) M = fmaxf(M, a.part[(size_t)rr * a.split + q].m);
-        float tot = 0.0f, best = -INFINITY;
-        zlab = -INFINITY;
-        amax = 0x7fffffff;
-        for (int q = 0; q < a.split; ++q) {
-            const PartStat p = a.part[(size_t)rr * a.split + q];
-            tot += p.s * expf(p.m - M);
-            zlab = fmaxf(zlab, p.zlab);
-            if (p.m > best || (p.m == best && p.amax < amax)) { best = p.m; amax = p.amax; }
-        }
-        return M + logf(tot);
-    };
-    auto upa_of = [&](int r0, Upa3& u) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            RowStat t;
-            t.E = a.slice[r0 + q].E;
-            t.lab = rm[r0 + q].lab;
-            u.set(q, t);
-        }
-    };
     FoldOut f;
     if (fold_wg < 0) {
         f = rows_fold<kRowsT>(a, blockIdx.x == 0, sh);
@@ -812,19 +643,14 @@ __global__ __launch_bounds__(kRowsT) void rows_finish_kernel(RowsArgs a, int gsp
     if (a.mode == VAA_LOSS_UADA_DDP && !zero_fill) return;  // slice already written by the statistics kernel
     // ---- gradient of this row (part h) ----
     const SliceStat ms = a.slice[r];
-    float kce = nrow > 0 ? (float)(dce / nrow) : 0.0f, kE = 0.0f;
-    if (a.mode == VAA_LOSS_UPA) {
-        kce = 0.0f;
-        if (me.ord < 3 && r - me.ord >= 0 && r - me.ord + 2 < Rn) {
-            Upa3 u;
-            upa_of(r - me.ord, u);
-            kE = (float)(u.dE(me.ord, (double)a.alpha, (double)a.beta, aux1, a.B) / 255.0);
-        }
-    } else if (a.mode != VAA_LOSS_CE && me.lab > 2) {
-        const double q = (double)ms.E / 256.0, t = (me.lab > 31872) ? 0.0 : 1.0;
-        kE = (float)((double)a.w * a.w * 2.0 * (q - t) / nact / 256.0);
-    }
     if (!full_grad) {  // slice-only modes (UPA; UADA_DDP only when FULL storage was asked for)
+        float kE = 0.0f;
+        if (a.mode == VAA_LOSS_UPA) {
+            if (me.ord < 3 && r - me.ord >= 0 && r - me.ord + 2 < Rn)
+                kE = (float)(upa_load<false>(a.slice, rm, r - me.ord).dE(me.ord, (double)a.alpha, (double)a.beta, aux1, a.B) / 255.0);
+        } else if (a.mode != VAA_LOSS_CE && me.lab > 2) {
+            kE = mse_kE(a.w, ms.E, me.lab, nact);
+        }
         constexpr int nthr = kNA / N;
         if (zero_fill) {
             float o[N];
@@ -838,31 +664,15 @@ __global__ __launch_bounds__(kRowsT) void rows_finish_kernel(RowsArgs a, int gsp
             float x[N], o[N];
             Vec<T>::load(z + kA0 + tid * N, x);
 #pragma unroll
-            for (int e = 0; e < N; ++e) o[e] = kE * expf(x[e] - ms.alse) * ((float)(tid * N + e + 1) - ms.E);
+            for (int e = 0; e < N; ++e) o[e] = slice_grad(x[e], tid * N + e, kE, ms.alse, ms.E);
             store_slice_or_row<T>(a, r, kA0 + tid * N, o);
         }
         return;
     }
     float zl;
     int am;
-    const float lse = row_lse(r, zl, am);
-    T* g = reinterpret_cast<T*>(a.grad) + (size_t)r * a.V;
-#pragma unroll
-    for (int c = 0; c < MAXV; ++c) {
-        const int q = v_lo + tid + c * kRowsT;
-        if (q >= v_hi) continue;
-        const int v0 = q * N;
-        const bool in_slice = (v0 >= kA0 && v0 < kA0 + kNA);
-        float o[N];
-#pragma unroll
-        for (int e = 0; e < N; ++e) {
-            float gv = 0.0f;
-            if (kce != 0.0f) gv = kce * (expf(v[c][e] - lse) - ((v0 + e) == me.lab ? 1.0f : 0.0f));
-            if (in_slice && kE != 0.0f) gv += kE * expf(v[c][e] - ms.alse) * ((float)(v0 + e - kA0 + 1) - ms.E);
-            o[e] = gv;
-        }
-        Vec<T>::store(g + (size_t)v0, o);
-    }
+    const float lse = row_lse<false>(a.part, a.split, r, zl, am);
+    rows_full_gradient<T, kRowsT>(a, nrow > 0 ? (float)(dce / nrow) : 0.0f, nact, r, v_lo, v_hi, v, lse, ms.alse, ms.E);
 }
 
 // Step epilogue (vaa_step_epilogue[_seg]): ONE launch between the backward and the gradient exchange, over P gradients of n elements (the
@@ -1148,10 +958,9 @@ static bool rows_grid_resident(K kernel, int threads, long grid, int variant) {
         }
         slots[variant][dev].store(have, std::memory_order_relaxed);
     }
-    const long cus_per_cu = have;
     // half of what fits: a second launch of the same shape from ANOTHER process (the GPU shared by two ranks or tenants) still finds room,
     // so two waiting grids can never hold the slots each other's last workgroups need
-    return cus_per_cu > 0 && 2 * grid <= cus_per_cu;
+    return have > 0 && 2 * grid <= have;
 }
 
 // Inside this process at most ONE stream has one-pass launches in flight: a request from another stream is admitted only once the owner
@@ -1178,12 +987,10 @@ static bool rows_one_pass_wanted() {  // VAA_K3_ONE_PASS=1 / 0 overrides the def
 }
 
 static bool rows_one_pass_fits(const RowsArgs& a, int dtype) {
-    const long grid = (long)a.R * a.split;
-    if (rows_threads(a.V) == 256)
-        return dtype == VAA_DTYPE_F32 ? rows_grid_resident(rows_stats_kernel<float, 256, true>, 256, grid, 0)
-                                      : rows_grid_resident(rows_stats_kernel<uint16_t, 256, true>, 256, grid, 1);
-    return dtype == VAA_DTYPE_F32 ? rows_grid_resident(rows_stats_kernel<float, 512, true>, 512, grid, 2)
-                                  : rows_grid_resident(rows_stats_kernel<uint16_t, 512, true>, 512, grid, 3);
+    const int nt = rows_threads(a.V);
+    return with_rows_inst(dtype, nt, [&](auto t, auto n, const char*) {
+        return rows_grid_resident(rows_stats_kernel<decltype(t), decltype(n)::value, true>, nt, (long)a.R * a.split, rows_inst_variant(dtype, nt));
+    });
 }
 
 static int launch_rows_stats(const RowsArgs& a, int dtype, hipStream_t st, const char* who, unsigned* bar = nullptr, unsigned gen = 0u) {
@@ -1193,24 +1000,26 @@ static int launch_rows_stats(const RowsArgs& a, int dtype, hipStream_t st, const
         const char* ev = getenv("VAA_K3_HANDOVER_POLLS");
         if (ev && *ev) polls = atoi(ev);
     }
-    const int nt = rows_threads(a.V);
     const dim3 gs((unsigned)(a.R * a.split));
-    unsigned* nobar = nullptr;
-    if (bar) {  // one pass: statistics, grid barrier, fold, full-row gradient from the registers
-        if (dtype == VAA_DTYPE_F32) {
-            if (nt == 256) VAA_LAUNCH((rows_stats_kernel<float, 256, true>), gs, dim3(256), 0, st, a, bar, gen, err, polls);
-            else VAA_LAUNCH((rows_stats_kernel<float, 512, true>), gs, dim3(512), 0, st, a, bar, gen, err, polls);
-        } else {
-            if (nt == 256) VAA_LAUNCH((rows_stats_kernel<uint16_t, 256, true>), gs, dim3(256), 0, st, a, bar, gen, err, polls);
-            else VAA_LAUNCH((rows_stats_kernel<uint16_t, 512, true>), gs, dim3(512), 0, st, a, bar, gen, err, polls);
-        }
-    } else if (dtype == VAA_DTYPE_F32) {
-        if (nt == 256) VAA_LAUNCH((rows_stats_kernel<float, 256, false>), gs, dim3(256), 0, st, a, nobar, 0u, nobar, 0);
-        else VAA_LAUNCH((rows_stats_kernel<float, 512, false>), gs, dim3(512), 0, st, a, nobar, 0u, nobar, 0);
-    } else {
-        if (nt == 256) VAA_LAUNCH((rows_stats_kernel<uint16_t, 256, false>), gs, dim3(256), 0, st, a, nobar, 0u, nobar, 0);
-        else VAA_LAUNCH((rows_stats_kernel<uint16_t, 512, false>), gs, dim3(512), 0, st, a, nobar, 0u, nobar, 0);
-    }
+    with_rows_inst(dtype, rows_threads(a.V), [&](auto t, auto n, const char* inst) {
+        using T = decltype(t);
+        constexpr int NT = decltype(n)::value;
+        static const std::string one = rows_inst_name("rows_stats_kernel", inst, ", true"), two = rows_inst_name("rows_stats_kernel", inst, ", false");
+        // one pass: statistics, grid barrier, fold, full-row gradient from the registers
+        if (bar) launch_k(one.c_str(), rows_stats_kernel<T, NT, true>, gs, dim3(NT), 0, st, a, bar, gen, err, polls);
+        else launch_k(two.c_str(), rows_stats_kernel<T, NT, false>, gs, dim3(NT), 0, st, a, bar, 0u, err, 0);
+        return 0;
+    });
+    return check_launch(who);
+}
+
+static int launch_rows_finish(const RowsArgs& a, int dtype, unsigned G, int gsplit, int fold_wg, hipStream_t st, const char* who) {
+    with_rows_inst(dtype, rows_threads(a.V), [&](auto t, auto n, const char* inst) {
+        constexpr int NT = decltype(n)::value;
+        static const std::string name = rows_inst_name("rows_finish_kernel", inst, "");
+        launch_k(name.c_str(), rows_finish_kernel<decltype(t), NT>, dim3(G), dim3(NT), 0, st, a, gsplit, fold_wg);
+        return 0;
+    });
     return check_launch(who);
 }
 
@@ -1256,7 +1065,6 @@ extern "C" int vaa_loss_rows_fwd_bwd(const void* logits, int dtype, const void* 
     if (rc != VAA_OK) return rc;
     // the finishing pass: per (row, part) when a full-row gradient (or a zero fill) has to be written, else one workgroup per row
     // (UPA slice) or a single workgroup (UADA_DDP slice: only the scalars are left to do)
-    const int nt = rows_threads(V);
     const bool full_rows = grad && grad_kind == VAA_GRAD_FULL;
     const int gsplit = full_rows ? a.split : 1;
     unsigned G = full_rows ? (unsigned)(R * gsplit) : ((grad && mode == VAA_LOSS_UPA) ? (unsigned)R : 1u);
@@ -1265,14 +1073,7 @@ extern "C" int vaa_loss_rows_fwd_bwd(const void* logits, int dtype, const void* 
     const bool ce_fold_wg = !(ce_ev && ce_ev[0] == '0');
     const int fold_wg = (full_rows && mode == VAA_LOSS_CE && ce_fold_wg) ? (int)G : -1;
     if (fold_wg >= 0) ++G;
-    if (dtype == VAA_DTYPE_F32) {
-        if (nt == 256) VAA_LAUNCH((rows_finish_kernel<float, 256>), dim3(G), dim3(256), 0, st, a, gsplit, fold_wg);
-        else VAA_LAUNCH((rows_finish_kernel<float, 512>), dim3(G), dim3(512), 0, st, a, gsplit, fold_wg);
-    } else {
-        if (nt == 256) VAA_LAUNCH((rows_finish_kernel<uint16_t, 256>), dim3(G), dim3(256), 0, st, a, gsplit, fold_wg);
-        else VAA_LAUNCH((rows_finish_kernel<uint16_t, 512>), dim3(G), dim3(512), 0, st, a, gsplit, fold_wg);
-    }
-    return check_launch("vaa_loss_rows_fwd_bwd(finish)");
+    return launch_rows_finish(a, dtype, G, gsplit, fold_wg, st, "vaa_loss_rows_fwd_bwd(finish)");
 }
 
 // The finishing pass behind vaa_head_loss_rows_stats (LM head fused with K3's statistics): the fold of the rows into the scalars, the
@@ -1304,11 +1105,8 @@ extern "C" int vaa_head_loss_rows_finish(const void* rowmap, int R, int B, int L
     if (rc != VAA_OK) return rc;
     a.ldz = kNA;
     a.zcol0 = kA0;
-    hipStream_t st = (hipStream_t)stream;
     const unsigned G = grad_slice ? (unsigned)R : 1u;  // one workgroup per row writes its slice; the scalars alone take one workgroup
-    if (rows_threads(V) == 256) VAA_LAUNCH((rows_finish_kernel<uint16_t, 256>), dim3(G), dim3(256), 0, st, a, 1, -1);
-    else VAA_LAUNCH((rows_finish_kernel<uint16_t, 512>), dim3(G), dim3(512), 0, st, a, 1, -1);
-    return check_launch(who);
+    return launch_rows_finish(a, VAA_DTYPE_BF16, G, 1, -1, (hipStream_t)stream, who);
 }
 
 // The statistics pass of vaa_loss_rows_fwd_bwd alone (UADA_DDP mode: it also writes the gradient slice, which needs nothing from other

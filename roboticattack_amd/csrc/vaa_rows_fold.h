@@ -1,5 +1,6 @@
-// vaa_rows_fold.h — the fold of K3's per-row statistics into the loss scalars (and what it is made of), shared by vaa_loss.hip (K3, the step
-// epilogue) and vaa_head_slice.hip (K3s: the slice-only LM head that folds inside its own launch). One source, same bits.
+// vaa_rows_fold.h — the device primitives of the K3 loss family and the fold of its per-row statistics into the loss scalars, shared by
+// vaa_loss.hip (K3, the step epilogue), vaa_head.hip (K3h's finishing launch) and vaa_head_slice.hip (K3s: the slice-only LM head that folds
+// inside its own launch). The forms of the family are bit-equal because each piece of arithmetic is written here once.
 #pragma once
 #include <math.h>
 
@@ -24,6 +25,119 @@ __device__ __forceinline__ double bin_center(int tok) {  // ActionTokenizer.deco
     int d = 32000 - tok - 1;
     d = d < 0 ? 0 : (d > 254 ? 254 : d);
     return -1.0 + (2.0 * d + 1.0) / 255.0;
+}
+
+// 16 bytes of logits <-> fp32 registers
+template <typename T>
+struct Vec;
+template <>
+struct Vec<float> {
+    static constexpr int N = 4;
+    __device__ static void load(const float* p, float* v) {
+        float4 r = *reinterpret_cast<const float4*>(p);
+        v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
+    }
+    __device__ static void store(float* p, const float* v) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
+    __device__ static float get(const float* p) { return *p; }
+};
+template <>
+struct Vec<uint16_t> {  // bf16 bits
+    static constexpr int N = 8;
+    __device__ static void load(const uint16_t* p, float* v) {
+        uint4 r = *reinterpret_cast<const uint4*>(p);
+        const uint32_t w[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { v[2 * q] = __uint_as_float(w[q] << 16); v[2 * q + 1] = __uint_as_float(w[q] & 0xffff0000u); }
+    }
+    __device__ static void store(uint16_t* p, const float* v) {
+        uint4 r;
+        r.x = f32_to_bf16_bits(v[0]) | (f32_to_bf16_bits(v[1]) << 16);
+        r.y = f32_to_bf16_bits(v[2]) | (f32_to_bf16_bits(v[3]) << 16);
+        r.z = f32_to_bf16_bits(v[4]) | (f32_to_bf16_bits(v[5]) << 16);
+        r.w = f32_to_bf16_bits(v[6]) | (f32_to_bf16_bits(v[7]) << 16);
+        *reinterpret_cast<uint4*>(p) = r;
+    }
+    __device__ static float get(const uint16_t* p) { return bf16_bits_to_f32(*p); }
+};
+
+// neutral element of the combination of a row's parts (row_lse): "no full-vocabulary statistics"
+__device__ __forceinline__ PartStat neutral_part() {
+    PartStat p;
+    p.m = -INFINITY; p.s = 0.0f; p.zlab = -INFINITY; p.amax = 0x7fffffff;
+    return p;
+}
+
+// maximum with its index over a wave, lowest index on ties (torch.argmax); every lane gets the result
+__device__ __forceinline__ void wave_argmax(float& m, int& mi) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float om = __shfl_xor(m, o, 64);
+        const int oi = __shfl_xor(mi, o, 64);
+        if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+    }
+}
+// ... and over a workgroup of NT threads: waves through LDS, combined in wave order by every thread. `z` (with its own LDS words `redz`) is
+// max-reduced on the way when given. No barrier follows the combination: a caller that writes the LDS words again (a next row, another
+// reduction through the same words) puts its own barrier in front of that write.
+template <int NT>
+__device__ __forceinline__ void block_argmax(float& m, int& mi, float* redm, int* redi, float* z = nullptr, float* redz = nullptr) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    wave_argmax(m, mi);
+    if (z) *z = wave_max(*z);
+    if (lane == 0) {
+        redm[wv] = m; redi[wv] = mi;
+        if (z) redz[wv] = *z;
+    }
+    __syncthreads();
+    m = redm[0]; mi = redi[0];
+    if (z) *z = redz[0];
+    for (int q = 1; q < NT / 64; ++q) {
+        if (redm[q] > m || (redm[q] == m && redi[q] < mi)) { m = redm[q]; mi = redi[q]; }
+        if (z) *z = fmaxf(*z, redz[q]);
+    }
+}
+
+// Soft-argmax statistics of the 256 action logits by ONE wave (UADA.py:384-389, UPA.py:370-374): lane l holds the N logits of columns
+// [l N, l N + N), -inf in lanes that own none. alse = log-sum-exp over the slice, E = sum_a softmax_a (a + 1), pred = kA0 + argmax.
+template <int N>
+__device__ __forceinline__ void slice_soft_argmax(const float (&x)[N], float& alse, float& E, int& pred) {
+    const int lane = threadIdx.x & 63;
+    int ai = 0;
+#pragma unroll
+    for (int e = 1; e < N; ++e) if (x[e] > x[ai]) ai = e;
+    float bestv = x[ai], am = x[ai];  // (the lane maximum IS x[ai])
+    int besti = lane * N + ai;
+    wave_argmax(bestv, besti);
+    am = wave_max(am);
+    float es = 0.0f, ew = 0.0f;
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+        const float ex = expf(x[e] - am);
+        es += ex;
+        ew += ex * (float)(lane * N + e + 1);
+    }
+    es = wave_sum(es);
+    ew = wave_sum(ew);
+    alse = am + logf(es);
+    E = ew / es;
+    pred = kA0 + besti;
+}
+
+// d [w^2 mean((E / 256 - t)^2)] / d E of one action row (UADA.py:390-394; A-D10: the target 1/256 -> 0), nact = rows the mean runs over
+// (an int count or a folded double: converted where it divides)
+template <typename C>
+__device__ __forceinline__ float mse_kE(float w, float E, int lab, C nact) {
+    const double q = (double)E / 256.0, t = (lab > 31872) ? 0.0 : 1.0;
+    return (float)((double)w * w * 2.0 * (q - t) / nact / 256.0);
+}
+// d E / d z of action bin a (0-based) times kE: kE p_a ((a + 1) - E)
+__device__ __forceinline__ float slice_grad(float z, int a, float kE, float alse, float E) { return kE * expf(z - alse) * ((float)(a + 1) - E); }
+// d total / d z of the logit in column `col` of a row: kce (softmax - onehot), plus the slice term in the action columns
+__device__ __forceinline__ float logit_grad(float z, int col, int lab, float kce, float lse, bool in_slice, float kE, float alse, float E) {
+    float gv = 0.0f;
+    if (kce != 0.0f) gv = kce * (expf(z - lse) - (col == lab ? 1.0f : 0.0f));
+    if (in_slice && kE != 0.0f) gv += slice_grad(z, col - kA0, kE, alse, E);
+    return gv;
 }
 
 // block-wide sums of NV doubles at once (fixed order: lanes by xor-shuffle, then waves 0..15) -> deterministic
@@ -120,6 +234,58 @@ __device__ __forceinline__ void stat_store(S* p, const S& v) {
     for (int z = 0; z < 4; ++z) __hip_atomic_store(reinterpret_cast<unsigned*>(p) + z, w[z], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// Combines the `split` parts of row rr: returns its log-sum-exp, with the label's logit and the full-vocabulary argmax (lowest index on ties)
+template <bool COH>
+__device__ __forceinline__ float row_lse(const PartStat* part, int split, int rr, float& zlab, int& amax) {
+    float M = -INFINITY, tot = 0.0f, best = -INFINITY;
+    zlab = -INFINITY;
+    amax = 0x7fffffff;
+    constexpr int kHeld = 8;
+    if (COH && split <= kHeld) {  // coherent loads are not merged by the compiler: fetch every part ONCE, all requests in flight together
+        PartStat ps[kHeld];
+#pragma unroll
+        for (int q = 0; q < kHeld; ++q)
+            if (q < split) ps[q] = stat_load<COH>(&part[(size_t)rr * split + q]);
+#pragma unroll
+        for (int q = 0; q < kHeld; ++q)
+            if (q < split) M = fmaxf(M, ps[q].m);
+#pragma unroll
+        for (int q = 0; q < kHeld; ++q)
+            if (q < split) {
+                tot += ps[q].s * expf(ps[q].m - M);
+                zlab = fmaxf(zlab, ps[q].zlab);
+                if (ps[q].m > best || (ps[q].m == best && ps[q].amax < amax)) { best = ps[q].m; amax = ps[q].amax; }
+            }
+        if (M == -INFINITY) { zlab = 0.0f; amax = -1; return 0.0f; }  // every part neutral: a slice-only step (see below)
+        return M + logf(tot);
+    }
+    for (int q = 0; q < split; ++q) M = fmaxf(M, stat_load<COH>(&part[(size_t)rr * split + q]).m);
+    for (int q = 0; q < split; ++q) {
+        const PartStat p = stat_load<COH>(&part[(size_t)rr * split + q]);
+        tot += p.s * expf(p.m - M);
+        zlab = fmaxf(zlab, p.zlab);
+        if (p.m > best || (p.m == best && p.amax < amax)) { best = p.m; amax = p.amax; }
+    }
+    // every part neutral {m = -inf, s = 0}: the row has NO full-vocabulary statistics — a slice-only step (vaa_head_slice_fwd_bwd: the loop
+    // reads CE / the full argmax on 1 of innerLoop steps, UADA_ddp.py:214-221, and never in UPA's reverse-direction mode, UPA.py:145-186).
+    // The row then adds 0 to CE and -1 to pred_full; real logits never have a maximum of -inf
+    if (M == -INFINITY) { zlab = 0.0f; amax = -1; return 0.0f; }
+    return M + logf(tot);
+}
+// the E / label of the three consecutive rows r0.. (a sample's first three labelled rows)
+template <bool COH>
+__device__ __forceinline__ Upa3 upa_load(const SliceStat* slice, const RowMap* rm, int r0) {
+    Upa3 u;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        RowStat t;
+        t.E = stat_load<COH>(&slice[r0 + q]).E;
+        t.lab = rm[r0 + q].lab;
+        u.set(q, t);
+    }
+    return u;
+}
+
 // Folds the R compact row statistics into the loss scalars in a fixed order (thread t takes rows t, t + kRowsT, ...; block_sums), and — for
 // the publishing workgroup — writes scalars[8] and the two prediction maps. Shared by rows_finish_kernel and the step epilogue.
 template <int kRowsT, bool COH>
@@ -128,42 +294,6 @@ __device__ __forceinline__ FoldOut rows_fold(const RowsArgs& a, bool publish, do
     const RowMap* rm = reinterpret_cast<const RowMap*>(a.rowmap + 4);
     const int Rdev = a.rowmap[0];
     const int Rn = min(a.R, Rdev);  // rows both the caller and the map know: a mismatch publishes NaN and never leaves the map
-    auto row_lse = [&](int rr, float& zlab, int& amax) {  // combine the parts of row rr
-        float M = -INFINITY, tot = 0.0f, best = -INFINITY;
-        zlab = -INFINITY;
-        amax = 0x7fffffff;
-        constexpr int kHeld = 8;
-        if (COH && a.split <= kHeld) {  // coherent loads are not merged by the compiler: fetch every part ONCE, all requests in flight together
-            PartStat ps[kHeld];
-#pragma unroll
-            for (int q = 0; q < kHeld; ++q)
-                if (q < a.split) ps[q] = stat_load<COH>(&a.part[(size_t)rr * a.split + q]);
-#pragma unroll
-            for (int q = 0; q < kHeld; ++q)
-                if (q < a.split) M = fmaxf(M, ps[q].m);
-#pragma unroll
-            for (int q = 0; q < kHeld; ++q)
-                if (q < a.split) {
-                    tot += ps[q].s * expf(ps[q].m - M);
-                    zlab = fmaxf(zlab, ps[q].zlab);
-                    if (ps[q].m > best || (ps[q].m == best && ps[q].amax < amax)) { best = ps[q].m; amax = ps[q].amax; }
-                }
-            if (M == -INFINITY) { zlab = 0.0f; amax = -1; return 0.0f; }  // every part neutral: a slice-only step (see below)
-            return M + logf(tot);
-        }
-        for (int q = 0; q < a.split; ++q) M = fmaxf(M, stat_load<COH>(&a.part[(size_t)rr * a.split + q]).m);
-        for (int q = 0; q < a.split; ++q) {
-            const PartStat p = stat_load<COH>(&a.part[(size_t)rr * a.split + q]);
-            tot += p.s * expf(p.m - M);
-            zlab = fmaxf(zlab, p.zlab);
-            if (p.m > best || (p.m == best && p.amax < amax)) { best = p.m; amax = p.amax; }
-        }
-        // every part neutral {m = -inf, s = 0}: the row has NO full-vocabulary statistics — a slice-only step (vaa_head_slice_fwd_bwd: the loop
-        // reads CE / the full argmax on 1 of innerLoop steps, UADA_ddp.py:214-221, and never in UPA's reverse-direction mode, UPA.py:145-186).
-        // The row then adds 0 to CE and -1 to pred_full; real logits never have a maximum of -inf
-        if (M == -INFINITY) { zlab = 0.0f; amax = -1; return 0.0f; }
-        return M + logf(tot);
-    };
     const bool handing = COH && ho.words != nullptr;
     auto clear_maps = [&]() {
         const int P0 = a.B * (a.L - 1);
@@ -182,7 +312,7 @@ __device__ __forceinline__ FoldOut rows_fold(const RowsArgs& a, bool publish, do
         int am;
         SliceStat ss_early = {0.f, 0.f, 0, 0};
         if (handing) ss_early = stat_load<COH>(&a.slice[rr]);  // requested together with the parts: one round trip for the whole row
-        const float lse = row_lse(rr, zl, am);
+        const float lse = row_lse<COH>(a.part, a.split, rr, zl, am);
         if (handing)  // the row's workgroups take their log-sum-exp from here instead of combining the parts again
             __hip_atomic_store(reinterpret_cast<unsigned*>(&a.slice[rr].pad), __float_as_uint(lse), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (rr == tid) first_am = am;
@@ -197,14 +327,7 @@ __device__ __forceinline__ FoldOut rows_fold(const RowsArgs& a, bool publish, do
             acc[2] += fabs(ap - ag) / (ag > 0 ? fabs(ag + 1.0) : fabs(ag - 1.0));
         }
         if (a.mode == VAA_LOSS_UPA && m.ord == 0 && rr + 2 < Rn) {  // first three labelled rows of a sample are consecutive ranks
-            Upa3 u;
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                RowStat t;
-                t.E = stat_load<COH>(&a.slice[rr + q]).E;
-                t.lab = rm[rr + q].lab;
-                u.set(q, t);
-            }
+            const Upa3 u = upa_load<COH>(a.slice, rm, rr);
             double c1, nd;
             u.terms(c1, nd);
             acc[5] += c1;
@@ -257,7 +380,7 @@ __device__ __forceinline__ FoldOut rows_fold(const RowsArgs& a, bool publish, do
                 int am = first_am;
                 if (rr != tid) {  // more rows than threads: combine the parts again
                     float zl;
-                    row_lse(rr, zl, am);
+                    row_lse<COH>(a.part, a.split, rr, zl, am);
                 }
                 a.pred_full[pos] = am;
             }

@@ -482,12 +482,8 @@ class PatchApplyResizedEmbed(torch.autograd.Function):
 # ------------------------------------------------------------------------------------------------------
 # K3
 # ------------------------------------------------------------------------------------------------------
-def loss_fwd_bwd(logits, labels, mode: int, w: float = 5.0, alpha: float = 0.8, beta: float = 0.2, scale: float = 1.0,
-                 layout: int = LAYOUT_FULL, want_grad: bool = True, want_pred: bool = True, glogits=None, want_pred_full: bool = False):
-    """K3. Returns (scalars f32[8] on device, pred_tokens i32 [B,L-1] or None, glogits or None[, pred_full i32 [B,L-1]]).
-
-    scalars = [total, CE, w^2*MSE, UPA angle, UPA dist, #CE rows, #action rows, UAD]. pred_tokens = 31744 + argmax of the action
-    slice (what UAD uses, UADA.py:395); pred_full (want_pred_full) = argmax over the whole vocabulary (UADA.py:165-167 metrics)."""
+def _dtype_code(logits) -> int:
+    """The library's dtype code of a logits tensor (f32 | bf16) on the device."""
     if logits.dtype == torch.float32:
         dt = _lib.DTYPE_F32
     elif logits.dtype == torch.bfloat16:
@@ -495,6 +491,40 @@ def loss_fwd_bwd(logits, labels, mode: int, w: float = 5.0, alpha: float = 0.8, 
     else:
         raise _lib.VaaError(f"logits: unsupported dtype {logits.dtype}")
     _need(logits, logits.dtype, "logits")
+    return dt
+
+
+def _loss_params(w, alpha, beta, scale):
+    return _lib.f32x([w, alpha, beta, scale])
+
+
+def _pred_maps(B: int, L: int, device, want: bool = True, want_full=None):
+    """The two [B, L-1] prediction maps K3 fills (action-slice argmax, full-vocabulary argmax), None for one that is not wanted."""
+    want_full = want if want_full is None else want_full
+    return tuple(torch.empty((B, L - 1), dtype=torch.int32, device=device) if on else None for on in (want, want_full))
+
+
+def _loss_forward(ctx, scalars, pred, pred_full, *saved):
+    """The forward tail of the K3 autograd Functions: (total, scalars f32[8], pred_slice, pred_full) with `saved` kept for the backward."""
+    ctx.save_for_backward(*saved)
+    ctx.mark_non_differentiable(scalars, pred, pred_full)
+    return scalars[0].clone(), scalars, pred, pred_full
+
+
+def _loss_backward(g, gtotal, n_args: int, w_head=None):
+    """... and their backward: the gradient the forward produced times d / d total (through the LM-head rows w_head when the forward's first
+    argument was the hidden rows), then None for the other n_args - 1 arguments of the forward."""
+    d = g * gtotal.to(g.dtype)
+    return (d if w_head is None else d @ w_head,) + (None,) * (n_args - 1)
+
+
+def loss_fwd_bwd(logits, labels, mode: int, w: float = 5.0, alpha: float = 0.8, beta: float = 0.2, scale: float = 1.0,
+                 layout: int = LAYOUT_FULL, want_grad: bool = True, want_pred: bool = True, glogits=None, want_pred_full: bool = False):
+    """K3. Returns (scalars f32[8] on device, pred_tokens i32 [B,L-1] or None, glogits or None[, pred_full i32 [B,L-1]]).
+
+    scalars = [total, CE, w^2*MSE, UPA angle, UPA dist, #CE rows, #action rows, UAD]. pred_tokens = 31744 + argmax of the action
+    slice (what UAD uses, UADA.py:395); pred_full (want_pred_full) = argmax over the whole vocabulary (UADA.py:165-167 metrics)."""
+    dt = _dtype_code(logits)
     _need(labels, torch.int64, "labels")
     B, Lt = int(labels.shape[0]), int(labels.shape[1])
     if layout == LAYOUT_FULL:
@@ -508,15 +538,13 @@ def loss_fwd_bwd(logits, labels, mode: int, w: float = 5.0, alpha: float = 0.8, 
     L = _lib.lib()
     ws = _workspace(logits.device, L.vaa_loss_ws_bytes(B, Lt), "k3")
     scalars = torch.empty(8, dtype=torch.float32, device=logits.device)
-    pred = torch.empty((B, Lt - 1), dtype=torch.int32, device=logits.device) if want_pred else None
-    pred_full = torch.empty((B, Lt - 1), dtype=torch.int32, device=logits.device) if want_pred_full else None
+    pred, pred_full = _pred_maps(B, Lt, logits.device, want_pred, want_pred_full)
     if want_grad and glogits is None:
         glogits = torch.zeros_like(logits) if layout == LAYOUT_FULL else torch.empty_like(logits)
     with _timed("K3_loss_fwd_bwd", B=B, L=Lt, V=V, dtype=str(logits.dtype), rows=(int(logits.shape[0]) if layout == LAYOUT_ROWS else -1)):
         rc = L.vaa_loss_fwd_bwd_ex(
-            logits.data_ptr(), dt, int(layout), labels.data_ptr(), B, S, Lt, V, int(mode), _lib.f32x([w, alpha, beta, scale]),
-            scalars.data_ptr(), pred.data_ptr() if want_pred else None, pred_full.data_ptr() if want_pred_full else None,
-            glogits.data_ptr() if want_grad else None, ws.data_ptr(), ws.numel(), _stream())
+            logits.data_ptr(), dt, int(layout), labels.data_ptr(), B, S, Lt, V, int(mode), _loss_params(w, alpha, beta, scale),
+            scalars.data_ptr(), _ptr(pred), _ptr(pred_full), glogits.data_ptr() if want_grad else None, ws.data_ptr(), ws.numel(), _stream())
     _lib.check(rc, "vaa_loss_fwd_bwd")
     if want_pred_full:
         return scalars, pred, (glogits if want_grad else None), pred_full
@@ -531,23 +559,17 @@ class DiscrepancyLoss(torch.autograd.Function):
     def forward(ctx, logits, labels, mode, w, alpha, beta, scale, layout):
         scalars, pred, g, pred_full = loss_fwd_bwd(logits.detach(), labels, mode, w, alpha, beta, scale, layout, want_grad=True,
                                                    want_pred_full=True)
-        ctx.save_for_backward(g)
-        ctx.mark_non_differentiable(scalars, pred, pred_full)
-        return scalars[0].clone(), scalars, pred, pred_full
+        return _loss_forward(ctx, scalars, pred, pred_full, g)
 
     @staticmethod
     def backward(ctx, gtotal, _gs, _gp, _gf):
-        (g,) = ctx.saved_tensors
-        return g * gtotal.to(g.dtype), None, None, None, None, None, None, None
+        return _loss_backward(ctx.saved_tensors[0], gtotal, 8)
 
 
 # ------------------------------------------------------------------------------------------------------
 # K3 on the labelled rows with a prebuilt row map (what the attack loops use)
 # ------------------------------------------------------------------------------------------------------
 ACTION_LO, N_ACTION = 31744, 256
-import os as _os
-
-
 SLICE_MODES = (LOSS_UADA_DDP, LOSS_UPA)  # gradient confined to the 256 action columns
 
 
@@ -582,13 +604,7 @@ def loss_rows_fwd_bwd(logits, rowmap: LossRowMap, mode: int, w: float = 5.0, alp
                       want_grad: bool = True, grad_kind: int = GRAD_FULL, want_pred: bool = True, grad=None):
     """K3 on logits [R,V] of the labelled rows. Returns (scalars f32[8], pred_slice i32 [B,L-1] | None, pred_full i32 [B,L-1] | None,
     grad [R,V] | [R,256] | None). pred_slice = 31744 + argmax of the action logits (UAD), pred_full = argmax over the vocabulary."""
-    if logits.dtype == torch.float32:
-        dt = _lib.DTYPE_F32
-    elif logits.dtype == torch.bfloat16:
-        dt = _lib.DTYPE_BF16
-    else:
-        raise _lib.VaaError(f"logits: unsupported dtype {logits.dtype}")
-    _need(logits, logits.dtype, "logits")
+    dt = _dtype_code(logits)
     if logits.dim() != 2:
         raise _lib.VaaError(f"logits: expected [R,V], got {tuple(logits.shape)}")
     R, V = int(logits.shape[0]), int(logits.shape[1])
@@ -596,15 +612,14 @@ def loss_rows_fwd_bwd(logits, rowmap: LossRowMap, mode: int, w: float = 5.0, alp
     L = _lib.lib()
     ws = _workspace(logits.device, L.vaa_loss_rows_ws_bytes(R), "k3")
     scalars = torch.empty(8, dtype=torch.float32, device=logits.device)
-    pred = torch.empty((B, Lt - 1), dtype=torch.int32, device=logits.device) if want_pred else None
-    pred_full = torch.empty((B, Lt - 1), dtype=torch.int32, device=logits.device) if want_pred else None
+    pred, pred_full = _pred_maps(B, Lt, logits.device, want_pred)
     if want_grad and grad is None:
         grad = torch.empty((R, N_ACTION if grad_kind == GRAD_SLICE else V), dtype=logits.dtype, device=logits.device)
     ws = ws if R > 0 else _workspace(logits.device, 256, "k3")
     with _timed("K3_loss_rows_fwd_bwd", B=B, L=Lt, V=V, dtype=str(logits.dtype), rows=R, grad_kind=grad_kind):
-        rc = L.vaa_loss_rows_fwd_bwd(logits.data_ptr(), dt, rowmap.buf.data_ptr(), R, B, Lt, V, int(mode), _lib.f32x([w, alpha, beta, scale]),
-                                     scalars.data_ptr(), pred.data_ptr() if want_pred else None, pred_full.data_ptr() if want_pred else None,
-                                     grad.data_ptr() if want_grad else None, int(grad_kind), ws.data_ptr(), ws.numel(), _stream())
+        rc = L.vaa_loss_rows_fwd_bwd(logits.data_ptr(), dt, rowmap.buf.data_ptr(), R, B, Lt, V, int(mode), _loss_params(w, alpha, beta, scale),
+                                     scalars.data_ptr(), _ptr(pred), _ptr(pred_full), grad.data_ptr() if want_grad else None, int(grad_kind),
+                                     ws.data_ptr(), ws.numel(), _stream())
     _lib.check(rc, "vaa_loss_rows_fwd_bwd")
     return scalars, pred, pred_full, (grad if want_grad else None)
 
@@ -612,18 +627,17 @@ def loss_rows_fwd_bwd(logits, rowmap: LossRowMap, mode: int, w: float = 5.0, alp
 def loss_rows_stats(logits, rowmap: LossRowMap, mode: int, w: float = 5.0, alpha: float = 0.8, beta: float = 0.2, scale: float = 1.0, grad=None):
     """The statistics pass of K3 alone (vaa_loss_rows_stats). In LOSS_UADA_DDP mode `grad` [R,256] receives the gradient slice in the same pass.
     Returns the workspace tensor that step_epilogue folds into the scalars."""
-    dt = _lib.DTYPE_F32 if logits.dtype == torch.float32 else _lib.DTYPE_BF16
-    _need(logits, logits.dtype, "logits")
-    if logits.dim() != 2 or logits.dtype not in (torch.float32, torch.bfloat16):
-        raise _lib.VaaError(f"logits: expected f32|bf16 [R,V], got {logits.dtype} {tuple(logits.shape)}")
+    dt = _dtype_code(logits)
+    if logits.dim() != 2:
+        raise _lib.VaaError(f"logits: expected [R,V], got {tuple(logits.shape)}")
     R, V = int(logits.shape[0]), int(logits.shape[1])
     L = _lib.lib()
     ws = _workspace(logits.device, L.vaa_loss_rows_ws_bytes(R), "k3")
     if grad is not None:
         _need(grad, logits.dtype, "grad", (R, N_ACTION))
     with _timed("K3_loss_rows_stats", B=rowmap.B, L=rowmap.L, V=V, rows=R):
-        rc = L.vaa_loss_rows_stats(logits.data_ptr(), dt, rowmap.buf.data_ptr(), R, rowmap.B, rowmap.L, V, int(mode), _lib.f32x([w, alpha, beta, scale]),
-                                   grad.data_ptr() if grad is not None else None, GRAD_SLICE, ws.data_ptr(), ws.numel(), _stream())
+        rc = L.vaa_loss_rows_stats(logits.data_ptr(), dt, rowmap.buf.data_ptr(), R, rowmap.B, rowmap.L, V, int(mode), _loss_params(w, alpha, beta, scale),
+                                   _ptr(grad), GRAD_SLICE, ws.data_ptr(), ws.numel(), _stream())
     _lib.check(rc, "vaa_loss_rows_stats")
     return ws
 
@@ -656,8 +670,8 @@ def _head_stats(hidden, w_head, rowmap, mode, w, alpha, beta, scale, grad, want_
     dbg = torch.empty((R, V), dtype=torch.bfloat16, device=hidden.device) if want_logits else None
     with _timed("K3_head_loss_rows_stats", rows=R, V=V, D=D):
         rc = L.vaa_head_loss_rows_stats(hidden.data_ptr(), w_head.data_ptr(), D, rowmap.buf.data_ptr(), R, rowmap.B, rowmap.L, V, int(mode),
-                                        _lib.f32x([w, alpha, beta, scale]), grad.data_ptr() if grad is not None else None, ws.data_ptr(), ws.numel(),
-                                        hws.data_ptr(), hws.numel(), dbg.data_ptr() if dbg is not None else None, _stream())
+                                        _loss_params(w, alpha, beta, scale), _ptr(grad), ws.data_ptr(), ws.numel(), hws.data_ptr(), hws.numel(),
+                                        _ptr(dbg), _stream())
     _lib.check(rc, "vaa_head_loss_rows_stats")
     return ws, hws, dbg
 
@@ -677,12 +691,11 @@ def head_loss_rows_fwd_bwd(hidden, w_head, rowmap: "LossRowMap", mode: int, w: f
     ws, hws, lg = _head_stats(hidden, w_head, rowmap, mode, w, alpha, beta, scale, grad if mode == LOSS_UADA_DDP else None, want_logits)
     L = _lib.lib()
     scalars = torch.empty(8, dtype=torch.float32, device=dev)
-    pred = torch.empty((rowmap.B, rowmap.L - 1), dtype=torch.int32, device=dev) if want_pred else None
-    pred_full = torch.empty((rowmap.B, rowmap.L - 1), dtype=torch.int32, device=dev) if want_pred else None
+    pred, pred_full = _pred_maps(rowmap.B, rowmap.L, dev, want_pred)
     with _timed("K3_head_loss_rows_finish", rows=R, V=V):
-        rc = L.vaa_head_loss_rows_finish(rowmap.buf.data_ptr(), R, rowmap.B, rowmap.L, V, int(mode), _lib.f32x([w, alpha, beta, scale]), ws.data_ptr(), ws.numel(),
-                                         hws.data_ptr(), hws.numel(), scalars.data_ptr(), pred.data_ptr() if want_pred else None,
-                                         pred_full.data_ptr() if want_pred else None, grad.data_ptr() if (want_grad and mode == LOSS_UPA) else None, _stream())
+        rc = L.vaa_head_loss_rows_finish(rowmap.buf.data_ptr(), R, rowmap.B, rowmap.L, V, int(mode), _loss_params(w, alpha, beta, scale), ws.data_ptr(), ws.numel(),
+                                         hws.data_ptr(), hws.numel(), scalars.data_ptr(), _ptr(pred), _ptr(pred_full),
+                                         grad.data_ptr() if (want_grad and mode == LOSS_UPA) else None, _stream())
     _lib.check(rc, "vaa_head_loss_rows_finish")
     return (scalars, pred, pred_full, grad, lg) if want_logits else (scalars, pred, pred_full, grad)
 
@@ -734,14 +747,11 @@ def head_slice_fwd_bwd(hidden, w_head, rowmap: "LossRowMap", mode: int, w: float
     dh = torch.empty((R, D), dtype=torch.bfloat16, device=dev) if want_dh else None
     gs = torch.empty((R, N_ACTION), dtype=torch.bfloat16, device=dev) if want_grad_slice else None
     scalars = torch.empty(8, dtype=torch.float32, device=dev) if want_scalars else None
-    pred = torch.empty((rowmap.B, rowmap.L - 1), dtype=torch.int32, device=dev) if want_scalars else None
-    pred_full = torch.empty((rowmap.B, rowmap.L - 1), dtype=torch.int32, device=dev) if want_scalars else None
+    pred, pred_full = _pred_maps(rowmap.B, rowmap.L, dev, want_scalars)
     with _timed("K3s_head_slice_fwd_bwd", rows=R, D=D):
-        rc = L.vaa_head_slice_fwd_bwd(hidden.data_ptr(), w_head.data_ptr(), wt.data_ptr() if wt is not None else None, D, rowmap.buf.data_ptr(), R,
-                                      rowmap.B, rowmap.L, V, int(mode), _lib.f32x([w, alpha, beta, scale]), dh.data_ptr() if dh is not None else None,
-                                      gs.data_ptr() if gs is not None else None, lws.data_ptr(), lws.numel(),
-                                      scalars.data_ptr() if scalars is not None else None, pred.data_ptr() if pred is not None else None,
-                                      pred_full.data_ptr() if pred_full is not None else None, zws.data_ptr(), zws.numel(), _stream())
+        rc = L.vaa_head_slice_fwd_bwd(hidden.data_ptr(), w_head.data_ptr(), _ptr(wt), D, rowmap.buf.data_ptr(), R, rowmap.B, rowmap.L, V, int(mode),
+                                      _loss_params(w, alpha, beta, scale), _ptr(dh), _ptr(gs), lws.data_ptr(), lws.numel(), _ptr(scalars), _ptr(pred),
+                                      _ptr(pred_full), zws.data_ptr(), zws.numel(), _stream())
     _lib.check(rc, "vaa_head_slice_fwd_bwd")
     return {"dh": dh, "ws": lws, "zs": zws, "scalars": scalars, "pred": pred, "pred_full": pred_full, "grad_slice": gs}
 
@@ -777,15 +787,12 @@ def _step_epilogue(P, partials, msg, scalars, rowmap, R, V, mode, w, alpha, beta
     _need(scalars, torch.float32, "scalars", (P, 8) if seg else (8,))
     if msg.numel() < P * (n + 4):
         raise _lib.VaaError(f"msg: needs {P * (n + 4)} floats, has {msg.numel()}")
-    pred = pred_full = None
-    if rowmap is not None and want_pred:
-        pred = torch.empty((rowmap.B, rowmap.L - 1), dtype=torch.int32, device=msg.device)
-        pred_full = torch.empty((rowmap.B, rowmap.L - 1), dtype=torch.int32, device=msg.device)
+    fold = rowmap is not None
+    pred, pred_full = _pred_maps(rowmap.B, rowmap.L, msg.device) if fold and want_pred else (None, None)
     common = ((partials.data_ptr(), nparts, n) + ((P,) if seg else ())
-              + (rowmap.buf.data_ptr() if rowmap is not None else None, int(R), rowmap.B if rowmap is not None else 0,
-                 rowmap.L if rowmap is not None else 0, int(V), int(mode), _lib.f32x([w, alpha, beta, scale]),
-                 loss_ws.data_ptr() if loss_ws is not None else None, loss_ws.numel() if loss_ws is not None else 0, scalars.data_ptr(),
-                 pred.data_ptr() if pred is not None else None, pred_full.data_ptr() if pred_full is not None else None, msg.data_ptr()))
+              + (rowmap.buf.data_ptr() if fold else None, int(R), rowmap.B if fold else 0, rowmap.L if fold else 0, int(V), int(mode),
+                 _loss_params(w, alpha, beta, scale), _ptr(loss_ws), loss_ws.numel() if loss_ws is not None else 0, scalars.data_ptr(),
+                 _ptr(pred), _ptr(pred_full), msg.data_ptr()))
     with _timed("EPI_" + name[4:], n=n, parts=nparts, **({"P": P} if seg else {})):
         if update is None:
             rc = getattr(_lib.lib(), name)(*common, _stream())
@@ -797,10 +804,9 @@ def _step_epilogue(P, partials, msg, scalars, rowmap, R, V, mode, w, alpha, beta
             sp = u.get("stat_part")
             if sp is not None:
                 _need(sp, torch.float64, "stat_part", (P * ((n + 63) // 64), 2))
-            rc = getattr(_lib.lib(), name + "_update")(*common, u["patch"].data_ptr(), u["m"].data_ptr() if u.get("m") is not None else None,
-                                                       u["v"].data_ptr() if u.get("v") is not None else None, int(u["mode"]), float(u["lr"]),
+            rc = getattr(_lib.lib(), name + "_update")(*common, u["patch"].data_ptr(), _ptr(u.get("m")), _ptr(u.get("v")), int(u["mode"]), float(u["lr"]),
                                                        float(u.get("beta1", 0.9)), float(u.get("beta2", 0.999)), float(u.get("eps", 1e-6)),
-                                                       int(u["step"]), sp.data_ptr() if sp is not None else None, _stream())
+                                                       int(u["step"]), _ptr(sp), _stream())
     _lib.check(rc, name)
     return pred, pred_full
 
@@ -811,14 +817,11 @@ class DiscrepancyLossRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, rowmap, mode, w, alpha, beta, scale):
         scalars, pred, pred_full, g = loss_rows_fwd_bwd(logits.detach(), rowmap, mode, w, alpha, beta, scale, want_grad=True, grad_kind=GRAD_FULL)
-        ctx.save_for_backward(g)
-        ctx.mark_non_differentiable(scalars, pred, pred_full)
-        return scalars[0].clone(), scalars, pred, pred_full
+        return _loss_forward(ctx, scalars, pred, pred_full, g)
 
     @staticmethod
     def backward(ctx, gtotal, _gs, _gp, _gf):
-        (g,) = ctx.saved_tensors
-        return g * gtotal.to(g.dtype), None, None, None, None, None, None
+        return _loss_backward(ctx.saved_tensors[0], gtotal, 7)
 
 
 class HeadLossRows(torch.autograd.Function):
@@ -832,17 +835,13 @@ class HeadLossRows(torch.autograd.Function):
         sliced = mode in SLICE_MODES
         scalars, pred, pred_full, g = loss_rows_fwd_bwd(logits, rowmap, mode, w, alpha, beta, scale, want_grad=True,
                                                         grad_kind=GRAD_SLICE if sliced else GRAD_FULL)
-        ctx.save_for_backward(g, weight)
         ctx.sliced = sliced
-        ctx.mark_non_differentiable(scalars, pred, pred_full)
-        return scalars[0].clone(), scalars, pred, pred_full
+        return _loss_forward(ctx, scalars, pred, pred_full, g, weight)
 
     @staticmethod
     def backward(ctx, gtotal, _gs, _gp, _gf):
         g, weight = ctx.saved_tensors
-        wsel = weight[ACTION_LO : ACTION_LO + N_ACTION] if ctx.sliced else weight
-        dh = (g * gtotal.to(g.dtype)) @ wsel
-        return dh, None, None, None, None, None, None, None
+        return _loss_backward(g, gtotal, 8, weight[ACTION_LO : ACTION_LO + N_ACTION] if ctx.sliced else weight)
 
 
 class HeadLossRowsFused(torch.autograd.Function):
@@ -852,15 +851,12 @@ class HeadLossRowsFused(torch.autograd.Function):
     @staticmethod
     def forward(ctx, hidden, weight, rowmap, mode, w, alpha, beta, scale):
         scalars, pred, pred_full, g = head_loss_rows_fwd_bwd(hidden.detach().contiguous(), weight, rowmap, mode, w, alpha, beta, scale, want_grad=True)
-        ctx.save_for_backward(g, weight)
-        ctx.mark_non_differentiable(scalars, pred, pred_full)
-        return scalars[0].clone(), scalars, pred, pred_full
+        return _loss_forward(ctx, scalars, pred, pred_full, g, weight)
 
     @staticmethod
     def backward(ctx, gtotal, _gs, _gp, _gf):
         g, weight = ctx.saved_tensors
-        dh = (g * gtotal.to(g.dtype)) @ weight[ACTION_LO : ACTION_LO + N_ACTION]
-        return dh, None, None, None, None, None, None, None
+        return _loss_backward(g, gtotal, 8, weight[ACTION_LO : ACTION_LO + N_ACTION])
 
 
 _silent_cache = {}
@@ -897,14 +893,11 @@ class HeadSliceLoss(torch.autograd.Function):
         else:
             scalars, pred = _silent_outputs(h.device, rowmap.B, rowmap.L)
             pred_full = pred
-        ctx.save_for_backward(o["dh"])
-        ctx.mark_non_differentiable(scalars, pred, pred_full)
-        return scalars[0].clone(), scalars, pred, pred_full
+        return _loss_forward(ctx, scalars, pred, pred_full, o["dh"])
 
     @staticmethod
     def backward(ctx, gtotal, _gs, _gp, _gf):
-        (dh,) = ctx.saved_tensors
-        return dh * gtotal.to(dh.dtype), None, None, None, None, None, None, None, None, None
+        return _loss_backward(ctx.saved_tensors[0], gtotal, 10)
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from roboticattack_amd import cli  # noqa: E402
 from roboticattack_amd import dist as vdist  # noqa: E402
-from roboticattack_amd.attack.uada_ddp import parse_maskidx_sweep  # noqa: E402
+from roboticattack_amd.attack.uada_ddp import parse_maskidx_sweep, parse_target_sweep  # noqa: E402
 from white_patch.UADA_ddp import OpenVLAAttacker  # noqa: E402
 
 
@@ -58,6 +58,8 @@ def main(args):
         instance_params.update(attack_type=args.attack, alpha=args.alpha, belta=args.belta, target_action=args.targetAction)
     if args.maskidx_sweep:  # extension: one patch per maskidx group in one loop (patches under {path}/<group tag>/)
         instance_params.update(maskidx_sweep=args.maskidx_sweep)
+    if args.target_sweep:  # extension: one TMA patch per (maskidx, target) group in one loop (--attack TMA; patches under {path}/<group tag>/)
+        instance_params.update(target_sweep=args.target_sweep)
     OpenVLAAttacker._attack_entry(rank, instance_params, world)
     print("Attack done!")
 
@@ -74,6 +76,8 @@ def arg_parser(argv=None):
     parser.add_argument("--targetAction", default=0, type=float)
     # extension: a maskidx sweep, groups separated by ';' ("0;0,1,2"): one patch per group, optimised together; empty = one patch for --maskidx
     parser.add_argument("--maskidx_sweep", default="", type=parse_maskidx_sweep)
+    # extension: a TMA target sweep, groups "maskidx[,maskidx...]:target" separated by ';' ("0:0;1:0;6:1"): one patch per group; needs --attack TMA
+    parser.add_argument("--target_sweep", default="", type=parse_target_sweep)
     return parser.parse_args(argv)
 
 

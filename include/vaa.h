@@ -266,7 +266,8 @@ int vaa_step_epilogue_update(const float* partials, int nparts, int n, const voi
  *             it in VAA_LOSS_UADA_DDP mode: each row's gradient is normalised by ITS GROUP's action-row count, so dhidden / grad_slice / the row
  *             statistics of group p's rows are bit for bit those of the call on group p's rows alone with the group's ordinary map (an ordinary map
  *             gives the old bits). Folds inside those calls (scalars != NULL, vaa_head_loss_rows_finish) treat the map as ONE batch: per-group
- *             scalars come from vaa_step_epilogue_seg. UPA's batch means are not per group: the segmented map serves VAA_LOSS_UADA_DDP only.
+ *             scalars come from vaa_step_epilogue_seg. UPA's batch means are not per group: the segmented map serves VAA_LOSS_UADA_DDP there, and
+ *             VAA_LOSS_CE through vaa_loss_rows_fwd_bwd_seg (the target sweep below).
  *   vaa_step_epilogue_seg: ONE launch, vaa_step_epilogue per group (the same kernel: vaa_step_epilogue is its one-group case): partials
  *             [P*nparts][n] (group p's nparts tiles at p*nparts: K2' with one partial per image, nparts = Bp) ->
  *               msg[p*n .. (p+1)*n)  = group p's fixed-order sum: bitwise vaa_step_epilogue over those nparts tiles
@@ -292,6 +293,31 @@ int vaa_step_epilogue_seg_update(const float* partials, int nparts, int n, int P
                                  float beta2, float eps, int step, double* stat_part, void* stream);
 int vaa_patch_update_seg(float* patch, const float* g, float* m, float* v, int n, int P, int mode, float lr, float beta1, float beta2,
                          float eps, int step, float l1_clip, float grad_scale, float* stats, void* stream);
+
+/*
+ * TARGET SWEEP — P TMA patch groups (TMA.py's target-token CE, one (maskidx, target action) pair per group: the released T-dof1 .. T-dof7 family)
+ * in ONE step. The gradient of the cross-entropy needs every logit, so the head stays the hipBLASLt GEMM — run ONCE over the rows of all groups —
+ * and K3 takes the segmented row map in VAA_LOSS_CE mode:
+ *   vaa_loss_rows_fwd_bwd_seg: vaa_loss_rows_fwd_bwd (its two launches, the same kernels: that call is their one-batch case) on logits [R,V] of
+ *             P groups of B/P images; rowmap from vaa_loss_rowmap_build_seg (groups may label different numbers of rows), or an ordinary map
+ *             with P = 1 (the bits of vaa_loss_rows_fwd_bwd). Row r's gradient = scale / nrow_g (softmax - onehot) with nrow_g the row count of
+ *             ITS group; one fold workgroup per group, past the gradient workgroups (no gradient waits for a fold), folds the group with its own
+ *             map into scalars[8g .. 8g+8) and rows g*B/P .. of pred_tokens / pred_full_tokens [B, L-1]. At V = 32,064 a row is split into 4 parts
+ *             for every R, so group g's gradient rows, scalars and prediction-map rows are bit for bit those of vaa_loss_rows_fwd_bwd on the
+ *             group's logits rows alone with its ordinary map. VAA_LOSS_CE with VAA_GRAD_FULL only (else VAA_E_UNSUPPORTED); grad may be NULL
+ *             (evaluation); always two launches (VAA_K3_ONE_PASS does not apply). scalars dev f32 [P,8]; the other arguments as
+ *             vaa_loss_rows_fwd_bwd.
+ *   vaa_step_epilogue_seg_tail[_update]: vaa_step_epilogue_seg[_update] in its pass-through form (K2's fixed-order sums of P groups, + K4) whose
+ *             message tail carries scalars that are final already: msg[P*n + 4g ..) = scalars_in[8g + {1, 2, 7, 0}] = group g's {CE, w^2*MSE, UAD,
+ *             total}. For the step whose scalars the loop reads; every other step keeps vaa_step_epilogue_seg's zero tail.
+ */
+int vaa_loss_rows_fwd_bwd_seg(const void* logits, int dtype, const void* rowmap, int R, int B, int L, int V, int P, int mode, const float* params,
+                              float* scalars, int32_t* pred_tokens, int32_t* pred_full_tokens, void* grad, int grad_kind, void* ws,
+                              size_t ws_bytes, void* stream);
+int vaa_step_epilogue_seg_tail(const float* partials, int nparts, int n, int P, const float* scalars_in, float* msg, void* stream);
+int vaa_step_epilogue_seg_tail_update(const float* partials, int nparts, int n, int P, const float* scalars_in, float* msg, float* patch, float* m,
+                                      float* v, int opt_mode, float lr, float beta1, float beta2, float eps, int step, double* stat_part,
+                                      void* stream);
 
 /*
  * LM head FUSED with K3's statistics (SURVEY.md section 8f-2 as the survey wrote it; for callers that own the LM-head weight) — replaces

@@ -69,6 +69,9 @@ EXPORTS = (
     "vaa_step_epilogue_seg",
     "vaa_step_epilogue_seg_update",
     "vaa_patch_update_seg",
+    "vaa_loss_rows_fwd_bwd_seg",
+    "vaa_step_epilogue_seg_tail",
+    "vaa_step_epilogue_seg_tail_update",
     "vaa_async_error",
     "vaa_prof_start",
     "vaa_prof_stop",
@@ -229,6 +232,12 @@ def lib() -> C.CDLL:
                                                f32, f32, f32, i32, vp, vp]
     L.vaa_patch_update_seg.restype = i32
     L.vaa_patch_update_seg.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, i32, f32, f32, vp, vp]
+    L.vaa_loss_rows_fwd_bwd_seg.restype = i32
+    L.vaa_loss_rows_fwd_bwd_seg.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, i32, C.POINTER(f32), vp, vp, vp, vp, i32, vp, sz, vp]
+    L.vaa_step_epilogue_seg_tail.restype = i32
+    L.vaa_step_epilogue_seg_tail.argtypes = [vp, i32, i32, i32, vp, vp, vp]
+    L.vaa_step_epilogue_seg_tail_update.restype = i32
+    L.vaa_step_epilogue_seg_tail_update.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, i32, vp, vp]
     L.vaa_async_error.restype = i32
     L.vaa_async_error.argtypes = []
     L.vaa_prof_start.restype = i32

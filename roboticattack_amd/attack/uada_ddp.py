@@ -76,18 +76,42 @@ def sweep_rows(bs: int, sweep) -> int:
     return sum(bs * (len(m) + 1) for m in sweep)
 
 
+def parse_target_sweep(text):
+    """CLI form of a target sweep: "0:0;1:0;0,1,2:0.25" -> [([0], 0.0), ([1], 0.0), ([0, 1, 2], 0.25)] (maskidx[,maskidx...]:target per group);
+    "" / None -> None (no sweep)."""
+    if text is None or not str(text).strip():
+        return None
+    out = []
+    for part in str(text).split(";"):
+        idx, sep, target = part.partition(":")
+        if not sep or not target.strip():
+            raise ValueError(f"target sweep: every group reads maskidx[,maskidx...]:target, got {part!r}")
+        out.append(([int(v) for v in idx.split(",") if v.strip() != ""], float(target)))
+    return out
+
+
+def target_sweep_tag(maskidx, target) -> str:
+    """Directory / log tag of a target sweep group: ([0], 0.25) -> "maskidx0-target0.25", ([0, 1], 0) -> "maskidx0-1-target0" (%g of the
+    target: equal groups give the same string, different ones different strings)."""
+    return f"{sweep_tag(maskidx)}-target{float(target):g}"
+
+
 class OpenVLAAttacker(AttackBase):
     val_batches = 100  # UADA_ddp.py:240
     val_every = 200  # UADA_ddp.py:233
 
     def __init__(self, vla_path, dataset_name, save_dir="", resize_patch=False, patch_size=[3, 50, 50], lr=0.01, bs=1, warmup=20,
                  num_iter=10000, maskidx=[], innerLoop=1, geometry=True, use_wandb=True, MSE_weights=1,
-                 model_factory=None, dataset_factory=None, device=None, attack_type="UADA", alpha=0.8, belta=0.2, target_action=0.0, maskidx_sweep=None):
+                 model_factory=None, dataset_factory=None, device=None, attack_type="UADA", alpha=0.8, belta=0.2, target_action=0.0, maskidx_sweep=None,
+                 target_sweep=None):
         """`attack_type`, `alpha`, `belta`, `target_action` are EXTENSIONS (the reference ships DDP for UADA only):
         "UPA" = UPA.py's reverse-direction loss + L1 grad clip, "TMA" = TMA.py's target-token CE, same data-parallel loop.
         `maskidx_sweep` (EXTENSION): a list of maskidx lists optimises one patch per list in ONE loop — every group sees the same frames, draws and
         schedule, and group p ends where a standalone run with maskidx = maskidx_sweep[p] and the same seed ends (DESIGN.md §maskidx sweep).
-        None keeps the loop above exactly as it is; `maskidx` is then unused."""
+        None keeps the loop above exactly as it is; `maskidx` is then unused.
+        `target_sweep` (EXTENSION, attack_type="TMA" only): a list of (maskidx list, target action value) pairs optimises one TMA patch per pair in
+        ONE loop the same way — group p ends where a standalone TMA run with maskidx = maskidx_p, target_action = target_p and the same seed ends
+        (DESIGN.md §maskidx sweep); `maskidx` and `target_action` are then unused. None: no target sweep."""
         rank, world, local = vdist.env_rank_world()
         if device is None:
             device = vdist.local_device()
@@ -109,6 +133,9 @@ class OpenVLAAttacker(AttackBase):
         self.maskidx_sweep = None
         if maskidx_sweep is not None:
             self.maskidx_sweep = self._check_sweep(maskidx_sweep)
+        self.target_sweep = None
+        if target_sweep is not None:
+            self.target_sweep = self._check_target_sweep(target_sweep, maskidx_sweep)
 
     def _check_sweep(self, sweep):
         """Refuses (ValueError naming the limit) what the batched sweep does not cover."""
@@ -134,6 +161,28 @@ class OpenVLAAttacker(AttackBase):
                              f"(K3s covers at most {SWEEP_MAX_ROWS} rows)")
         return sweep
 
+    def _check_target_sweep(self, sweep, maskidx_sweep):
+        """Refuses (ValueError naming the limit) what the batched target sweep does not cover."""
+        if maskidx_sweep is not None:
+            raise ValueError("target_sweep: cannot be combined with maskidx_sweep (one kind of sweep per run)")
+        sweep = [([int(v) for v in m], float(t)) for m, t in sweep]
+        if not sweep or any(len(m) == 0 for m, _ in sweep):
+            raise ValueError("target_sweep: needs at least one group, and every group at least one maskidx")
+        if any(v < 0 or v > 6 or len(set(m)) != len(m) for m, _ in sweep for v in m):
+            raise ValueError(f"target_sweep: every maskidx is a distinct DoF index 0..6, got {sweep}")
+        if len({target_sweep_tag(m, t) for m, t in sweep}) != len(sweep):
+            raise ValueError(f"target_sweep: groups must be distinct, got {sweep}")
+        if self.attack_type != "TMA":
+            raise ValueError(f"target_sweep: TMA only (got attack_type={self.attack_type!r}; UADA sweeps go through maskidx_sweep, UPA sweeps are not implemented)")
+        if self.randomPatchTransform.resize_patch:
+            raise ValueError("target_sweep: resize_patch=True is not supported (one patch size per group only)")
+        if not self.fused_ddp_available():
+            raise ValueError("target_sweep: needs the fused path (a model that exposes its patch-embed weights and hidden rows, VAA_FUSED_EPILOGUE != 0)")
+        if len(sweep) * self.bs > SWEEP_MAX_IMAGES:
+            raise ValueError(f"target_sweep: {len(sweep)} groups x bs {self.bs} = {len(sweep) * self.bs} images per rank exceed the limit of "
+                             f"{SWEEP_MAX_IMAGES} (K2' one partial tile per image)")
+        return sweep
+
     def setup(self, rank, world_size):
         vdist.init_process_group(device=self.device if self.device.type == "cuda" else None)
         if self.device.type == "cuda":
@@ -156,7 +205,7 @@ class OpenVLAAttacker(AttackBase):
             self.cleanup()
 
     def _attack(self, rank, world_size):
-        if self.maskidx_sweep is not None:
+        if self.maskidx_sweep is not None or self.target_sweep is not None:
             return self._attack_sweep(rank, world_size)
         dev = self.device
         if rank == 0:
@@ -207,11 +256,21 @@ class OpenVLAAttacker(AttackBase):
         """The loop above for P patch groups at once (UADA, fused path): one [P*bs] step per inner step — K1 tile-major with one patch per group,
         ONE forward / backward, K3s with the segmented row map, K2' with a partial per image, the segmented epilogue (+ AdamW of every group);
         at world > 1 ONE all-reduce of [P gradients | P x 4 scalars] and the segmented K4. The RNG streams are consumed as by ONE standalone run:
-        one patch init (every group starts from it), one transform draw per frame and step, shared by the groups."""
+        one patch init (every group starts from it), one transform draw per frame and step, shared by the groups.
+        A target sweep (TMA) is the same loop with the groups' target labels and, per step, ONE hipBLASLt head + K3 in LOSS_CE mode over the
+        segmented map (target_sweep_step) in place of K3s."""
         dev = self.device
-        sweep = self.maskidx_sweep
+        tma = self.target_sweep is not None
+        sweep = self.target_sweep if tma else self.maskidx_sweep
         P = len(sweep)
-        self.sweep_tags = [sweep_tag(m) for m in sweep]
+        if tma:
+            from ..labels import tma_target_tokens
+
+            self.sweep_tags = [target_sweep_tag(m, t) for m, t in sweep]
+            self._tma_targets = [tma_target_tokens(float(t) * torch.ones(7).numpy(), m, self.action_tokenizer).to(dev) for m, t in sweep]
+        else:
+            self.sweep_tags = [sweep_tag(m) for m in sweep]
+        what = "TMA target sweep" if tma else "UADA maskidx sweep"
         if rank == 0:
             p0 = torch.rand(self.patch_size).to(dev)  # UADA_ddp.py:140-141, drawn once: every group's standalone run draws this patch
         else:
@@ -240,24 +299,28 @@ class OpenVLAAttacker(AttackBase):
             img_all = img.repeat(P, 1, 1, 1).contiguous()
             ids_all = input_ids.repeat(P, 1).contiguous()
             am_all = attention_mask.repeat(P, 1).contiguous() if attention_mask is not None else None
-            labels_all = mask_labels_sweep(labels, sweep)
+            labels_all = torch.cat([self._sweep_group_labels(labels, g) for g in range(P)], dim=0)
             row_index = self.vla.label_row_index(labels_all)
             R = int(row_index.numel())
             if R == 0:
-                raise ValueError("maskidx sweep: no labelled position in the batch")
-            if not self._slice_head(R, None, W):
+                raise ValueError(f"{what}: no labelled position in the batch")
+            if not tma and not self._slice_head(R, None, W):
                 raise ValueError(f"maskidx sweep: K3s does not take {R} labelled rows per rank here (limit {SWEEP_MAX_ROWS} rows, bf16 head)")
             segmap = ops.LossRowMapSeg(labels_all, P)
             pack = self.vla.make_pack(am_all) if (hasattr(self.vla, "make_pack") and am_all is not None) else None
 
             def step(inner_loop):
                 upd = optimizer.fused_update_args() if world_size == 1 else None
-                self.sweep_step(img_all, patches, ids_all, labels_all, row_index, segmap, pack, w, V, sync.buf, scalars, inner_loop == self.innerLoop - 1, upd)
+                read = inner_loop == self.innerLoop - 1  # the step whose loss scalars the loop reads (UADA_ddp.py:214-221)
+                if tma:
+                    self.target_sweep_step(img_all, patches, ids_all, row_index, segmap, pack, sync.buf, scalars, read, upd)
+                else:
+                    self.sweep_step(img_all, patches, ids_all, labels_all, row_index, segmap, pack, w, V, sync.buf, scalars, read, upd)
                 return None if world_size == 1 else sync.allreduce_packed
 
             s_sum, device_failure = self._inner_loop(optimizer, sync, world_size, step)
             self._end_outer(i, rank, world_size, scheduler, optimizer, s_sum, device_failure,
-                            f"UADA maskidx sweep (data parallel) outer iteration {i}", tags=self.sweep_tags)
+                            f"{what} (data parallel) outer iteration {i}", tags=self.sweep_tags)
         return patches
 
     def _inner_loop(self, optimizer, sync, world_size, step):
@@ -328,10 +391,38 @@ class OpenVLAAttacker(AttackBase):
         h = self.vla.hidden_rows(input_ids, None, row_index, patch_embeds=pe, pack=pack)
         return self.slice_step_tail(h, segmap, w, V, sink, msg, scalars, full_ce, update, P=int(patches.shape[0]))
 
+    def target_sweep_step(self, img_all, patches, input_ids, row_index, segmap, pack, msg, scalars, read, update=None):
+        """One inner step of the target sweep up to the exchange: K1 (one draw per frame, every group) -> body over P*bs images -> ONE hipBLASLt head
+        over the rows of all groups -> K3 in LOSS_CE mode with the segmented map (each row normalised by its group's row count, every group folded on
+        its own) -> ONE dh = g @ W, backward, K2' (a partial per image) -> ONE segmented epilogue in its pass-through form: msg = [P gradients |
+        P x {CE, 0, UAD, total}] on the step whose scalars are `read` (K3 made them final before the backward), a zero tail on the others (`scalars`
+        [P,8] is then left as it is); `update` = AdamW of every group inside the launch."""
+        sink = {}
+        P = int(patches.shape[0])
+        pe = self.randomPatchTransform.apply_sweep_batch(img_all, patches, self.mean, self.std, self.geometry, sink)
+        h = self.vla.hidden_rows(input_ids, None, row_index, patch_embeds=pe, pack=pack)
+        total, sc, _, pred_full = ops.HeadLossRowsSeg.apply(h, self.vla.lm_head.weight, segmap, P, 1.0)
+        total.backward()
+        if not read:
+            ops.step_epilogue_seg(sink["partials"], msg, scalars, P, update=update)
+            return None
+        ops.step_epilogue_seg_tail(sink["partials"], msg, sc, P, update=update)
+        return pred_full
+
+    def _sweep_group_labels(self, labels, g):
+        """Group g's labels of a sweep (a new tensor): masked with its maskidx (UADA_ddp.py:89-97), or its TMA target labels (TMA.py:124-129)."""
+        if self.target_sweep is not None:
+            from ..labels import tma_target_labels
+
+            return tma_target_labels(labels, self._tma_targets[g])
+        return self.mask_labels(labels.clone(), self.maskidx_sweep[g])
+
     def validate_sweep(self, i, patches, rank):
         """validate() per group: every validation batch is drawn ONCE (the RNG consumption of one standalone pass) and evaluated with each group's
         patch and labels; per group the averages, the AVG all-reduces, best-patch selection and the files under save_dir/<group tag>/."""
-        rbs = [ValReadback(self.val_batches, self.device) for _ in self.maskidx_sweep]
+        tma = self.target_sweep is not None
+        mode = ops.LOSS_CE if tma else ops.LOSS_UADA_DDP
+        rbs = [ValReadback(self.val_batches, self.device) for _ in self.sweep_tags]
         last_images = [None] * len(rbs)
         ph, pw = int(patches.shape[2]), int(patches.shape[3])
         with torch.no_grad():
@@ -341,16 +432,17 @@ class OpenVLAAttacker(AttackBase):
                 pixel_values, labels, attention_mask, input_ids = to_dev(data, self.device)
                 img = self.randomPatchTransform.stage_images(pixel_values)
                 draws = self.randomPatchTransform.draw_params(int(img.shape[0]), ph, pw, self.geometry)
-                for g, m in enumerate(self.maskidx_sweep):
+                for g in range(len(rbs)):
                     modified = self.randomPatchTransform.apply_random_patch_batch(img, patches[g].detach(), mean=self.mean, std=self.std,
                                                                                    geometry=self.geometry, draws=draws)
-                    lab = self.mask_labels(labels.clone(), m)
-                    _, sc, _ = self.model_loss(input_ids, attention_mask, modified, lab, ops.LOSS_UADA_DDP, w=float(self.MSE_weights), need_grad=False)
+                    lab = self._sweep_group_labels(labels, g)
+                    _, sc, _ = self.model_loss(input_ids, attention_mask, modified, lab, mode, w=float(self.MSE_weights), need_grad=False)
                     rbs[g].add(sc)
                     last_images[g] = modified
         self.last_val_log = {}
         for g, tag in enumerate(self.sweep_tags):
-            self.last_val_log[tag] = self._val_record(i, rank, rbs[g].read()[0], 2, patches[g], last_images[g], tag)
+            # selection metric: MSE distance (UADA) or the attack loss (TMA), as validate() picks it
+            self.last_val_log[tag] = self._val_record(i, rank, rbs[g].read()[0], 0 if tma else 2, patches[g], last_images[g], tag)
 
     def _loss_mode(self):
         return {"UADA": ops.LOSS_UADA_DDP, "UPA": ops.LOSS_UPA, "TMA": ops.LOSS_CE}[self.attack_type]

@@ -602,8 +602,10 @@ __global__ __launch_bounds__(kRowsT) void rows_stats_kernel(RowsArgs a, unsigned
 // fold_wg >= 0 (VAA_LOSS_CE with a full-row gradient: d total / d z = scale / nrow (softmax - onehot) needs the row's own parts and the row COUNT
 // of the map, nothing of other rows): workgroup fold_wg — one past the gradient workgroups — folds and publishes the scalars, every other
 // workgroup goes straight to its gradient (same parts, same formulas: the bits of the all-fold form) instead of waiting for a fold it does not use.
+// P > 0 (vaa_loss_rows_fwd_bwd_seg: VAA_LOSS_CE over P groups, a segmented map or an ordinary one with P = 1): P fold workgroups fold_wg + g, each
+// with its group's view (rows_group_view: scalars[8g..], its rows of the prediction maps); a gradient row takes the row count of ITS group.
 template <typename T, int kRowsT>
-__global__ __launch_bounds__(kRowsT) void rows_finish_kernel(RowsArgs a, int gsplit, int fold_wg) {
+__global__ __launch_bounds__(kRowsT) void rows_finish_kernel(RowsArgs a, int gsplit, int fold_wg, int P) {
     constexpr int N = Vec<T>::N;
     const int r = blockIdx.x / gsplit, h = blockIdx.x - r * gsplit;
     const int tid = threadIdx.x;
@@ -627,12 +629,13 @@ __global__ __launch_bounds__(kRowsT) void rows_finish_kernel(RowsArgs a, int gsp
     FoldOut f;
     if (fold_wg < 0) {
         f = rows_fold<kRowsT>(a, blockIdx.x == 0, sh);
-    } else if ((int)blockIdx.x == fold_wg) {
-        (void)rows_fold<kRowsT>(a, true, sh);
+    } else if ((int)blockIdx.x >= fold_wg) {
+        (void)rows_fold<kRowsT>(P > 0 ? rows_group_view(a, P, (int)blockIdx.x - fold_wg) : a, true, sh);
         return;
     } else {  // what rows_fold returns for VAA_LOSS_CE, as far as the gradient reads it
         f.Rn = min(a.R, a.rowmap[0]);
         f.nrow = (double)f.Rn;
+        if (P > 0 && r < f.Rn && a.rowmap[2] > 0) f.nrow = (double)row_label_count(a.rowmap, rowmap_seg_table(a.B, a.L), rm[r].b);
         f.nact = 0.0; f.aux1 = 0.0;
         f.dce = (double)a.scale;
     }
@@ -686,7 +689,7 @@ __global__ __launch_bounds__(kRowsT) void rows_finish_kernel(RowsArgs a, int gsp
 struct EpiArgs {
     const float* partials;
     float* msg;
-    const float* scalars_in;  // pass-through form: final scalars copied into the tail (nullptr: zero tail)
+    const float* scalars_in;  // pass-through form: final scalars [P,8] copied into the groups' tails (nullptr: zero tail)
     int n, nparts, nred, P, fold;
     int seg;                  // the fold reads the row map's header for its groups (vaa_step_epilogue_seg); 0: the map is folded as is, R rows
     int fuse_update;          // single-GPU step: K4's per-element update applied right where the gradient element is produced
@@ -727,28 +730,11 @@ __global__ __launch_bounds__(256) void step_epilogue_kernel(EpiArgs e, RowsArgs 
     if (!e.fold) {
         if (threadIdx.x < 4) {
             const int src = threadIdx.x == 3 ? 0 : (threadIdx.x == 2 ? 7 : (int)threadIdx.x + 1);  // CE, w^2*MSE, UAD, total
-            tail[threadIdx.x] = e.scalars_in ? e.scalars_in[src] : 0.0f;
+            tail[threadIdx.x] = e.scalars_in ? e.scalars_in[8 * g + src] : 0.0f;
         }
         return;
     }
-    RowsArgs ag = a;
-    if (e.seg) {  // group g's view: its own map, its rows of the statistics, its images of the prediction maps, its scalars
-        const int* map = a.rowmap;
-        const int Pm = map[2], Bp = a.B / e.P;
-        const bool total_ok = map[0] == a.R && (Pm == e.P || (Pm == 0 && e.P == 1));
-        int r0 = 0;
-        if (Pm > 0 && g < Pm) {
-            r0 = map[rowmap_seg_table(a.B, a.L) + 4 * g];
-            ag.rowmap = map + rowmap_seg_sub(a.B, a.L, Pm, g);
-        }
-        ag.R = total_ok ? ag.rowmap[0] : -1;  // a map of another batch than the caller states: rows_fold publishes NaN and never reads it
-        ag.B = Bp;
-        ag.part = a.part + (size_t)r0 * a.split;
-        ag.slice = a.slice + r0;
-        ag.scalars = a.scalars + 8 * g;
-        if (a.pred_tokens) ag.pred_tokens = a.pred_tokens + (size_t)g * Bp * (a.L - 1);
-        if (a.pred_full) ag.pred_full = a.pred_full + (size_t)g * Bp * (a.L - 1);
-    }
+    const RowsArgs ag = e.seg ? rows_group_view(a, e.P, g) : a;  // seg: the group's own map, statistics rows, prediction-map rows and scalars
     double (*sh)[7] = reinterpret_cast<double (*)[7]>(&sl[0][0][0]);
     const FoldOut f = rows_fold<256>(ag, true, sh);
     if (threadIdx.x == 0) {
@@ -1013,11 +999,11 @@ static int launch_rows_stats(const RowsArgs& a, int dtype, hipStream_t st, const
     return check_launch(who);
 }
 
-static int launch_rows_finish(const RowsArgs& a, int dtype, unsigned G, int gsplit, int fold_wg, hipStream_t st, const char* who) {
+static int launch_rows_finish(const RowsArgs& a, int dtype, unsigned G, int gsplit, int fold_wg, hipStream_t st, const char* who, int P = 0) {
     with_rows_inst(dtype, rows_threads(a.V), [&](auto t, auto n, const char* inst) {
         constexpr int NT = decltype(n)::value;
         static const std::string name = rows_inst_name("rows_finish_kernel", inst, "");
-        launch_k(name.c_str(), rows_finish_kernel<decltype(t), NT>, dim3(G), dim3(NT), 0, st, a, gsplit, fold_wg);
+        launch_k(name.c_str(), rows_finish_kernel<decltype(t), NT>, dim3(G), dim3(NT), 0, st, a, gsplit, fold_wg, P);
         return 0;
     });
     return check_launch(who);
@@ -1025,18 +1011,21 @@ static int launch_rows_finish(const RowsArgs& a, int dtype, unsigned G, int gspl
 
 }  // namespace vaa
 
-extern "C" int vaa_loss_rows_fwd_bwd(const void* logits, int dtype, const void* rowmap, int R, int B, int L, int V, int mode,
-                                     const float* params, float* scalars, int32_t* pred_tokens, int32_t* pred_full_tokens, void* grad,
-                                     int grad_kind, void* ws, size_t ws_bytes, void* stream) {
-    using namespace vaa;
-    const char* who = "vaa_loss_rows_fwd_bwd";
+namespace vaa {
+
+// vaa_loss_rows_fwd_bwd (P = 0: the map is one batch, scalars[8]) and vaa_loss_rows_fwd_bwd_seg (P > 0 groups, VAA_LOSS_CE, scalars [P,8]: the same
+// two launches — every row's gradient normalised by its group's row count, one fold workgroup per group past the gradient workgroups)
+static int loss_rows_impl(const char* who, int P, const void* logits, int dtype, const void* rowmap, int R, int B, int L, int V, int mode,
+                          const float* params, float* scalars, int32_t* pred_tokens, int32_t* pred_full_tokens, void* grad, int grad_kind, void* ws,
+                          size_t ws_bytes, void* stream) {
+    const bool seg = P > 0;
     if (!logits || !scalars) {
         set_error("%s: null pointer argument", who);
         return VAA_E_INVALID;
     }
     if (R == 0 && B > 0 && L > 1) {  // nothing is labelled: every scalar is 0 (the reference's means over empty sets are not defined), no prediction
         hipStream_t st0 = (hipStream_t)stream;
-        hipError_t e = hipMemsetAsync(scalars, 0, 8 * sizeof(float), st0);
+        hipError_t e = hipMemsetAsync(scalars, 0, (size_t)(seg ? P : 1) * 8 * sizeof(float), st0);
         if (e == hipSuccess && pred_tokens) e = hipMemsetAsync(pred_tokens, 0xff, (size_t)B * (L - 1) * sizeof(int32_t), st0);
         if (e == hipSuccess && pred_full_tokens) e = hipMemsetAsync(pred_full_tokens, 0xff, (size_t)B * (L - 1) * sizeof(int32_t), st0);
         if (e != hipSuccess) { set_error("%s: %s", who, hipGetErrorString(e)); return VAA_E_LAUNCH; }
@@ -1052,7 +1041,8 @@ extern "C" int vaa_loss_rows_fwd_bwd(const void* logits, int dtype, const void* 
     // Admitted when the grid takes at most HALF of the slots the runtime reports (residency is what a waiting grid relies on), outside
     // stream capture (the hand-over generation is a launch argument) and while no OTHER stream of this process has such launches in
     // flight; anything else takes the two launches. VAA_K3_ONE_PASS=0 turns it off.
-    if (rows_one_pass_wanted() && grad && grad_kind == VAA_GRAD_FULL && (mode == VAA_LOSS_UADA || mode == VAA_LOSS_CE) && (long)R * a.split <= 1024 && R < 65536) {
+    // (the groups of a segmented call add no hand-over between workgroups: always the two launches)
+    if (!seg && rows_one_pass_wanted() && grad && grad_kind == VAA_GRAD_FULL && (mode == VAA_LOSS_UADA || mode == VAA_LOSS_CE) && (long)R * a.split <= 1024 && R < 65536) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         const hipError_t ce = hipStreamIsCapturing(st, &cs);
         if (ce != hipSuccess) (void)hipGetLastError();
@@ -1061,7 +1051,7 @@ extern "C" int vaa_loss_rows_fwd_bwd(const void* logits, int dtype, const void* 
         unsigned* bar = (capturing || !rows_one_pass_fits(a, dtype) || !rows_one_pass_stream_ok(st)) ? nullptr : rows_bar_for(st, &gen);
         if (bar) return launch_rows_stats(a, dtype, st, "vaa_loss_rows_fwd_bwd(one pass)", bar, gen);
     }
-    rc = launch_rows_stats(a, dtype, st, "vaa_loss_rows_fwd_bwd(stats)");
+    rc = launch_rows_stats(a, dtype, st, seg ? "vaa_loss_rows_fwd_bwd_seg(stats)" : "vaa_loss_rows_fwd_bwd(stats)");
     if (rc != VAA_OK) return rc;
     // the finishing pass: per (row, part) when a full-row gradient (or a zero fill) has to be written, else one workgroup per row
     // (UPA slice) or a single workgroup (UADA_DDP slice: only the scalars are left to do)
@@ -1071,9 +1061,42 @@ extern "C" int vaa_loss_rows_fwd_bwd(const void* logits, int dtype, const void* 
     // CE full-row gradient: the fold moves to a workgroup of its own (rows_finish_kernel); VAA_K3_CE_FOLD_WG=0 keeps the all-fold form
     const char* ce_ev = getenv("VAA_K3_CE_FOLD_WG");
     const bool ce_fold_wg = !(ce_ev && ce_ev[0] == '0');
-    const int fold_wg = (full_rows && mode == VAA_LOSS_CE && ce_fold_wg) ? (int)G : -1;
-    if (fold_wg >= 0) ++G;
-    return launch_rows_finish(a, dtype, G, gsplit, fold_wg, st, "vaa_loss_rows_fwd_bwd(finish)");
+    int fold_wg = (full_rows && mode == VAA_LOSS_CE && ce_fold_wg) ? (int)G : -1;
+    if (seg) {  // the groups' fold workgroups behind the gradient workgroups (none without a gradient)
+        fold_wg = full_rows ? (int)G : 0;
+        G = (unsigned)(fold_wg + P);
+    } else if (fold_wg >= 0) {
+        ++G;
+    }
+    return launch_rows_finish(a, dtype, G, gsplit, fold_wg, st, seg ? "vaa_loss_rows_fwd_bwd_seg(finish)" : "vaa_loss_rows_fwd_bwd(finish)", P);
+}
+
+}  // namespace vaa
+
+extern "C" int vaa_loss_rows_fwd_bwd(const void* logits, int dtype, const void* rowmap, int R, int B, int L, int V, int mode,
+                                     const float* params, float* scalars, int32_t* pred_tokens, int32_t* pred_full_tokens, void* grad,
+                                     int grad_kind, void* ws, size_t ws_bytes, void* stream) {
+    return vaa::loss_rows_impl("vaa_loss_rows_fwd_bwd", 0, logits, dtype, rowmap, R, B, L, V, mode, params, scalars, pred_tokens, pred_full_tokens, grad,
+                               grad_kind, ws, ws_bytes, stream);
+}
+
+// TARGET SWEEP: K3 in VAA_LOSS_CE mode over P groups (a segmented row map: vaa_loss_rowmap_build_seg; or an ordinary map with P = 1) behind ONE
+// LM-head GEMM. Group g's gradient rows, scalars[8g..] and prediction-map rows are bit for bit vaa_loss_rows_fwd_bwd on the group's rows alone.
+extern "C" int vaa_loss_rows_fwd_bwd_seg(const void* logits, int dtype, const void* rowmap, int R, int B, int L, int V, int P, int mode,
+                                         const float* params, float* scalars, int32_t* pred_tokens, int32_t* pred_full_tokens, void* grad,
+                                         int grad_kind, void* ws, size_t ws_bytes, void* stream) {
+    using namespace vaa;
+    const char* who = "vaa_loss_rows_fwd_bwd_seg";
+    if (P <= 0 || P > 512 || B <= 0 || B % P != 0) {
+        set_error("%s: bad arguments (B=%d P=%d: B must be P groups of equal size, P <= 512)", who, B, P);
+        return VAA_E_INVALID;
+    }
+    if (mode != VAA_LOSS_CE || grad_kind != VAA_GRAD_FULL) {
+        set_error("%s: mode %d / grad_kind %d — per-group folds behind the GEMM head serve VAA_LOSS_CE with full-row gradients only", who, mode, grad_kind);
+        return VAA_E_UNSUPPORTED;
+    }
+    return loss_rows_impl(who, P, logits, dtype, rowmap, R, B, L, V, mode, params, scalars, pred_tokens, pred_full_tokens, grad, grad_kind, ws, ws_bytes,
+                          stream);
 }
 
 // The finishing pass behind vaa_head_loss_rows_stats (LM head fused with K3's statistics): the fold of the rows into the scalars, the
@@ -1131,12 +1154,15 @@ extern "C" int vaa_loss_rows_stats(const void* logits, int dtype, const void* ro
 
 namespace vaa {
 
-// vaa_step_epilogue[_update] (seg = 0: P = 1, the row map folded as is, any loss mode; the pass-through tail copies `scalars`) and
-// vaa_step_epilogue_seg[_update] (seg = 1: P groups, each folded with its own part of a segmented map, VAA_LOSS_UADA_DDP; a zero pass-through tail)
-static int step_epilogue_impl(const char* who, bool seg, const float* partials, int nparts, int n, int P, const void* rowmap, int R, int B, int L,
+// vaa_step_epilogue[_update] (kEpiOne: P = 1, the row map folded as is, any loss mode; the pass-through tail copies `scalars`),
+// vaa_step_epilogue_seg[_update] (kEpiSeg: P groups, each folded with its own part of a segmented map, VAA_LOSS_UADA_DDP; a zero pass-through tail)
+// and vaa_step_epilogue_seg_tail[_update] (kEpiSegTail: P groups, pass-through only, group g's tail copies the final `scalars`[8g..] of an earlier fold)
+enum { kEpiOne = 0, kEpiSeg = 1, kEpiSegTail = 2 };
+static int step_epilogue_impl(const char* who, int kind, const float* partials, int nparts, int n, int P, const void* rowmap, int R, int B, int L,
                               int V, int mode, const float* params, const void* loss_ws, size_t loss_ws_bytes, float* scalars, int32_t* pred_tokens,
                               int32_t* pred_full_tokens, float* msg, const UpdArgs* upd, double* stat_part, void* stream) {
-    if (!partials || !msg || (!seg && !scalars) || nparts <= 0 || n <= 0 || P <= 0 || P > 512) {
+    const bool seg = kind == kEpiSeg;
+    if (!partials || !msg || (!seg && !scalars) || nparts <= 0 || n <= 0 || P <= 0 || P > 512 || (kind == kEpiSegTail && rowmap)) {
         set_error("%s: bad arguments (nparts=%d n=%d P=%d)", who, nparts, n, P);
         return VAA_E_INVALID;
     }
@@ -1170,7 +1196,7 @@ static int step_epilogue_impl(const char* who, bool seg, const float* partials, 
 // The single-GPU step has no exchange between the gradient and the update: K4 (vaa_patch_update without L1 clip, grad_scale = 1) is applied by
 // the epilogue on every gradient element as it is produced — same per-element arithmetic, same bits in patch / m / v. The logged statistics come
 // back as per-block partial sums stat_part [P*ceil(n/64)][2] = {sum |g|, sum g} (fp64) for the caller to add.
-static int step_epilogue_update(const char* who, bool seg, const float* partials, int nparts, int n, int P, const void* rowmap, int R, int B, int L,
+static int step_epilogue_update(const char* who, int kind, const float* partials, int nparts, int n, int P, const void* rowmap, int R, int B, int L,
                                 int V, int mode, const float* params, const void* loss_ws, size_t loss_ws_bytes, float* scalars, int32_t* pred_tokens,
                                 int32_t* pred_full_tokens, float* msg, float* patch, float* m, float* v, int opt_mode, float lr, float beta1,
                                 float beta2, float eps, int step, double* stat_part, void* stream) {
@@ -1184,7 +1210,7 @@ static int step_epilogue_update(const char* who, bool seg, const float* partials
     }
     UpdArgs u = upd_args(opt_mode, lr, beta1, beta2, eps, step, 0.0f, 1.0f);
     u.patch = patch; u.m = m; u.v = v; u.n = n;
-    return step_epilogue_impl(who, seg, partials, nparts, n, P, rowmap, R, B, L, V, mode, params, loss_ws, loss_ws_bytes, scalars, pred_tokens,
+    return step_epilogue_impl(who, kind, partials, nparts, n, P, rowmap, R, B, L, V, mode, params, loss_ws, loss_ws_bytes, scalars, pred_tokens,
                               pred_full_tokens, msg, &u, stat_part, stream);
 }
 
@@ -1193,7 +1219,7 @@ static int step_epilogue_update(const char* who, bool seg, const float* partials
 extern "C" int vaa_step_epilogue(const float* partials, int nparts, int n, const void* rowmap, int R, int B, int L, int V, int mode,
                                  const float* params, const void* loss_ws, size_t loss_ws_bytes, float* scalars, int32_t* pred_tokens,
                                  int32_t* pred_full_tokens, float* msg, void* stream) {
-    return vaa::step_epilogue_impl("vaa_step_epilogue", false, partials, nparts, n, 1, rowmap, R, B, L, V, mode, params, loss_ws, loss_ws_bytes, scalars,
+    return vaa::step_epilogue_impl("vaa_step_epilogue", vaa::kEpiOne, partials, nparts, n, 1, rowmap, R, B, L, V, mode, params, loss_ws, loss_ws_bytes, scalars,
                                    pred_tokens, pred_full_tokens, msg, nullptr, nullptr, stream);
 }
 
@@ -1201,7 +1227,7 @@ extern "C" int vaa_step_epilogue_update(const float* partials, int nparts, int n
                                         const float* params, const void* loss_ws, size_t loss_ws_bytes, float* scalars, int32_t* pred_tokens,
                                         int32_t* pred_full_tokens, float* msg, float* patch, float* m, float* v, int opt_mode, float lr, float beta1,
                                         float beta2, float eps, int step, double* stat_part, void* stream) {
-    return vaa::step_epilogue_update("vaa_step_epilogue_update", false, partials, nparts, n, 1, rowmap, R, B, L, V, mode, params, loss_ws, loss_ws_bytes,
+    return vaa::step_epilogue_update("vaa_step_epilogue_update", vaa::kEpiOne, partials, nparts, n, 1, rowmap, R, B, L, V, mode, params, loss_ws, loss_ws_bytes,
                                      scalars, pred_tokens, pred_full_tokens, msg, patch, m, v, opt_mode, lr, beta1, beta2, eps, step, stat_part, stream);
 }
 
@@ -1278,7 +1304,7 @@ extern "C" int vaa_loss_rowmap_build_seg(const int64_t* labels, int B, int L, in
 extern "C" int vaa_step_epilogue_seg(const float* partials, int nparts, int n, int P, const void* rowmap, int R, int B, int L, int V, int mode,
                                      const float* params, const void* loss_ws, size_t loss_ws_bytes, float* scalars, int32_t* pred_tokens,
                                      int32_t* pred_full_tokens, float* msg, void* stream) {
-    return vaa::step_epilogue_impl("vaa_step_epilogue_seg", true, partials, nparts, n, P, rowmap, R, B, L, V, mode, params, loss_ws, loss_ws_bytes, scalars,
+    return vaa::step_epilogue_impl("vaa_step_epilogue_seg", vaa::kEpiSeg, partials, nparts, n, P, rowmap, R, B, L, V, mode, params, loss_ws, loss_ws_bytes, scalars,
                                    pred_tokens, pred_full_tokens, msg, nullptr, nullptr, stream);
 }
 
@@ -1286,7 +1312,23 @@ extern "C" int vaa_step_epilogue_seg_update(const float* partials, int nparts, i
                                             const float* params, const void* loss_ws, size_t loss_ws_bytes, float* scalars, int32_t* pred_tokens,
                                             int32_t* pred_full_tokens, float* msg, float* patch, float* m, float* v, int opt_mode, float lr, float beta1,
                                             float beta2, float eps, int step, double* stat_part, void* stream) {
-    return vaa::step_epilogue_update("vaa_step_epilogue_seg_update", true, partials, nparts, n, P, rowmap, R, B, L, V, mode, params, loss_ws,
+    return vaa::step_epilogue_update("vaa_step_epilogue_seg_update", vaa::kEpiSeg, partials, nparts, n, P, rowmap, R, B, L, V, mode, params, loss_ws,
                                      loss_ws_bytes, scalars, pred_tokens, pred_full_tokens, msg, patch, m, v, opt_mode, lr, beta1, beta2, eps, step,
                                      stat_part, stream);
+}
+
+// The sweep step whose loss scalars are final BEFORE the backward (a target sweep: vaa_loss_rows_fwd_bwd_seg folded them): the pass-through form
+// with group g's tail msg[P*n + 4g ..) = scalars_in[8g + {1, 2, 7, 0}] — on the step whose scalars the loop reads; the zero tail of
+// vaa_step_epilogue_seg on every other step.
+extern "C" int vaa_step_epilogue_seg_tail(const float* partials, int nparts, int n, int P, const float* scalars_in, float* msg, void* stream) {
+    return vaa::step_epilogue_impl("vaa_step_epilogue_seg_tail", vaa::kEpiSegTail, partials, nparts, n, P, nullptr, 0, 0, 0, 0, 0, nullptr, nullptr, 0,
+                                   const_cast<float*>(scalars_in), nullptr, nullptr, msg, nullptr, nullptr, stream);
+}
+
+extern "C" int vaa_step_epilogue_seg_tail_update(const float* partials, int nparts, int n, int P, const float* scalars_in, float* msg, float* patch,
+                                                 float* m, float* v, int opt_mode, float lr, float beta1, float beta2, float eps, int step,
+                                                 double* stat_part, void* stream) {
+    return vaa::step_epilogue_update("vaa_step_epilogue_seg_tail_update", vaa::kEpiSegTail, partials, nparts, n, P, nullptr, 0, 0, 0, 0, 0, nullptr, nullptr,
+                                     0, const_cast<float*>(scalars_in), nullptr, nullptr, msg, patch, m, v, opt_mode, lr, beta1, beta2, eps, step, stat_part,
+                                     stream);
 }

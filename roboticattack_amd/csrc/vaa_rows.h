@@ -32,15 +32,19 @@ int rows_split(int R, int V);
 // The group's own map is what vaa_step_epilogue_seg folds with: bit for bit the fold a standalone run of that group performs.
 inline __host__ __device__ int rowmap_seg_table(int B, int L) { return 4 + 4 * B * (L - 1); }
 inline __host__ __device__ int rowmap_seg_sub(int B, int L, int P, int g) { return rowmap_seg_table(B, L) + 4 * P + g * (4 + 4 * (B / P) * (L - 1)); }
-// the count that normalises row b's gradient (the kE term of UADA_ddp.py:99-124's mean over action rows): its group's on a segmented map
-__device__ __forceinline__ int row_action_count(const int* rowmap, int tbl, int b) {
+// word w of image b's group in a segmented map's table (1: rows, 2: action rows) — on an ordinary map the header's count of the whole batch
+__device__ __forceinline__ int row_group_word(const int* rowmap, int tbl, int b, int w) {
     const int P = rowmap[2];
-    if (P <= 0) return rowmap[1];
+    if (P <= 0) return rowmap[w - 1];
     const int Bp = rowmap[3] > 0 ? rowmap[3] : 1;
     int g = b / Bp;
     g = g < 0 ? 0 : (g >= P ? P - 1 : g);
-    return rowmap[tbl + 4 * g + 2];
+    return rowmap[tbl + 4 * g + w];
 }
+// the count that normalises row b's gradient (the kE term of UADA_ddp.py:99-124's mean over action rows): its group's on a segmented map
+__device__ __forceinline__ int row_action_count(const int* rowmap, int tbl, int b) { return row_group_word(rowmap, tbl, b, 2); }
+// ... and the one of the cross-entropy mean over ALL labelled rows (TMA.py:148): the rows of its group
+__device__ __forceinline__ int row_label_count(const int* rowmap, int tbl, int b) { return row_group_word(rowmap, tbl, b, 1); }
 
 // head workspace of vaa_head_loss_rows_stats: [R][ceil(V / 128)] PartStat, then (256-byte aligned) the action-column logits [R][256] bf16
 constexpr int kHeadCols = 128;  // vocabulary columns per workgroup of head_stats_kernel

@@ -198,6 +198,28 @@ struct RowsArgs {
     float w, alpha, beta, scale;
 };
 
+// Group g's view of a call over P groups (a segmented map, or an ordinary map with P = 1): its own map, its rows of the statistics, its
+// images of the prediction maps, its scalars[8g..] — what a standalone call on the group alone is handed, so rows_fold on it folds those bits.
+__device__ __forceinline__ RowsArgs rows_group_view(const RowsArgs& a, int P, int g) {
+    RowsArgs ag = a;
+    const int* map = a.rowmap;
+    const int Pm = map[2], Bp = a.B / P;
+    const bool total_ok = map[0] == a.R && (Pm == P || (Pm == 0 && P == 1));
+    int r0 = 0;
+    if (Pm > 0 && g < Pm) {
+        r0 = map[rowmap_seg_table(a.B, a.L) + 4 * g];
+        ag.rowmap = map + rowmap_seg_sub(a.B, a.L, Pm, g);
+    }
+    ag.R = total_ok ? ag.rowmap[0] : -1;  // a map of another batch than the caller states: rows_fold publishes NaN and never reads it
+    ag.B = Bp;
+    ag.part = a.part + (size_t)r0 * a.split;
+    ag.slice = a.slice + r0;
+    ag.scalars = a.scalars + 8 * g;
+    if (a.pred_tokens) ag.pred_tokens = a.pred_tokens + (size_t)g * Bp * (a.L - 1);
+    if (a.pred_full) ag.pred_full = a.pred_full + (size_t)g * Bp * (a.L - 1);
+    return ag;
+}
+
 struct FoldOut {
     double nrow, nact, CE, MSE, UAD, total, aux0, aux1, dce;
     int Rn;

@@ -624,6 +624,33 @@ def loss_rows_fwd_bwd(logits, rowmap: LossRowMap, mode: int, w: float = 5.0, alp
     return scalars, pred, pred_full, (grad if want_grad else None)
 
 
+def loss_rows_fwd_bwd_seg(logits, rowmap, P: int, mode: int = LOSS_CE, w: float = 5.0, alpha: float = 0.8, beta: float = 0.2, scale: float = 1.0,
+                          want_grad: bool = True, want_pred: bool = True, grad=None):
+    """K3 in LOSS_CE mode on logits [R,V] of P groups (vaa_loss_rows_fwd_bwd_seg; `rowmap` a LossRowMapSeg of P groups, or a LossRowMap with P = 1):
+    every row's gradient is normalised by its group's row count, every group folded on its own. Returns (scalars f32 [P,8], pred_slice, pred_full
+    i32 [B,L-1] | None (group g's images at rows g*B/P ..), grad [R,V] | None): per group the bits of loss_rows_fwd_bwd on the group's rows alone."""
+    dt = _dtype_code(logits)
+    if logits.dim() != 2:
+        raise _lib.VaaError(f"logits: expected [R,V], got {tuple(logits.shape)}")
+    R, V = int(logits.shape[0]), int(logits.shape[1])
+    P = int(P)
+    B, Lt = rowmap.B, rowmap.L
+    if getattr(rowmap, "P", 1) != P:
+        raise _lib.VaaError(f"loss_rows_fwd_bwd_seg: the row map holds {getattr(rowmap, 'P', 1)} groups, the call states {P}")
+    L = _lib.lib()
+    ws = _workspace(logits.device, max(L.vaa_loss_rows_ws_bytes(R), 256), "k3")
+    scalars = torch.empty((P, 8), dtype=torch.float32, device=logits.device)
+    pred, pred_full = _pred_maps(B, Lt, logits.device, want_pred)
+    if want_grad and grad is None:
+        grad = torch.empty((R, V), dtype=logits.dtype, device=logits.device)
+    with _timed("K3_loss_rows_fwd_bwd_seg", B=B, L=Lt, V=V, dtype=str(logits.dtype), rows=R, P=P):
+        rc = L.vaa_loss_rows_fwd_bwd_seg(logits.data_ptr(), dt, rowmap.buf.data_ptr(), R, B, Lt, V, P, int(mode), _loss_params(w, alpha, beta, scale),
+                                         scalars.data_ptr(), _ptr(pred), _ptr(pred_full), grad.data_ptr() if want_grad else None, GRAD_FULL,
+                                         ws.data_ptr(), ws.numel(), _stream())
+    _lib.check(rc, "vaa_loss_rows_fwd_bwd_seg")
+    return scalars, pred, pred_full, (grad if want_grad else None)
+
+
 def loss_rows_stats(logits, rowmap: LossRowMap, mode: int, w: float = 5.0, alpha: float = 0.8, beta: float = 0.2, scale: float = 1.0, grad=None):
     """The statistics pass of K3 alone (vaa_loss_rows_stats). In LOSS_UADA_DDP mode `grad` [R,256] receives the gradient slice in the same pass.
     Returns the workspace tensor that step_epilogue folds into the scalars."""
@@ -774,6 +801,39 @@ def step_epilogue_seg(partials, msg, scalars, P: int, rowmap=None, R: int = 0, V
     return _step_epilogue(int(P), partials, msg, scalars, rowmap, R, V, mode, w, alpha, beta, scale, loss_ws, want_pred, update)
 
 
+def step_epilogue_seg_tail(partials, msg, scalars_in, P: int, update=None):
+    """vaa_step_epilogue_seg_tail[_update]: step_epilogue_seg's pass-through form for a step whose loss scalars are final already (a target sweep:
+    loss_rows_fwd_bwd_seg folded them before the backward) — msg = [P gradients | P x scalars_in[g, (1, 2, 7, 0)]]; `update` as step_epilogue_seg's."""
+    P = int(P)
+    _need(partials, torch.float32, "partials")
+    rows, n = int(partials.shape[0]), int(partials.shape[1])
+    if rows % P != 0:
+        raise _lib.VaaError(f"partials: {rows} tiles are not {P} equal groups")
+    _need(msg, torch.float32, "msg")
+    _need(scalars_in, torch.float32, "scalars_in", (P, 8))
+    if msg.numel() < P * (n + 4):
+        raise _lib.VaaError(f"msg: needs {P * (n + 4)} floats, has {msg.numel()}")
+    common = (partials.data_ptr(), rows // P, n, P, scalars_in.data_ptr(), msg.data_ptr())
+    with _timed("EPI_step_epilogue_seg_tail", n=n, parts=rows // P, P=P):
+        if update is None:
+            rc = _lib.lib().vaa_step_epilogue_seg_tail(*common, _stream())
+        else:
+            rc = _lib.lib().vaa_step_epilogue_seg_tail_update(*common, *_update_args(update, P, n), _stream())
+    _lib.check(rc, "vaa_step_epilogue_seg_tail")
+
+
+def _update_args(u, P, n):
+    """The K4 arguments of the *_update epilogues from an `update` dict (PatchOptimizer.fused_update_args)."""
+    _need(u["patch"], torch.float32, "patch")
+    if u["patch"].numel() != P * n:
+        raise _lib.VaaError(f"update: patch has {u['patch'].numel()} elements, the gradients {P} x {n}")
+    sp = u.get("stat_part")
+    if sp is not None:
+        _need(sp, torch.float64, "stat_part", (P * ((n + 63) // 64), 2))
+    return (u["patch"].data_ptr(), _ptr(u.get("m")), _ptr(u.get("v")), int(u["mode"]), float(u["lr"]), float(u.get("beta1", 0.9)),
+            float(u.get("beta2", 0.999)), float(u.get("eps", 1e-6)), int(u["step"]), _ptr(sp))
+
+
 def _step_epilogue(P, partials, msg, scalars, rowmap, R, V, mode, w, alpha, beta, scale, loss_ws, want_pred, update):
     """The body of step_epilogue (P None: one group, scalars f32[8], vaa_step_epilogue[_update]) and step_epilogue_seg (vaa_step_epilogue_seg[_update])."""
     seg, P = P is not None, P or 1
@@ -797,16 +857,7 @@ def _step_epilogue(P, partials, msg, scalars, rowmap, R, V, mode, w, alpha, beta
         if update is None:
             rc = getattr(_lib.lib(), name)(*common, _stream())
         else:
-            u = update
-            _need(u["patch"], torch.float32, "patch")
-            if u["patch"].numel() != P * n:
-                raise _lib.VaaError(f"update: patch has {u['patch'].numel()} elements, the gradients {P} x {n}")
-            sp = u.get("stat_part")
-            if sp is not None:
-                _need(sp, torch.float64, "stat_part", (P * ((n + 63) // 64), 2))
-            rc = getattr(_lib.lib(), name + "_update")(*common, u["patch"].data_ptr(), _ptr(u.get("m")), _ptr(u.get("v")), int(u["mode"]), float(u["lr"]),
-                                                       float(u.get("beta1", 0.9)), float(u.get("beta2", 0.999)), float(u.get("eps", 1e-6)),
-                                                       int(u["step"]), _ptr(sp), _stream())
+            rc = getattr(_lib.lib(), name + "_update")(*common, *_update_args(update, P, n), _stream())
     _lib.check(rc, name)
     return pred, pred_full
 
@@ -842,6 +893,25 @@ class HeadLossRows(torch.autograd.Function):
     def backward(ctx, gtotal, _gs, _gp, _gf):
         g, weight = ctx.saved_tensors
         return _loss_backward(g, gtotal, 8, weight[ACTION_LO : ACTION_LO + N_ACTION] if ctx.sliced else weight)
+
+
+class HeadLossRowsSeg(torch.autograd.Function):
+    """HeadLossRows for a target sweep (LOSS_CE, P groups): ONE hipBLASLt head over the rows of all groups, K3 with the segmented row map
+    (loss_rows_fwd_bwd_seg), ONE dh = g @ W. Returns (total = sum of the groups' totals — the groups share no parameter, so every patch gets its
+    own group's gradient —, scalars f32 [P,8], pred_slice, pred_full)."""
+
+    @staticmethod
+    def forward(ctx, hidden, weight, rowmap, P, scale):
+        logits = torch.nn.functional.linear(hidden.detach(), weight)
+        scalars, pred, pred_full, g = loss_rows_fwd_bwd_seg(logits, rowmap, P, LOSS_CE, scale=scale, want_grad=True)
+        ctx.save_for_backward(g, weight)
+        ctx.mark_non_differentiable(scalars, pred, pred_full)
+        return scalars[:, 0].sum(), scalars, pred, pred_full
+
+    @staticmethod
+    def backward(ctx, gtotal, _gs, _gp, _gf):
+        g, weight = ctx.saved_tensors
+        return _loss_backward(g, gtotal, 5, weight)
 
 
 class HeadLossRowsFused(torch.autograd.Function):

@@ -1,0 +1,386 @@
+"""GPU tests of the TMA target sweep (P (maskidx, target) groups optimised in one step of the data-parallel loop).
+
+Kernels: K3 in LOSS_CE mode over a segmented row map (vaa_loss_rows_fwd_bwd_seg) gives every group the bits of vaa_loss_rows_fwd_bwd on that group's
+rows alone, and the C oracle's cross-entropy; the pass-through epilogue carries the groups' final scalars in its tail. Loop: every group of a target
+sweep over SurrogateHeadVLA follows the standalone product run of its (maskidx, target_action)."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN
+from oracle import c_oracle
+from roboticattack_amd import synthetic
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+V = 32064
+GROUPS = [([0], 0.0), ([0, 1], 0.25), ([0, 1, 2, 3, 4, 5, 6], -0.5)]  # 1, 2 and 7 labelled rows per image
+
+
+@pytest.fixture(scope="module")
+def ops():
+    from roboticattack_amd import ops as _ops
+
+    _ops.device_check()
+    return _ops
+
+
+def _bits(t):
+    t = t.contiguous()
+    return t.view(torch.int16) if t.element_size() == 2 else t.view(torch.int32)
+
+
+def _rows(labels):
+    B, L = labels.shape
+    return [(b, 256 + k) for b in range(B) for k in range(L - 1) if labels[b, k + 1] != -100]
+
+
+def _rows_split(R, V):
+    """The library's rule for the parts a row of K3's ROWS path is split into (vaa_loss.hip: rows_split): doubled up to 4 while R * parts < 256,
+    then until a part fits threads x 32 logits (256 threads for V <= 32,768)."""
+    nt = 256 if V <= 4 * 256 * 32 else 512
+    s = 1
+    while s < 4 and R * s < 256:
+        s <<= 1
+    while (V + s - 1) // s > nt * 32:
+        s <<= 1
+    return s
+
+
+def test_rows_are_split_into_four_parts_for_every_row_count_at_the_openvla_vocabulary():
+    """V = 32,064 > 2 x 8,192 logits: a row needs 4 parts to fit, and the occupancy rule never goes past 4 — so a row's statistics (its parts) do not
+    depend on how many rows share the call, which is what makes a group of a segmented call bit-equal to the call on the group alone."""
+    assert {_rows_split(R, V) for R in range(1, 4097)} == {4}
+
+
+def _case(Bp, seed, dtype):
+    from roboticattack_amd.labels import tma_target_labels, tma_target_tokens
+
+    _, labels, _ = synthetic.synth_text_batch(seed, Bp)
+    groups = [tma_target_labels(labels, tma_target_tokens(t * np.ones(7), m)) for m, t in GROUPS]
+    counts = [len(_rows(x.numpy())) for x in groups]
+    assert counts == [Bp * len(m) for m, _ in GROUPS]  # unequal row counts per group
+    r0 = np.concatenate([[0], np.cumsum(counts)]).astype(int)
+    rs = np.random.RandomState(seed)
+    z = (rs.standard_normal((int(r0[-1]), V)) * 2).astype(np.float32)
+    z[:, 31744:32000] += (rs.standard_normal((int(r0[-1]), 256)) * 3).astype(np.float32)
+    z[::3, 1234] = 40.0  # rows whose top-1 token is not an action token
+    return groups, torch.cat(groups).to(DEV), torch.from_numpy(z).to(dtype).to(DEV), r0
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("Bp", [4, 3])
+def test_segmented_ce_k3_bitwise_per_group_and_against_the_oracle(ops, Bp, dtype):
+    P = len(GROUPS)
+    groups, lab_all, z, r0 = _case(Bp, 60 + Bp, dtype)
+    L = lab_all.shape[1]
+    seg = ops.LossRowMapSeg(lab_all, P)
+    scale = 0.5
+    ops.prof_start(64)
+    g = torch.full_like(z, float("nan"))
+    sc, pred, pf, _ = ops.loss_rows_fwd_bwd_seg(z, seg, P, ops.LOSS_CE, scale=scale, grad=g)
+    torch.cuda.synchronize()
+    names = [nm for nm, _ in ops.prof_collect()]
+    ops.async_error_check()
+    assert len(names) == 2 and "rows_stats_kernel" in names[0] and "false" in names[0] and "rows_finish_kernel" in names[1]  # two launches for all groups
+    assert sc.shape == (P, 8) and torch.isfinite(g.float()).all() and torch.isfinite(sc).all()
+    # evaluation only (no gradient): the same scalars and maps
+    sc_e, pred_e, pf_e, g_e = ops.loss_rows_fwd_bwd_seg(z, seg, P, ops.LOSS_CE, scale=scale, want_grad=False)
+    assert g_e is None and torch.equal(sc_e, sc) and torch.equal(pred_e, pred) and torch.equal(pf_e, pf)
+    for q, (m, t) in enumerate(GROUPS):
+        a, b = int(r0[q]), int(r0[q + 1])
+        rm_q = ops.LossRowMap(groups[q].to(DEV))
+        zq = z[a:b].contiguous()
+        sc_q, pred_q, pf_q, g_q = ops.loss_rows_fwd_bwd(zq, rm_q, ops.LOSS_CE, scale=scale, grad_kind=ops.GRAD_FULL)
+        torch.cuda.synchronize()
+        assert torch.equal(_bits(g[a:b]), _bits(g_q)), (q, float((g[a:b].float() - g_q.float()).abs().max()))
+        assert torch.equal(_bits(sc[q]), _bits(sc_q)), (q, sc[q], sc_q)
+        assert torch.equal(pred[q * Bp : (q + 1) * Bp], pred_q) and torch.equal(pf[q * Bp : (q + 1) * Bp], pf_q)
+        assert float(sc_q[5]) == b - a and float(g_q.float().abs().max()) > 0
+        # the group against the C oracle's CE on the group alone: the tolerances of test_gpu_kernels.py's rows-path CE cases
+        rows = _rows(groups[q].numpy())
+        rb, rp = np.array([r[0] for r in rows]), np.array([r[1] for r in rows])
+        full = torch.zeros((Bp, 256 + L, V), dtype=torch.float32)
+        full[torch.from_numpy(rb), torch.from_numpy(rp)] = zq.float().cpu()
+        so, go = c_oracle.loss(full.numpy(), groups[q].numpy(), c_oracle.MODE_CE, w=5.0, scale=scale)
+        gor = go[rb, rp]
+        got = sc[q].cpu().numpy()
+        assert np.allclose(got[:5], so[:5], rtol=3e-5, atol=3e-5) and abs(so[0] - scale * so[1]) <= 1e-6 * abs(so[0]), (got, so)
+        gtol = (1e-2 if dtype == torch.bfloat16 else 2e-4) * max(np.abs(gor).max(), 1e-30)
+        assert np.abs(g[a:b].float().cpu().numpy() - gor).max() <= gtol
+        zf = zq.float().cpu().numpy()
+        exp_full = np.full((Bp, L - 1), -1)
+        for i, (bb, p) in enumerate(rows):
+            exp_full[bb, p - 256] = int(zf[i].argmax())
+        assert np.array_equal(pf_q.cpu().numpy(), exp_full)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_ordinary_map_at_one_group_gives_the_old_call_its_bits(ops, dtype):
+    from roboticattack_amd.labels import tma_target_labels, tma_target_tokens
+
+    _, labels, _ = synthetic.synth_text_batch(9, 6)
+    labels = tma_target_labels(labels, tma_target_tokens(0.25 * np.ones(7), [0, 1, 2])).to(DEV)
+    R = len(_rows(labels.cpu().numpy()))
+    gen = torch.Generator(device=DEV).manual_seed(9)
+    z = (torch.randn(R, V, device=DEV, generator=gen) * 2).to(dtype)
+    rm, seg1 = ops.LossRowMap(labels), ops.LossRowMapSeg(labels, 1)
+    sc0, p0, f0, g0 = ops.loss_rows_fwd_bwd(z, rm, ops.LOSS_CE, scale=1.0, grad_kind=ops.GRAD_FULL)
+    for rowmap in (rm, seg1):  # an ordinary map with P = 1, and a one-group segmented map
+        sc1, p1, f1, g1 = ops.loss_rows_fwd_bwd_seg(z, rowmap, 1, ops.LOSS_CE, scale=1.0)
+        torch.cuda.synchronize()
+        assert torch.equal(_bits(g0), _bits(g1)) and torch.equal(_bits(sc0), _bits(sc1[0])) and torch.equal(p0, p1) and torch.equal(f0, f1)
+    with pytest.raises(Exception, match="VAA_LOSS_CE"):
+        ops.loss_rows_fwd_bwd_seg(z, seg1, 1, ops.LOSS_UADA)
+    ops.async_error_check()
+
+
+def test_epilogue_tail_carries_the_given_scalars_and_the_other_forms_keep_their_bits(ops):
+    P, Bp, n = 3, 4, 3 * 50 * 50
+    nred = (n + 63) // 64
+    gen = torch.Generator(device=DEV).manual_seed(11)
+    partials = torch.randn(P * Bp, n, device=DEV, generator=gen) * 1e-3
+    sc_in = torch.randn(P, 8, device=DEV, generator=gen)
+    patch0 = torch.rand(P * n, device=DEV, generator=gen)
+    m0 = torch.randn(P * n, device=DEV, generator=gen) * 1e-4
+    v0 = torch.rand(P * n, device=DEV, generator=gen) * 1e-7
+
+    def upd(p, m, v, sp):
+        return dict(patch=p, m=m, v=v, mode=ops.OPT_ADAMW_HF, lr=2e-3, step=3, stat_part=sp)
+
+    # the zero-tail pass-through form (existing): untouched scalars, zero tail
+    msg_z, sc_z = torch.full((P * (n + 4),), 7.0, device=DEV), sc_in.clone()
+    ops.step_epilogue_seg(partials, msg_z, sc_z, P)
+    pz, mz, vz = patch0.clone(), m0.clone(), v0.clone()
+    spz = torch.zeros((P * nred, 2), dtype=torch.float64, device=DEV)
+    msg_zu = torch.full((P * (n + 4),), 7.0, device=DEV)
+    ops.step_epilogue_seg(partials, msg_zu, sc_z, P, update=upd(pz, mz, vz, spz))
+    # the new form: the same sums (and update), the tail = the given scalars
+    msg_t = torch.full((P * (n + 4),), 7.0, device=DEV)
+    ops.step_epilogue_seg_tail(partials, msg_t, sc_in, P)
+    pt, mt, vt = patch0.clone(), m0.clone(), v0.clone()
+    spt = torch.zeros((P * nred, 2), dtype=torch.float64, device=DEV)
+    msg_tu = torch.full((P * (n + 4),), 7.0, device=DEV)
+    ops.step_epilogue_seg_tail(partials, msg_tu, sc_in, P, update=upd(pt, mt, vt, spt))
+    torch.cuda.synchronize()
+    ops.async_error_check()
+    assert torch.equal(msg_z[P * n :], torch.zeros(4 * P, device=DEV)) and torch.equal(msg_zu, msg_z) and torch.equal(sc_z, sc_in)
+    assert torch.equal(msg_t[: P * n], msg_z[: P * n]) and torch.equal(msg_tu, msg_t)
+    assert torch.equal(msg_t[P * n :].view(P, 4), sc_in[:, [1, 2, 7, 0]])
+    assert torch.equal(pt, pz) and torch.equal(mt, mz) and torch.equal(vt, vz) and torch.equal(spt, spz) and not torch.equal(pt, patch0)
+    for q in range(P):  # ... and per group the standalone epilogue's pass-through form (tail = its scalars) and fused update
+        pg = partials[q * Bp : (q + 1) * Bp].contiguous()
+        msg_g = torch.zeros(n + 4, device=DEV)
+        sl = slice(q * n, (q + 1) * n)
+        p_g, m_g, v_g = patch0[sl].clone(), m0[sl].clone(), v0[sl].clone()
+        sp_g = torch.zeros((nred, 2), dtype=torch.float64, device=DEV)
+        ops.step_epilogue(pg, msg_g, sc_in[q].contiguous(), update=upd(p_g, m_g, v_g, sp_g))
+        torch.cuda.synchronize()
+        assert torch.equal(msg_t[sl], msg_g[:n]) and torch.equal(msg_t[P * n + 4 * q : P * n + 4 * q + 4], msg_g[n:])
+        assert torch.equal(pt[sl], p_g) and torch.equal(mt[sl], m_g) and torch.equal(vt[sl], v_g) and torch.equal(spt[q * nred : (q + 1) * nred], sp_g)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# the loop (the harness of test_gpu_sweep.py::_run, for the TMA attack)
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+class _Fresh:
+    def __init__(self, seeds, b, kind="smooth"):
+        self.seeds, self.b, self.kind = seeds, b, kind
+
+    def __iter__(self):
+        for s in self.seeds:
+            yield synthetic.synth_batch(s, self.b, self.kind)
+
+
+def _seed():
+    import random
+
+    random.seed(42)
+    np.random.seed(42)
+    torch.manual_seed(42)
+
+
+def _run(d, save_dir, maskidx=None, target=0.0, sweep=None, rank=0, world=1):
+    """One product TMA run of the data-parallel loop on the golden's setup (its sizes, seeds and schedule): a standalone run (maskidx, target) or a
+    target sweep. Returns (per-step patches [steps, P, 3, 50, 50], host logs per outer iteration, attacker, kernel names of the TRAINING steps)."""
+    from roboticattack_amd import ops, optim
+    from roboticattack_amd.attack import uada_ddp
+    from roboticattack_amd.surrogate import SurrogateHeadVLA
+
+    n_it, inner, bs = int(d["num_iter"]), int(d["inner"]), int(d["bs"])
+    nval = int(d["val_batches"])
+    snaps, logs, names = [], [], []
+
+    def snap(patch):
+        snaps.append(patch.detach().cpu().numpy().copy().reshape((-1, 3, 50, 50)))
+
+    class Att(uada_ddp.OpenVLAAttacker):
+        val_batches = 100
+
+        def target_sweep_step(self, img, patches, *a, **k):
+            r = super().target_sweep_step(img, patches, *a, **k)
+            if world == 1:  # AdamW ran inside the epilogue
+                snap(patches)
+            return r
+
+        def assert_finite_state(self, patch, optimizer, host, where, **kw):
+            logs.append(np.array(host, dtype=np.float64).copy())
+            return super().assert_finite_state(patch, optimizer, host, where, **kw)
+
+        def _val(self, f, *a):  # the kernel trace covers the training steps only
+            names.extend(nm for nm, _ in ops.prof_collect())
+            r = f(*a)
+            ops.prof_start(8192)
+            return r
+
+        def validate(self, *a):
+            return self._val(super().validate, *a)
+
+        def validate_sweep(self, *a):
+            return self._val(super().validate_sweep, *a)
+
+    orig = optim.PatchOptimizer.step
+
+    def rec(self, *a, **k):  # every step that goes through K4 as a launch of its own (the standalone loop; every loop at world > 1)
+        r = orig(self, *a, **k)
+        snap(self.patch)
+        return r
+
+    optim.PatchOptimizer.step = rec
+    try:
+        att = Att(vla_path="x", dataset_name="synthetic", save_dir=save_dir, patch_size=[3, 50, 50], lr=float(d["lr"]), bs=bs, warmup=int(d["warmup"]),
+                  num_iter=n_it, maskidx=maskidx if maskidx is not None else [0], innerLoop=inner, geometry=True, use_wandb=False,
+                  MSE_weights=int(d["MSE_weights"]), device=torch.device(DEV), attack_type="TMA", target_action=target, target_sweep=sweep,
+                  model_factory=lambda path, dev: SurrogateHeadVLA(seed=int(d["model_seed"])).to(dev),
+                  dataset_factory=lambda name, b, r, w: (_Fresh([int(d["train_seed0"]) + w * i + r for i in range(n_it)], bs),
+                                                         _Fresh([int(d["val_seed0"]) + w * i + r for i in range(nval)], bs)))
+        _seed()
+        ops.prof_start(8192)
+        att.attack(rank, world)
+        names.extend(nm for nm, _ in ops.prof_collect())
+    finally:
+        optim.PatchOptimizer.step = orig
+    return np.stack(snaps), np.stack(logs), att, names
+
+
+def _env(monkeypatch):
+    import socket
+
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    for k, v in dict(RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port)).items():
+        monkeypatch.setenv(k, v)
+    for k in ("VAA_FULL_CE_EVERY_STEP", "VAA_HEAD_EVERY_STEP", "VAA_K3_ONE_PASS", "VAA_K3_CE_FOLD_WG", "VAA_FUSED_EPILOGUE", "VAA_FUSED_EMBED_GRAD"):
+        monkeypatch.delenv(k, raising=False)
+
+
+SWEEP3 = [([0, 1], 0.0), ([0], 0.25), ([0, 1, 2], -0.5)]
+
+
+def test_target_sweep_trajectory_vs_standalone_tma_runs(tmp_path, monkeypatch):
+    """target_sweep=[([0,1], 0), ([0], 0.25), ([0,1,2], -0.5)] on the setup of traj_ddp_k3s.npz (SurrogateHeadVLA, its sizes, seeds and schedule;
+    bs 3 per group): every group's per-inner-step patches are within 1e-4 of its standalone product run (attack_type="TMA", that maskidx /
+    target_action, same seed) — the body runs at batch P*Bp, so the groups are not bit-equal —, its train log and first validation averages
+    within the relative bounds test_gpu_sweep.py uses; K3 runs once per training step for all groups; per-group files exist."""
+    _env(monkeypatch)
+    d = np.load(os.path.join(GOLDEN, "traj_ddp_k3s.npz"))
+    n_it, inner = int(d["num_iter"]), int(d["inner"])
+    snaps, logs, att, names = _run(d, str(tmp_path / "sweep"), sweep=SWEEP3)
+    assert snaps.shape == (n_it * inner, 3, 3, 50, 50) and logs.shape == (n_it, 3, 4)
+    # ONE head GEMM's worth of K3 per training step: one statistics + one finishing launch for all groups, one K2' and one epilogue
+    assert sum("rows_stats_kernel" in nm for nm in names) == n_it * inner and sum("rows_finish_kernel" in nm for nm in names) == n_it * inner
+    assert sum("embed_dgrad" in nm for nm in names) == n_it * inner and sum("step_epilogue_kernel" in nm for nm in names) == n_it * inner
+    assert not any("head_slice_kernel" in nm for nm in names)
+    tags = ["maskidx0-1-target0", "maskidx0-target0.25", "maskidx0-1-2-target-0.5"]
+    assert att.sweep_tags == tags and set(att.last_train_log) == set(tags)
+    for tag in tags:
+        assert os.path.exists(tmp_path / "sweep" / tag / "last" / "patch.pt") and os.path.exists(tmp_path / "sweep" / tag / "0" / "patch.pt")
+    for g, (m, t) in enumerate(SWEEP3):
+        s_snaps, s_logs, s_att, s_names = _run(d, str(tmp_path / f"solo{g}"), maskidx=m, target=t)
+        assert s_snaps.shape == (n_it * inner, 1, 3, 50, 50)
+        e = np.abs(snaps[:, g] - s_snaps[:, 0]).reshape(n_it * inner, -1).max(1)
+        print(f"group {g} per-step max |sweep - standalone|:", ["%.2e" % v for v in e])
+        assert e.max() <= 1e-4, e
+        assert np.abs(s_snaps[-1, 0] - s_snaps[0, 0]).max() > 1e-3 and np.abs(snaps[-1, g] - snaps[0, g]).max() > 1e-3  # the patches really moved
+        print(f"group {g} train CE sweep / standalone:", logs[:, g, 0], s_logs[:, 0])
+        np.testing.assert_allclose(logs[:, g, 0], s_logs[:, 0], rtol=3e-4)
+        np.testing.assert_allclose(logs[:, g, 3], s_logs[:, 3], rtol=3e-4)
+        np.testing.assert_allclose(logs[:, g, 2], s_logs[:, 2], atol=2e-4)
+        np.testing.assert_allclose([att.val_MSE_Distance[tags[g]][0]], [s_att.val_MSE_Distance[0]], rtol=2e-3)  # the selection metric: scalar 0
+        np.testing.assert_allclose([att.val_CE_loss[tags[g]][0]], [s_att.val_CE_loss[0]], rtol=3e-4)
+        np.testing.assert_allclose([att.val_UAD[tags[g]][0]], [s_att.val_UAD[0]], atol=2e-5)
+        last = torch.load(tmp_path / "sweep" / tags[g] / "last" / "patch.pt").numpy()
+        assert np.abs(last - torch.load(tmp_path / f"solo{g}" / "last" / "patch.pt").numpy()).max() <= 1e-4
+    assert np.abs(snaps[-1, 0] - snaps[-1, 1]).max() > 1e-3  # different groups, different patches
+
+
+def test_one_group_target_sweep_vs_the_existing_tma_loop(tmp_path, monkeypatch):
+    """A one-group target sweep is bitwise the existing TMA loop (attack_type="TMA", that maskidx / target_action, same seed): K1 through the
+    per-image descriptor pastes the same pixels, K2' leaves the same partial tiles, and the fused epilogue (fixed-order sum + AdamW per element)
+    reproduces the separate K2-reduce, message copy and K4 launches — what README.md claims for UADA holds for the CE path too."""
+    _env(monkeypatch)
+    d = np.load(os.path.join(GOLDEN, "traj_ddp_k3s.npz"))
+    n_it, inner = int(d["num_iter"]), int(d["inner"])
+    one, one_logs, one_att, _ = _run(d, str(tmp_path / "one"), sweep=[([0, 1], 0.25)])
+    base, base_logs, base_att, _ = _run(d, str(tmp_path / "base"), maskidx=[0, 1], target=0.25)
+    e = np.abs(one[:, 0] - base[:, 0]).reshape(n_it * inner, -1).max(1)
+    print("one-group sweep per-step max |sweep - existing loop|:", ["%.2e" % v for v in e])
+    assert np.array_equal(one, base) and np.array_equal(one_logs.reshape(-1, 4), base_logs)
+    assert np.abs(base[-1, 0] - base[0, 0]).max() > 1e-3
+    assert one_att.val_MSE_Distance["maskidx0-1-target0.25"] == base_att.val_MSE_Distance
+    assert one_att.val_CE_loss["maskidx0-1-target0.25"] == base_att.val_CE_loss
+
+
+def _sweep2_worker(rank, world, port, out_dir, golden_path, sweep):
+    import sys
+
+    from conftest import ROOT
+
+    sys.path.insert(0, ROOT)
+    os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), VAA_DIST_BACKEND="gloo")
+    for k in ("VAA_FULL_CE_EVERY_STEP", "VAA_HEAD_EVERY_STEP", "VAA_K3_ONE_PASS", "VAA_K3_CE_FOLD_WG"):
+        os.environ.pop(k, None)
+    d = np.load(golden_path)
+    if sweep:
+        snaps, logs, att, names = _run(d, os.path.join(out_dir, f"rank{rank}"), sweep=[([0, 1], 0.25), ([0, 1, 2], 0.0)], rank=rank, world=world)
+        tag = "sweep"
+    else:
+        snaps, logs, att, names = _run(d, os.path.join(out_dir, f"solo{rank}"), maskidx=[0, 1], target=0.25, rank=rank, world=world)
+        tag = "solo"
+    np.savez(os.path.join(out_dir, f"{tag}_r{rank}.npz"), snaps=snaps, logs=logs, n_stats=sum("rows_stats_kernel" in n for n in names))
+
+
+def test_target_sweep_two_ranks_group0_vs_standalone_two_rank_run(tmp_path):
+    """Two ranks (gloo on one GPU, as test_sweep_two_ranks_group0_vs_reference_loop) of a target sweep [([0,1], 0.25), ([0,1,2], 0)]: ONE all-reduce
+    of [2 gradients | 2 x 4 scalars] per step and the segmented K4; the ranks are bit-identical after every step; group 0 is within 1e-4 of the
+    standalone two-rank TMA run (maskidx [0,1], target 0.25)."""
+    import socket
+
+    import torch.multiprocessing as mp
+
+    golden = os.path.join(GOLDEN, "traj_ddp2_k3s.npz")
+    d = np.load(golden)
+    n_it, inner = int(d["num_iter"]), int(d["inner"])
+    for sweep in (True, False):
+        s = socket.socket()
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+        s.close()
+        mp.spawn(_sweep2_worker, args=(2, port, str(tmp_path), golden, sweep), nprocs=2, join=True)
+    r0, r1 = np.load(tmp_path / "sweep_r0.npz"), np.load(tmp_path / "sweep_r1.npz")
+    assert r0["snaps"].shape == (n_it * inner, 2, 3, 50, 50) and r0["logs"].shape == (n_it, 2, 4)
+    assert np.array_equal(r0["snaps"], r1["snaps"]) and np.array_equal(r0["logs"], r1["logs"])
+    assert int(r0["n_stats"]) == n_it * inner
+    s0, s1 = np.load(tmp_path / "solo_r0.npz"), np.load(tmp_path / "solo_r1.npz")
+    assert np.array_equal(s0["snaps"], s1["snaps"])
+    err = np.abs(r0["snaps"][:, 0] - s0["snaps"][:, 0]).reshape(n_it * inner, -1).max(1)
+    print("group 0 per-step max |sweep - standalone two-rank run|:", ["%.2e" % e for e in err])
+    assert err.max() <= 1e-4, err
+    assert np.abs(r0["snaps"][-1, 0] - r0["snaps"][0, 0]).max() > 1e-3 and np.abs(r0["snaps"][-1, 1] - r0["snaps"][0, 1]).max() > 1e-3
+    np.testing.assert_allclose(r0["logs"][:, 0, 0], s0["logs"][:, 0], rtol=3e-4)
+    assert os.path.exists(tmp_path / "rank0" / "maskidx0-1-target0.25" / "last" / "patch.pt")
+    assert os.path.exists(tmp_path / "rank0" / "maskidx0-1-2-target0" / "last" / "patch.pt") and not os.path.exists(tmp_path / "rank1" / "maskidx0-1-target0.25")

@@ -2,7 +2,10 @@
 """Measures the maskidx sweep step against P standalone steps (one GPU, world size 1, the fused data-parallel UADA step with AdamW inside the
 epilogue): OpenVLA-7B shapes with random weights by default.
 
-    python tools/sweep_bench.py --configs 2x8,8x4,8x8 --steps 10 --warmup 3 [--vla random:openvla-7b] [--out file.json]
+    python tools/sweep_bench.py --configs 2x8,8x4,8x8 --steps 10 --warmup 3 [--vla random:openvla-7b] [--out file.json] [--attack tma]
+
+--attack tma measures the TMA target sweep step (one DoF per group, the T-dof1 .. T-dof7 family) against P standalone TMA steps of the
+data-parallel loop (the unfused step: K1, model, hipBLASLt head + K3, backward with K2', message, K4).
 
 For each (P, Bp): ms per standalone step at bs = Bp (maskidx [0]), ms per sweep step over P groups x Bp images (one DoF per group), their ratio, and the library's own kernels per step (vaa_prof per-dispatch timer: the hand-written microseconds of one step).
 Every step runs with full_ce on its last inner step only, as the loop does (innerLoop = `--inner`)."""
@@ -24,9 +27,15 @@ def _groups(P):
     return [[q % 7] for q in range(P)]
 
 
-def measure(att, P, Bp, steps, warmup, inner, sweep):
-    from roboticattack_amd import ops, synthetic
+def _target_groups(P):
+    """--attack tma: one DoF per group like the released T-dof1 .. T-dof7 family, target 0 (then 0.5 for an eighth group and beyond)."""
+    return [([q % 7], 0.0 if q < 7 else 0.5) for q in range(P)]
+
+
+def measure(att, P, Bp, steps, warmup, inner, sweep, attack="uada"):
+    from roboticattack_amd import dist as vdist, ops, synthetic
     from roboticattack_amd.attack.uada_ddp import mask_labels_sweep
+    from roboticattack_amd.labels import tma_target_labels, tma_target_tokens
     from roboticattack_amd.optim import PatchOptimizer, SweepPatchOptimizer
 
     dev = att.device
@@ -35,7 +44,36 @@ def measure(att, P, Bp, steps, warmup, inner, sweep):
     labels = batch["labels"].to(dev)
     ids, am = batch["input_ids"].to(dev), batch["attention_mask"].to(dev)
     n = 3 * 50 * 50
-    if sweep:
+    if attack == "tma" and sweep:
+        patches = torch.rand(P, 3, 50, 50, device=dev, requires_grad=True)
+        opt = SweepPatchOptimizer(patches, 1e-3)
+        img = pv.repeat(P, 1, 1, 1).contiguous()
+        ids_all, am_all = ids.repeat(P, 1).contiguous(), am.repeat(P, 1).contiguous()
+        lab = torch.cat([tma_target_labels(labels, tma_target_tokens(t * np.ones(7), m).to(dev)) for m, t in _target_groups(P)])
+        row_index = att.vla.label_row_index(lab)
+        segmap = ops.LossRowMapSeg(lab, P)
+        pack = att.vla.make_pack(am_all) if hasattr(att.vla, "make_pack") else None
+        msg = torch.zeros(P * (n + 4), device=dev)
+        sc = torch.zeros((P, 8), device=dev)
+
+        def step(k):
+            att.target_sweep_step(img, patches, ids_all, row_index, segmap, pack, msg, sc, k % inner == inner - 1, opt.fused_update_args())
+    elif attack == "tma":  # the standalone TMA step of the data-parallel loop (OpenVLAAttacker._attack, attack_type="TMA", world 1)
+        patch = torch.rand(3, 50, 50, device=dev, requires_grad=True)
+        opt = PatchOptimizer(patch, 1e-3)
+        lab = tma_target_labels(labels, tma_target_tokens(np.zeros(7), [0]).to(dev))
+        sync = vdist.PatchGradSync(patch.numel(), 4, dev)
+        pick = torch.tensor([1, 2, 7, 0], dtype=torch.int64, device=dev)
+
+        def step(k):
+            opt.zero_grad()
+            full_ce = k % inner == inner - 1
+            pix = att.randomPatchTransform.apply_random_patch_batch(pv, patch, mean=att.mean, std=att.std, geometry=True)
+            total, scal, _ = att.model_loss(ids, am, pix, lab, ops.LOSS_CE, w=5.0, full_ce=full_ce, read_scalars=full_ce)
+            total.backward()
+            g_sum, _ = sync.allreduce_step(patch.grad, scal, pick)
+            opt.step(grad=g_sum.view_as(patch), grad_scale=1.0)
+    elif sweep:
         groups = _groups(P)
         patches = torch.rand(P, 3, 50, 50, device=dev, requires_grad=True)
         opt = SweepPatchOptimizer(patches, 1e-3)
@@ -90,6 +128,8 @@ def main():
     ap.add_argument("--inner", type=int, default=50)
     ap.add_argument("--vla", default="random:openvla-7b")
     ap.add_argument("--out", default="")
+    ap.add_argument("--attack", default="uada", choices=["uada", "tma"],
+                    help="tma: the target sweep step (one hipBLASLt head + segmented K3 for all groups) against P standalone TMA steps of the data-parallel loop")
     a = ap.parse_args()
     os.environ.setdefault("RANK", "0")
     os.environ.setdefault("WORLD_SIZE", "1")
@@ -106,9 +146,9 @@ def main():
     for cfg in a.configs.split(","):
         P, Bp = (int(v) for v in cfg.split("x"))
         if Bp not in solo:
-            solo[Bp] = measure(att, 1, Bp, a.steps, a.warmup, a.inner, sweep=False)
-        sw = measure(att, P, Bp, a.steps, a.warmup, a.inner, sweep=True)
-        rec = dict(P=P, Bp=Bp, images=P * Bp, standalone_ms=round(solo[Bp][0], 2), P_standalone_ms=round(P * solo[Bp][0], 2),
+            solo[Bp] = measure(att, 1, Bp, a.steps, a.warmup, a.inner, sweep=False, attack=a.attack)
+        sw = measure(att, P, Bp, a.steps, a.warmup, a.inner, sweep=True, attack=a.attack)
+        rec = dict(attack=a.attack, P=P, Bp=Bp, images=P * Bp, standalone_ms=round(solo[Bp][0], 2), P_standalone_ms=round(P * solo[Bp][0], 2),
                    sweep_ms=round(sw[0], 2), ratio=round(sw[0] / (P * solo[Bp][0]), 3), standalone_hand_us=round(solo[Bp][1], 1),
                    sweep_hand_us=round(sw[1], 1), sweep_hand_kernels_us={k: round(v, 1) for k, v in sorted(sw[2].items())})
         print(json.dumps(rec), flush=True)

@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from roboticattack_amd import cli  # noqa: E402
 from roboticattack_amd import dist as vdist  # noqa: E402
-from roboticattack_amd.attack.uada_ddp import parse_maskidx_sweep, parse_target_sweep  # noqa: E402
+from roboticattack_amd.attack.uada_ddp import parse_maskidx_sweep, parse_target_sweep, parse_upa_sweep  # noqa: E402
 from white_patch.UADA_ddp import OpenVLAAttacker  # noqa: E402
 
 
@@ -60,6 +60,8 @@ def main(args):
         instance_params.update(maskidx_sweep=args.maskidx_sweep)
     if args.target_sweep:  # extension: one TMA patch per (maskidx, target) group in one loop (--attack TMA; patches under {path}/<group tag>/)
         instance_params.update(target_sweep=args.target_sweep)
+    if args.upa_sweep:  # extension: one UPA patch per (alpha, belta) group in one loop (--attack UPA; patches under {path}/<group tag>/)
+        instance_params.update(upa_sweep=args.upa_sweep)
     OpenVLAAttacker._attack_entry(rank, instance_params, world)
     print("Attack done!")
 
@@ -78,6 +80,8 @@ def arg_parser(argv=None):
     parser.add_argument("--maskidx_sweep", default="", type=parse_maskidx_sweep)
     # extension: a TMA target sweep, groups "maskidx[,maskidx...]:target" separated by ';' ("0:0;1:0;6:1"): one patch per group; needs --attack TMA
     parser.add_argument("--target_sweep", default="", type=parse_target_sweep)
+    # extension: a UPA weight sweep, groups "alpha:belta" separated by ';' ("0.8:0.2;0.5:0.5"): one patch per group; needs --attack UPA
+    parser.add_argument("--upa_sweep", default="", type=parse_upa_sweep)
     return parser.parse_args(argv)
 
 

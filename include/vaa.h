@@ -57,6 +57,7 @@ extern "C" {
 /* gradient storage of vaa_loss_rows_fwd_bwd */
 #define VAA_GRAD_FULL 0  /* [R,V], the logits' dtype */
 #define VAA_GRAD_SLICE 1 /* [R,256]: the action columns 31744..31999 only (UADA_DDP / UPA: the gradient is zero elsewhere) */
+#define VAA_SEG_UPA_MAX_GROUPS 32 /* groups of one vaa_loss_rows_fwd_bwd_seg_upa call: their parameters travel in the launch's arguments */
 
 /* optimiser modes (K4) */
 #define VAA_OPT_ADAMW_HF 0 /* transformers==4.40.1 AdamW.step (eps outside bias correction) + clamp(0,1)  UADA.py:155-156 */
@@ -266,8 +267,9 @@ int vaa_step_epilogue_update(const float* partials, int nparts, int n, const voi
  *             it in VAA_LOSS_UADA_DDP mode: each row's gradient is normalised by ITS GROUP's action-row count, so dhidden / grad_slice / the row
  *             statistics of group p's rows are bit for bit those of the call on group p's rows alone with the group's ordinary map (an ordinary map
  *             gives the old bits). Folds inside those calls (scalars != NULL, vaa_head_loss_rows_finish) treat the map as ONE batch: per-group
- *             scalars come from vaa_step_epilogue_seg. UPA's batch means are not per group: the segmented map serves VAA_LOSS_UADA_DDP there, and
- *             VAA_LOSS_CE through vaa_loss_rows_fwd_bwd_seg (the target sweep below).
+ *             scalars come from vaa_step_epilogue_seg. UPA's batch means are not per group: the segmented map serves VAA_LOSS_UADA_DDP there,
+ *             VAA_LOSS_CE through vaa_loss_rows_fwd_bwd_seg (the target sweep below) and VAA_LOSS_UPA — whose batch means ARE folded per group —
+ *             through vaa_loss_rows_fwd_bwd_seg_upa (the UPA sweep below).
  *   vaa_step_epilogue_seg: ONE launch, vaa_step_epilogue per group (the same kernel: vaa_step_epilogue is its one-group case): partials
  *             [P*nparts][n] (group p's nparts tiles at p*nparts: K2' with one partial per image, nparts = Bp) ->
  *               msg[p*n .. (p+1)*n)  = group p's fixed-order sum: bitwise vaa_step_epilogue over those nparts tiles
@@ -318,6 +320,30 @@ int vaa_step_epilogue_seg_tail(const float* partials, int nparts, int n, int P, 
 int vaa_step_epilogue_seg_tail_update(const float* partials, int nparts, int n, int P, const float* scalars_in, float* msg, float* patch, float* m,
                                       float* v, int opt_mode, float lr, float beta1, float beta2, float eps, int step, double* stat_part,
                                       void* stream);
+
+/*
+ * UPA SWEEP — P UPA patch groups (UPA.py's reverse-direction loss alpha*mean(cos+1) + beta/(mean||e-l|| + 1e-3), one (alpha, beta) pair per group)
+ * in ONE step. Reverse-direction UPA leaves the labels unmasked (8 labelled rows per image), so the head is the hipBLASLt GEMM — run ONCE over the
+ * rows of all groups, no row limit — and K3 takes the segmented row map in VAA_LOSS_UPA mode with slice storage:
+ *   vaa_loss_rows_fwd_bwd_seg_upa: vaa_loss_rows_fwd_bwd(VAA_LOSS_UPA, VAA_GRAD_SLICE) (its two launches, the same kernels) on logits [R,V] of P
+ *             groups of B/P images; rowmap from vaa_loss_rowmap_build_seg, or an ordinary map with P = 1 (the bits of vaa_loss_rows_fwd_bwd).
+ *             group_params host f32 [P][4] = {w, alpha, beta, scale} per group; they travel in the launch's arguments, so P <= VAA_SEG_UPA_MAX_GROUPS (else
+ *             VAA_E_UNSUPPORTED). The batch means of UPA.py:375-384 run over the B/P images of a row's OWN group: the workgroup of a gradient row
+ *             folds its group's statistics (the group's own map, rows and parameters — indices relative to the group) in the fixed order of the
+ *             one-batch call, and the workgroup of a group's first row publishes scalars[8g .. 8g+8) and rows g*B/P .. of pred_tokens /
+ *             pred_full_tokens [B, L-1]; nothing is handed over between workgroups (always two launches: VAA_K3_ONE_PASS does not apply). Group g's
+ *             gradient-slice rows, scalars and prediction-map rows are bit for bit those of vaa_loss_rows_fwd_bwd on the group's logits rows alone
+ *             with its ordinary map and its (alpha, beta), bf16 and fp32. Every group must label at least one row (UPA's labels are unmasked); a
+ *             group without rows has no workgroup and its outputs are left as they were. grad_slice dev [R,256] in `dtype` (16-byte aligned, as
+ *             logits) or NULL (evaluation: one workgroup per group); scalars dev f32 [P,8]; ws >= vaa_loss_rows_ws_bytes(R); the other arguments as
+ *             vaa_loss_rows_fwd_bwd.
+ *   The step ends like the target sweep's: the loss scalars are final before the backward, so vaa_step_epilogue_seg_tail carries them on the step
+ *   whose scalars are read and vaa_step_epilogue_seg (zero tail) on the others; the L1 clip (UPA.py:157) needs the whole gradient's norm, so K4 is
+ *   never fused into the epilogue here: vaa_patch_update_seg with l1_clip = 1e-3 follows at every world size.
+ */
+int vaa_loss_rows_fwd_bwd_seg_upa(const void* logits, int dtype, const void* rowmap, int R, int B, int L, int V, int P, const float* group_params,
+                                  float* scalars, int32_t* pred_tokens, int32_t* pred_full_tokens, void* grad_slice, void* ws, size_t ws_bytes,
+                                  void* stream);
 
 /*
  * LM head FUSED with K3's statistics (SURVEY.md section 8f-2 as the survey wrote it; for callers that own the LM-head weight) — replaces

@@ -17,6 +17,7 @@ LOSS_UADA, LOSS_UADA_DDP, LOSS_UPA, LOSS_CE = 0, 1, 2, 3
 DTYPE_F32, DTYPE_BF16 = 0, 1
 LAYOUT_FULL, LAYOUT_ROWS = 0, 1
 GRAD_FULL, GRAD_SLICE = 0, 1
+SEG_UPA_MAX_GROUPS = 32  # VAA_SEG_UPA_MAX_GROUPS: groups of one vaa_loss_rows_fwd_bwd_seg_upa call
 OPT_ADAMW_HF, OPT_PGD_SIGN = 0, 1
 
 MODEL_OP_EXPORTS = ("vaa_model_rope", "vaa_model_swiglu_fwd", "vaa_model_swiglu_bwd", "vaa_model_rmsnorm_fwd", "vaa_model_rmsnorm_bwd",
@@ -72,6 +73,7 @@ EXPORTS = (
     "vaa_loss_rows_fwd_bwd_seg",
     "vaa_step_epilogue_seg_tail",
     "vaa_step_epilogue_seg_tail_update",
+    "vaa_loss_rows_fwd_bwd_seg_upa",
     "vaa_async_error",
     "vaa_prof_start",
     "vaa_prof_stop",
@@ -238,6 +240,8 @@ def lib() -> C.CDLL:
     L.vaa_step_epilogue_seg_tail.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     L.vaa_step_epilogue_seg_tail_update.restype = i32
     L.vaa_step_epilogue_seg_tail_update.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, i32, vp, vp]
+    L.vaa_loss_rows_fwd_bwd_seg_upa.restype = i32
+    L.vaa_loss_rows_fwd_bwd_seg_upa.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, C.POINTER(f32), vp, vp, vp, vp, vp, sz, vp]
     L.vaa_async_error.restype = i32
     L.vaa_async_error.argtypes = []
     L.vaa_prof_start.restype = i32

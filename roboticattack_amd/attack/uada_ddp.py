@@ -96,6 +96,29 @@ def target_sweep_tag(maskidx, target) -> str:
     return f"{sweep_tag(maskidx)}-target{float(target):g}"
 
 
+def parse_upa_sweep(text):
+    """CLI form of a UPA sweep: "0.8:0.2;0.5:0.5" -> [(0.8, 0.2), (0.5, 0.5)] (alpha:belta per group); "" / None -> None (no sweep)."""
+    if text is None or not str(text).strip():
+        return None
+    out = []
+    for part in str(text).split(";"):
+        alpha, sep, belta = part.partition(":")
+        try:
+            pair = (float(alpha), float(belta)) if sep else None
+        except ValueError:
+            pair = None
+        if pair is None:
+            raise ValueError(f"UPA sweep: every group reads alpha:belta, got {part!r}")
+        out.append(pair)
+    return out
+
+
+def upa_sweep_tag(alpha, belta) -> str:
+    """Directory / log tag of a UPA sweep group: (0.8, 0.2) -> "alpha0.8-belta0.2" (%g of the weights: equal groups give the same string,
+    different ones different strings)."""
+    return f"alpha{float(alpha):g}-belta{float(belta):g}"
+
+
 class OpenVLAAttacker(AttackBase):
     val_batches = 100  # UADA_ddp.py:240
     val_every = 200  # UADA_ddp.py:233
@@ -103,7 +126,7 @@ class OpenVLAAttacker(AttackBase):
     def __init__(self, vla_path, dataset_name, save_dir="", resize_patch=False, patch_size=[3, 50, 50], lr=0.01, bs=1, warmup=20,
                  num_iter=10000, maskidx=[], innerLoop=1, geometry=True, use_wandb=True, MSE_weights=1,
                  model_factory=None, dataset_factory=None, device=None, attack_type="UADA", alpha=0.8, belta=0.2, target_action=0.0, maskidx_sweep=None,
-                 target_sweep=None):
+                 target_sweep=None, upa_sweep=None):
         """`attack_type`, `alpha`, `belta`, `target_action` are EXTENSIONS (the reference ships DDP for UADA only):
         "UPA" = UPA.py's reverse-direction loss + L1 grad clip, "TMA" = TMA.py's target-token CE, same data-parallel loop.
         `maskidx_sweep` (EXTENSION): a list of maskidx lists optimises one patch per list in ONE loop — every group sees the same frames, draws and
@@ -111,7 +134,10 @@ class OpenVLAAttacker(AttackBase):
         None keeps the loop above exactly as it is; `maskidx` is then unused.
         `target_sweep` (EXTENSION, attack_type="TMA" only): a list of (maskidx list, target action value) pairs optimises one TMA patch per pair in
         ONE loop the same way — group p ends where a standalone TMA run with maskidx = maskidx_p, target_action = target_p and the same seed ends
-        (DESIGN.md §maskidx sweep); `maskidx` and `target_action` are then unused. None: no target sweep."""
+        (DESIGN.md §maskidx sweep); `maskidx` and `target_action` are then unused. None: no target sweep.
+        `upa_sweep` (EXTENSION, attack_type="UPA" only): a list of (alpha, belta) pairs optimises one UPA patch per pair in ONE loop the same way —
+        group p ends where a standalone UPA run with alpha = alpha_p, belta = belta_p and the same seed ends (DESIGN.md §maskidx sweep); `alpha` and
+        `belta` are then unused. None: no UPA sweep."""
         rank, world, local = vdist.env_rank_world()
         if device is None:
             device = vdist.local_device()
@@ -136,6 +162,9 @@ class OpenVLAAttacker(AttackBase):
         self.target_sweep = None
         if target_sweep is not None:
             self.target_sweep = self._check_target_sweep(target_sweep, maskidx_sweep)
+        self.upa_sweep = None
+        if upa_sweep is not None:
+            self.upa_sweep = self._check_upa_sweep(upa_sweep, maskidx_sweep, target_sweep)
 
     def _check_sweep(self, sweep):
         """Refuses (ValueError naming the limit) what the batched sweep does not cover."""
@@ -183,6 +212,31 @@ class OpenVLAAttacker(AttackBase):
                              f"{SWEEP_MAX_IMAGES} (K2' one partial tile per image)")
         return sweep
 
+    def _check_upa_sweep(self, sweep, maskidx_sweep, target_sweep):
+        """Refuses (ValueError naming the limit) what the batched UPA sweep does not cover."""
+        if maskidx_sweep is not None or target_sweep is not None:
+            raise ValueError("upa_sweep: cannot be combined with maskidx_sweep or target_sweep (one kind of sweep per run)")
+        sweep = [(float(a), float(b)) for a, b in sweep]
+        if not sweep:
+            raise ValueError("upa_sweep: needs at least one (alpha, belta) group")
+        if not all(np.isfinite(v) for pair in sweep for v in pair):
+            raise ValueError(f"upa_sweep: every alpha / belta is a finite number, got {sweep}")
+        if len({upa_sweep_tag(a, b) for a, b in sweep}) != len(sweep):
+            raise ValueError(f"upa_sweep: groups must be distinct, got {sweep}")
+        if self.attack_type != "UPA":
+            raise ValueError(f"upa_sweep: UPA only (got attack_type={self.attack_type!r}; UADA sweeps go through maskidx_sweep, TMA sweeps through target_sweep)")
+        if self.randomPatchTransform.resize_patch:
+            raise ValueError("upa_sweep: resize_patch=True is not supported (one patch size per group only)")
+        if not self.fused_ddp_available():
+            raise ValueError("upa_sweep: needs the fused path (a model that exposes its patch-embed weights and hidden rows, VAA_FUSED_EPILOGUE != 0)")
+        if len(sweep) * self.bs > SWEEP_MAX_IMAGES:
+            raise ValueError(f"upa_sweep: {len(sweep)} groups x bs {self.bs} = {len(sweep) * self.bs} images per rank exceed the limit of "
+                             f"{SWEEP_MAX_IMAGES} (K2' one partial tile per image)")
+        if len(sweep) > ops.SEG_UPA_MAX_GROUPS:
+            raise ValueError(f"upa_sweep: {len(sweep)} groups exceed the limit of {ops.SEG_UPA_MAX_GROUPS} (the groups' loss weights travel in K3's "
+                             f"launch arguments)")
+        return sweep
+
     def setup(self, rank, world_size):
         vdist.init_process_group(device=self.device if self.device.type == "cuda" else None)
         if self.device.type == "cuda":
@@ -205,7 +259,7 @@ class OpenVLAAttacker(AttackBase):
             self.cleanup()
 
     def _attack(self, rank, world_size):
-        if self.maskidx_sweep is not None or self.target_sweep is not None:
+        if self.maskidx_sweep is not None or self.target_sweep is not None or self.upa_sweep is not None:
             return self._attack_sweep(rank, world_size)
         dev = self.device
         if rank == 0:
@@ -258,19 +312,23 @@ class OpenVLAAttacker(AttackBase):
         at world > 1 ONE all-reduce of [P gradients | P x 4 scalars] and the segmented K4. The RNG streams are consumed as by ONE standalone run:
         one patch init (every group starts from it), one transform draw per frame and step, shared by the groups.
         A target sweep (TMA) is the same loop with the groups' target labels and, per step, ONE hipBLASLt head + K3 in LOSS_CE mode over the
-        segmented map (target_sweep_step) in place of K3s."""
+        segmented map (target_sweep_step) in place of K3s. A UPA sweep is that loop again with every group's labels left unmasked, K3 in LOSS_UPA
+        mode with the group's (alpha, belta) (upa_sweep_step) and — the L1 clip needs the whole gradient's norm — the segmented K4 behind the
+        epilogue at every world size."""
         dev = self.device
-        tma = self.target_sweep is not None
-        sweep = self.target_sweep if tma else self.maskidx_sweep
+        tma, upa = self.target_sweep is not None, self.upa_sweep is not None
+        sweep = self.target_sweep if tma else (self.upa_sweep if upa else self.maskidx_sweep)
         P = len(sweep)
-        if tma:
+        if upa:
+            self.sweep_tags = [upa_sweep_tag(a, b) for a, b in sweep]
+        elif tma:
             from ..labels import tma_target_tokens
 
             self.sweep_tags = [target_sweep_tag(m, t) for m, t in sweep]
             self._tma_targets = [tma_target_tokens(float(t) * torch.ones(7).numpy(), m, self.action_tokenizer).to(dev) for m, t in sweep]
         else:
             self.sweep_tags = [sweep_tag(m) for m in sweep]
-        what = "TMA target sweep" if tma else "UADA maskidx sweep"
+        what = "TMA target sweep" if tma else ("UPA weight sweep" if upa else "UADA maskidx sweep")
         if rank == 0:
             p0 = torch.rand(self.patch_size).to(dev)  # UADA_ddp.py:140-141, drawn once: every group's standalone run draws this patch
         else:
@@ -278,7 +336,7 @@ class OpenVLAAttacker(AttackBase):
         vdist.broadcast_patch(p0, src=0)
         patches = p0.unsqueeze(0).repeat(P, *([1] * p0.dim())).contiguous().requires_grad_(True)
         self.patch = patches
-        optimizer = SweepPatchOptimizer(patches, self.lr, "adamW")
+        optimizer = SweepPatchOptimizer(patches, self.lr, "adamW", l1_clip=1e-3 if upa else 0.0)  # UPA.py:157, per group
         scheduler = CosineWarmupSchedule(optimizer, self.warmup, int(self.num_iter), 0.5)
         sync = vdist.PatchGradSync(patches.numel(), 4 * P, dev)
         scalars = torch.zeros((P, 8), dtype=torch.float32, device=dev)
@@ -304,14 +362,17 @@ class OpenVLAAttacker(AttackBase):
             R = int(row_index.numel())
             if R == 0:
                 raise ValueError(f"{what}: no labelled position in the batch")
-            if not tma and not self._slice_head(R, None, W):
+            if not tma and not upa and not self._slice_head(R, None, W):
                 raise ValueError(f"maskidx sweep: K3s does not take {R} labelled rows per rank here (limit {SWEEP_MAX_ROWS} rows, bf16 head)")
             segmap = ops.LossRowMapSeg(labels_all, P)
             pack = self.vla.make_pack(am_all) if (hasattr(self.vla, "make_pack") and am_all is not None) else None
 
             def step(inner_loop):
-                upd = optimizer.fused_update_args() if world_size == 1 else None
                 read = inner_loop == self.innerLoop - 1  # the step whose loss scalars the loop reads (UADA_ddp.py:214-221)
+                if upa:  # the clip keeps K4 out of the epilogue: at world 1 the exchange hands the message back as it is, K4 follows
+                    self.upa_sweep_step(img_all, patches, ids_all, row_index, segmap, pack, sync.buf, scalars, read)
+                    return sync.allreduce_packed
+                upd = optimizer.fused_update_args() if world_size == 1 else None
                 if tma:
                     self.target_sweep_step(img_all, patches, ids_all, row_index, segmap, pack, sync.buf, scalars, read, upd)
                 else:
@@ -409,8 +470,31 @@ class OpenVLAAttacker(AttackBase):
         ops.step_epilogue_seg_tail(sink["partials"], msg, sc, P, update=update)
         return pred_full
 
+    def upa_sweep_step(self, img_all, patches, input_ids, row_index, segmap, pack, msg, scalars, read, pairs=None):
+        """One inner step of the UPA sweep up to the exchange: K1 (one draw per frame, every group) -> body over P*bs images -> ONE hipBLASLt head
+        over the rows of all groups -> K3 in LOSS_UPA mode with the segmented map (every group's batch means and (alpha, belta) its own) -> ONE
+        dh = g_slice @ W[31744:32000], backward, K2' (a partial per image) -> ONE segmented epilogue in its pass-through form: msg = [P gradients |
+        P x {CE, w^2*MSE, UAD, total}] on the step whose scalars are `read`, a zero tail on the others (`scalars` [P,8] is then left as it is). K4
+        is never fused here: the caller runs the segmented K4 with the L1 clip on the (all-reduced) message. `pairs`: the groups' (alpha, belta), the
+        attacker's `upa_sweep` when None."""
+        sink = {}
+        P = int(patches.shape[0])
+        pe = self.randomPatchTransform.apply_sweep_batch(img_all, patches, self.mean, self.std, self.geometry, sink)
+        h = self.vla.hidden_rows(input_ids, None, row_index, patch_embeds=pe, pack=pack)
+        total, sc, _, pred_full = ops.HeadLossRowsSegUpa.apply(h, self.vla.lm_head.weight, segmap, P, self.upa_sweep if pairs is None else pairs,
+                                                              float(self.MSE_weights), 1.0)
+        total.backward()
+        if not read:
+            ops.step_epilogue_seg(sink["partials"], msg, scalars, P)
+            return None
+        ops.step_epilogue_seg_tail(sink["partials"], msg, sc, P)
+        return pred_full
+
     def _sweep_group_labels(self, labels, g):
-        """Group g's labels of a sweep (a new tensor): masked with its maskidx (UADA_ddp.py:89-97), or its TMA target labels (TMA.py:124-129)."""
+        """Group g's labels of a sweep (a new tensor): masked with its maskidx (UADA_ddp.py:89-97), its TMA target labels (TMA.py:124-129), or —
+        UPA reverse_direction — left unmasked (UPA.py:127-129)."""
+        if self.upa_sweep is not None:
+            return labels.clone()
         if self.target_sweep is not None:
             from ..labels import tma_target_labels
 
@@ -420,8 +504,8 @@ class OpenVLAAttacker(AttackBase):
     def validate_sweep(self, i, patches, rank):
         """validate() per group: every validation batch is drawn ONCE (the RNG consumption of one standalone pass) and evaluated with each group's
         patch and labels; per group the averages, the AVG all-reduces, best-patch selection and the files under save_dir/<group tag>/."""
-        tma = self.target_sweep is not None
-        mode = ops.LOSS_CE if tma else ops.LOSS_UADA_DDP
+        tma, upa = self.target_sweep is not None, self.upa_sweep is not None
+        mode = ops.LOSS_CE if tma else (ops.LOSS_UPA if upa else ops.LOSS_UADA_DDP)
         rbs = [ValReadback(self.val_batches, self.device) for _ in self.sweep_tags]
         last_images = [None] * len(rbs)
         ph, pw = int(patches.shape[2]), int(patches.shape[3])
@@ -436,13 +520,14 @@ class OpenVLAAttacker(AttackBase):
                     modified = self.randomPatchTransform.apply_random_patch_batch(img, patches[g].detach(), mean=self.mean, std=self.std,
                                                                                    geometry=self.geometry, draws=draws)
                     lab = self._sweep_group_labels(labels, g)
-                    _, sc, _ = self.model_loss(input_ids, attention_mask, modified, lab, mode, w=float(self.MSE_weights), need_grad=False)
+                    ab = dict(alpha=self.upa_sweep[g][0], beta=self.upa_sweep[g][1]) if upa else {}
+                    _, sc, _ = self.model_loss(input_ids, attention_mask, modified, lab, mode, w=float(self.MSE_weights), need_grad=False, **ab)
                     rbs[g].add(sc)
                     last_images[g] = modified
         self.last_val_log = {}
         for g, tag in enumerate(self.sweep_tags):
-            # selection metric: MSE distance (UADA) or the attack loss (TMA), as validate() picks it
-            self.last_val_log[tag] = self._val_record(i, rank, rbs[g].read()[0], 0 if tma else 2, patches[g], last_images[g], tag)
+            # selection metric: MSE distance (UADA) or the attack loss (TMA, UPA), as validate() picks it
+            self.last_val_log[tag] = self._val_record(i, rank, rbs[g].read()[0], 0 if (tma or upa) else 2, patches[g], last_images[g], tag)
 
     def _loss_mode(self):
         return {"UADA": ops.LOSS_UADA_DDP, "UPA": ops.LOSS_UPA, "TMA": ops.LOSS_CE}[self.attack_type]

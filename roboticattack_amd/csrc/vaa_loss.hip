@@ -604,12 +604,35 @@ __global__ __launch_bounds__(kRowsT) void rows_stats_kernel(RowsArgs a, unsigned
 // workgroup goes straight to its gradient (same parts, same formulas: the bits of the all-fold form) instead of waiting for a fold it does not use.
 // P > 0 (vaa_loss_rows_fwd_bwd_seg: VAA_LOSS_CE over P groups, a segmented map or an ordinary one with P = 1): P fold workgroups fold_wg + g, each
 // with its group's view (rows_group_view: scalars[8g..], its rows of the prediction maps); a gradient row takes the row count of ITS group.
+// P > 0 in VAA_LOSS_UPA mode (vaa_loss_rows_fwd_bwd_seg_upa: one (alpha, beta) pair per group, gp = the groups' {w, alpha, beta, scale}): the
+// gradient needs the batch means of the row's OWN group (UPA.py:375-387), so a row's workgroup IS its group's view — it folds that group in
+// rows_fold's fixed order with the group's parameters and indexes the view's rows (row r of the call = row r - r0 of the group); the first row
+// of each group publishes the group's scalars and prediction-map rows. Without a gradient: workgroup g folds and publishes group g.
+constexpr int kSegUpaMaxP = VAA_SEG_UPA_MAX_GROUPS;  // groups whose parameters travel by value in the launch's arguments
+struct GroupParams {
+    float v[kSegUpaMaxP][4];
+};
+
 template <typename T, int kRowsT>
-__global__ __launch_bounds__(kRowsT) void rows_finish_kernel(RowsArgs a, int gsplit, int fold_wg, int P) {
+__global__ __launch_bounds__(kRowsT) void rows_finish_kernel(RowsArgs a, int gsplit, int fold_wg, int P, GroupParams gp) {
     constexpr int N = Vec<T>::N;
     const int r = blockIdx.x / gsplit, h = blockIdx.x - r * gsplit;
     const int tid = threadIdx.x;
     __shared__ double sh[kRowsT / 64][7];
+    const bool upa_seg = P > 0 && a.mode == VAA_LOSS_UPA;
+    int rl = r;  // this row's index in the view that is folded (the whole call's, or its group's)
+    if (upa_seg) {
+        int g = (int)blockIdx.x - fold_wg;  // no gradient: one workgroup per group
+        if (fold_wg < 0) {                  // a gradient row: the group of its image, as row_label_count finds it
+            const int Pm = a.rowmap[2], Bm = a.rowmap[3] > 0 ? a.rowmap[3] : 1;
+            g = Pm > 0 ? reinterpret_cast<const RowMap*>(a.rowmap + 4)[r].b / Bm : 0;
+            g = g < 0 ? 0 : (g >= Pm ? max(Pm - 1, 0) : g);
+        }
+        g = __builtin_amdgcn_readfirstlane(min(g, P - 1));
+        if (fold_wg < 0 && a.rowmap[2] > 0) rl = r - a.rowmap[rowmap_seg_table(a.B, a.L) + 4 * g];
+        a = rows_group_view(a, P, g);  // (logits and grad stay the call's: they are indexed by r)
+        a.w = gp.v[g][0]; a.alpha = gp.v[g][1]; a.beta = gp.v[g][2]; a.scale = gp.v[g][3];
+    }
     const RowMap* rm = reinterpret_cast<const RowMap*>(a.rowmap + 4);
     // this workgroup's part of its row: issue the loads before the fold (addresses do not depend on it)
     const bool full_grad = a.grad && !a.grad_slice && (a.mode == VAA_LOSS_UADA || a.mode == VAA_LOSS_CE);
@@ -628,9 +651,9 @@ __global__ __launch_bounds__(kRowsT) void rows_finish_kernel(RowsArgs a, int gsp
     }
     FoldOut f;
     if (fold_wg < 0) {
-        f = rows_fold<kRowsT>(a, blockIdx.x == 0, sh);
+        f = rows_fold<kRowsT>(a, upa_seg ? rl == 0 : blockIdx.x == 0, sh);
     } else if ((int)blockIdx.x >= fold_wg) {
-        (void)rows_fold<kRowsT>(P > 0 ? rows_group_view(a, P, (int)blockIdx.x - fold_wg) : a, true, sh);
+        (void)rows_fold<kRowsT>(P > 0 && !upa_seg ? rows_group_view(a, P, (int)blockIdx.x - fold_wg) : a, true, sh);
         return;
     } else {  // what rows_fold returns for VAA_LOSS_CE, as far as the gradient reads it
         f.Rn = min(a.R, a.rowmap[0]);
@@ -641,16 +664,16 @@ __global__ __launch_bounds__(kRowsT) void rows_finish_kernel(RowsArgs a, int gsp
     }
     const int Rn = f.Rn;
     const double nrow = f.nrow, nact = f.nact, dce = f.dce, aux1 = f.aux1;
-    if (!a.grad || r >= Rn) return;
-    const RowMap me = rm[r];
+    if (!a.grad || rl < 0 || rl >= Rn) return;
+    const RowMap me = rm[rl];
     if (a.mode == VAA_LOSS_UADA_DDP && !zero_fill) return;  // slice already written by the statistics kernel
     // ---- gradient of this row (part h) ----
-    const SliceStat ms = a.slice[r];
+    const SliceStat ms = a.slice[rl];
     if (!full_grad) {  // slice-only modes (UPA; UADA_DDP only when FULL storage was asked for)
         float kE = 0.0f;
-        if (a.mode == VAA_LOSS_UPA) {
-            if (me.ord < 3 && r - me.ord >= 0 && r - me.ord + 2 < Rn)
-                kE = (float)(upa_load<false>(a.slice, rm, r - me.ord).dE(me.ord, (double)a.alpha, (double)a.beta, aux1, a.B) / 255.0);
+        if (a.mode == VAA_LOSS_UPA) {  // (rows of the folded view: a sample's three rows and the bound Rn are its group's on a segmented call)
+            if (me.ord < 3 && rl - me.ord >= 0 && rl - me.ord + 2 < Rn)
+                kE = (float)(upa_load<false>(a.slice, rm, rl - me.ord).dE(me.ord, (double)a.alpha, (double)a.beta, aux1, a.B) / 255.0);
         } else if (a.mode != VAA_LOSS_CE && me.lab > 2) {
             kE = mse_kE(a.w, ms.E, me.lab, nact);
         }
@@ -999,11 +1022,13 @@ static int launch_rows_stats(const RowsArgs& a, int dtype, hipStream_t st, const
     return check_launch(who);
 }
 
-static int launch_rows_finish(const RowsArgs& a, int dtype, unsigned G, int gsplit, int fold_wg, hipStream_t st, const char* who, int P = 0) {
+static int launch_rows_finish(const RowsArgs& a, int dtype, unsigned G, int gsplit, int fold_wg, hipStream_t st, const char* who, int P = 0,
+                              const GroupParams* gp = nullptr) {
+    static const GroupParams no_groups = {};
     with_rows_inst(dtype, rows_threads(a.V), [&](auto t, auto n, const char* inst) {
         constexpr int NT = decltype(n)::value;
         static const std::string name = rows_inst_name("rows_finish_kernel", inst, "");
-        launch_k(name.c_str(), rows_finish_kernel<decltype(t), NT>, dim3(G), dim3(NT), 0, st, a, gsplit, fold_wg, P);
+        launch_k(name.c_str(), rows_finish_kernel<decltype(t), NT>, dim3(G), dim3(NT), 0, st, a, gsplit, fold_wg, P, gp ? *gp : no_groups);
         return 0;
     });
     return check_launch(who);
@@ -1015,9 +1040,11 @@ namespace vaa {
 
 // vaa_loss_rows_fwd_bwd (P = 0: the map is one batch, scalars[8]) and vaa_loss_rows_fwd_bwd_seg (P > 0 groups, VAA_LOSS_CE, scalars [P,8]: the same
 // two launches — every row's gradient normalised by its group's row count, one fold workgroup per group past the gradient workgroups)
+// and vaa_loss_rows_fwd_bwd_seg_upa (P > 0 groups, VAA_LOSS_UPA with slice storage, gp = the groups' parameters: the same two launches — every row's
+// workgroup folds its own group, or one workgroup per group when no gradient is asked for)
 static int loss_rows_impl(const char* who, int P, const void* logits, int dtype, const void* rowmap, int R, int B, int L, int V, int mode,
                           const float* params, float* scalars, int32_t* pred_tokens, int32_t* pred_full_tokens, void* grad, int grad_kind, void* ws,
-                          size_t ws_bytes, void* stream) {
+                          size_t ws_bytes, void* stream, const GroupParams* gp = nullptr) {
     const bool seg = P > 0;
     if (!logits || !scalars) {
         set_error("%s: null pointer argument", who);
@@ -1034,6 +1061,10 @@ static int loss_rows_impl(const char* who, int P, const void* logits, int dtype,
     RowsArgs a;
     int rc = rows_args(who, logits, dtype, rowmap, R, B, L, V, mode, params, scalars, pred_tokens, pred_full_tokens, grad, grad_kind, ws, ws_bytes, a);
     if (rc != VAA_OK) return rc;
+    if (gp && ((((uintptr_t)logits) | ((uintptr_t)grad)) & 15u)) {  // the rows are read and written in 16-byte pieces
+        set_error("%s: logits and grad_slice must be 16-byte aligned", who);
+        return VAA_E_INVALID;
+    }
     hipStream_t st = (hipStream_t)stream;
     // Full-row gradients (UADA's 1/CE^2, CE) in ONE launch: the statistics pass keeps its logits in registers across a grid-wide hand-over
     // and writes the gradient from them, so every row is read once (16.4 MB instead of 25.4 MB at R' = 128) — bitwise the outputs of the
@@ -1051,7 +1082,7 @@ static int loss_rows_impl(const char* who, int P, const void* logits, int dtype,
         unsigned* bar = (capturing || !rows_one_pass_fits(a, dtype) || !rows_one_pass_stream_ok(st)) ? nullptr : rows_bar_for(st, &gen);
         if (bar) return launch_rows_stats(a, dtype, st, "vaa_loss_rows_fwd_bwd(one pass)", bar, gen);
     }
-    rc = launch_rows_stats(a, dtype, st, seg ? "vaa_loss_rows_fwd_bwd_seg(stats)" : "vaa_loss_rows_fwd_bwd(stats)");
+    rc = launch_rows_stats(a, dtype, st, seg ? (gp ? "vaa_loss_rows_fwd_bwd_seg_upa(stats)" : "vaa_loss_rows_fwd_bwd_seg(stats)") : "vaa_loss_rows_fwd_bwd(stats)");
     if (rc != VAA_OK) return rc;
     // the finishing pass: per (row, part) when a full-row gradient (or a zero fill) has to be written, else one workgroup per row
     // (UPA slice) or a single workgroup (UADA_DDP slice: only the scalars are left to do)
@@ -1062,13 +1093,16 @@ static int loss_rows_impl(const char* who, int P, const void* logits, int dtype,
     const char* ce_ev = getenv("VAA_K3_CE_FOLD_WG");
     const bool ce_fold_wg = !(ce_ev && ce_ev[0] == '0');
     int fold_wg = (full_rows && mode == VAA_LOSS_CE && ce_fold_wg) ? (int)G : -1;
-    if (seg) {  // the groups' fold workgroups behind the gradient workgroups (none without a gradient)
+    if (seg && gp) {  // UPA groups: a gradient row folds its own group (G = R above); evaluation takes one workgroup per group
+        fold_wg = grad ? -1 : 0;
+        if (!grad) G = (unsigned)P;
+    } else if (seg) {  // the groups' fold workgroups behind the gradient workgroups (none without a gradient)
         fold_wg = full_rows ? (int)G : 0;
         G = (unsigned)(fold_wg + P);
     } else if (fold_wg >= 0) {
         ++G;
     }
-    return launch_rows_finish(a, dtype, G, gsplit, fold_wg, st, seg ? "vaa_loss_rows_fwd_bwd_seg(finish)" : "vaa_loss_rows_fwd_bwd(finish)", P);
+    return launch_rows_finish(a, dtype, G, gsplit, fold_wg, st, seg ? (gp ? "vaa_loss_rows_fwd_bwd_seg_upa(finish)" : "vaa_loss_rows_fwd_bwd_seg(finish)") : "vaa_loss_rows_fwd_bwd(finish)", P, gp);
 }
 
 }  // namespace vaa
@@ -1097,6 +1131,33 @@ extern "C" int vaa_loss_rows_fwd_bwd_seg(const void* logits, int dtype, const vo
     }
     return loss_rows_impl(who, P, logits, dtype, rowmap, R, B, L, V, mode, params, scalars, pred_tokens, pred_full_tokens, grad, grad_kind, ws, ws_bytes,
                           stream);
+}
+
+// UPA SWEEP: K3 in VAA_LOSS_UPA mode over P groups, one (alpha, beta) pair each, behind ONE LM-head GEMM. UPA's batch means (UPA.py:375-384) run over
+// the images of a row's own group, so group g's gradient-slice rows, scalars[8g..] and prediction-map rows are bit for bit
+// vaa_loss_rows_fwd_bwd(VAA_LOSS_UPA, VAA_GRAD_SLICE) on the group's rows alone with its (alpha, beta).
+extern "C" int vaa_loss_rows_fwd_bwd_seg_upa(const void* logits, int dtype, const void* rowmap, int R, int B, int L, int V, int P,
+                                             const float* group_params, float* scalars, int32_t* pred_tokens, int32_t* pred_full_tokens,
+                                             void* grad_slice, void* ws, size_t ws_bytes, void* stream) {
+    using namespace vaa;
+    const char* who = "vaa_loss_rows_fwd_bwd_seg_upa";
+    if (P <= 0 || B <= 0 || B % P != 0) {
+        set_error("%s: bad arguments (B=%d P=%d: B must be P groups of equal size, P <= %d)", who, B, P, kSegUpaMaxP);
+        return VAA_E_INVALID;
+    }
+    if (P > kSegUpaMaxP) {
+        set_error("%s: %d groups exceed the limit of %d (the groups' parameters travel in the launch's arguments)", who, P, kSegUpaMaxP);
+        return VAA_E_UNSUPPORTED;
+    }
+    if (!logits || !rowmap || !group_params || !scalars) {
+        set_error("%s: null pointer argument", who);
+        return VAA_E_INVALID;
+    }
+    GroupParams gp = {};
+    for (int g = 0; g < P; ++g)
+        for (int q = 0; q < 4; ++q) gp.v[g][q] = group_params[4 * g + q];
+    return loss_rows_impl(who, P, logits, dtype, rowmap, R, B, L, V, VAA_LOSS_UPA, group_params, scalars, pred_tokens, pred_full_tokens, grad_slice,
+                          VAA_GRAD_SLICE, ws, ws_bytes, stream, &gp);
 }
 
 // The finishing pass behind vaa_head_loss_rows_stats (LM head fused with K3's statistics): the fold of the rows into the scalars, the

@@ -2,10 +2,13 @@
 """Measures the maskidx sweep step against P standalone steps (one GPU, world size 1, the fused data-parallel UADA step with AdamW inside the
 epilogue): OpenVLA-7B shapes with random weights by default.
 
-    python tools/sweep_bench.py --configs 2x8,8x4,8x8 --steps 10 --warmup 3 [--vla random:openvla-7b] [--out file.json] [--attack tma]
+    python tools/sweep_bench.py --configs 2x8,8x4,8x8 --steps 10 --warmup 3 [--vla random:openvla-7b] [--out file.json] [--attack tma|upa]
 
 --attack tma measures the TMA target sweep step (one DoF per group, the T-dof1 .. T-dof7 family) against P standalone TMA steps of the
 data-parallel loop (the unfused step: K1, model, hipBLASLt head + K3, backward with K2', message, K4).
+
+--attack upa measures the UPA weight sweep step (one (alpha, belta) pair per group, labels unmasked: 8 labelled rows per image) against P
+standalone UPA steps of the data-parallel loop (K1, model, the loop's own head choice + K3, backward with K2', message, K4 with the L1 clip).
 
 For each (P, Bp): ms per standalone step at bs = Bp (maskidx [0]), ms per sweep step over P groups x Bp images (one DoF per group), their ratio, and the library's own kernels per step (vaa_prof per-dispatch timer: the hand-written microseconds of one step).
 Every step runs with full_ce on its last inner step only, as the loop does (innerLoop = `--inner`)."""
@@ -32,6 +35,11 @@ def _target_groups(P):
     return [([q % 7], 0.0 if q < 7 else 0.5) for q in range(P)]
 
 
+def _upa_groups(P):
+    """--attack upa: P distinct (alpha, belta) pairs from (1, 0) towards (0, 1)."""
+    return [(1.0 - q / max(P, 2), q / max(P, 2)) for q in range(P)]
+
+
 def measure(att, P, Bp, steps, warmup, inner, sweep, attack="uada"):
     from roboticattack_amd import dist as vdist, ops, synthetic
     from roboticattack_amd.attack.uada_ddp import mask_labels_sweep
@@ -44,7 +52,39 @@ def measure(att, P, Bp, steps, warmup, inner, sweep, attack="uada"):
     labels = batch["labels"].to(dev)
     ids, am = batch["input_ids"].to(dev), batch["attention_mask"].to(dev)
     n = 3 * 50 * 50
-    if attack == "tma" and sweep:
+    if attack == "upa" and sweep:
+        pairs = _upa_groups(P)
+        patches = torch.rand(P, 3, 50, 50, device=dev, requires_grad=True)
+        opt = SweepPatchOptimizer(patches, 1e-3, l1_clip=1e-3)
+        img = pv.repeat(P, 1, 1, 1).contiguous()
+        ids_all, am_all = ids.repeat(P, 1).contiguous(), am.repeat(P, 1).contiguous()
+        lab = labels.repeat(P, 1).contiguous()  # reverse-direction UPA: every group keeps the unmasked labels
+        row_index = att.vla.label_row_index(lab)
+        segmap = ops.LossRowMapSeg(lab, P)
+        pack = att.vla.make_pack(am_all) if hasattr(att.vla, "make_pack") else None
+        sync = vdist.PatchGradSync(patches.numel(), 4 * P, dev)
+        sc = torch.zeros((P, 8), device=dev)
+
+        def step(k):
+            att.upa_sweep_step(img, patches, ids_all, row_index, segmap, pack, sync.buf, sc, k % inner == inner - 1, pairs=pairs)
+            g_sum, _ = sync.allreduce_packed()
+            opt.step(grad=g_sum.view_as(patches), grad_scale=1.0)
+    elif attack == "upa":  # the standalone UPA step of the data-parallel loop (OpenVLAAttacker._attack, attack_type="UPA", world 1)
+        patch = torch.rand(3, 50, 50, device=dev, requires_grad=True)
+        opt = PatchOptimizer(patch, 1e-3, l1_clip=1e-3)
+        lab = labels.clone()
+        sync = vdist.PatchGradSync(patch.numel(), 4, dev)
+        pick = torch.tensor([1, 2, 7, 0], dtype=torch.int64, device=dev)
+
+        def step(k):
+            opt.zero_grad()
+            full_ce = k % inner == inner - 1
+            pix = att.randomPatchTransform.apply_random_patch_batch(pv, patch, mean=att.mean, std=att.std, geometry=True)
+            total, scal, _ = att.model_loss(ids, am, pix, lab, ops.LOSS_UPA, w=5.0, alpha=0.8, beta=0.2, full_ce=full_ce, read_scalars=full_ce)
+            total.backward()
+            g_sum, _ = sync.allreduce_step(patch.grad, scal, pick)
+            opt.step(grad=g_sum.view_as(patch), grad_scale=1.0)
+    elif attack == "tma" and sweep:
         patches = torch.rand(P, 3, 50, 50, device=dev, requires_grad=True)
         opt = SweepPatchOptimizer(patches, 1e-3)
         img = pv.repeat(P, 1, 1, 1).contiguous()
@@ -128,8 +168,9 @@ def main():
     ap.add_argument("--inner", type=int, default=50)
     ap.add_argument("--vla", default="random:openvla-7b")
     ap.add_argument("--out", default="")
-    ap.add_argument("--attack", default="uada", choices=["uada", "tma"],
-                    help="tma: the target sweep step (one hipBLASLt head + segmented K3 for all groups) against P standalone TMA steps of the data-parallel loop")
+    ap.add_argument("--attack", default="uada", choices=["uada", "tma", "upa"],
+                    help="tma: the target sweep step (one hipBLASLt head + segmented K3 for all groups) against P standalone TMA steps of the data-parallel "
+                         "loop; upa: the UPA weight sweep step against P standalone UPA steps of that loop")
     a = ap.parse_args()
     os.environ.setdefault("RANK", "0")
     os.environ.setdefault("WORLD_SIZE", "1")

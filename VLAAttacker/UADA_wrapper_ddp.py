@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from roboticattack_amd import cli  # noqa: E402
 from roboticattack_amd import dist as vdist  # noqa: E402
-from roboticattack_amd.attack.uada_ddp import parse_maskidx_sweep, parse_target_sweep, parse_upa_sweep  # noqa: E402
+from roboticattack_amd.attack.sweep import KINDS  # noqa: E402
 from white_patch.UADA_ddp import OpenVLAAttacker  # noqa: E402
 
 
@@ -56,12 +56,9 @@ def main(args):
     }
     if args.attack != "UADA":  # extension: the same data-parallel loop for UPA / TMA (BASELINE configs 4-5)
         instance_params.update(attack_type=args.attack, alpha=args.alpha, belta=args.belta, target_action=args.targetAction)
-    if args.maskidx_sweep:  # extension: one patch per maskidx group in one loop (patches under {path}/<group tag>/)
-        instance_params.update(maskidx_sweep=args.maskidx_sweep)
-    if args.target_sweep:  # extension: one TMA patch per (maskidx, target) group in one loop (--attack TMA; patches under {path}/<group tag>/)
-        instance_params.update(target_sweep=args.target_sweep)
-    if args.upa_sweep:  # extension: one UPA patch per (alpha, belta) group in one loop (--attack UPA; patches under {path}/<group tag>/)
-        instance_params.update(upa_sweep=args.upa_sweep)
+    for kind in KINDS:  # extensions: one patch per group of a sweep in one loop (patches under {path}/<group tag>/)
+        if getattr(args, kind.param):
+            instance_params[kind.param] = getattr(args, kind.param)
     OpenVLAAttacker._attack_entry(rank, instance_params, world)
     print("Attack done!")
 
@@ -76,12 +73,10 @@ def arg_parser(argv=None):
     parser.add_argument("--alpha", type=float, default=0.8)
     parser.add_argument("--belta", type=float, default=0.2)
     parser.add_argument("--targetAction", default=0, type=float)
-    # extension: a maskidx sweep, groups separated by ';' ("0;0,1,2"): one patch per group, optimised together; empty = one patch for --maskidx
-    parser.add_argument("--maskidx_sweep", default="", type=parse_maskidx_sweep)
-    # extension: a TMA target sweep, groups "maskidx[,maskidx...]:target" separated by ';' ("0:0;1:0;6:1"): one patch per group; needs --attack TMA
-    parser.add_argument("--target_sweep", default="", type=parse_target_sweep)
-    # extension: a UPA weight sweep, groups "alpha:belta" separated by ';' ("0.8:0.2;0.5:0.5"): one patch per group; needs --attack UPA
-    parser.add_argument("--upa_sweep", default="", type=parse_upa_sweep)
+    # extensions: a sweep optimises one patch per group, groups separated by ';'; empty = one patch for the flags above
+    #   --maskidx_sweep "0;0,1,2"; --target_sweep "0:0;1:0;6:1" (maskidx[,maskidx...]:target, needs --attack TMA); --upa_sweep "0.8:0.2;0.5:0.5" (alpha:belta, --attack UPA)
+    for kind in KINDS:
+        parser.add_argument("--" + kind.param, default="", type=kind.parse)
     return parser.parse_args(argv)
 
 

@@ -21,8 +21,11 @@ from .. import _lib
 from .. import dist as vdist
 from .. import ops
 from ..labels import mask_labels as _mask_labels
+from ..labels import tma_target_labels, tma_target_tokens
 from ..optim import CosineWarmupSchedule, PatchOptimizer, SweepPatchOptimizer
 from .engine import AttackBase, ValReadback, to_dev, wandb, wandb_enabled
+from .sweep import (KINDS, SWEEP_MAX_IMAGES, SWEEP_MAX_ROWS, check as check_sweep, mask_labels_sweep, parse_maskidx_sweep,  # noqa: F401 (the names
+                    parse_target_sweep, parse_upa_sweep, sweep_rows, sweep_tag, target_sweep_tag, upa_sweep_tag)  # live in sweep.py; importable here)
 
 
 def default_model_factory(vla_path: str, device):
@@ -50,75 +53,6 @@ def default_dataset_factory(dataset_name: str, bs: int, rank: int, world: int):
     return (SyntheticLoader(bs, seed=1234 + 1000003 * rank, kind="noise"), SyntheticLoader(bs, seed=99991 + 1000003 * rank, kind="noise"))
 
 
-SWEEP_MAX_ROWS = 128    # labelled rows per rank K3s covers (vaa_head_slice_applies)
-SWEEP_MAX_IMAGES = 512  # images per rank K2' keeps one partial tile each (vaa_patch_grad_partials)
-
-
-def parse_maskidx_sweep(text):
-    """CLI form of a sweep: "0;0,1,2" -> [[0], [0, 1, 2]]; "" / None -> None (no sweep)."""
-    if text is None or not str(text).strip():
-        return None
-    return [[int(v) for v in part.split(",") if v.strip() != ""] for part in str(text).split(";")]
-
-
-def sweep_tag(maskidx) -> str:
-    """Directory / log tag of a sweep group: [0] -> "maskidx0", [0, 1, 2] -> "maskidx0-1-2"."""
-    return "maskidx" + "-".join(str(int(v)) for v in maskidx)
-
-
-def mask_labels_sweep(labels, sweep):
-    """[Bp, L] labels -> [P*Bp, L]: group p's copy masked with maskidx_p (mask_labels, UADA_ddp.py:89-97)."""
-    return torch.cat([_mask_labels(labels.clone(), m) for m in sweep], dim=0)
-
-
-def sweep_rows(bs: int, sweep) -> int:
-    """Labelled rows per rank of a sweep step: every sample keeps |maskidx_p| action tokens + EOS."""
-    return sum(bs * (len(m) + 1) for m in sweep)
-
-
-def parse_target_sweep(text):
-    """CLI form of a target sweep: "0:0;1:0;0,1,2:0.25" -> [([0], 0.0), ([1], 0.0), ([0, 1, 2], 0.25)] (maskidx[,maskidx...]:target per group);
-    "" / None -> None (no sweep)."""
-    if text is None or not str(text).strip():
-        return None
-    out = []
-    for part in str(text).split(";"):
-        idx, sep, target = part.partition(":")
-        if not sep or not target.strip():
-            raise ValueError(f"target sweep: every group reads maskidx[,maskidx...]:target, got {part!r}")
-        out.append(([int(v) for v in idx.split(",") if v.strip() != ""], float(target)))
-    return out
-
-
-def target_sweep_tag(maskidx, target) -> str:
-    """Directory / log tag of a target sweep group: ([0], 0.25) -> "maskidx0-target0.25", ([0, 1], 0) -> "maskidx0-1-target0" (%g of the
-    target: equal groups give the same string, different ones different strings)."""
-    return f"{sweep_tag(maskidx)}-target{float(target):g}"
-
-
-def parse_upa_sweep(text):
-    """CLI form of a UPA sweep: "0.8:0.2;0.5:0.5" -> [(0.8, 0.2), (0.5, 0.5)] (alpha:belta per group); "" / None -> None (no sweep)."""
-    if text is None or not str(text).strip():
-        return None
-    out = []
-    for part in str(text).split(";"):
-        alpha, sep, belta = part.partition(":")
-        try:
-            pair = (float(alpha), float(belta)) if sep else None
-        except ValueError:
-            pair = None
-        if pair is None:
-            raise ValueError(f"UPA sweep: every group reads alpha:belta, got {part!r}")
-        out.append(pair)
-    return out
-
-
-def upa_sweep_tag(alpha, belta) -> str:
-    """Directory / log tag of a UPA sweep group: (0.8, 0.2) -> "alpha0.8-belta0.2" (%g of the weights: equal groups give the same string,
-    different ones different strings)."""
-    return f"alpha{float(alpha):g}-belta{float(belta):g}"
-
-
 class OpenVLAAttacker(AttackBase):
     val_batches = 100  # UADA_ddp.py:240
     val_every = 200  # UADA_ddp.py:233
@@ -129,15 +63,10 @@ class OpenVLAAttacker(AttackBase):
                  target_sweep=None, upa_sweep=None):
         """`attack_type`, `alpha`, `belta`, `target_action` are EXTENSIONS (the reference ships DDP for UADA only):
         "UPA" = UPA.py's reverse-direction loss + L1 grad clip, "TMA" = TMA.py's target-token CE, same data-parallel loop.
-        `maskidx_sweep` (EXTENSION): a list of maskidx lists optimises one patch per list in ONE loop — every group sees the same frames, draws and
-        schedule, and group p ends where a standalone run with maskidx = maskidx_sweep[p] and the same seed ends (DESIGN.md §maskidx sweep).
-        None keeps the loop above exactly as it is; `maskidx` is then unused.
-        `target_sweep` (EXTENSION, attack_type="TMA" only): a list of (maskidx list, target action value) pairs optimises one TMA patch per pair in
-        ONE loop the same way — group p ends where a standalone TMA run with maskidx = maskidx_p, target_action = target_p and the same seed ends
-        (DESIGN.md §maskidx sweep); `maskidx` and `target_action` are then unused. None: no target sweep.
-        `upa_sweep` (EXTENSION, attack_type="UPA" only): a list of (alpha, belta) pairs optimises one UPA patch per pair in ONE loop the same way —
-        group p ends where a standalone UPA run with alpha = alpha_p, belta = belta_p and the same seed ends (DESIGN.md §maskidx sweep); `alpha` and
-        `belta` are then unused. None: no UPA sweep."""
+        `maskidx_sweep`, `target_sweep` (attack_type="TMA" only), `upa_sweep` (attack_type="UPA" only) are EXTENSIONS, at most one per run (sweep.KINDS):
+        a list of maskidx lists / (maskidx list, target action value) pairs / (alpha, belta) pairs optimises one patch per entry in ONE loop — every
+        group sees the same frames, draws and schedule, and group p ends where a standalone run with entry p in place of `maskidx` / `maskidx` and
+        `target_action` / `alpha` and `belta` (then unused) and the same seed ends (DESIGN.md §maskidx sweep). None keeps the loop as it is."""
         rank, world, local = vdist.env_rank_world()
         if device is None:
             device = vdist.local_device()
@@ -156,86 +85,15 @@ class OpenVLAAttacker(AttackBase):
         if attack_type not in ("UADA", "UPA", "TMA"):
             raise ValueError(f"attack_type must be UADA, UPA or TMA, got {attack_type!r}")
         self.attack_type, self.alpha, self.belta, self.target_action = attack_type, alpha, belta, target_action
-        self.maskidx_sweep = None
-        if maskidx_sweep is not None:
-            self.maskidx_sweep = self._check_sweep(maskidx_sweep)
-        self.target_sweep = None
-        if target_sweep is not None:
-            self.target_sweep = self._check_target_sweep(target_sweep, maskidx_sweep)
-        self.upa_sweep = None
-        if upa_sweep is not None:
-            self.upa_sweep = self._check_upa_sweep(upa_sweep, maskidx_sweep, target_sweep)
-
-    def _check_sweep(self, sweep):
-        """Refuses (ValueError naming the limit) what the batched sweep does not cover."""
-        sweep = [[int(v) for v in m] for m in sweep]
-        if not sweep or any(len(m) == 0 for m in sweep):
-            raise ValueError("maskidx_sweep: needs at least one group, and every group at least one maskidx")
-        if any(v < 0 or v > 6 or len(set(m)) != len(m) for m in sweep for v in m):
-            raise ValueError(f"maskidx_sweep: every maskidx is a distinct DoF index 0..6, got {sweep}")
-        if len({sweep_tag(m) for m in sweep}) != len(sweep):
-            raise ValueError(f"maskidx_sweep: groups must be distinct, got {sweep}")
-        if self.attack_type != "UADA":
-            raise ValueError(f"maskidx_sweep: UADA only (got attack_type={self.attack_type!r}; UPA / TMA sweeps are not implemented)")
-        if self.randomPatchTransform.resize_patch:
-            raise ValueError("maskidx_sweep: resize_patch=True is not supported (one patch size per group only)")
-        if not self.fused_ddp_available():
-            raise ValueError("maskidx_sweep: needs the fused path (a model that exposes its patch-embed weights and hidden rows, VAA_FUSED_EPILOGUE != 0)")
-        if len(sweep) * self.bs > SWEEP_MAX_IMAGES:
-            raise ValueError(f"maskidx_sweep: {len(sweep)} groups x bs {self.bs} = {len(sweep) * self.bs} images per rank exceed the limit of "
-                             f"{SWEEP_MAX_IMAGES} (K2' one partial tile per image)")
-        rows = sweep_rows(self.bs, sweep)
-        if rows > SWEEP_MAX_ROWS:
-            raise ValueError(f"maskidx_sweep: {rows} labelled rows per rank (sum of bs x (|maskidx| + 1)) exceed the limit of {SWEEP_MAX_ROWS} "
-                             f"(K3s covers at most {SWEEP_MAX_ROWS} rows)")
-        return sweep
-
-    def _check_target_sweep(self, sweep, maskidx_sweep):
-        """Refuses (ValueError naming the limit) what the batched target sweep does not cover."""
-        if maskidx_sweep is not None:
-            raise ValueError("target_sweep: cannot be combined with maskidx_sweep (one kind of sweep per run)")
-        sweep = [([int(v) for v in m], float(t)) for m, t in sweep]
-        if not sweep or any(len(m) == 0 for m, _ in sweep):
-            raise ValueError("target_sweep: needs at least one group, and every group at least one maskidx")
-        if any(v < 0 or v > 6 or len(set(m)) != len(m) for m, _ in sweep for v in m):
-            raise ValueError(f"target_sweep: every maskidx is a distinct DoF index 0..6, got {sweep}")
-        if len({target_sweep_tag(m, t) for m, t in sweep}) != len(sweep):
-            raise ValueError(f"target_sweep: groups must be distinct, got {sweep}")
-        if self.attack_type != "TMA":
-            raise ValueError(f"target_sweep: TMA only (got attack_type={self.attack_type!r}; UADA sweeps go through maskidx_sweep, UPA sweeps are not implemented)")
-        if self.randomPatchTransform.resize_patch:
-            raise ValueError("target_sweep: resize_patch=True is not supported (one patch size per group only)")
-        if not self.fused_ddp_available():
-            raise ValueError("target_sweep: needs the fused path (a model that exposes its patch-embed weights and hidden rows, VAA_FUSED_EPILOGUE != 0)")
-        if len(sweep) * self.bs > SWEEP_MAX_IMAGES:
-            raise ValueError(f"target_sweep: {len(sweep)} groups x bs {self.bs} = {len(sweep) * self.bs} images per rank exceed the limit of "
-                             f"{SWEEP_MAX_IMAGES} (K2' one partial tile per image)")
-        return sweep
-
-    def _check_upa_sweep(self, sweep, maskidx_sweep, target_sweep):
-        """Refuses (ValueError naming the limit) what the batched UPA sweep does not cover."""
-        if maskidx_sweep is not None or target_sweep is not None:
-            raise ValueError("upa_sweep: cannot be combined with maskidx_sweep or target_sweep (one kind of sweep per run)")
-        sweep = [(float(a), float(b)) for a, b in sweep]
-        if not sweep:
-            raise ValueError("upa_sweep: needs at least one (alpha, belta) group")
-        if not all(np.isfinite(v) for pair in sweep for v in pair):
-            raise ValueError(f"upa_sweep: every alpha / belta is a finite number, got {sweep}")
-        if len({upa_sweep_tag(a, b) for a, b in sweep}) != len(sweep):
-            raise ValueError(f"upa_sweep: groups must be distinct, got {sweep}")
-        if self.attack_type != "UPA":
-            raise ValueError(f"upa_sweep: UPA only (got attack_type={self.attack_type!r}; UADA sweeps go through maskidx_sweep, TMA sweeps through target_sweep)")
-        if self.randomPatchTransform.resize_patch:
-            raise ValueError("upa_sweep: resize_patch=True is not supported (one patch size per group only)")
-        if not self.fused_ddp_available():
-            raise ValueError("upa_sweep: needs the fused path (a model that exposes its patch-embed weights and hidden rows, VAA_FUSED_EPILOGUE != 0)")
-        if len(sweep) * self.bs > SWEEP_MAX_IMAGES:
-            raise ValueError(f"upa_sweep: {len(sweep)} groups x bs {self.bs} = {len(sweep) * self.bs} images per rank exceed the limit of "
-                             f"{SWEEP_MAX_IMAGES} (K2' one partial tile per image)")
-        if len(sweep) > ops.SEG_UPA_MAX_GROUPS:
-            raise ValueError(f"upa_sweep: {len(sweep)} groups exceed the limit of {ops.SEG_UPA_MAX_GROUPS} (the groups' loss weights travel in K3's "
-                             f"launch arguments)")
-        return sweep
+        # at most one kind of sweep; the parameters are checked in KINDS' order, so a refusal of an earlier one comes first
+        self.sweep_kind = self.sweep_groups = None
+        given = dict(maskidx_sweep=maskidx_sweep, target_sweep=target_sweep, upa_sweep=upa_sweep)
+        for kind in KINDS:
+            groups = given[kind.param]
+            if groups is not None:
+                groups = check_sweep(self, kind, groups)
+                self.sweep_kind, self.sweep_groups = kind, groups
+            setattr(self, kind.param, groups)
 
     def setup(self, rank, world_size):
         vdist.init_process_group(device=self.device if self.device.type == "cuda" else None)
@@ -259,21 +117,14 @@ class OpenVLAAttacker(AttackBase):
             self.cleanup()
 
     def _attack(self, rank, world_size):
-        if self.maskidx_sweep is not None or self.target_sweep is not None or self.upa_sweep is not None:
+        if self.sweep_kind is not None:
             return self._attack_sweep(rank, world_size)
         dev = self.device
-        if rank == 0:
-            patch = torch.rand(self.patch_size).to(dev)  # UADA_ddp.py:140-141
-        else:
-            patch = torch.empty(self.patch_size).to(dev)
-        vdist.broadcast_patch(patch, src=0)  # C1
-        patch.requires_grad_(True)
+        patch = self._initial_patch(rank).requires_grad_(True)
         self.patch = patch
         optimizer = PatchOptimizer(patch, self.lr, "adamW", l1_clip=1e-3 if self.attack_type == "UPA" else 0.0)  # UPA.py:157
         scheduler = CosineWarmupSchedule(optimizer, self.warmup, int(self.num_iter), 0.5)
         if self.attack_type == "TMA":
-            from ..labels import tma_target_tokens
-
             self._tma_target = tma_target_tokens(float(self.target_action) * torch.ones(7).numpy(), self.maskidx, self.action_tokenizer).to(dev)
         sync = vdist.PatchGradSync(patch.numel(), 4, dev)
         pick = torch.tensor([1, 2, 7, 0], dtype=torch.int64, device=dev)  # CE, w^2*MSE, UAD, total of K3's scalars
@@ -305,54 +156,38 @@ class OpenVLAAttacker(AttackBase):
             self._end_outer(i, rank, world_size, scheduler, optimizer, s_sum, device_failure, f"{self.attack_type} (data parallel) outer iteration {i}")
         return patch
 
-    # ---- maskidx sweep: P patches in one loop ----
-    def _attack_sweep(self, rank, world_size):
-        """The loop above for P patch groups at once (UADA, fused path): one [P*bs] step per inner step — K1 tile-major with one patch per group,
-        ONE forward / backward, K3s with the segmented row map, K2' with a partial per image, the segmented epilogue (+ AdamW of every group);
-        at world > 1 ONE all-reduce of [P gradients | P x 4 scalars] and the segmented K4. The RNG streams are consumed as by ONE standalone run:
-        one patch init (every group starts from it), one transform draw per frame and step, shared by the groups.
-        A target sweep (TMA) is the same loop with the groups' target labels and, per step, ONE hipBLASLt head + K3 in LOSS_CE mode over the
-        segmented map (target_sweep_step) in place of K3s. A UPA sweep is that loop again with every group's labels left unmasked, K3 in LOSS_UPA
-        mode with the group's (alpha, belta) (upa_sweep_step) and — the L1 clip needs the whole gradient's norm — the segmented K4 behind the
-        epilogue at every world size."""
-        dev = self.device
-        tma, upa = self.target_sweep is not None, self.upa_sweep is not None
-        sweep = self.target_sweep if tma else (self.upa_sweep if upa else self.maskidx_sweep)
-        P = len(sweep)
-        if upa:
-            self.sweep_tags = [upa_sweep_tag(a, b) for a, b in sweep]
-        elif tma:
-            from ..labels import tma_target_tokens
+    def _initial_patch(self, rank):
+        """UADA_ddp.py:140-141: the patch drawn on rank 0 (ONE torch.rand) and broadcast to every rank (C1)."""
+        patch = (torch.rand if rank == 0 else torch.empty)(self.patch_size).to(self.device)
+        vdist.broadcast_patch(patch, src=0)
+        return patch
 
-            self.sweep_tags = [target_sweep_tag(m, t) for m, t in sweep]
-            self._tma_targets = [tma_target_tokens(float(t) * torch.ones(7).numpy(), m, self.action_tokenizer).to(dev) for m, t in sweep]
-        else:
-            self.sweep_tags = [sweep_tag(m) for m in sweep]
-        what = "TMA target sweep" if tma else ("UPA weight sweep" if upa else "UADA maskidx sweep")
-        if rank == 0:
-            p0 = torch.rand(self.patch_size).to(dev)  # UADA_ddp.py:140-141, drawn once: every group's standalone run draws this patch
-        else:
-            p0 = torch.empty(self.patch_size).to(dev)
-        vdist.broadcast_patch(p0, src=0)
+    # ---- sweeps: P patches in one loop ----
+    def _attack_sweep(self, rank, world_size):
+        """The loop above for the P patch groups of a sweep at once (fused path): one [P*bs] step per inner step (sweep_step) — K1 tile-major with one
+        patch per group, ONE forward / backward, the kind's head with the segmented row map, K2' with a partial per image, the segmented epilogue
+        (+ AdamW of every group); at world > 1, and for a kind that keeps K4 out of the epilogue, ONE all-reduce of [P gradients | P x 4 scalars]
+        and the segmented K4. The RNG streams are consumed as by ONE standalone run: one patch init (every group starts from it), one transform draw
+        per frame and step, shared by the groups. What differs between the kinds is stated in sweep.KINDS."""
+        dev, kind, groups, P = self.device, self.sweep_kind, self.sweep_groups, len(self.sweep_groups)
+        self.sweep_tags = [kind.tag(g) for g in groups]
+        kind.prepare(self, groups)
+        p0 = self._initial_patch(rank)  # drawn once: every group's standalone run draws this patch
         patches = p0.unsqueeze(0).repeat(P, *([1] * p0.dim())).contiguous().requires_grad_(True)
         self.patch = patches
-        optimizer = SweepPatchOptimizer(patches, self.lr, "adamW", l1_clip=1e-3 if upa else 0.0)  # UPA.py:157, per group
+        optimizer = SweepPatchOptimizer(patches, self.lr, "adamW", l1_clip=kind.l1_clip)  # per group
         scheduler = CosineWarmupSchedule(optimizer, self.warmup, int(self.num_iter), 0.5)
         sync = vdist.PatchGradSync(patches.numel(), 4 * P, dev)
         scalars = torch.zeros((P, 8), dtype=torch.float32, device=dev)
-        W = self.vla.lm_head.weight
-        V = int(W.shape[0])
-        w = float(self.MSE_weights)
+        fused_k4 = kind.k4_in_epilogue and world_size == 1  # nothing to exchange: AdamW runs inside the epilogue launch
         self.MSE_Distance_best = {t: 1000000 for t in self.sweep_tags}
-        self.val_CE_loss = {t: [] for t in self.sweep_tags}
-        self.val_MSE_Distance = {t: [] for t in self.sweep_tags}
-        self.val_UAD = {t: [] for t in self.sweep_tags}
+        self.val_CE_loss, self.val_MSE_Distance, self.val_UAD = ({t: [] for t in self.sweep_tags} for _ in range(3))
 
         for i, data in enumerate(self.train_loader):
             if i == self.num_iter:
                 break
             pixel_values, labels, attention_mask, input_ids = to_dev(data, dev)
-            # the batch replicated to P groups ONCE per outer iteration (frames, ids, mask), the labels masked per group, ONE segmented row map
+            # the batch replicated to P groups ONCE per outer iteration (frames, ids, mask), the labels per group, ONE segmented row map
             img = self.randomPatchTransform.stage_images(pixel_values)
             img_all = img.repeat(P, 1, 1, 1).contiguous()
             ids_all = input_ids.repeat(P, 1).contiguous()
@@ -361,28 +196,39 @@ class OpenVLAAttacker(AttackBase):
             row_index = self.vla.label_row_index(labels_all)
             R = int(row_index.numel())
             if R == 0:
-                raise ValueError(f"{what}: no labelled position in the batch")
-            if not tma and not upa and not self._slice_head(R, None, W):
-                raise ValueError(f"maskidx sweep: K3s does not take {R} labelled rows per rank here (limit {SWEEP_MAX_ROWS} rows, bf16 head)")
+                raise ValueError(f"{kind.what}: no labelled position in the batch")
+            if kind.row_limit is not None and not self._slice_head(R, None, self.vla.lm_head.weight):
+                raise ValueError(f"{kind.what}: K3s does not take {R} labelled rows per rank here (limit {kind.row_limit} rows, bf16 head)")
             segmap = ops.LossRowMapSeg(labels_all, P)
             pack = self.vla.make_pack(am_all) if (hasattr(self.vla, "make_pack") and am_all is not None) else None
 
             def step(inner_loop):
                 read = inner_loop == self.innerLoop - 1  # the step whose loss scalars the loop reads (UADA_ddp.py:214-221)
-                if upa:  # the clip keeps K4 out of the epilogue: at world 1 the exchange hands the message back as it is, K4 follows
-                    self.upa_sweep_step(img_all, patches, ids_all, row_index, segmap, pack, sync.buf, scalars, read)
-                    return sync.allreduce_packed
-                upd = optimizer.fused_update_args() if world_size == 1 else None
-                if tma:
-                    self.target_sweep_step(img_all, patches, ids_all, row_index, segmap, pack, sync.buf, scalars, read, upd)
-                else:
-                    self.sweep_step(img_all, patches, ids_all, labels_all, row_index, segmap, pack, w, V, sync.buf, scalars, read, upd)
-                return None if world_size == 1 else sync.allreduce_packed
+                self.sweep_step(img_all, patches, ids_all, row_index, segmap, pack, sync.buf, scalars, read,
+                                optimizer.fused_update_args() if fused_k4 else None)
+                return None if fused_k4 else sync.allreduce_packed  # (world 1: the exchange hands the message back as it is, K4 follows)
 
             s_sum, device_failure = self._inner_loop(optimizer, sync, world_size, step)
             self._end_outer(i, rank, world_size, scheduler, optimizer, s_sum, device_failure,
-                            f"{what} (data parallel) outer iteration {i}", tags=self.sweep_tags)
+                            f"{kind.what} (data parallel) outer iteration {i}", tags=self.sweep_tags)
         return patches
+
+    def sweep_step(self, img_all, patches, input_ids, row_index, segmap, pack, msg, scalars, read, update=None, groups=None):
+        """One inner step of a sweep up to the exchange: K1 (one draw per frame, every group) -> body over P*bs images -> the kind's head over the
+        rows of all groups -> backward, K2' (a partial per image) -> ONE segmented epilogue: msg = [P gradients | P x 4 scalars] on the step whose
+        scalars are `read`, a zero tail on the others (`scalars` [P,8] is then left as it is); `update` = AdamW of every group inside that launch.
+        Returns the full-vocabulary predictions on the `read` step, else None. `groups`: the attacker's `sweep_groups` when None. Per kind:
+          maskidx — K3s with the segmented map (each row normalised by its group's count; K3h behind it when `read`), the epilogue folds K3's
+            statistics per group: tail {CE, w^2*MSE, UAD, total}, `scalars` [P,8] written;
+          target — ONE hipBLASLt head, K3 in LOSS_CE mode (each row normalised by its group's row count, every group folded on its own), ONE
+            dh = g @ W; K3 made the scalars final before the backward, so the epilogue passes them through: tail {CE, 0, UAD, total};
+          UPA — that head with K3 in LOSS_UPA mode (every group's batch means and (alpha, belta) its own), ONE dh = g_slice @ W[31744:32000]: tail
+            {CE, w^2*MSE, UAD, total}. K4 is never fused (`update` None): the caller runs the segmented K4 with the L1 clip on the exchanged message."""
+        sink = {}
+        P = int(patches.shape[0])
+        pe = self.randomPatchTransform.apply_sweep_batch(img_all, patches, self.mean, self.std, self.geometry, sink)
+        h = self.vla.hidden_rows(input_ids, None, row_index, patch_embeds=pe, pack=pack)
+        return self.sweep_kind.head(self, h, segmap, self.sweep_groups if groups is None else groups, P, read, sink, msg, scalars, update)
 
     def _inner_loop(self, optimizer, sync, world_size, step):
         """The inner steps of one outer iteration (both loops above). `step(inner_loop)` runs this rank's step up to the exchange and returns the
@@ -443,69 +289,14 @@ class OpenVLAAttacker(AttackBase):
         if i % self.val_every == 0:
             (self.validate if tags is None else self.validate_sweep)(i, optimizer.patch, rank)
 
-    def sweep_step(self, img_all, patches, input_ids, labels_all, row_index, segmap, pack, w, V, msg, scalars, full_ce, update=None):
-        """One inner step of the sweep up to the exchange: K1 (one draw per frame, every group) -> body over P*bs images -> K3s (segmented map: each
-        row normalised by its group's count; K3h behind it when `full_ce`) -> K2' (a partial per image) -> ONE segmented epilogue: msg = [P gradients
-        | P x {CE, w^2*MSE, UAD, total}] (zero tail unless `full_ce`), scalars [P,8] folded per group; `update` = AdamW of every group inside it."""
-        sink = {}
-        pe = self.randomPatchTransform.apply_sweep_batch(img_all, patches, self.mean, self.std, self.geometry, sink)
-        h = self.vla.hidden_rows(input_ids, None, row_index, patch_embeds=pe, pack=pack)
-        return self.slice_step_tail(h, segmap, w, V, sink, msg, scalars, full_ce, update, P=int(patches.shape[0]))
-
-    def target_sweep_step(self, img_all, patches, input_ids, row_index, segmap, pack, msg, scalars, read, update=None):
-        """One inner step of the target sweep up to the exchange: K1 (one draw per frame, every group) -> body over P*bs images -> ONE hipBLASLt head
-        over the rows of all groups -> K3 in LOSS_CE mode with the segmented map (each row normalised by its group's row count, every group folded on
-        its own) -> ONE dh = g @ W, backward, K2' (a partial per image) -> ONE segmented epilogue in its pass-through form: msg = [P gradients |
-        P x {CE, 0, UAD, total}] on the step whose scalars are `read` (K3 made them final before the backward), a zero tail on the others (`scalars`
-        [P,8] is then left as it is); `update` = AdamW of every group inside the launch."""
-        sink = {}
-        P = int(patches.shape[0])
-        pe = self.randomPatchTransform.apply_sweep_batch(img_all, patches, self.mean, self.std, self.geometry, sink)
-        h = self.vla.hidden_rows(input_ids, None, row_index, patch_embeds=pe, pack=pack)
-        total, sc, _, pred_full = ops.HeadLossRowsSeg.apply(h, self.vla.lm_head.weight, segmap, P, 1.0)
-        total.backward()
-        if not read:
-            ops.step_epilogue_seg(sink["partials"], msg, scalars, P, update=update)
-            return None
-        ops.step_epilogue_seg_tail(sink["partials"], msg, sc, P, update=update)
-        return pred_full
-
-    def upa_sweep_step(self, img_all, patches, input_ids, row_index, segmap, pack, msg, scalars, read, pairs=None):
-        """One inner step of the UPA sweep up to the exchange: K1 (one draw per frame, every group) -> body over P*bs images -> ONE hipBLASLt head
-        over the rows of all groups -> K3 in LOSS_UPA mode with the segmented map (every group's batch means and (alpha, belta) its own) -> ONE
-        dh = g_slice @ W[31744:32000], backward, K2' (a partial per image) -> ONE segmented epilogue in its pass-through form: msg = [P gradients |
-        P x {CE, w^2*MSE, UAD, total}] on the step whose scalars are `read`, a zero tail on the others (`scalars` [P,8] is then left as it is). K4
-        is never fused here: the caller runs the segmented K4 with the L1 clip on the (all-reduced) message. `pairs`: the groups' (alpha, belta), the
-        attacker's `upa_sweep` when None."""
-        sink = {}
-        P = int(patches.shape[0])
-        pe = self.randomPatchTransform.apply_sweep_batch(img_all, patches, self.mean, self.std, self.geometry, sink)
-        h = self.vla.hidden_rows(input_ids, None, row_index, patch_embeds=pe, pack=pack)
-        total, sc, _, pred_full = ops.HeadLossRowsSegUpa.apply(h, self.vla.lm_head.weight, segmap, P, self.upa_sweep if pairs is None else pairs,
-                                                              float(self.MSE_weights), 1.0)
-        total.backward()
-        if not read:
-            ops.step_epilogue_seg(sink["partials"], msg, scalars, P)
-            return None
-        ops.step_epilogue_seg_tail(sink["partials"], msg, sc, P)
-        return pred_full
-
     def _sweep_group_labels(self, labels, g):
-        """Group g's labels of a sweep (a new tensor): masked with its maskidx (UADA_ddp.py:89-97), its TMA target labels (TMA.py:124-129), or —
-        UPA reverse_direction — left unmasked (UPA.py:127-129)."""
-        if self.upa_sweep is not None:
-            return labels.clone()
-        if self.target_sweep is not None:
-            from ..labels import tma_target_labels
-
-            return tma_target_labels(labels, self._tma_targets[g])
-        return self.mask_labels(labels.clone(), self.maskidx_sweep[g])
+        """Group g's labels of a sweep (a new tensor): masked with its maskidx, its TMA target labels, or left unmasked — the kind's."""
+        return self.sweep_kind.group_labels(self, labels, g)
 
     def validate_sweep(self, i, patches, rank):
         """validate() per group: every validation batch is drawn ONCE (the RNG consumption of one standalone pass) and evaluated with each group's
         patch and labels; per group the averages, the AVG all-reduces, best-patch selection and the files under save_dir/<group tag>/."""
-        tma, upa = self.target_sweep is not None, self.upa_sweep is not None
-        mode = ops.LOSS_CE if tma else (ops.LOSS_UPA if upa else ops.LOSS_UADA_DDP)
+        kind = self.sweep_kind
         rbs = [ValReadback(self.val_batches, self.device) for _ in self.sweep_tags]
         last_images = [None] * len(rbs)
         ph, pw = int(patches.shape[2]), int(patches.shape[3])
@@ -520,14 +311,13 @@ class OpenVLAAttacker(AttackBase):
                     modified = self.randomPatchTransform.apply_random_patch_batch(img, patches[g].detach(), mean=self.mean, std=self.std,
                                                                                    geometry=self.geometry, draws=draws)
                     lab = self._sweep_group_labels(labels, g)
-                    ab = dict(alpha=self.upa_sweep[g][0], beta=self.upa_sweep[g][1]) if upa else {}
-                    _, sc, _ = self.model_loss(input_ids, attention_mask, modified, lab, mode, w=float(self.MSE_weights), need_grad=False, **ab)
+                    _, sc, _ = self.model_loss(input_ids, attention_mask, modified, lab, kind.loss_mode, w=float(self.MSE_weights), need_grad=False,
+                                               **kind.loss_args(self.sweep_groups[g]))
                     rbs[g].add(sc)
                     last_images[g] = modified
         self.last_val_log = {}
         for g, tag in enumerate(self.sweep_tags):
-            # selection metric: MSE distance (UADA) or the attack loss (TMA, UPA), as validate() picks it
-            self.last_val_log[tag] = self._val_record(i, rank, rbs[g].read()[0], 0 if (tma or upa) else 2, patches[g], last_images[g], tag)
+            self.last_val_log[tag] = self._val_record(i, rank, rbs[g].read()[0], kind.select_metric, patches[g], last_images[g], tag)
 
     def _loss_mode(self):
         return {"UADA": ops.LOSS_UADA_DDP, "UPA": ops.LOSS_UPA, "TMA": ops.LOSS_CE}[self.attack_type]
@@ -536,8 +326,6 @@ class OpenVLAAttacker(AttackBase):
         if self.attack_type == "UADA":
             return self.mask_labels(labels, self.maskidx)
         if self.attack_type == "TMA":
-            from ..labels import tma_target_labels
-
             return tma_target_labels(labels, self._tma_target)
         return labels  # UPA reverse_direction: labels stay unmasked (UPA.py:127-129)
 

@@ -625,64 +625,53 @@ def loss_rows_fwd_bwd(logits, rowmap: LossRowMap, mode: int, w: float = 5.0, alp
     return scalars, pred, pred_full, (grad if want_grad else None)
 
 
-def loss_rows_fwd_bwd_seg(logits, rowmap, P: int, mode: int = LOSS_CE, w: float = 5.0, alpha: float = 0.8, beta: float = 0.2, scale: float = 1.0,
-                          want_grad: bool = True, want_pred: bool = True, grad=None):
-    """K3 in LOSS_CE mode on logits [R,V] of P groups (vaa_loss_rows_fwd_bwd_seg; `rowmap` a LossRowMapSeg of P groups, or a LossRowMap with P = 1):
-    every row's gradient is normalised by its group's row count, every group folded on its own. Returns (scalars f32 [P,8], pred_slice, pred_full
-    i32 [B,L-1] | None (group g's images at rows g*B/P ..), grad [R,V] | None): per group the bits of loss_rows_fwd_bwd on the group's rows alone."""
+def _loss_rows_seg(name, logits, rowmap, P, grad_cols, want_grad, want_pred, grad, call):
+    """The body of the segmented K3 calls (vaa_<name>): logits [R,V] of P groups, `rowmap` a LossRowMapSeg of P groups or a LossRowMap with P = 1,
+    a gradient of `grad_cols` columns per row (None: full rows). `call(lib, front, outs, tail)` places the entry point's own arguments between the shared ones.
+    Returns (scalars f32 [P,8], pred_slice, pred_full i32 [B,L-1] | None (group g's images at rows g*B/P ..), grad | None)."""
     dt = _dtype_code(logits)
     if logits.dim() != 2:
         raise _lib.VaaError(f"logits: expected [R,V], got {tuple(logits.shape)}")
     R, V = int(logits.shape[0]), int(logits.shape[1])
-    P = int(P)
-    B, Lt = rowmap.B, rowmap.L
+    B, Lt, grad_cols = rowmap.B, rowmap.L, grad_cols or V
     if getattr(rowmap, "P", 1) != P:
-        raise _lib.VaaError(f"loss_rows_fwd_bwd_seg: the row map holds {getattr(rowmap, 'P', 1)} groups, the call states {P}")
+        raise _lib.VaaError(f"{name}: the row map holds {getattr(rowmap, 'P', 1)} groups, the call states {P}")
     L = _lib.lib()
     ws = _workspace(logits.device, max(L.vaa_loss_rows_ws_bytes(R), 256), "k3")
     scalars = torch.empty((P, 8), dtype=torch.float32, device=logits.device)
     pred, pred_full = _pred_maps(B, Lt, logits.device, want_pred)
     if want_grad and grad is None:
-        grad = torch.empty((R, V), dtype=logits.dtype, device=logits.device)
-    with _timed("K3_loss_rows_fwd_bwd_seg", B=B, L=Lt, V=V, dtype=str(logits.dtype), rows=R, P=P):
-        rc = L.vaa_loss_rows_fwd_bwd_seg(logits.data_ptr(), dt, rowmap.buf.data_ptr(), R, B, Lt, V, P, int(mode), _loss_params(w, alpha, beta, scale),
-                                         scalars.data_ptr(), _ptr(pred), _ptr(pred_full), grad.data_ptr() if want_grad else None, GRAD_FULL,
-                                         ws.data_ptr(), ws.numel(), _stream())
-    _lib.check(rc, "vaa_loss_rows_fwd_bwd_seg")
+        grad = torch.empty((R, grad_cols), dtype=logits.dtype, device=logits.device)
+    elif want_grad:
+        _need(grad, logits.dtype, "grad", (R, grad_cols))
+    with _timed("K3_" + name, B=B, L=Lt, V=V, dtype=str(logits.dtype), rows=R, P=P):
+        rc = call(L, (logits.data_ptr(), dt, rowmap.buf.data_ptr(), R, B, Lt, V, P),
+                  (scalars.data_ptr(), _ptr(pred), _ptr(pred_full), grad.data_ptr() if want_grad else None), (ws.data_ptr(), ws.numel(), _stream()))
+    _lib.check(rc, "vaa_" + name)
     return scalars, pred, pred_full, (grad if want_grad else None)
+
+
+def loss_rows_fwd_bwd_seg(logits, rowmap, P: int, mode: int = LOSS_CE, w: float = 5.0, alpha: float = 0.8, beta: float = 0.2, scale: float = 1.0,
+                          want_grad: bool = True, want_pred: bool = True, grad=None):
+    """K3 in LOSS_CE mode on logits [R,V] of P groups (vaa_loss_rows_fwd_bwd_seg): every row's gradient is normalised by its group's row count, every
+    group folded on its own. Returns _loss_rows_seg's tuple with grad [R,V]: per group the bits of loss_rows_fwd_bwd on the group's rows alone."""
+    params = _loss_params(w, alpha, beta, scale)
+    return _loss_rows_seg("loss_rows_fwd_bwd_seg", logits, rowmap, int(P), None, want_grad, want_pred, grad,
+                          lambda L, front, outs, tail: L.vaa_loss_rows_fwd_bwd_seg(*front, int(mode), params, *outs, GRAD_FULL, *tail))
 
 
 def loss_rows_fwd_bwd_seg_upa(logits, rowmap, P: int, pairs, w: float = 5.0, scale: float = 1.0, want_grad: bool = True, want_pred: bool = True,
                               grad=None):
-    """K3 in LOSS_UPA mode on logits [R,V] of P groups with one (alpha, beta) pair each (vaa_loss_rows_fwd_bwd_seg_upa; `rowmap` a LossRowMapSeg of
-    P groups, or a LossRowMap with P = 1; `pairs` = P (alpha, beta) tuples): UPA's batch means are folded per group. Returns (scalars f32 [P,8],
-    pred_slice, pred_full i32 [B,L-1] | None (group g's images at rows g*B/P ..), grad_slice [R,256] | None): per group the bits of
+    """K3 in LOSS_UPA mode on logits [R,V] of P groups with one (alpha, beta) pair each (vaa_loss_rows_fwd_bwd_seg_upa; `pairs` = P (alpha, beta)
+    tuples): UPA's batch means are folded per group. Returns _loss_rows_seg's tuple with grad_slice [R,256]: per group the bits of
     loss_rows_fwd_bwd(LOSS_UPA, GRAD_SLICE) on the group's rows alone with its pair."""
-    dt = _dtype_code(logits)
-    if logits.dim() != 2:
-        raise _lib.VaaError(f"logits: expected [R,V], got {tuple(logits.shape)}")
-    R, V = int(logits.shape[0]), int(logits.shape[1])
     P = int(P)
-    B, Lt = rowmap.B, rowmap.L
-    if getattr(rowmap, "P", 1) != P:
-        raise _lib.VaaError(f"loss_rows_fwd_bwd_seg_upa: the row map holds {getattr(rowmap, 'P', 1)} groups, the call states {P}")
     pairs = [(float(a), float(b)) for a, b in pairs]
     if len(pairs) != P:
         raise _lib.VaaError(f"loss_rows_fwd_bwd_seg_upa: {len(pairs)} (alpha, beta) pairs for {P} groups")
-    L = _lib.lib()
-    ws = _workspace(logits.device, max(L.vaa_loss_rows_ws_bytes(R), 256), "k3")
-    scalars = torch.empty((P, 8), dtype=torch.float32, device=logits.device)
-    pred, pred_full = _pred_maps(B, Lt, logits.device, want_pred)
-    if want_grad and grad is None:
-        grad = torch.empty((R, N_ACTION), dtype=logits.dtype, device=logits.device)
-    if want_grad:
-        _need(grad, logits.dtype, "grad", (R, N_ACTION))
     params = _lib.f32x([x for a, b in pairs for x in (w, a, b, scale)])
-    with _timed("K3_loss_rows_fwd_bwd_seg_upa", B=B, L=Lt, V=V, dtype=str(logits.dtype), rows=R, P=P):
-        rc = L.vaa_loss_rows_fwd_bwd_seg_upa(logits.data_ptr(), dt, rowmap.buf.data_ptr(), R, B, Lt, V, P, params, scalars.data_ptr(), _ptr(pred),
-                                             _ptr(pred_full), grad.data_ptr() if want_grad else None, ws.data_ptr(), ws.numel(), _stream())
-    _lib.check(rc, "vaa_loss_rows_fwd_bwd_seg_upa")
-    return scalars, pred, pred_full, (grad if want_grad else None)
+    return _loss_rows_seg("loss_rows_fwd_bwd_seg_upa", logits, rowmap, P, N_ACTION, want_grad, want_pred, grad,
+                          lambda L, front, outs, tail: L.vaa_loss_rows_fwd_bwd_seg_upa(*front, params, *outs, *tail))
 
 
 def loss_rows_stats(logits, rowmap: LossRowMap, mode: int, w: float = 5.0, alpha: float = 0.8, beta: float = 0.2, scale: float = 1.0, grad=None):
@@ -941,33 +930,23 @@ def _head_seg_forward(ctx, hidden, weight, k3):
 
 
 class HeadLossRowsSeg(torch.autograd.Function):
-    """HeadLossRows for a target sweep (LOSS_CE, P groups): ONE hipBLASLt head over the rows of all groups, K3 with the segmented row map
-    (loss_rows_fwd_bwd_seg), ONE dh = g @ W. Returns (total = sum of the groups' totals — the groups share no parameter, so every patch gets its
-    own group's gradient —, scalars f32 [P,8], pred_slice, pred_full)."""
+    """HeadLossRows for the sweeps on the GEMM head (P groups): ONE hipBLASLt head over the rows of all groups, K3 with the segmented row map, ONE
+    head backward. `pairs` None (a target sweep): LOSS_CE (loss_rows_fwd_bwd_seg), full-row gradient, dh = g @ W. `pairs` = the groups'
+    (alpha, beta) (a UPA sweep): LOSS_UPA with `w` (loss_rows_fwd_bwd_seg_upa), dh = g_slice [R,256] @ W[31744:32000] — HeadLossRows' 256-column
+    contraction. Returns (total = sum of the groups' totals — the groups share no parameter, so every patch gets its own group's gradient —,
+    scalars f32 [P,8], pred_slice, pred_full)."""
 
     @staticmethod
-    def forward(ctx, hidden, weight, rowmap, P, scale):
+    def forward(ctx, hidden, weight, rowmap, P, pairs, w, scale):
+        ctx.sliced = pairs is not None
+        if ctx.sliced:
+            return _head_seg_forward(ctx, hidden, weight, lambda z: loss_rows_fwd_bwd_seg_upa(z, rowmap, P, pairs, w=w, scale=scale, want_grad=True))
         return _head_seg_forward(ctx, hidden, weight, lambda z: loss_rows_fwd_bwd_seg(z, rowmap, P, LOSS_CE, scale=scale, want_grad=True))
 
     @staticmethod
     def backward(ctx, gtotal, _gs, _gp, _gf):
         g, weight = ctx.saved_tensors
-        return _loss_backward(g, gtotal, 5, weight)
-
-
-class HeadLossRowsSegUpa(torch.autograd.Function):
-    """HeadLossRowsSeg for a UPA sweep (LOSS_UPA, P groups with one (alpha, beta) pair each): ONE hipBLASLt head over the rows of all groups, K3 with
-    the segmented row map (loss_rows_fwd_bwd_seg_upa), ONE dh = g_slice [R,256] @ W[31744:32000] — HeadLossRows' 256-column contraction. Returns
-    (total = sum of the groups' totals, scalars f32 [P,8], pred_slice, pred_full)."""
-
-    @staticmethod
-    def forward(ctx, hidden, weight, rowmap, P, pairs, w, scale):
-        return _head_seg_forward(ctx, hidden, weight, lambda z: loss_rows_fwd_bwd_seg_upa(z, rowmap, P, pairs, w=w, scale=scale, want_grad=True))
-
-    @staticmethod
-    def backward(ctx, gtotal, _gs, _gp, _gf):
-        g, weight = ctx.saved_tensors
-        return _loss_backward(g, gtotal, 7, weight[ACTION_LO : ACTION_LO + N_ACTION])
+        return _loss_backward(g, gtotal, 7, weight[ACTION_LO : ACTION_LO + N_ACTION] if ctx.sliced else weight)
 
 
 class HeadLossRowsFused(torch.autograd.Function):

@@ -12,9 +12,9 @@ import torch
 from conftest import GOLDEN
 from oracle import c_oracle
 from roboticattack_amd import synthetic
+from sweep_harness import DEV, env, run, spawn2, worker_env
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 V = 32064
 SWEEP = [[0], [0, 1], [0, 1, 2, 3, 4, 5, 6]]
 
@@ -178,85 +178,17 @@ def test_unsegmented_map_through_new_entry_points_gives_old_bits(ops):
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # the loop
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-class _Fresh:
-    def __init__(self, seeds, b, kind="smooth"):
-        self.seeds, self.b, self.kind = seeds, b, kind
-
-    def __iter__(self):
-        for s in self.seeds:
-            yield synthetic.synth_batch(s, self.b, self.kind)
-
-
-def _seed():
-    import random
-
-    random.seed(42)
-    np.random.seed(42)
-    torch.manual_seed(42)
-
-
-def _run(d, save_dir, maskidx=None, sweep=None, rank=0, world=1, nval=None):
-    """One product run of the data-parallel loop on the golden's setup; returns (per-step patches [steps, P, ...], host logs, attacker, kernel names)."""
-    from roboticattack_amd import ops
-    from roboticattack_amd.attack import uada_ddp
-    from roboticattack_amd.surrogate import SurrogateHeadVLA
-
-    n_it, inner, bs = int(d["num_iter"]), int(d["inner"]), int(d["bs"])
-    nval = int(d["val_batches"]) if nval is None else nval
-    snaps, logs = [], []
-
-    class Att(uada_ddp.OpenVLAAttacker):
-        val_batches = 100
-
-        def fused_ddp_step(self, pixel_values, patch, *a, **k):
-            r = super().fused_ddp_step(pixel_values, patch, *a, **k)
-            if world == 1:
-                snaps.append(patch.detach().cpu().numpy().copy()[None])
-            return r
-
-        def sweep_step(self, img, patches, *a, **k):
-            r = super().sweep_step(img, patches, *a, **k)
-            if world == 1:
-                snaps.append(patches.detach().cpu().numpy().copy())
-            return r
-
-        def assert_finite_state(self, patch, optimizer, host, where, **kw):
-            if world > 1:
-                snaps.append(patch.detach().cpu().numpy().copy().reshape((-1,) + tuple(self.patch_size)))
-            logs.append(np.array(host, dtype=np.float64).copy())
-            return super().assert_finite_state(patch, optimizer, host, where, **kw)
-
-    att = Att(vla_path="x", dataset_name="synthetic", save_dir=save_dir, patch_size=[3, 50, 50], lr=float(d["lr"]), bs=bs, warmup=int(d["warmup"]),
-              num_iter=n_it, maskidx=maskidx if maskidx is not None else [int(v) for v in d["maskidx"]], innerLoop=inner, geometry=True, use_wandb=False,
-              MSE_weights=int(d["MSE_weights"]), device=torch.device(DEV), maskidx_sweep=sweep,
-              model_factory=lambda path, dev: SurrogateHeadVLA(seed=int(d["model_seed"])).to(dev),
-              dataset_factory=lambda name, b, r, w: (_Fresh([int(d["train_seed0"]) + w * i + r for i in range(n_it)], bs),
-                                                     _Fresh([int(d["val_seed0"]) + w * i + r for i in range(nval)], bs)))
-    _seed()
-    ops.prof_start(8192)
-    att.attack(rank, world)
-    names = [nm for nm, _ in ops.prof_collect()]
-    return np.stack(snaps), np.stack(logs), att, names
-
-
-def _env(monkeypatch):
-    import socket
-
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    for k, v in dict(RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port)).items():
-        monkeypatch.setenv(k, v)
-    for k in ("VAA_FULL_CE_EVERY_STEP", "VAA_HEAD_EVERY_STEP"):
-        monkeypatch.delenv(k, raising=False)
+def _run(d, save_dir, maskidx=None, sweep=None, **kw):
+    """One product run of the data-parallel UADA loop on the golden's setup (sweep_harness.run); returns (per-step patches [steps, P, ...], host
+    logs, attacker, kernel names of the training steps)."""
+    return run(d, save_dir, maskidx=maskidx if maskidx is not None else [int(v) for v in d["maskidx"]], maskidx_sweep=sweep, **kw)[:4]
 
 
 def test_sweep_trajectory_vs_reference_loop_and_standalone_runs(tmp_path, monkeypatch):
     """maskidx_sweep=[[0,1], [0], [0,1,2]] over the golden setup of test_ddp_trajectory_k3s_vs_reference_loop (traj_ddp_k3s.npz, SurrogateHeadVLA,
     bs 3 per group): group 0 reproduces the reference loop's trajectory, saved patch, train log and validation averages; groups 1 and 2 their
     standalone product runs; K3s runs once per training step; a one-group sweep is bitwise the existing loop."""
-    _env(monkeypatch)
+    env(monkeypatch)
     d = np.load(os.path.join(GOLDEN, "traj_ddp_k3s.npz"))
     n_it, inner = int(d["num_iter"]), int(d["inner"])
     sweep = [[0, 1], [0], [0, 1, 2]]
@@ -301,46 +233,20 @@ def test_sweep_trajectory_vs_reference_loop_and_standalone_runs(tmp_path, monkey
 
 
 def _sweep2_worker(rank, world, port, out_dir, golden_path):
-    import sys
-
-    from conftest import ROOT
-
-    sys.path.insert(0, ROOT)
-    os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), VAA_DIST_BACKEND="gloo")
-    for k in ("VAA_FULL_CE_EVERY_STEP", "VAA_HEAD_EVERY_STEP"):
-        os.environ.pop(k, None)
-    from roboticattack_amd import optim
-
+    worker_env(rank, world, port)
     d = np.load(golden_path)
-    snaps = []
-    orig = optim.SweepPatchOptimizer.step
-
-    def rec(self, *a, **k):
-        r = orig(self, *a, **k)
-        snaps.append(self.patch.detach().cpu().numpy().copy())
-        return r
-
-    optim.SweepPatchOptimizer.step = rec
-    _, logs, att, names = _run(d, os.path.join(out_dir, f"rank{rank}"), sweep=[[0, 1], [0, 1, 2]], rank=rank, world=world)
-    np.savez(os.path.join(out_dir, f"sweep_r{rank}.npz"), snaps=np.stack(snaps), logs=logs, n_slice=sum("head_slice_kernel" in n for n in names),
+    snaps, logs, att, names = _run(d, os.path.join(out_dir, f"rank{rank}"), sweep=[[0, 1], [0, 1, 2]], rank=rank, world=world)  # snaps: behind every K4
+    np.savez(os.path.join(out_dir, f"sweep_r{rank}.npz"), snaps=snaps, logs=logs, n_slice=sum("head_slice_kernel" in n for n in names),
              val=np.array([att.val_MSE_Distance["maskidx0-1"][0], att.val_UAD["maskidx0-1"][0]] if rank == 0 else [0.0, 0.0]))
 
 
 def test_sweep_two_ranks_group0_vs_reference_loop(tmp_path):
     """Two ranks (gloo on one GPU, as test_ddp_two_rank_trajectory_k3s_vs_reference_loop) of a sweep [[0,1], [0,1,2]]: ONE all-reduce of
     [2 gradients | 2 x 4 scalars] per step and the segmented K4; group 0 reproduces traj_ddp2_k3s.npz, the ranks are bit-identical."""
-    import socket
-
-    import torch.multiprocessing as mp
-
     golden = os.path.join(GOLDEN, "traj_ddp2_k3s.npz")
     d = np.load(golden)
     n_it, inner = int(d["num_iter"]), int(d["inner"])
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    mp.spawn(_sweep2_worker, args=(2, port, str(tmp_path), golden), nprocs=2, join=True)
+    spawn2(_sweep2_worker, str(tmp_path), golden)
     r0, r1 = np.load(tmp_path / "sweep_r0.npz"), np.load(tmp_path / "sweep_r1.npz")
     assert np.array_equal(r0["snaps"], r1["snaps"]) and np.array_equal(r0["logs"], r1["logs"])
     assert int(r0["n_slice"]) == n_it * inner

@@ -13,9 +13,9 @@ import torch
 from conftest import GOLDEN
 from oracle import c_oracle
 from roboticattack_amd import synthetic
+from sweep_harness import DEV, env, run, spawn2, worker_env
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 V = 32064
 PAIRS = [(0.8, 0.2), (0.2, 0.8), (1.0, 0.0), (0.0, 1.0), (0.5, 0.5), (2.0, 0.05), (0.3, 0.7)]  # far apart, incl. one term switched off
 
@@ -217,106 +217,13 @@ def test_epilogue_tail_then_clipped_k4_is_bitwise_p_standalone_sequences(ops):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-# the loop (the harness of test_gpu_tma_sweep.py::_run, for the UPA attack)
+# the loop
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-class _Fresh:
-    def __init__(self, seeds, b, kind="smooth"):
-        self.seeds, self.b, self.kind = seeds, b, kind
-
-    def __iter__(self):
-        for s in self.seeds:
-            yield synthetic.synth_batch(s, self.b, self.kind)
-
-
-def _seed():
-    import random
-
-    random.seed(42)
-    np.random.seed(42)
-    torch.manual_seed(42)
-
-
-def _run(d, save_dir, pair=(0.8, 0.2), sweep=None, rank=0, world=1):
-    """One product UPA run of the data-parallel loop on the golden's setup (its sizes, seeds and schedule): a standalone run (alpha, belta) or a UPA
-    sweep. Returns (per-step patches [steps, P, 3, 50, 50], host logs per outer iteration, attacker, kernel names of the TRAINING steps, call counts
-    of the training steps)."""
-    from roboticattack_amd import ops, optim
-    from roboticattack_amd.attack import uada_ddp
-    from roboticattack_amd.surrogate import SurrogateHeadVLA
-
-    n_it, inner, bs = int(d["num_iter"]), int(d["inner"]), int(d["bs"])
-    nval = int(d["val_batches"])
-    snaps, logs, names = [], [], []
-    counts = dict(head=0, k3=0, back=0, k4=0)
-
-    class Att(uada_ddp.OpenVLAAttacker):
-        val_batches = 100
-
-        def assert_finite_state(self, patch, optimizer, host, where, **kw):
-            logs.append(np.array(host, dtype=np.float64).copy())
-            return super().assert_finite_state(patch, optimizer, host, where, **kw)
-
-        def _val(self, f, *a):  # the kernel trace covers the training steps only
-            names.extend(nm for nm, _ in ops.prof_collect())
-            r = f(*a)
-            ops.prof_start(8192)
-            return r
-
-        def validate(self, *a):
-            return self._val(super().validate, *a)
-
-        def validate_sweep(self, *a):
-            return self._val(super().validate_sweep, *a)
-
-    orig = optim.PatchOptimizer.step
-    orig_head, orig_k3, orig_back = ops._head_seg_forward, ops.loss_rows_fwd_bwd_seg_upa, ops._loss_backward
-
-    def rec(self, *a, **k):  # UPA's clip keeps K4 a launch of its own in every loop: the patch after every inner step
-        r = orig(self, *a, **k)
-        counts["k4"] += 1
-        snaps.append(self.patch.detach().cpu().numpy().copy().reshape((-1, 3, 50, 50)))
-        return r
-
-    def count(key, f):
-        def g(*a, **k):
-            counts[key] += 1
-            return f(*a, **k)
-
-        return g
-
-    optim.PatchOptimizer.step = rec
-    ops._head_seg_forward, ops.loss_rows_fwd_bwd_seg_upa, ops._loss_backward = count("head", orig_head), count("k3", orig_k3), count("back", orig_back)
-    try:
-        att = Att(vla_path="x", dataset_name="synthetic", save_dir=save_dir, patch_size=[3, 50, 50], lr=float(d["lr"]), bs=bs, warmup=int(d["warmup"]),
-                  num_iter=n_it, maskidx=[0], innerLoop=inner, geometry=True, use_wandb=False, MSE_weights=int(d["MSE_weights"]),
-                  device=torch.device(DEV), attack_type="UPA", alpha=pair[0], belta=pair[1], upa_sweep=sweep,
-                  model_factory=lambda path, dev: SurrogateHeadVLA(seed=int(d["model_seed"])).to(dev),
-                  dataset_factory=lambda name, b, r, w: (_Fresh([int(d["train_seed0"]) + w * i + r for i in range(n_it)], bs),
-                                                         _Fresh([int(d["val_seed0"]) + w * i + r for i in range(nval)], bs)))
-        _seed()
-        ops.prof_start(8192)
-        att.attack(rank, world)
-        names.extend(nm for nm, _ in ops.prof_collect())
-    finally:
-        optim.PatchOptimizer.step = orig
-        ops._head_seg_forward, ops.loss_rows_fwd_bwd_seg_upa, ops._loss_backward = orig_head, orig_k3, orig_back
-    return np.stack(snaps), np.stack(logs), att, names, counts
-
-
-def _env(monkeypatch, gemm_head=False):
-    import socket
-
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    for k, v in dict(RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port)).items():
-        monkeypatch.setenv(k, v)
-    for k in ("VAA_FULL_CE_EVERY_STEP", "VAA_HEAD_EVERY_STEP", "VAA_K3_ONE_PASS", "VAA_K3_CE_FOLD_WG", "VAA_FUSED_EPILOGUE", "VAA_FUSED_EMBED_GRAD",
-              "VAA_FUSED_HEAD"):
-        monkeypatch.delenv(k, raising=False)
-    if gemm_head:
-        monkeypatch.setenv("VAA_FUSED_HEAD", "0")
+def _run(d, save_dir, pair=(0.8, 0.2), sweep=None, **kw):
+    """One product UPA run of the data-parallel loop on the golden's setup (sweep_harness.run): a standalone run (alpha, belta) or a UPA sweep.
+    Returns (per-step patches [steps, P, 3, 50, 50], host logs per outer iteration, attacker, kernel names of the TRAINING steps, call counts of
+    the training steps)."""
+    return run(d, save_dir, "UPA", alpha=pair[0], belta=pair[1], upa_sweep=sweep, **kw)
 
 
 SWEEP3 = [(0.8, 0.2), (0.2, 0.8), (1.0, 0.0)]
@@ -328,7 +235,7 @@ def test_one_group_upa_sweep_is_the_existing_upa_loop_bit_for_bit(tmp_path, monk
     after every inner step (4 outer x 3 inner), the train logs and the validation averages are bit for bit equal — K1 through the per-image
     descriptor pastes the same pixels, K2' leaves the same partial tiles, the pass-through epilogue reproduces K2's final sum and the message, and the
     segmented K4 with the clip is K4's one-group case."""
-    _env(monkeypatch, gemm_head=True)
+    env(monkeypatch, gemm_head=True)
     d = np.load(os.path.join(GOLDEN, "traj_ddp_k3s.npz"))
     n_it, inner = int(d["num_iter"]), int(d["inner"])
     assert n_it >= 3 and inner >= 3
@@ -356,7 +263,7 @@ def test_upa_sweep_trajectory_vs_standalone_upa_runs(tmp_path, monkeypatch):
     for all groups; per-group files exist.
 
     Measured on one MI355X (12 steps): see DESIGN.md section 6a."""
-    _env(monkeypatch)
+    env(monkeypatch)
     d = np.load(os.path.join(GOLDEN, "traj_ddp_k3s.npz"))
     n_it, inner = int(d["num_iter"]), int(d["inner"])
     steps = n_it * inner
@@ -390,14 +297,7 @@ def test_upa_sweep_trajectory_vs_standalone_upa_runs(tmp_path, monkeypatch):
 
 
 def _sweep2_worker(rank, world, port, out_dir, golden_path, group):
-    import sys
-
-    from conftest import ROOT
-
-    sys.path.insert(0, ROOT)
-    os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), VAA_DIST_BACKEND="gloo")
-    for k in ("VAA_FULL_CE_EVERY_STEP", "VAA_HEAD_EVERY_STEP", "VAA_K3_ONE_PASS", "VAA_K3_CE_FOLD_WG", "VAA_FUSED_HEAD"):
-        os.environ.pop(k, None)
+    worker_env(rank, world, port)
     d = np.load(golden_path)
     if group < 0:  # the sweep
         snaps, logs, att, names, counts = _run(d, os.path.join(out_dir, f"rank{rank}"), sweep=SWEEP3, rank=rank, world=world)
@@ -413,19 +313,11 @@ def test_upa_sweep_two_ranks_vs_standalone_two_rank_runs(tmp_path):
     """Two ranks (gloo on one GPU, as test_target_sweep_two_ranks_group0_vs_standalone_two_rank_run) of the three-group UPA sweep: ONE all-reduce of
     [3 gradients | 3 x 4 scalars] per step and the segmented K4 with the clip; the ranks are bit-identical after every step; every group is within
     1e-4 of the standalone two-rank UPA run at its pair, and the groups are at least 10x further apart than the largest deviation."""
-    import socket
-
-    import torch.multiprocessing as mp
-
     golden = os.path.join(GOLDEN, "traj_ddp2_k3s.npz")
     d = np.load(golden)
     n_it, inner = int(d["num_iter"]), int(d["inner"])
     for group in (-1, 0, 1, 2):
-        s = socket.socket()
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-        s.close()
-        mp.spawn(_sweep2_worker, args=(2, port, str(tmp_path), golden, group), nprocs=2, join=True)
+        spawn2(_sweep2_worker, str(tmp_path), golden, group)
     r0, r1 = np.load(tmp_path / "sweep_r0.npz"), np.load(tmp_path / "sweep_r1.npz")
     assert r0["snaps"].shape == (n_it * inner, 3, 3, 50, 50) and r0["logs"].shape == (n_it, 3, 4)
     assert np.array_equal(r0["snaps"], r1["snaps"]) and np.array_equal(r0["logs"], r1["logs"])

@@ -1,27 +1,18 @@
 """CPU tests of the maskidx sweep's host side: CLI parsing, group tags, per-group label masking, the refusals, the C-ABI size rule of the
 segmented row map and the RNG consumption of one sweep step (one draw per frame, shared by every group)."""
-import importlib.util
-import os
 import random
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
 from roboticattack_amd import _lib, synthetic
-from roboticattack_amd.attack import uada_ddp
-
-
-def _wrapper():
-    spec = importlib.util.spec_from_file_location("uada_wrapper_ddp_sweep", os.path.join(ROOT, "VLAAttacker", "UADA_wrapper_ddp.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+from roboticattack_amd.attack import sweep, uada_ddp
+from sweep_harness import attacker, fused, wrapper
 
 
 def test_cli_parses_the_sweep():
-    w = _wrapper()
+    w = wrapper("uada_wrapper_ddp_sweep")
     assert w.arg_parser(["--maskidx_sweep", "0;0,1,2"]).maskidx_sweep == [[0], [0, 1, 2]]
     assert w.arg_parser(["--maskidx_sweep", "0;0,1,2,3,4,5,6"]).maskidx_sweep == [[0], [0, 1, 2, 3, 4, 5, 6]]
     assert w.arg_parser([]).maskidx_sweep is None  # default: no sweep, today's loop
@@ -46,45 +37,52 @@ def test_labels_are_masked_per_group():
     assert torch.equal(labels, synthetic.synth_text_batch(3, 4)[1])  # the loader's labels are not touched
 
 
-def _attacker(monkeypatch, tmp_path, model="head", **kw):
-    from roboticattack_amd.surrogate import SurrogateHeadVLA, SurrogateVLA
-
-    for k, v in dict(RANK="0", WORLD_SIZE="1", LOCAL_RANK="0").items():
-        monkeypatch.setenv(k, v)
-    factory = (lambda p, d: SurrogateHeadVLA(seed=1)) if model == "head" else (lambda p, d: SurrogateVLA(seed=1))
-    args = dict(vla_path="x", dataset_name="synthetic", save_dir=str(tmp_path), patch_size=[3, 50, 50], bs=3, use_wandb=False, device="cpu",
-                model_factory=factory, dataset_factory=lambda *a: (None, None))
-    args.update(kw)
-    return uada_ddp.OpenVLAAttacker(**args)
-
-
 def test_refusals_name_their_limit(monkeypatch, tmp_path):
-    monkeypatch.delenv("VAA_FUSED_EPILOGUE", raising=False)
-    monkeypatch.delenv("VAA_FUSED_EMBED_GRAD", raising=False)
-    monkeypatch.setattr(uada_ddp.OpenVLAAttacker, "fused_ddp_available", lambda self: hasattr(self.vla, "hidden_rows")
-                        and hasattr(self.vla, "patch_embed_params") and not self.randomPatchTransform.resize_patch)
-    ok = _attacker(monkeypatch, tmp_path, maskidx_sweep=[[0], [0, 1, 2]])
+    fused(monkeypatch)
+    ok = attacker(monkeypatch, tmp_path, maskidx_sweep=[[0], [0, 1, 2]])
     assert ok.maskidx_sweep == [[0], [0, 1, 2]]
-    assert _attacker(monkeypatch, tmp_path).maskidx_sweep is None  # no sweep requested: the attacker is today's
+    assert attacker(monkeypatch, tmp_path).maskidx_sweep is None  # no sweep requested: the attacker is today's
     with pytest.raises(ValueError, match="UADA only"):
-        _attacker(monkeypatch, tmp_path, attack_type="UPA", maskidx_sweep=[[0]])
+        attacker(monkeypatch, tmp_path, attack_type="UPA", maskidx_sweep=[[0]])
     with pytest.raises(ValueError, match="UADA only"):
-        _attacker(monkeypatch, tmp_path, attack_type="TMA", maskidx_sweep=[[0]])
+        attacker(monkeypatch, tmp_path, attack_type="TMA", maskidx_sweep=[[0]])
     with pytest.raises(ValueError, match="resize_patch"):
-        _attacker(monkeypatch, tmp_path, resize_patch=True, maskidx_sweep=[[0]])
+        attacker(monkeypatch, tmp_path, resize_patch=True, maskidx_sweep=[[0]])
     with pytest.raises(ValueError, match="fused path"):
-        _attacker(monkeypatch, tmp_path, model="plain", maskidx_sweep=[[0]])
+        attacker(monkeypatch, tmp_path, model="plain", maskidx_sweep=[[0]])
     with pytest.raises(ValueError, match="limit of 128"):  # 2 x 20 x 8 = 320 labelled rows
-        _attacker(monkeypatch, tmp_path, bs=20, maskidx_sweep=[[0, 1, 2, 3, 4, 5, 6], [0, 1, 2, 3, 4, 5]])
+        attacker(monkeypatch, tmp_path, bs=20, maskidx_sweep=[[0, 1, 2, 3, 4, 5, 6], [0, 1, 2, 3, 4, 5]])
     with pytest.raises(ValueError, match="144 labelled rows"):  # 16 x 4 + 16 x 5
-        _attacker(monkeypatch, tmp_path, bs=16, maskidx_sweep=[[0, 1, 2], [0, 1, 2, 3]])
-    _attacker(monkeypatch, tmp_path, bs=16, maskidx_sweep=[[0], [0, 1, 2]])  # 32 + 64 = 96 rows: accepted
+        attacker(monkeypatch, tmp_path, bs=16, maskidx_sweep=[[0, 1, 2], [0, 1, 2, 3]])
+    attacker(monkeypatch, tmp_path, bs=16, maskidx_sweep=[[0], [0, 1, 2]])  # 32 + 64 = 96 rows: accepted
     with pytest.raises(ValueError, match="limit of 512"):  # 6 x 100 images
-        _attacker(monkeypatch, tmp_path, bs=100, maskidx_sweep=[[0], [1], [2], [3], [4], [5]])
+        attacker(monkeypatch, tmp_path, bs=100, maskidx_sweep=[[0], [1], [2], [3], [4], [5]])
     with pytest.raises(ValueError, match="distinct"):
-        _attacker(monkeypatch, tmp_path, maskidx_sweep=[[0], [0]])
+        attacker(monkeypatch, tmp_path, maskidx_sweep=[[0], [0]])
     with pytest.raises(ValueError, match="0..6"):
-        _attacker(monkeypatch, tmp_path, maskidx_sweep=[[7]])
+        attacker(monkeypatch, tmp_path, maskidx_sweep=[[7]])
+
+
+def test_every_kind_states_its_own_facts_once(monkeypatch, tmp_path):
+    """Per kind of sweep.KINDS: its parameter alone makes it the attacker's kind, its tags read back as its groups through its own CLI form, and
+    its attack type, clip and selection metric are the standalone mode's (UPA.py:157; validate(): MSE distance for UADA, else the attack loss)."""
+    fused(monkeypatch)
+    given = dict(maskidx_sweep=[[0], (0, 1, 2)], target_sweep=[([0], 0), ((0, 1, 2), -0.5)], upa_sweep=[(0.8, 0.2), [1, 0], (-0.25, 2e-3)])
+    facts = dict(maskidx_sweep=("UADA", 0.0, 2), target_sweep=("TMA", 0.0, 0), upa_sweep=("UPA", 1e-3, 0))
+    # a tag in its kind's CLI form (the fixed prefixes come off, as test_upa_sweep_host.py reads a UPA tag back)
+    cli = dict(maskidx_sweep=lambda t: t[len("maskidx"):].replace("-", ","),
+               target_sweep=lambda t: t[len("maskidx"):].split("-target")[0].replace("-", ",") + ":" + t.split("-target")[1],
+               upa_sweep=lambda t: t[len("alpha"):].replace("-belta", ":"))
+    assert [k.param for k in sweep.KINDS] == list(given) and sweep.KINDS == (sweep.MASKIDX, sweep.TARGET, sweep.UPA)
+    for kind in sweep.KINDS:
+        att = attacker(monkeypatch, tmp_path, attack_type=kind.attack_type, **{kind.param: given[kind.param]})
+        assert att.sweep_kind is kind and att.sweep_groups == getattr(att, kind.param) == kind.normalise(given[kind.param])
+        assert [getattr(att, k.param) for k in sweep.KINDS if k is not kind] == [None, None] and not hasattr(att, "sweep_tags")
+        for group in att.sweep_groups:
+            assert kind.parse(cli[kind.param](kind.tag(group))) == [group], (kind.param, group)
+        assert (kind.attack_type, kind.l1_clip, kind.select_metric) == facts[kind.param]
+    plain = attacker(monkeypatch, tmp_path)
+    assert plain.sweep_kind is None and plain.sweep_groups is None
 
 
 def test_segmented_rowmap_sizes_without_gpu():

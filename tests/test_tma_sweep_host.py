@@ -1,25 +1,15 @@
 """CPU tests of the TMA target sweep's host side: CLI parsing, group tags, per-group target labels, every refusal, the untouched maskidx
 sweep / no-sweep attacker, and the argument checks of the new C-ABI entry points (no kernel is launched)."""
-import importlib.util
-import os
-
 import pytest
 import torch
 
-from conftest import ROOT
 from roboticattack_amd import _lib, synthetic
 from roboticattack_amd.attack import uada_ddp
-
-
-def _wrapper():
-    spec = importlib.util.spec_from_file_location("uada_wrapper_ddp_target_sweep", os.path.join(ROOT, "VLAAttacker", "UADA_wrapper_ddp.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+from sweep_harness import attacker, fused, wrapper
 
 
 def test_cli_parses_the_target_sweep():
-    w = _wrapper()
+    w = wrapper("uada_wrapper_ddp_target_sweep")
     a = w.arg_parser(["--attack", "TMA", "--target_sweep", "0:0;1:0;6:1"])
     assert a.target_sweep == [([0], 0.0), ([1], 0.0), ([6], 1.0)] and a.attack == "TMA"
     assert w.arg_parser(["--target_sweep", "0,1,2:0.25;0,1,2,3,4,5,6:-0.5"]).target_sweep == [([0, 1, 2], 0.25), ([0, 1, 2, 3, 4, 5, 6], -0.5)]
@@ -39,80 +29,61 @@ def test_group_tags_are_equal_for_equal_groups_and_distinct_otherwise():
     assert all(tag(m, t).startswith(uada_ddp.sweep_tag(m) + "-target") for m, t in groups)
 
 
-def _attacker(monkeypatch, tmp_path, model="head", **kw):
-    from roboticattack_amd.surrogate import SurrogateHeadVLA, SurrogateVLA
-
-    for k, v in dict(RANK="0", WORLD_SIZE="1", LOCAL_RANK="0").items():
-        monkeypatch.setenv(k, v)
-    factory = (lambda p, d: SurrogateHeadVLA(seed=1)) if model == "head" else (lambda p, d: SurrogateVLA(seed=1))
-    args = dict(vla_path="x", dataset_name="synthetic", save_dir=str(tmp_path), patch_size=[3, 50, 50], bs=3, use_wandb=False, device="cpu",
-                model_factory=factory, dataset_factory=lambda *a: (None, None))
-    args.update(kw)
-    return uada_ddp.OpenVLAAttacker(**args)
-
-
-def _fused(monkeypatch):
-    monkeypatch.delenv("VAA_FUSED_EPILOGUE", raising=False)
-    monkeypatch.delenv("VAA_FUSED_EMBED_GRAD", raising=False)
-    monkeypatch.setattr(uada_ddp.OpenVLAAttacker, "fused_ddp_available", lambda self: hasattr(self.vla, "hidden_rows")
-                        and hasattr(self.vla, "patch_embed_params") and not self.randomPatchTransform.resize_patch)
-
-
 def test_target_sweep_refusals_name_their_limit(monkeypatch, tmp_path):
-    _fused(monkeypatch)
-    ok = _attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=[([0], 0), ((0, 1, 2), 0.25)])
+    fused(monkeypatch)
+    ok = attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=[([0], 0), ((0, 1, 2), 0.25)])
     assert ok.target_sweep == [([0], 0.0), ([0, 1, 2], 0.25)] and ok.maskidx_sweep is None
     with pytest.raises(ValueError, match="at least one group"):
-        _attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=[])
+        attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=[])
     with pytest.raises(ValueError, match="at least one maskidx"):
-        _attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=[([], 0.0)])
+        attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=[([], 0.0)])
     with pytest.raises(ValueError, match="distinct"):
-        _attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=[([0], 0.0), ([0], 0)])
-    _attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=[([0], 0.0), ([0], 0.5)])  # same maskidx, another target: two groups
+        attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=[([0], 0.0), ([0], 0)])
+    attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=[([0], 0.0), ([0], 0.5)])  # same maskidx, another target: two groups
     with pytest.raises(ValueError, match="0..6"):
-        _attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=[([7], 0.0)])
+        attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=[([7], 0.0)])
     with pytest.raises(ValueError, match="0..6"):
-        _attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=[([1, 1], 0.0)])
+        attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=[([1, 1], 0.0)])
     for other in ("UADA", "UPA"):
         with pytest.raises(ValueError, match="TMA only"):
-            _attacker(monkeypatch, tmp_path, attack_type=other, target_sweep=[([0], 0.0)])
+            attacker(monkeypatch, tmp_path, attack_type=other, target_sweep=[([0], 0.0)])
     with pytest.raises(ValueError, match="resize_patch"):
-        _attacker(monkeypatch, tmp_path, attack_type="TMA", resize_patch=True, target_sweep=[([0], 0.0)])
+        attacker(monkeypatch, tmp_path, attack_type="TMA", resize_patch=True, target_sweep=[([0], 0.0)])
     with pytest.raises(ValueError, match="fused path"):
-        _attacker(monkeypatch, tmp_path, attack_type="TMA", model="plain", target_sweep=[([0], 0.0)])
+        attacker(monkeypatch, tmp_path, attack_type="TMA", model="plain", target_sweep=[([0], 0.0)])
     with pytest.raises(ValueError, match="limit of 512"):  # 6 x 100 images
-        _attacker(monkeypatch, tmp_path, attack_type="TMA", bs=100, target_sweep=[([q], 0.0) for q in range(6)])
-    _attacker(monkeypatch, tmp_path, attack_type="TMA", bs=63, target_sweep=[([0, 1, 2, 3, 4, 5, 6], 0.1 * q) for q in range(8)])  # 504 images, 3528 rows: no row limit behind the GEMM head
+        attacker(monkeypatch, tmp_path, attack_type="TMA", bs=100, target_sweep=[([q], 0.0) for q in range(6)])
+    attacker(monkeypatch, tmp_path, attack_type="TMA", bs=63, target_sweep=[([0, 1, 2, 3, 4, 5, 6], 0.1 * q) for q in range(8)])  # 504 images, 3528 rows: no row limit behind the GEMM head
     with pytest.raises(ValueError, match="maskidx_sweep"):
-        _attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=[([0], 0.0)], maskidx_sweep=[[0]])
+        attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=[([0], 0.0)], maskidx_sweep=[[0]])
     with pytest.raises(ValueError, match="maskidx_sweep"):  # also when the maskidx sweep itself would be accepted
-        _attacker(monkeypatch, tmp_path, attack_type="UADA", target_sweep=[([0], 0.0)], maskidx_sweep=[[0]])
+        attacker(monkeypatch, tmp_path, attack_type="UADA", target_sweep=[([0], 0.0)], maskidx_sweep=[[0]])
 
 
 def test_maskidx_sweep_and_plain_attacker_are_untouched(monkeypatch, tmp_path):
-    _fused(monkeypatch)
+    fused(monkeypatch)
     for other in ("TMA", "UPA"):
         with pytest.raises(ValueError, match="UADA only"):
-            _attacker(monkeypatch, tmp_path, attack_type=other, maskidx_sweep=[[0]])
-    plain = _attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=None, maskidx=[0, 1], target_action=0.25)
+            attacker(monkeypatch, tmp_path, attack_type=other, maskidx_sweep=[[0]])
+    plain = attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=None, maskidx=[0, 1], target_action=0.25)
     assert plain.target_sweep is None and plain.maskidx_sweep is None and plain.maskidx == [0, 1] and plain.target_action == 0.25
     assert not hasattr(plain, "sweep_tags")
-    uada = _attacker(monkeypatch, tmp_path, maskidx_sweep=[[0], [0, 1, 2]])
+    uada = attacker(monkeypatch, tmp_path, maskidx_sweep=[[0], [0, 1, 2]])
     assert uada.maskidx_sweep == [[0], [0, 1, 2]] and uada.target_sweep is None
 
 
 def test_group_labels_are_the_standalone_target_labels(monkeypatch, tmp_path):
     from roboticattack_amd.labels import tma_target_labels, tma_target_tokens
 
-    _fused(monkeypatch)
+    fused(monkeypatch)
     sweep = [([0], 0.0), ([0, 1, 2], 0.25), ([0, 1, 2, 3, 4, 5, 6], -0.5)]
-    att = _attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=sweep)
+    att = attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=sweep)
     att._tma_targets = [tma_target_tokens(float(t) * torch.ones(7).numpy(), m, att.action_tokenizer) for m, t in sweep]
     _, labels, _ = synthetic.synth_text_batch(3, 4)
     keep = labels.clone()
     for g, (m, t) in enumerate(sweep):
         got = att._sweep_group_labels(labels, g)
-        solo = _attacker(monkeypatch, tmp_path, attack_type="TMA", maskidx=m, target_action=t)
+        solo = attacker(monkeypatch, tmp_path, attack_type="TMA", maskidx=m, target_action=t)
         solo._tma_target = tma_target_tokens(float(t) * torch.ones(7).numpy(), m, solo.action_tokenizer)
         assert torch.equal(got, solo._prepare_labels(labels)) and torch.equal(got, tma_target_labels(labels, att._tma_targets[g]))
         assert int((got[:, 1:] != -100).sum()) == 4 * len(m)  # the target vector labels the maskidx DoFs only (EOS is position 7: never in 0..6)

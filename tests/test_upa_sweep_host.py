@@ -1,25 +1,15 @@
 """CPU tests of the UPA weight sweep's host side: CLI parsing, group tags, every refusal, the refusals of the older sweeps, the untouched plain UPA
 attacker, the groups' unmasked labels, and the argument checks of the new C-ABI entry point (no kernel is launched)."""
-import importlib.util
-import os
-
 import pytest
 import torch
 
-from conftest import ROOT
 from roboticattack_amd import _lib, synthetic
 from roboticattack_amd.attack import uada_ddp
-
-
-def _wrapper():
-    spec = importlib.util.spec_from_file_location("uada_wrapper_ddp_upa_sweep", os.path.join(ROOT, "VLAAttacker", "UADA_wrapper_ddp.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+from sweep_harness import attacker, fused, wrapper
 
 
 def test_cli_parses_the_upa_sweep():
-    w = _wrapper()
+    w = wrapper("uada_wrapper_ddp_upa_sweep")
     a = w.arg_parser(["--attack", "UPA", "--upa_sweep", "0.8:0.2;0.5:0.5"])
     assert a.upa_sweep == [(0.8, 0.2), (0.5, 0.5)] and a.attack == "UPA"
     assert w.arg_parser(["--upa_sweep", "1:0; 0:1 ;2e-1:-0.5"]).upa_sweep == [(1.0, 0.0), (0.0, 1.0), (0.2, -0.5)]
@@ -42,79 +32,60 @@ def test_tags_round_trip_and_tell_groups_apart():
         assert uada_ddp.parse_upa_sweep(t[len("alpha"):].replace("-belta", ":")) == [(float(a), float(b))]
 
 
-def _attacker(monkeypatch, tmp_path, model="head", **kw):
-    from roboticattack_amd.surrogate import SurrogateHeadVLA, SurrogateVLA
-
-    for k, v in dict(RANK="0", WORLD_SIZE="1", LOCAL_RANK="0").items():
-        monkeypatch.setenv(k, v)
-    factory = (lambda p, d: SurrogateHeadVLA(seed=1)) if model == "head" else (lambda p, d: SurrogateVLA(seed=1))
-    args = dict(vla_path="x", dataset_name="synthetic", save_dir=str(tmp_path), patch_size=[3, 50, 50], bs=3, use_wandb=False, device="cpu",
-                model_factory=factory, dataset_factory=lambda *a: (None, None))
-    args.update(kw)
-    return uada_ddp.OpenVLAAttacker(**args)
-
-
-def _fused(monkeypatch):
-    monkeypatch.delenv("VAA_FUSED_EPILOGUE", raising=False)
-    monkeypatch.delenv("VAA_FUSED_EMBED_GRAD", raising=False)
-    monkeypatch.setattr(uada_ddp.OpenVLAAttacker, "fused_ddp_available", lambda self: hasattr(self.vla, "hidden_rows")
-                        and hasattr(self.vla, "patch_embed_params") and not self.randomPatchTransform.resize_patch)
-
-
 def test_upa_sweep_refusals_name_their_limit(monkeypatch, tmp_path):
-    _fused(monkeypatch)
-    ok = _attacker(monkeypatch, tmp_path, attack_type="UPA", upa_sweep=[(0.8, 0.2), [0.5, 0.5], (1, 0)])
+    fused(monkeypatch)
+    ok = attacker(monkeypatch, tmp_path, attack_type="UPA", upa_sweep=[(0.8, 0.2), [0.5, 0.5], (1, 0)])
     assert ok.upa_sweep == [(0.8, 0.2), (0.5, 0.5), (1.0, 0.0)] and ok.maskidx_sweep is None and ok.target_sweep is None
     for other in ("UADA", "TMA"):
         with pytest.raises(ValueError, match="UPA only"):
-            _attacker(monkeypatch, tmp_path, attack_type=other, upa_sweep=[(0.8, 0.2)])
+            attacker(monkeypatch, tmp_path, attack_type=other, upa_sweep=[(0.8, 0.2)])
     with pytest.raises(ValueError, match="cannot be combined with maskidx_sweep or target_sweep"):
-        _attacker(monkeypatch, tmp_path, attack_type="UADA", maskidx_sweep=[[0]], upa_sweep=[(0.8, 0.2)])
+        attacker(monkeypatch, tmp_path, attack_type="UADA", maskidx_sweep=[[0]], upa_sweep=[(0.8, 0.2)])
     with pytest.raises(ValueError, match="cannot be combined with maskidx_sweep or target_sweep"):
-        _attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=[([0], 0.0)], upa_sweep=[(0.8, 0.2)])
+        attacker(monkeypatch, tmp_path, attack_type="TMA", target_sweep=[([0], 0.0)], upa_sweep=[(0.8, 0.2)])
     with pytest.raises(ValueError, match="at least one"):
-        _attacker(monkeypatch, tmp_path, attack_type="UPA", upa_sweep=[])
+        attacker(monkeypatch, tmp_path, attack_type="UPA", upa_sweep=[])
     for bad in (float("nan"), float("inf"), -float("inf")):
         with pytest.raises(ValueError, match="finite"):
-            _attacker(monkeypatch, tmp_path, attack_type="UPA", upa_sweep=[(0.8, 0.2), (bad, 0.5)])
+            attacker(monkeypatch, tmp_path, attack_type="UPA", upa_sweep=[(0.8, 0.2), (bad, 0.5)])
         with pytest.raises(ValueError, match="finite"):
-            _attacker(monkeypatch, tmp_path, attack_type="UPA", upa_sweep=[(0.5, bad)])
+            attacker(monkeypatch, tmp_path, attack_type="UPA", upa_sweep=[(0.5, bad)])
     with pytest.raises(ValueError, match="distinct"):
-        _attacker(monkeypatch, tmp_path, attack_type="UPA", upa_sweep=[(0.8, 0.2), (0.5, 0.5), (0.8, 0.2)])
+        attacker(monkeypatch, tmp_path, attack_type="UPA", upa_sweep=[(0.8, 0.2), (0.5, 0.5), (0.8, 0.2)])
     with pytest.raises(ValueError, match="resize_patch"):
-        _attacker(monkeypatch, tmp_path, attack_type="UPA", resize_patch=True, upa_sweep=[(0.8, 0.2)])
+        attacker(monkeypatch, tmp_path, attack_type="UPA", resize_patch=True, upa_sweep=[(0.8, 0.2)])
     with pytest.raises(ValueError, match="fused path"):
-        _attacker(monkeypatch, tmp_path, attack_type="UPA", model="plain", upa_sweep=[(0.8, 0.2)])
+        attacker(monkeypatch, tmp_path, attack_type="UPA", model="plain", upa_sweep=[(0.8, 0.2)])
     with pytest.raises(ValueError, match="limit of 512"):  # 6 x 100 images
-        _attacker(monkeypatch, tmp_path, attack_type="UPA", bs=100, upa_sweep=[(0.1 * q, 0.5) for q in range(6)])
-    _attacker(monkeypatch, tmp_path, attack_type="UPA", bs=64, upa_sweep=[(0.1 * q, 0.5) for q in range(8)])  # 512 images, 4096 rows: no row limit behind the GEMM head
+        attacker(monkeypatch, tmp_path, attack_type="UPA", bs=100, upa_sweep=[(0.1 * q, 0.5) for q in range(6)])
+    attacker(monkeypatch, tmp_path, attack_type="UPA", bs=64, upa_sweep=[(0.1 * q, 0.5) for q in range(8)])  # 512 images, 4096 rows: no row limit behind the GEMM head
     cap = _lib.SEG_UPA_MAX_GROUPS
     assert cap == 32
     with pytest.raises(ValueError, match=f"limit of {cap}"):
-        _attacker(monkeypatch, tmp_path, attack_type="UPA", bs=1, upa_sweep=[(0.01 * q, 0.5) for q in range(cap + 1)])
-    _attacker(monkeypatch, tmp_path, attack_type="UPA", bs=1, upa_sweep=[(0.01 * q, 0.5) for q in range(cap)])
+        attacker(monkeypatch, tmp_path, attack_type="UPA", bs=1, upa_sweep=[(0.01 * q, 0.5) for q in range(cap + 1)])
+    attacker(monkeypatch, tmp_path, attack_type="UPA", bs=1, upa_sweep=[(0.01 * q, 0.5) for q in range(cap)])
 
 
 def test_older_sweeps_keep_their_refusals_and_the_plain_upa_attacker_is_untouched(monkeypatch, tmp_path):
-    _fused(monkeypatch)
+    fused(monkeypatch)
     with pytest.raises(ValueError, match="UADA only"):
-        _attacker(monkeypatch, tmp_path, attack_type="UPA", maskidx_sweep=[[0]])
+        attacker(monkeypatch, tmp_path, attack_type="UPA", maskidx_sweep=[[0]])
     with pytest.raises(ValueError, match="TMA only"):
-        _attacker(monkeypatch, tmp_path, attack_type="UPA", target_sweep=[([0], 0.0)])
+        attacker(monkeypatch, tmp_path, attack_type="UPA", target_sweep=[([0], 0.0)])
     with pytest.raises(ValueError, match="UADA only"):  # ... also beside a UPA sweep: the old parameters are not widened
-        _attacker(monkeypatch, tmp_path, attack_type="UPA", maskidx_sweep=[[0]], upa_sweep=[(0.8, 0.2)])
-    plain = _attacker(monkeypatch, tmp_path, attack_type="UPA", alpha=0.3, belta=0.7)
+        attacker(monkeypatch, tmp_path, attack_type="UPA", maskidx_sweep=[[0]], upa_sweep=[(0.8, 0.2)])
+    plain = attacker(monkeypatch, tmp_path, attack_type="UPA", alpha=0.3, belta=0.7)
     assert plain.upa_sweep is None and plain.maskidx_sweep is None and plain.target_sweep is None
     assert (plain.alpha, plain.belta) == (0.3, 0.7) and not hasattr(plain, "sweep_tags")
     _, labels, _ = synthetic.synth_text_batch(3, 4)
     assert plain._prepare_labels(labels) is labels and plain._loss_mode() == _lib.LOSS_UPA
-    default = _attacker(monkeypatch, tmp_path)
+    default = attacker(monkeypatch, tmp_path)
     assert default.upa_sweep is None and default.attack_type == "UADA"
 
 
 def test_every_group_keeps_the_unmasked_labels(monkeypatch, tmp_path):
-    _fused(monkeypatch)
-    att = _attacker(monkeypatch, tmp_path, attack_type="UPA", upa_sweep=[(0.8, 0.2), (0.2, 0.8)])
+    fused(monkeypatch)
+    att = attacker(monkeypatch, tmp_path, attack_type="UPA", upa_sweep=[(0.8, 0.2), (0.2, 0.8)])
     _, labels, _ = synthetic.synth_text_batch(3, 4)
     keep = labels.clone()
     for g in range(2):

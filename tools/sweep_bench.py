@@ -42,7 +42,7 @@ def _upa_groups(P):
 
 def measure(att, P, Bp, steps, warmup, inner, sweep, attack="uada"):
     from roboticattack_amd import dist as vdist, ops, synthetic
-    from roboticattack_amd.attack.uada_ddp import mask_labels_sweep
+    from roboticattack_amd.attack import sweep as kinds
     from roboticattack_amd.labels import tma_target_labels, tma_target_tokens
     from roboticattack_amd.optim import PatchOptimizer, SweepPatchOptimizer
 
@@ -52,85 +52,29 @@ def measure(att, P, Bp, steps, warmup, inner, sweep, attack="uada"):
     labels = batch["labels"].to(dev)
     ids, am = batch["input_ids"].to(dev), batch["attention_mask"].to(dev)
     n = 3 * 50 * 50
-    if attack == "upa" and sweep:
-        pairs = _upa_groups(P)
+    if sweep:  # the loop's own step (OpenVLAAttacker._attack_sweep at world 1) through the kind table
+        kind, make = dict(uada=(kinds.MASKIDX, _groups), tma=(kinds.TARGET, _target_groups), upa=(kinds.UPA, _upa_groups))[attack]
+        att.sweep_kind, att.sweep_groups = kind, make(P)
+        kind.prepare(att, att.sweep_groups)
         patches = torch.rand(P, 3, 50, 50, device=dev, requires_grad=True)
-        opt = SweepPatchOptimizer(patches, 1e-3, l1_clip=1e-3)
+        opt = SweepPatchOptimizer(patches, 1e-3, l1_clip=kind.l1_clip)
         img = pv.repeat(P, 1, 1, 1).contiguous()
         ids_all, am_all = ids.repeat(P, 1).contiguous(), am.repeat(P, 1).contiguous()
-        lab = labels.repeat(P, 1).contiguous()  # reverse-direction UPA: every group keeps the unmasked labels
+        lab = torch.cat([kind.group_labels(att, labels, g) for g in range(P)])
         row_index = att.vla.label_row_index(lab)
         segmap = ops.LossRowMapSeg(lab, P)
         pack = att.vla.make_pack(am_all) if hasattr(att.vla, "make_pack") else None
-        sync = vdist.PatchGradSync(patches.numel(), 4 * P, dev)
+        sync = None if kind.k4_in_epilogue else vdist.PatchGradSync(patches.numel(), 4 * P, dev)
+        msg = torch.zeros(P * (n + 4), device=dev) if sync is None else sync.buf
         sc = torch.zeros((P, 8), device=dev)
 
         def step(k):
-            att.upa_sweep_step(img, patches, ids_all, row_index, segmap, pack, sync.buf, sc, k % inner == inner - 1, pairs=pairs)
-            g_sum, _ = sync.allreduce_packed()
-            opt.step(grad=g_sum.view_as(patches), grad_scale=1.0)
-    elif attack == "upa":  # the standalone UPA step of the data-parallel loop (OpenVLAAttacker._attack, attack_type="UPA", world 1)
-        patch = torch.rand(3, 50, 50, device=dev, requires_grad=True)
-        opt = PatchOptimizer(patch, 1e-3, l1_clip=1e-3)
-        lab = labels.clone()
-        sync = vdist.PatchGradSync(patch.numel(), 4, dev)
-        pick = torch.tensor([1, 2, 7, 0], dtype=torch.int64, device=dev)
-
-        def step(k):
-            opt.zero_grad()
-            full_ce = k % inner == inner - 1
-            pix = att.randomPatchTransform.apply_random_patch_batch(pv, patch, mean=att.mean, std=att.std, geometry=True)
-            total, scal, _ = att.model_loss(ids, am, pix, lab, ops.LOSS_UPA, w=5.0, alpha=0.8, beta=0.2, full_ce=full_ce, read_scalars=full_ce)
-            total.backward()
-            g_sum, _ = sync.allreduce_step(patch.grad, scal, pick)
-            opt.step(grad=g_sum.view_as(patch), grad_scale=1.0)
-    elif attack == "tma" and sweep:
-        patches = torch.rand(P, 3, 50, 50, device=dev, requires_grad=True)
-        opt = SweepPatchOptimizer(patches, 1e-3)
-        img = pv.repeat(P, 1, 1, 1).contiguous()
-        ids_all, am_all = ids.repeat(P, 1).contiguous(), am.repeat(P, 1).contiguous()
-        lab = torch.cat([tma_target_labels(labels, tma_target_tokens(t * np.ones(7), m).to(dev)) for m, t in _target_groups(P)])
-        row_index = att.vla.label_row_index(lab)
-        segmap = ops.LossRowMapSeg(lab, P)
-        pack = att.vla.make_pack(am_all) if hasattr(att.vla, "make_pack") else None
-        msg = torch.zeros(P * (n + 4), device=dev)
-        sc = torch.zeros((P, 8), device=dev)
-
-        def step(k):
-            att.target_sweep_step(img, patches, ids_all, row_index, segmap, pack, msg, sc, k % inner == inner - 1, opt.fused_update_args())
-    elif attack == "tma":  # the standalone TMA step of the data-parallel loop (OpenVLAAttacker._attack, attack_type="TMA", world 1)
-        patch = torch.rand(3, 50, 50, device=dev, requires_grad=True)
-        opt = PatchOptimizer(patch, 1e-3)
-        lab = tma_target_labels(labels, tma_target_tokens(np.zeros(7), [0]).to(dev))
-        sync = vdist.PatchGradSync(patch.numel(), 4, dev)
-        pick = torch.tensor([1, 2, 7, 0], dtype=torch.int64, device=dev)
-
-        def step(k):
-            opt.zero_grad()
-            full_ce = k % inner == inner - 1
-            pix = att.randomPatchTransform.apply_random_patch_batch(pv, patch, mean=att.mean, std=att.std, geometry=True)
-            total, scal, _ = att.model_loss(ids, am, pix, lab, ops.LOSS_CE, w=5.0, full_ce=full_ce, read_scalars=full_ce)
-            total.backward()
-            g_sum, _ = sync.allreduce_step(patch.grad, scal, pick)
-            opt.step(grad=g_sum.view_as(patch), grad_scale=1.0)
-    elif sweep:
-        groups = _groups(P)
-        patches = torch.rand(P, 3, 50, 50, device=dev, requires_grad=True)
-        opt = SweepPatchOptimizer(patches, 1e-3)
-        img = pv.repeat(P, 1, 1, 1).contiguous()
-        ids_all, am_all = ids.repeat(P, 1).contiguous(), am.repeat(P, 1).contiguous()
-        lab = mask_labels_sweep(labels, groups)
-        row_index = att.vla.label_row_index(lab)
-        segmap = ops.LossRowMapSeg(lab, P)
-        pack = att.vla.make_pack(am_all) if hasattr(att.vla, "make_pack") else None
-        msg = torch.zeros(P * (n + 4), device=dev)
-        sc = torch.zeros((P, 8), device=dev)
-        W = att.vla.lm_head.weight
-
-        def step(k):
-            att.sweep_step(img, patches, ids_all, lab, row_index, segmap, pack, 5.0, int(W.shape[0]), msg, sc, k % inner == inner - 1,
-                           opt.fused_update_args())
-    else:
+            att.sweep_step(img, patches, ids_all, row_index, segmap, pack, msg, sc, k % inner == inner - 1,
+                           opt.fused_update_args() if sync is None else None)
+            if sync is not None:  # K4 behind the epilogue (the L1 clip)
+                g_sum, _ = sync.allreduce_packed()
+                opt.step(grad=g_sum.view_as(patches), grad_scale=1.0)
+    elif attack == "uada":
         patch = torch.rand(3, 50, 50, device=dev, requires_grad=True)
         opt = PatchOptimizer(patch, 1e-3)
         lab = att.mask_labels(labels.clone(), [0])
@@ -139,6 +83,22 @@ def measure(att, P, Bp, steps, warmup, inner, sweep, attack="uada"):
 
         def step(k):
             att.fused_ddp_step(pv, patch, ids, am, lab, True, 5.0, msg, sc, optimizer=opt, full_ce=k % inner == inner - 1)
+    else:  # the standalone TMA / UPA step of the data-parallel loop (OpenVLAAttacker._attack at world 1)
+        mode, lab, clip = (ops.LOSS_UPA, labels.clone(), 1e-3) if attack == "upa" else (
+            ops.LOSS_CE, tma_target_labels(labels, tma_target_tokens(np.zeros(7), [0]).to(dev)), 0.0)
+        patch = torch.rand(3, 50, 50, device=dev, requires_grad=True)
+        opt = PatchOptimizer(patch, 1e-3, l1_clip=clip)
+        sync = vdist.PatchGradSync(patch.numel(), 4, dev)
+        pick = torch.tensor([1, 2, 7, 0], dtype=torch.int64, device=dev)
+
+        def step(k):
+            opt.zero_grad()
+            full_ce = k % inner == inner - 1
+            pix = att.randomPatchTransform.apply_random_patch_batch(pv, patch, mean=att.mean, std=att.std, geometry=True)
+            total, scal, _ = att.model_loss(ids, am, pix, lab, mode, w=5.0, alpha=0.8, beta=0.2, full_ce=full_ce, read_scalars=full_ce)
+            total.backward()
+            g_sum, _ = sync.allreduce_step(patch.grad, scal, pick)
+            opt.step(grad=g_sum.view_as(patch), grad_scale=1.0)
 
     for k in range(warmup):
         step(k)
@@ -179,7 +139,7 @@ def main():
 
     torch.manual_seed(0)
     np.random.seed(0)
-    att = uada_ddp.OpenVLAAttacker(vla_path=a.vla, dataset_name="synthetic", bs=8, use_wandb=False, maskidx=[0],
+    att = uada_ddp.OpenVLAAttacker(vla_path=a.vla, dataset_name="synthetic", bs=8, use_wandb=False, maskidx=[0], MSE_weights=5,
                                    dataset_factory=lambda *x: (None, None))
     assert att.fused_ddp_available()
     out = []

@@ -32,6 +32,10 @@ int vaa_model_layernorm_bwd(const uint16_t* gh, const uint16_t* gpass, const uin
 /* Softmax attention on the matrix cores for short sequences. q,k,v,o: bf16 views [B,T,H,hd] given by element strides
  * {batch, token, head} (last dim contiguous, all strides % 8 == 0), hd % 8 == 0, hd <= 128. lse: float32 [B,H,T] (natural log).
  * causal != 0: query t sees keys <= t.
+ * 32-bit range: a (batch, head) slice is addressed with 32-bit byte counts and offsets, so for every operand the token stride must be
+ * >= 0 and ((T-1)*stride_t + hd)*2 as well as ((roundup(T,64)-1)*stride_t + padded hd)*2 (padded hd = 64 / 96 / 128) must be <= 2^31-1.
+ * scale must be finite and > 0 (the running max is taken before the scaling). Either violation returns VAA_E_UNSUPPORTED before any launch;
+ * both hold for vaa_model_attention_bwd too.
  * cu_seqlens (int32 [B+1], may be NULL): the B sequences are PACKED back to back along the token axis (the batch stride is unused),
  * sample b owning tokens cu[b] .. cu[b+1]-1; T is then the maximum length (lse and dsum stay [B,H,T]). */
 int vaa_model_attention_fwd(const uint16_t* q, const int64_t* q_str, const uint16_t* k, const int64_t* k_str, const uint16_t* v,

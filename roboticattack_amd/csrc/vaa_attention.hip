@@ -16,6 +16,7 @@
 // (batch, head) are placed on the same XCD (blockIdx % 8) so that its K/V stay in that XCD's L2.
 #include "vaa_common.h"
 
+#include <cmath>
 #include <cstdlib>
 #include <mutex>
 
@@ -686,6 +687,31 @@ static int launch_fwd(const AttnFwdArgs& a, hipStream_t st) {
 static bool strides_ok(const int64_t* s) { return s && (s[0] % 8) == 0 && (s[1] % 8) == 0 && (s[2] % 8) == 0; }
 static AttnStr mk(const int64_t* s) { AttnStr r; r.b = s[0]; r.t = s[1]; r.h = s[2]; return r; }
 
+// The kernels reach one (batch, head) slice through a 32-bit buffer descriptor (slice_rsrc: ((T-1)*stride_t + hd)*2 bytes) and the int byte
+// offsets of TileRegs::load (up to the last 16-byte chunk of the padded width in the last row of the last 64-row tile): both must fit in int.
+static bool range_ok(const int64_t* s, int T, int hd) {
+    const int64_t st = s[1];
+    if (st < 0 || st > INT32_MAX) return false;
+    const int hdp = hd <= 64 ? 64 : hd <= 96 ? 96 : 128;
+    const int64_t rows = ((int64_t)T + kTile - 1) / kTile * kTile;
+    return (((int64_t)T - 1) * st + hd) * 2 <= INT32_MAX && ((rows - 1) * st + hdp) * 2 <= INT32_MAX;
+}
+// Launch-independent preconditions shared by the two entries: 32-bit addressing of every operand, and a positive finite softmax scale
+// (the forward takes the running max BEFORE scaling: max commutes with the scaling only for scale > 0).
+static int check_range_and_scale(const char* who, const int64_t* const* strs, int nstr, int T, int hd, float scale) {
+    for (int i = 0; i < nstr; ++i)
+        if (!range_ok(strs[i], T, hd)) {
+            set_error("%s: operand %d exceeds the kernels' 32-bit addressing (T=%d hd=%d token stride=%lld: ((T-1)*stride+hd)*2 bytes and the tile "
+                      "offsets must stay <= 2^31-1)", who, i, T, hd, (long long)strs[i][1]);
+            return VAA_E_UNSUPPORTED;
+        }
+    if (!std::isfinite(scale) || !(scale > 0.0f)) {
+        set_error("%s: scale must be finite and > 0 (scale=%g)", who, (double)scale);
+        return VAA_E_UNSUPPORTED;
+    }
+    return VAA_OK;
+}
+
 }  // namespace vaa
 
 extern "C" int vaa_model_attention_fwd(const uint16_t* q, const int64_t* q_str, const uint16_t* k, const int64_t* k_str, const uint16_t* v,
@@ -700,6 +726,11 @@ extern "C" int vaa_model_attention_fwd(const uint16_t* q, const int64_t* q_str, 
         !strides_ok(o_str)) {
         set_error("vaa_model_attention_fwd: unsupported shape (B=%d H=%d T=%d hd=%d; hd %% 8 == 0, hd <= 128, strides %% 8 == 0)", B, H, T, hd);
         return VAA_E_UNSUPPORTED;
+    }
+    {
+        const int64_t* strs[] = {q_str, k_str, v_str, o_str};
+        const int rc = check_range_and_scale("vaa_model_attention_fwd", strs, 4, T, hd, scale);
+        if (rc != VAA_OK) return rc;
     }
     AttnFwdArgs a;
     a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse;
@@ -724,6 +755,11 @@ extern "C" int vaa_model_attention_bwd(const uint16_t* q, const int64_t* q_str, 
         !strides_ok(o_str) || !strides_ok(do_str) || !strides_ok(dq_str) || !strides_ok(dk_str) || !strides_ok(dv_str)) {
         set_error("vaa_model_attention_bwd: unsupported shape (B=%d H=%d T=%d hd=%d; hd %% 8 == 0, hd <= 128, strides %% 8 == 0)", B, H, T, hd);
         return VAA_E_UNSUPPORTED;
+    }
+    {
+        const int64_t* strs[] = {q_str, k_str, v_str, o_str, do_str, dq_str, dk_str, dv_str};
+        const int rc = check_range_and_scale("vaa_model_attention_bwd", strs, 8, T, hd, scale);
+        if (rc != VAA_OK) return rc;
     }
     AttnBwdArgs a;
     a.q = q; a.k = k; a.v = v; a.o = o; a.dout = dout; a.lse = lse; a.dsum = dsum; a.dq = dq; a.dk = dk; a.dv = dv;

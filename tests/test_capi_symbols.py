@@ -63,6 +63,41 @@ def test_sizes_and_argument_errors_without_gpu():
         _lib.check(rc, "vaa_patch_update")
 
 
+def test_attention_range_and_scale_guards_without_gpu():
+    """vaa_model_attention_{fwd,bwd} refuse, before any launch, a (batch, head) slice beyond the kernels' 32-bit addressing and a softmax scale
+    that is not finite and > 0. Small host buffers stand in for the operands (nothing dereferences them); skipped where a GPU is visible, so it
+    can never launch anything."""
+    import torch
+
+    if torch.cuda.is_available():
+        pytest.skip("host-side guards only: must not be able to launch")
+    L = _lib.lib()
+    buf = [(ctypes.c_uint16 * 64)() for _ in range(8)]
+    f32 = [(ctypes.c_float * 64)() for _ in range(2)]
+    p = lambda b: ctypes.cast(b, ctypes.c_void_p)
+    s3 = lambda t: (ctypes.c_int64 * 3)(0, t, 64)
+    ok = s3(64)
+
+    def fwd(T, strs, scale):
+        return L.vaa_model_attention_fwd(p(buf[0]), strs[0], p(buf[1]), strs[1], p(buf[2]), strs[2], p(buf[3]), strs[3], p(f32[0]), None, 1, 1, T, 64, 1,
+                                         scale, None)
+
+    def bwd(T, strs, scale):
+        return L.vaa_model_attention_bwd(p(buf[0]), strs[0], p(buf[1]), strs[1], p(buf[2]), strs[2], p(buf[3]), strs[3], p(buf[4]), strs[4], p(f32[0]),
+                                         p(f32[1]), p(buf[5]), strs[5], p(buf[6]), strs[6], p(buf[7]), strs[7], None, None, None, 1, 1, T, 64, 1, scale,
+                                         None)
+
+    for call, n in ((fwd, 4), (bwd, 8)):
+        for i in range(n):  # any one operand out of range
+            # the descriptor's byte count ((T-1)*stride + hd)*2 > 2^31-1
+            assert call(2, [s3(2 ** 30) if j == i else ok for j in range(n)], 0.125) == -2 and b"32-bit" in L.vaa_last_error()
+            # the byte count fits (2^30 + 2^24 + 128) but the last tile row's offset (127 rows at T = 65) does not
+            assert call(65, [s3(2 ** 23 + 2 ** 17) if j == i else ok for j in range(n)], 0.125) == -2 and b"32-bit" in L.vaa_last_error()
+            assert call(2, [s3(-64) if j == i else ok for j in range(n)], 0.125) == -2 and b"32-bit" in L.vaa_last_error()
+        for scale in (0.0, -0.125, float("nan"), float("inf")):
+            assert call(2, [ok] * n, scale) == -2 and b"scale must be finite and > 0" in L.vaa_last_error()
+
+
 def test_ops_refuse_cpu_tensors():
     import torch
 

@@ -52,7 +52,7 @@ def main(args):
         "vla_path": vla_path, "dataset_name": args.dataset, "save_dir": path, "resize_patch": args.resize_patch,
         "patch_size": args.patch_size, "lr": args.lr, "bs": args.bs, "warmup": args.warmup, "num_iter": args.iter,
         "maskidx": args.maskidx, "innerLoop": args.innerLoop, "geometry": args.geometry,
-        "use_wandb": args.wandb_project != "false", "MSE_weights": args.MSE_weights,
+        "use_wandb": args.wandb_project != "false", "MSE_weights": args.MSE_weights, "colorjitter": cli.colorjitter_arg(args),
     }
     if args.attack != "UADA":  # extension: the same data-parallel loop for UPA / TMA (BASELINE configs 4-5)
         instance_params.update(attack_type=args.attack, alpha=args.alpha, belta=args.belta, target_action=args.targetAction)

@@ -177,6 +177,32 @@ int vaa_patch_grad_gather_multi(const uint16_t* gout_bf16, const float* packed, 
                                 const float* std6, float* gpacked, void* stream);
 
 /*
+ * colorjitter (K0c) — a per-image photometric draw on the BASE patch in front of the same per-image-patch kernels, and its adjoint. The
+ * reference carries a `colorjitter=` flag from TMA.py into apply_random_patch_batch and never acts on it, so the
+ * arithmetic is defined HERE. With p = patch [3,ph,pw] in [0,1], N = ph*pw, gray(y) = 0.299 y_R + 0.587 y_G + 0.114 y_B and image b's
+ * factors (beta, kappa, sigma) = factors[b] (brightness, contrast, saturation; no hue term), in fp32 with every a*x + c one FMA on a rounded c:
+ *     y1 = clamp(beta*p, 0, 1)
+ *     m  = (1/N) * sum over the texels of gray(y1)                (one scalar per image; fixed-order fp64 sum, rounded once)
+ *     y2 = clamp(kappa*y1 + (1-kappa)*m, 0, 1)
+ *     y3 = clamp(sigma*y2 + (1-sigma)*gray(y2), 0, 1)             (gray per texel)
+ * factors (1, 1, 1) return p bit for bit. The draws stay on the host (RandomPatchTransform: 3*B random.uniform calls behind the placement draws).
+ *   factors  dev  [B,3] float32
+ *   pdesc    dev  [B,4] int32 = {ph, pw, offset_b, 0} as above — every image's patch has the base patch's size; an entry of another size
+ *             leaves that image unwritten (its adjoint zero) and raises the device-failure word (vaa_async_error)
+ * Forward, one launch: packed[offset_b ...] = y3 of image b — the layout the per-image-patch forms of K1 / K2 / K2' read.
+ * Adjoint: gpatch [3,ph,pw] = sum_b adjoint_b(gpacked_b), overwritten — the exact derivative of the above with torch.clamp's gate (the gradient
+ *             passes where 0 <= pre-clamp <= 1, bounds included), recomputed from patch and factors (no forward state), including both
+ *             coupling terms: the per-texel gray term of the saturation stage and the whole-patch mean term of the contrast stage,
+ *             (1-kappa)/N * w_c * (sum over texels and channels of the gated gradient G2' in front of the contrast clamp).
+ *             ws >= the adjoint's workspace size for (B,ph,pw): one partial per image, 0 for B = 1. Two launches whatever B is (per-image adjoint,
+ *             fixed-order fp64 sum over the images); the same arguments give the same bits.
+ */
+int vaa_patch_jitter_fwd(const float* patch, int ph, int pw, const float* factors, const int32_t* pdesc, int B, float* packed, void* stream);
+size_t vaa_patch_jitter_ws_bytes(int B, int ph, int pw);
+int vaa_patch_jitter_bwd(const float* gpacked, const float* patch, int ph, int pw, const float* factors, const int32_t* pdesc, int B,
+                         float* gpatch, void* ws, size_t ws_bytes, void* stream);
+
+/*
  * K3 — replaces HF Llama's `.loss` (via modeling_prismatic.py:404-415) + OpenVLAAttacker.weighted_loss
  * (UADA.py:381-406, UADA_ddp.py:99-124, UPA.py:367-387) and their autograd backward to the logits.
  *   logits   dev  f32|bf16, layout FULL [B,S,V] or ROWS [R,V]. For ROWS pass S = R (the number of rows, which must equal the number

@@ -197,6 +197,8 @@ def check(attacker, kind: SweepKind, groups):
         refuse(f"{kind.attack_type} only (got attack_type={attacker.attack_type!r}; {others})")
     if attacker.randomPatchTransform.resize_patch:
         refuse("resize_patch=True is not supported (one patch size per group only)")
+    if attacker.randomPatchTransform.colorjitter:
+        refuse("colorjitter is not supported (one shared patch per group only)")
     if not attacker.fused_ddp_available():
         refuse("needs the fused path (a model that exposes its patch-embed weights and hidden rows, VAA_FUSED_EPILOGUE != 0)")
     if P * bs > SWEEP_MAX_IMAGES:

@@ -2,8 +2,8 @@
 
 Loss = HF mean CE against a fixed target-token vector on the `maskidx` DoFs, divided by accumulate_steps (TMA.py:148);
 AdamW (+cosine) or PGD sign step (TMA.py:164-175); without geometry the patch is pasted by `paste_patch_fix`
-(mask rule canvas != -100, TMA.py:133-135), with geometry by `apply_random_patch_batch` (the `colorjitter=` kwarg the
-reference passes is ignored, Appendix A-D3). Validation: 100 batches, ASR / L1 metrics, best patch by L1 (TMA.py:202-383).
+(mask rule canvas != -100, TMA.py:133-135), with geometry or colorjitter by `apply_random_patch_batch` (the `colorjitter=` kwarg is dead in
+the reference, Appendix A-D3; here the training steps jitter the patch per image and validation evaluates it as it is saved). Validation: 100 batches, ASR / L1 metrics, best patch by L1 (TMA.py:202-383).
 """
 from __future__ import annotations
 
@@ -27,12 +27,13 @@ class OpenVLAAttacker(AttackBase):
         self.min_val_avg_CE_loss = 1000000
         self.min_val_avg_L1_loss = 1000000
 
-    def _images(self, pixel_values, patch, geometry, colorjitter, grad_sink=None):
+    def _images(self, pixel_values, patch, geometry, colorjitter, grad_sink=None, jitter=True):
+        """`colorjitter` picks the operator as in the reference (TMA.py:133-135); `jitter=False` (validation) pastes the patch un-jittered."""
         if not geometry and not colorjitter:
             return self.randomPatchTransform.paste_patch_fix(pixel_values, patch, mean=self.mean, std=self.std)
         kw = {"grad_sink": grad_sink} if grad_sink is not None else {}
         return self.randomPatchTransform.apply_random_patch_batch(pixel_values, patch, mean=self.mean, std=self.std,
-                                                                   geometry=geometry, colorjitter=colorjitter, **kw)
+                                                                   geometry=geometry, colorjitter=colorjitter if jitter else False, **kw)
 
     def calculate_relative_distance_target(self, pred, gt):
         """TMA.py:470-483."""
@@ -78,6 +79,7 @@ class OpenVLAAttacker(AttackBase):
     def patchattack_unconstrained(self, train_dataloader, val_dataloader, num_iter=5000, target_action=np.zeros(7),
                                   patch_size=[3, 50, 50], alpha=1 / 255, accumulate_steps=1, maskidx=[], warmup=20,
                                   filterGripTrainTo1=False, geometry=False, colorjitter=False, innerLoop=1, args=None):
+        self.randomPatchTransform.colorjitter = colorjitter
         self.val_CE_loss, self.val_L1_loss, self.val_ASR, self.val_inner_relatived_distance = [], [], [], []
         self.train_CE_loss, self.train_inner_avg_loss, self.train_inner_relatived_distance = [], [], []
         dev = self.device
@@ -162,7 +164,7 @@ class OpenVLAAttacker(AttackBase):
                     pixel_values = [pixel_values[b] for b in ok]
                     orig_gt.append(gt[ok])
                 val_num_sample += labels.shape[0]
-                modified_images = self._images(pixel_values, patch.detach(), geometry, colorjitter)
+                modified_images = self._images(pixel_values, patch.detach(), geometry, colorjitter, jitter=False)
                 newlabels = tma_target_labels(labels, target)
                 _, scalars, pred = self.model_loss(input_ids, attention_mask, modified_images, newlabels, ops.LOSS_CE, need_grad=False)
                 rb.add(scalars, pred, newlabels)

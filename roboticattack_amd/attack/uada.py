@@ -34,7 +34,8 @@ class OpenVLAAttacker(AttackBase):
         """One iteration of the hot inner loop (UADA.py:133-159). With K2' (a model that exposes its patch-embed weights) the step ends with ONE
         launch that adds K2''s partial tiles and applies AdamW + clamp; the logged gradient statistics are then folded once per outer iteration."""
         sink = self.fused_update_sink(optimizer)
-        pix = self.randomPatchTransform.apply_random_patch_batch(pixel_values, patch, mean=self.mean, std=self.std, geometry=geometry, **({"grad_sink": sink} if sink is not None else {}))
+        pix = self.randomPatchTransform.apply_random_patch_batch(pixel_values, patch, mean=self.mean, std=self.std, geometry=geometry,
+                                                                  colorjitter=self.randomPatchTransform.colorjitter, **({"grad_sink": sink} if sink is not None else {}))
         total, scalars, pred = self.model_loss(input_ids, attention_mask, pix, labels, self.loss_mode, w=self.mse_weight)
         total.backward()
         scalars_out[k, :8] = scalars
@@ -49,7 +50,10 @@ class OpenVLAAttacker(AttackBase):
 
     def patchattack_unconstrained(self, train_dataloader, val_dataloader, num_iter=5000, target_action=np.zeros(7),
                                   patch_size=[3, 50, 50], lr=1 / 255, accumulate_steps=1, maskidx=[], warmup=20,
-                                  filterGripTrainTo1=False, geometry=False, innerLoop=1, args=None):
+                                  filterGripTrainTo1=False, geometry=False, innerLoop=1, args=None, colorjitter=False):
+        """colorjitter (an EXTENSION: True or three strengths): every training step pastes a per-image brightness / contrast / saturation variant of
+        the patch; validation evaluates the patch as it is saved."""
+        self.randomPatchTransform.colorjitter = colorjitter
         self.val_CE_loss, self.val_MSE_Distance, self.val_UAD = [], [], []
         self.train_CE_loss, self.train_MSE_distance_loss, self.train_UAD = [], [], []
         dev = self.device

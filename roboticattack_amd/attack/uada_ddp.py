@@ -60,13 +60,15 @@ class OpenVLAAttacker(AttackBase):
     def __init__(self, vla_path, dataset_name, save_dir="", resize_patch=False, patch_size=[3, 50, 50], lr=0.01, bs=1, warmup=20,
                  num_iter=10000, maskidx=[], innerLoop=1, geometry=True, use_wandb=True, MSE_weights=1,
                  model_factory=None, dataset_factory=None, device=None, attack_type="UADA", alpha=0.8, belta=0.2, target_action=0.0, maskidx_sweep=None,
-                 target_sweep=None, upa_sweep=None):
+                 target_sweep=None, upa_sweep=None, colorjitter=False):
         """`attack_type`, `alpha`, `belta`, `target_action` are EXTENSIONS (the reference ships DDP for UADA only):
         "UPA" = UPA.py's reverse-direction loss + L1 grad clip, "TMA" = TMA.py's target-token CE, same data-parallel loop.
         `maskidx_sweep`, `target_sweep` (attack_type="TMA" only), `upa_sweep` (attack_type="UPA" only) are EXTENSIONS, at most one per run (sweep.KINDS):
         a list of maskidx lists / (maskidx list, target action value) pairs / (alpha, belta) pairs optimises one patch per entry in ONE loop — every
         group sees the same frames, draws and schedule, and group p ends where a standalone run with entry p in place of `maskidx` / `maskidx` and
-        `target_action` / `alpha` and `belta` (then unused) and the same seed ends (DESIGN.md §maskidx sweep). None keeps the loop as it is."""
+        `target_action` / `alpha` and `belta` (then unused) and the same seed ends (DESIGN.md §maskidx sweep). None keeps the loop as it is.
+        `colorjitter` is an EXTENSION (True or three strengths): every training step pastes a per-image brightness / contrast / saturation variant
+        of the patch through the per-image forms of K1 / K2'; validation evaluates the patch as it is saved. Not available with a sweep."""
         rank, world, local = vdist.env_rank_world()
         if device is None:
             device = vdist.local_device()
@@ -85,6 +87,7 @@ class OpenVLAAttacker(AttackBase):
         if attack_type not in ("UADA", "UPA", "TMA"):
             raise ValueError(f"attack_type must be UADA, UPA or TMA, got {attack_type!r}")
         self.attack_type, self.alpha, self.belta, self.target_action = attack_type, alpha, belta, target_action
+        self.randomPatchTransform.colorjitter = colorjitter
         # at most one kind of sweep; the parameters are checked in KINDS' order, so a refusal of an earlier one comes first
         self.sweep_kind = self.sweep_groups = None
         given = dict(maskidx_sweep=maskidx_sweep, target_sweep=target_sweep, upa_sweep=upa_sweep)
@@ -146,7 +149,8 @@ class OpenVLAAttacker(AttackBase):
                     self.fused_ddp_step(pixel_values, patch, input_ids, attention_mask, labels, self.geometry, float(self.MSE_weights),
                                         sync.buf, scalars, optimizer=optimizer if world_size == 1 else None, full_ce=full_ce)
                     return None if world_size == 1 else sync.allreduce_packed  # C3 + C4 in one message: [grad | CE, MSE, UAD, total]
-                pix = self.randomPatchTransform.apply_random_patch_batch(pixel_values, patch, mean=self.mean, std=self.std, geometry=self.geometry)
+                pix = self.randomPatchTransform.apply_random_patch_batch(pixel_values, patch, mean=self.mean, std=self.std, geometry=self.geometry,
+                                                                          colorjitter=self.randomPatchTransform.colorjitter)
                 total, sc, _ = self.model_loss(input_ids, attention_mask, pix, labels, self._loss_mode(), w=float(self.MSE_weights),
                                                alpha=self.alpha, beta=self.belta, full_ce=full_ce, read_scalars=full_ce)
                 total.backward()  # K2 inside

@@ -56,7 +56,8 @@ class OpenVLAAttacker(AttackBase):
     def inner_step(self, patch, optimizer, pixel_values, input_ids, attention_mask, labels, geometry, mode, scale, scalars_out, k, do_step=True, read_scalars=True):
         """One iteration of the hot inner loop (UPA.py:127-159): [K0 per-image patch resize ->] K1 -> model -> K3 (K3h when the loss lives in the
         action slice) -> backward -> K2 / K2' (MULTI forms with resize_patch) -> K4 with the L1 clip (UPA.py:157) in front of AdamW."""
-        pix = self.randomPatchTransform.apply_random_patch_batch(pixel_values, patch, mean=self.mean, std=self.std, geometry=geometry)
+        pix = self.randomPatchTransform.apply_random_patch_batch(pixel_values, patch, mean=self.mean, std=self.std, geometry=geometry,
+                                                                  colorjitter=self.randomPatchTransform.colorjitter)
         # the reverse-direction loop never reads output.loss nor a full-vocabulary argmax (UPA.py:145-150,171-186): slice-only head (K3s)
         # (`read_scalars`: the loop prints / logs the loss terms of the LAST inner step of an outer iteration only, UPA.py:171-186: the others skip the fold)
         total, scalars, pred = self.model_loss(input_ids, attention_mask, pix, labels, mode, alpha=self.alpha, beta=self.belta, scale=scale, full_ce=False,
@@ -73,7 +74,10 @@ class OpenVLAAttacker(AttackBase):
 
     def patchattack_unconstrained(self, train_dataloader, val_dataloader, num_iter=5000, target_action=np.zeros(7),
                                   patch_size=[3, 50, 50], lr=1 / 255, accumulate_steps=1, maskidx=[], warmup=20,
-                                  filterGripTrainTo1=False, geometry=False, innerLoop=1, guide=False, reverse_direction=False, args=None):
+                                  filterGripTrainTo1=False, geometry=False, innerLoop=1, guide=False, reverse_direction=False, args=None, colorjitter=False):
+        """colorjitter (an EXTENSION: True or three strengths): every training step pastes a per-image brightness / contrast / saturation variant of
+        the patch; validation evaluates the patch as it is saved."""
+        self.randomPatchTransform.colorjitter = colorjitter
         self.val_CE_loss, self.val_L1_loss, self.val_ASR, self.train_CE_loss, self.val_relative_distance = [], [], [], [], []
         dev = self.device
         patch = torch.rand(patch_size).to(dev)

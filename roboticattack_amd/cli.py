@@ -2,7 +2,8 @@
 
 Flag names, types and defaults are the reference's (UADA_wrapper.py:87-121, UADA_wrapper_ddp.py:87-119,
 TMA_wrapper.py:89-124, UPA_wrapper.py:90-127). Added flags (all optional, defaults keep reference behaviour where the
-environment allows): --vla_path (local checkpoint dir, or random:openvla-7b / random:tiny / surrogate), --data (synthetic).
+environment allows): --vla_path (local checkpoint dir, or random:openvla-7b / random:tiny / surrogate), --data (synthetic),
+--colorjitter / --colorjitter_strength (photometric draw on the patch in training steps; off by default).
 """
 from __future__ import annotations
 
@@ -17,6 +18,18 @@ import torch
 
 def list_of_ints(arg):
     return list(map(int, arg.split(",")))
+
+
+def three_floats(arg):
+    vals = tuple(map(float, arg.split(",")))
+    if len(vals) != 3:
+        raise argparse.ArgumentTypeError("three comma-separated floats expected (brightness,contrast,saturation)")
+    return vals
+
+
+def colorjitter_arg(args):
+    """--colorjitter / --colorjitter_strength as the attackers take them: False, or the three strengths."""
+    return tuple(args.colorjitter_strength) if args.colorjitter else False
 
 
 def str2bool(value):
@@ -78,6 +91,10 @@ def add_common(parser: argparse.ArgumentParser, *, lr, maskidx, iters, warmup, i
     parser.add_argument("--vla_path", default=None, type=str,
                         help="local OpenVLA checkpoint dir, or random:openvla-7b | random:tiny | surrogate (no network here)")
     parser.add_argument("--data", default="synthetic", type=str, help="data source; only 'synthetic' exists in this image")
+    parser.add_argument("--colorjitter", type=str2bool, default=False,
+                        help="training steps paste a per-image brightness / contrast / saturation variant of the patch")
+    parser.add_argument("--colorjitter_strength", type=three_floats, default=(0.2, 0.2, 0.2),
+                        help="brightness,contrast,saturation strengths s: factors ~ U(1-s, 1+s)")
 
 
 def resolve_device(index: int):

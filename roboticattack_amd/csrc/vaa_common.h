@@ -23,6 +23,7 @@ int check_launch(const char* what);  // the HIP runtime's last error, then async
 unsigned* async_error_word();        // pinned, device-mapped word kernels OR failure bits into (nullptr: allocation failed)
 int async_error_poll(const char* what, bool clear);
 constexpr unsigned VAA_ASYNC_K3_HANDOVER_TIMEOUT = 1u;
+constexpr unsigned VAA_ASYNC_JITTER_PDESC = 2u;  // vaa_patch_jitter_*: a descriptor entry whose size is not the base patch's (that image is left alone)
 // vaa_patch_grad.hip: gpatch[e] = sum_p partial[p][e] (p < nparts, e < n) in a fixed order with fp64 accumulation
 int launch_partial_reduce(const float* partial, float* gpatch, int n, int nparts, hipStream_t st, const char* who);
 

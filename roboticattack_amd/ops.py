@@ -313,9 +313,41 @@ def patch_resize_bwd(gpacked, pdesc, ph: int, pw: int):
     return g
 
 
+def patch_jitter_fwd(patch, factors, pdesc, total: int):
+    """colorjitter (K0c): base patch [3,ph,pw] f32, factors [B,3] f32 (brightness, contrast, saturation) -> packed f32 [total]: image b's
+    jittered patch [3,ph,pw] at pdesc[b].offset (include/vaa.h states the arithmetic)."""
+    _need(patch, torch.float32, "patch")
+    B = int(pdesc.shape[0])
+    _need(pdesc, torch.int32, "pdesc", (B, 4))
+    _need(factors, torch.float32, "factors", (B, 3))
+    packed = torch.zeros(int(total), dtype=torch.float32, device=patch.device)
+    with _timed("K0_patch_jitter_fwd", B=B):
+        rc = _lib.lib().vaa_patch_jitter_fwd(patch.data_ptr(), int(patch.shape[1]), int(patch.shape[2]), factors.data_ptr(), pdesc.data_ptr(), B,
+                                             packed.data_ptr(), _stream())
+    _lib.check(rc, "vaa_patch_jitter_fwd")
+    return packed
+
+
+def patch_jitter_bwd(gpacked, patch, factors, pdesc):
+    """Adjoint of patch_jitter_fwd summed over the images: gpacked f32 [total] -> d L / d base patch [3,ph,pw] (gates recomputed from `patch`)."""
+    _need(gpacked, torch.float32, "gpacked")
+    _need(patch, torch.float32, "patch")
+    B, ph, pw = int(pdesc.shape[0]), int(patch.shape[1]), int(patch.shape[2])
+    _need(pdesc, torch.int32, "pdesc", (B, 4))
+    _need(factors, torch.float32, "factors", (B, 3))
+    L = _lib.lib()
+    ws = _workspace(gpacked.device, L.vaa_patch_jitter_ws_bytes(B, ph, pw), "jitter")
+    g = torch.empty((3, ph, pw), dtype=torch.float32, device=gpacked.device)
+    with _timed("K0_patch_jitter_bwd", B=B):
+        rc = L.vaa_patch_jitter_bwd(gpacked.data_ptr(), patch.data_ptr(), ph, pw, factors.data_ptr(), pdesc.data_ptr(), B, g.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), _stream())
+    _lib.check(rc, "vaa_patch_jitter_bwd")
+    return g
+
+
 def patch_apply_fwd_multi(img_u8, packed, pdesc, max_hw, xy, theta, geometry: bool, mask_mode: int = MASK_LT_M20, want_keep: bool = True,
                           mean6=None, std6=None):
-    """K1 with one patch per image (packed/pdesc from patch_resize_fwd). max_hw = (max h, max w) over the batch (host ints)."""
+    """K1 with one patch per image (packed/pdesc from patch_resize_fwd or patch_jitter_fwd). max_hw = (max h, max w) over the batch (host ints)."""
     return _k1(img_u8, packed, xy, theta, geometry, mask_mode, mean6, std6, pdesc, max_hw, want_keep=want_keep)
 
 
@@ -325,7 +357,7 @@ def patch_grad_gather_multi(gout_bf16, packed, pdesc, max_hw, xy, theta, keep_bi
 
 
 # ------------------------------------------------------------------------------------------------------
-# autograd: the five Functions share one forward and one backward; each names its variant
+# autograd: the seven Functions share one forward and one backward; each names its variant
 # ------------------------------------------------------------------------------------------------------
 class PatchEmbeds(tuple):
     """(e0, e1): the two ViT patch-embed outputs [B,256,D] of a patched batch, standing in for `pixel_values` on the path that
@@ -352,10 +384,19 @@ def _resized_pack(patch, sizes):
     return patch_resize_fwd(patch, pdesc, total), pdesc, (int(pdesc_np[:, 0].max()), int(pdesc_np[:, 1].max()))
 
 
-def _paste_forward(ctx, p, img_u8, xy, theta, geometry, mask_mode, mean6, std6, pdesc=None, max_hw=None, embed=None, sink=None, base=None):
+def _jittered_pack(patch, factors):
+    """The prologue of colorjitter: factors [B,3] on the device -> (every image's own jittered patch, packed (K0c); pdesc on the device; (ph, pw))."""
+    ph, pw = int(patch.shape[1]), int(patch.shape[2])
+    pdesc_np, total = make_pdesc([(ph, pw)] * int(factors.shape[0]))
+    pdesc = torch.from_numpy(pdesc_np).to(patch.device, non_blocking=True)
+    return patch_jitter_fwd(patch, factors, pdesc, total), pdesc, (ph, pw)
+
+
+def _paste_forward(ctx, p, img_u8, xy, theta, geometry, mask_mode, mean6, std6, pdesc=None, max_hw=None, embed=None, sink=None, base=None, factors=None):
     """Forward of every PatchApply* Function. p: what K1 pastes — the patch, or with pdesc / max_hw the per-image patches. embed=None: K1 planar
     -> pixel values; embed=(w0, b0, wp0, w1, b1, wp1): K1 writes the two GEMM operands directly (tile-major: no [B,6,224,224] tensor, no im2col
-    copies) -> the two patch-embed outputs. base: the base patch p was resized from (the backward then ends in the resize adjoint)."""
+    copies) -> the two patch-embed outputs. base: the base patch p was resized from (the backward then ends in the resize adjoint) or, with
+    factors [B,3], jittered from (it ends in the jitter adjoint)."""
     if embed is None:
         ret, keep = _k1(img_u8, p, xy, theta, geometry, mask_mode, mean6, std6, pdesc, max_hw)
         mask = (keep,)
@@ -364,7 +405,9 @@ def _paste_forward(ctx, p, img_u8, xy, theta, geometry, mask_mode, mean6, std6, 
         t0, t1, keep_t, flags = _k1(img_u8, p, xy, theta, geometry, mask_mode, mean6, std6, pdesc, max_hw, tiles=True)
         ret = torch.nn.functional.linear(t0, w0, b0), torch.nn.functional.linear(t1, w1, b1)
         mask = (keep_t, flags, wp0, wp1)
-    ctx.save_for_backward(p, xy, theta if geometry else xy, pdesc if base is not None else xy, *mask)
+    jit = (base, factors) if factors is not None else (xy, xy)
+    ctx.save_for_backward(p, xy, theta if geometry else xy, pdesc if base is not None else xy, *jit, *mask)
+    ctx.jittered = factors is not None
     ctx.geometry, ctx.mask_mode, ctx.std6, ctx.sink = bool(geometry), int(mask_mode), std6, sink
     ctx.max_hw, ctx.base_hw = (max_hw, (int(base.shape[1]), int(base.shape[2]))) if base is not None else (None, None)
     return ret
@@ -372,8 +415,9 @@ def _paste_forward(ctx, p, img_u8, xy, theta, geometry, mask_mode, mean6, std6, 
 
 def _paste_backward(ctx, *grads):
     """Backward of every PatchApply* Function: K2 on the pixel gradient, or K2' on the gradients of the two patch-embed outputs. With a sink the
-    partial tiles are left in sink["partials"] for the caller's step epilogue and there is no gradient; a resized patch ends in the resize adjoint."""
-    p, xy, theta, pdesc, *mask = ctx.saved_tensors
+    partial tiles are left in sink["partials"] for the caller's step epilogue and there is no gradient; a resized patch ends in the resize adjoint,
+    a jittered one in the jitter adjoint."""
+    p, xy, theta, pdesc, base, factors, *mask = ctx.saved_tensors
     g = [t.to(torch.bfloat16).contiguous() for t in grads]
     if p.dim() == 4:  # a sweep's patches [P,3,ph,pw]: the keep words are given, K2' never reads patch values, only the [3,ph,pw] shape
         p = p[0]
@@ -394,7 +438,9 @@ def _paste_backward(ctx, *grads):
     if defer:
         ctx.sink["partials"] = out
         return None
-    return patch_resize_bwd(out, pdesc, *ctx.base_hw) if ctx.base_hw is not None else out
+    if ctx.base_hw is None:
+        return out
+    return patch_jitter_bwd(out, base, factors, pdesc) if ctx.jittered else patch_resize_bwd(out, pdesc, *ctx.base_hw)
 
 
 class PatchApply(torch.autograd.Function):
@@ -419,6 +465,21 @@ class PatchApplyResized(torch.autograd.Function):
         p = patch.detach().contiguous()
         packed, pdesc, max_hw = _resized_pack(p, sizes)
         return _paste_forward(ctx, packed, img_u8, xy, theta, geometry, mask_mode, mean6, std6, pdesc, max_hw, base=p)
+
+    @staticmethod
+    def backward(ctx, gout):
+        return (_paste_backward(ctx, gout),) + (None,) * 8
+
+
+class PatchApplyJittered(torch.autograd.Function):
+    """colorjitter: jitter (K0c) + K1 with per-image patches forward; K2 (per-image gradients) + jitter adjoint backward.
+    `factors` is a device tensor [B,3] f32 (brightness, contrast, saturation)."""
+
+    @staticmethod
+    def forward(ctx, patch, img_u8, factors, xy, theta, geometry, mask_mode, mean6=None, std6=None):
+        p = patch.detach().contiguous()
+        packed, pdesc, max_hw = _jittered_pack(p, factors)
+        return _paste_forward(ctx, packed, img_u8, xy, theta, geometry, mask_mode, mean6, std6, pdesc, max_hw, base=p, factors=factors)
 
     @staticmethod
     def backward(ctx, gout):
@@ -474,6 +535,22 @@ class PatchApplyResizedEmbed(torch.autograd.Function):
         p = patch.detach().contiguous()
         packed, pdesc, max_hw = _resized_pack(p, sizes)
         return _paste_forward(ctx, packed, img_u8, xy, theta, geometry, mask_mode, mean6, std6, pdesc, max_hw, embed=(w0, b0, wp0, w1, b1, wp1), base=p)
+
+    @staticmethod
+    def backward(ctx, d0, d1):
+        return (_paste_backward(ctx, d0, d1),) + (None,) * 14
+
+
+class PatchApplyJitteredEmbed(torch.autograd.Function):
+    """colorjitter with the pixel gradient un-materialised: jitter (K0c) + K1 tile-major with per-image patches + both patch-embed GEMMs
+    forward; K2' in per-image mode + the jitter adjoint backward."""
+
+    @staticmethod
+    def forward(ctx, patch, img_u8, factors, xy, theta, geometry, mask_mode, mean6, std6, w0, b0, wp0, w1, b1, wp1):
+        p = patch.detach().contiguous()
+        packed, pdesc, max_hw = _jittered_pack(p, factors)
+        return _paste_forward(ctx, packed, img_u8, xy, theta, geometry, mask_mode, mean6, std6, pdesc, max_hw, embed=(w0, b0, wp0, w1, b1, wp1),
+                              base=p, factors=factors)
 
     @staticmethod
     def backward(ctx, d0, d1):

@@ -11,7 +11,8 @@ Differences a caller can observe (all documented in DESIGN.md):
   * images may be a list of PIL images / HWC uint8 arrays (staged to the device once and cached while the same
     list object is passed again, i.e. for all innerLoop steps of an outer iteration) or a uint8 device tensor.
   * Appendix A defects: D1 (IndentationError) n/a; D2 (resize_patch UnboundLocalError) resolved as "scale the BASE
-    patch per image"; D3 (`colorjitter=` kwarg) accepted and ignored.
+    patch per image"; D3 (`colorjitter=` kwarg, dead in the reference) given a meaning here: a per-image brightness / contrast /
+    saturation draw on the patch (include/vaa.h states the arithmetic; `_draw_jitter` the draws). Off by default: zero extra RNG calls.
 """
 from __future__ import annotations
 
@@ -22,6 +23,20 @@ import torch
 
 from . import ops
 from .constants import IMG, MAX_ANGLE_DEG, MAX_SHEAR, P_IDENTITY
+
+JITTER_STRENGTH = (0.2, 0.2, 0.2)  # colorjitter=True: brightness, contrast, saturation factors ~ U(1 - s, 1 + s)
+
+
+def jitter_strength(colorjitter):
+    """`colorjitter` as the callers pass it -> None (off) or the three strengths (True: the default; a 3-tuple sets them)."""
+    if colorjitter is None or colorjitter is False:
+        return None
+    if colorjitter is True:
+        return JITTER_STRENGTH
+    s = tuple(float(v) for v in colorjitter)
+    if len(s) != 3 or not all(0.0 <= v <= 1.0 for v in s):
+        raise ValueError(f"colorjitter must be a bool or three strengths in [0, 1] (brightness, contrast, saturation), got {colorjitter!r}")
+    return s
 
 
 def _six(mean, std):
@@ -39,11 +54,13 @@ class RandomPatchTransform:
         self.shx = MAX_SHEAR  # :12
         self.shy = MAX_SHEAR  # :13
         self.resize_patch = resize_patch
+        self.colorjitter = False  # set by the attackers whose training steps jitter: those steps stay off the fused single-patch paths
         self._staged_key = None
         self._staged = None
         self.embed_with = None  # a model exposing patch_embed_params(): training calls then return ops.PatchEmbeds
         self.last_params = None  # (xy, theta) of the most recent call, host numpy (tests / logging)
         self.last_sizes = None   # resize_patch=True: per-image (h, w) of the most recent call
+        self.last_jitter = None  # colorjitter: per-image (brightness, contrast, saturation) factors of the most recent call, float32 [B,3]
 
     # ---- small tensor helpers kept for API compatibility (:16-24) ----
     def normalize(self, images, mean, std):
@@ -137,10 +154,19 @@ class RandomPatchTransform:
         where the warped canvas is >= -20, normalise twice and stack to 6 channels (:104-136). Differentiable w.r.t. patch.
         grad_sink (dict, one patch for the batch): the backward leaves K2's (or K2''s) partial tiles in grad_sink["partials"] instead of a
         patch gradient — the caller adds them with ops.step_epilogue (into the DDP message and / or straight through the optimiser).
-        draws: (xy, theta) host arrays from `draw_params` to use instead of drawing (a maskidx sweep hands every group the same draws)."""
+        draws: (xy, theta) host arrays from `draw_params` to use instead of drawing (a maskidx sweep hands every group the same draws).
+        colorjitter (True: strengths 0.2 each; or three strengths): every image pastes its own brightness / contrast / saturation variant of the
+        patch (`_apply_jittered`); False makes no extra RNG call."""
         mean6, std6 = _six(mean, std)
         img = self.stage_images(images)
         B = img.shape[0]
+        strength = jitter_strength(colorjitter)
+        if strength is not None:
+            if self.resize_patch:
+                raise ValueError("colorjitter with resize_patch is not supported")
+            if grad_sink is not None:
+                raise ValueError("grad_sink is not available with colorjitter (per-image gradients go through the jitter adjoint)")
+            return self._apply_jittered(img, patch, mean6, std6, geometry, out_dtype, strength, draws)
         if self.resize_patch:
             if grad_sink is not None:
                 raise ValueError("grad_sink is not available with resize_patch=True (per-image gradients go through the resize adjoint)")
@@ -203,6 +229,28 @@ class RandomPatchTransform:
         if emb is not None:
             return ops.PatchEmbeds(ops.PatchApplyResizedEmbed.apply(patch, img, sizes, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6, *emb))
         out = ops.PatchApplyResized.apply(patch, img, sizes, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6)
+        return out if out_dtype == torch.bfloat16 else out.to(out_dtype)
+
+    def _draw_jitter(self, batch, strength):
+        """3 * batch calls random.uniform(1 - s_k, 1 + s_k): image-major, in order brightness, contrast, saturation."""
+        f = np.empty((batch, 3), np.float32)
+        for b in range(batch):
+            for k in range(3):
+                f[b, k] = random.uniform(1.0 - strength[k], 1.0 + strength[k])
+        return f
+
+    def _apply_jittered(self, img, patch, mean6, std6, geometry, out_dtype, strength, draws=None):
+        """colorjitter: the placement draws of the un-jittered call first, then the factors. The whole batch is one jitter launch + one K1
+        launch with per-image patches (`ops.PatchApplyJittered`); the backward is K2 / K2' with per-image outputs + the jitter adjoint."""
+        B, ph, pw = int(img.shape[0]), int(patch.shape[1]), int(patch.shape[2])
+        xy_n, theta_n = draws if draws is not None else self._draw(B, ph, pw, geometry)
+        self.last_jitter = self._draw_jitter(B, strength)
+        xy, theta = self._to_dev(xy_n, theta_n)
+        factors = torch.from_numpy(self.last_jitter).to(self.device, non_blocking=True)
+        emb = self._embed_params(patch, out_dtype)
+        if emb is not None:
+            return ops.PatchEmbeds(ops.PatchApplyJitteredEmbed.apply(patch, img, factors, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6, *emb))
+        out = ops.PatchApplyJittered.apply(patch, img, factors, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6)
         return out if out_dtype == torch.bfloat16 else out.to(out_dtype)
 
     def _paste(self, images, patch, mean, std, out_dtype):

@@ -44,7 +44,8 @@ __device__ __forceinline__ size_t row_offset(const LossArgs& a, int b, int k, in
     return a.layout == VAA_LAYOUT_FULL ? ((size_t)b * a.S + (a.S - a.L + k)) * a.V : (size_t)rowidx * a.V;
 }
 
-// Label access: the whole [B,L] matrix staged in LDS as int16 (token ids < 32768, -100 stays -100) when it fits, else global.
+// Label access: the whole [B,L] matrix staged in LDS as int16 when it fits AND every token id does (V <= 32768: ids < 32768, -100 stays -100),
+// else global: at a wider vocabulary an id >= 32768 would wrap negative in 16 bits (a label that addresses memory in front of its row).
 struct Labels {
     const int64_t* g;
     const int16_t* l;  // nullptr -> read from global
@@ -57,7 +58,7 @@ __device__ __forceinline__ Labels stage_labels(const LossArgs& a, int16_t* lds) 
     lb.g = a.labels;
     lb.l = nullptr;
     const int n = a.B * a.L;
-    if (n <= kLabLds) {
+    if (n <= kLabLds && a.V <= 32768) {
         for (int e = threadIdx.x; e < n; e += NT) lds[e] = (int16_t)a.labels[e];
         lb.l = lds;
         __syncthreads();

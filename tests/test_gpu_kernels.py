@@ -529,6 +529,15 @@ def _check_rows(g_full, labels, d, pfx, rtol):
     return gr
 
 
+def _check_fp64(g_full, labels, logits, mode, **kw):
+    """The fp32 gradient of the labelled rows element by element against the fp64 reference's bound (tests/loss_ref.py), beside the max-norm checks."""
+    import loss_ref
+
+    rows = _rows(np.asarray(labels))
+    rb, rp = torch.tensor([r[0] for r in rows]), torch.tensor([r[1] for r in rows])
+    loss_ref.compare(loss_ref.loss_ref(logits[rb, rp].cpu(), torch.as_tensor(np.asarray(labels)), mode, **kw), grad=g_full[rb, rp], layout="ROWS", tag=mode)
+
+
 @pytest.mark.parametrize("tag", ["m0", "m012", "m6", "mall"])
 def test_k3_uada_vs_reference_golden(ops, tag):
     d = np.load(os.path.join(GOLDEN, f"k3_uada_{tag}.npz"))
@@ -540,10 +549,12 @@ def test_k3_uada_vs_reference_golden(ops, tag):
     assert abs(sc[0] - float(d["total"])) < 3e-5 and abs(sc[1] - float(d["ce"])) < 3e-5 and abs(sc[2] - float(d["mse"])) < 3e-5
     assert abs(sc[7] - float(d["uad"])) < 1e-6
     gr = _check_rows(g.cpu().numpy(), d["masked"], d, "uada", 2e-4)
+    _check_fp64(g, d["masked"], logits, "UADA", w=5.0)
     # DDP mode (no 1/CE term) with --MSE_weights
     sc2, _, g2 = ops.loss_fwd_bwd(logits, labels, ops.LOSS_UADA_DDP, w=float(d["ddp_w"]))
     assert abs(sc2.cpu().numpy()[0] - float(d["ddp_mse"])) < 3e-5
     _check_rows(g2.cpu().numpy(), d["masked"], d, "ddp", 2e-4)
+    _check_fp64(g2, d["masked"], logits, "UADA_DDP", w=float(d["ddp_w"]))
     # ROWS layout on the compacted labelled rows gives the same numbers
     rows = _rows(d["masked"])
     compact = logits[torch.tensor([r[0] for r in rows]), torch.tensor([r[1] for r in rows])].contiguous()
@@ -576,6 +587,7 @@ def test_k3_upa_vs_reference_golden(ops, tag):
     sc = sc.cpu().numpy()
     assert abs(sc[0] - float(d["total"])) < 3e-5 and abs(sc[3] - float(d["angle"])) < 3e-5 and abs(sc[4] - float(d["dist"])) < 3e-5
     _check_rows(g.cpu().numpy(), d["labels"], d, "upa", 2e-4)
+    _check_fp64(g, d["labels"], logits, "UPA", alpha=float(d["alpha"]), beta=float(d["belta"]))
 
 
 @pytest.mark.parametrize("tag", ["t0", "t012"])
@@ -586,6 +598,7 @@ def test_k3_tma_vs_reference_golden(ops, tag):
     sc, _, g = ops.loss_fwd_bwd(logits, _t(d["newlabels"]), ops.LOSS_CE, scale=1.0)
     assert abs(sc.cpu().numpy()[0] - float(d["ce"])) < 3e-5
     _check_rows(g.cpu().numpy(), d["newlabels"], d, "tma", 2e-4)
+    _check_fp64(g, d["newlabels"], logits, "CE", scale=1.0)
     sc2, _, g2 = ops.loss_fwd_bwd(logits, _t(d["newlabels"]), ops.LOSS_CE, scale=0.25)  # accumulate_steps = 4
     assert abs(sc2.cpu().numpy()[0] - 0.25 * float(d["ce"])) < 1e-5
     assert np.allclose(g2.cpu().numpy(), 0.25 * g.cpu().numpy(), rtol=1e-6, atol=1e-12)

@@ -54,6 +54,8 @@ def main(args):
         "maskidx": args.maskidx, "innerLoop": args.innerLoop, "geometry": args.geometry,
         "use_wandb": args.wandb_project != "false", "MSE_weights": args.MSE_weights, "colorjitter": cli.colorjitter_arg(args),
     }
+    if args.tv_weight or args.nps_weight:  # extension: total-variation / non-printability terms of the patch
+        instance_params.update(zip(("tv_weight", "nps_weight", "nps_palette"), cli.patch_reg_args(args)))
     if args.attack != "UADA":  # extension: the same data-parallel loop for UPA / TMA (BASELINE configs 4-5)
         instance_params.update(attack_type=args.attack, alpha=args.alpha, belta=args.belta, target_action=args.targetAction)
     for kind in KINDS:  # extensions: one patch per group of a sweep in one loop (patches under {path}/<group tag>/)

@@ -29,6 +29,7 @@ def main(args):
     os.makedirs(path, exist_ok=True)
     train_dataloader, val_dataloader = cli.synthetic_loaders(args.bs)
     attacker = OpenVLAAttacker(vla, None, path, optimizer="adamW", resize_patch=args.resize_patch, alpha=args.alpha, belta=args.belta)
+    attacker.set_patch_reg(*cli.patch_reg_args(args))
     attacker.patchattack_unconstrained(train_dataloader, val_dataloader, num_iter=args.iter, target_action=np.zeros(7),
                                        patch_size=args.patch_size, lr=args.lr, accumulate_steps=args.accumulate, maskidx=args.maskidx,
                                        warmup=args.warmup, filterGripTrainTo1=args.filterGripTrainTo1, geometry=args.geometry,

@@ -203,6 +203,38 @@ int vaa_patch_jitter_bwd(const float* gpacked, const float* patch, int ph, int p
                          float* gpatch, void* ws, size_t ws_bytes, void* stream);
 
 /*
+ * K6 — smoothness and printability terms of the patch: total variation (TV) and the non-printability score (NPS), values and gradient in ONE
+ * launch. The reference has no such term (they come with Thys et al.'s adversarial-patch code and Sharif et al.'s NPS), so the arithmetic is
+ * defined HERE. With p = patch [3,ph,pw], N = ph*pw texels t = (i,j), N3 = 3*N, q = palette [K,3] (1 <= K <= 64) and eps = 1e-6:
+ *     TV(p)  = ( sum_c sum_i sum_{j<pw-1} |p[c,i,j+1] - p[c,i,j]|  +  sum_c sum_{i<ph-1} sum_j |p[c,i+1,j] - p[c,i,j]| ) / N3
+ *     d_k(t) = sqrt( sum_c (p[c,t] - q[k,c])^2 + eps )
+ *     NPS(p) = ( sum_t min_k d_k(t) ) / N3
+ *     dTV/dp[c,i,j]  = ( sgn(p - left) - sgn(right - p) + sgn(p - up) - sgn(down - p) ) / N3     (absent neighbours contribute nothing; sgn(0) = 0)
+ *     dNPS/dp[c,t]   = (p[c,t] - q[k*,c]) / d_k*(t) / N3,   k* = the lowest index attaining the fp32 minimum
+ * The regulariser w_tv*TV + w_nps*NPS is minimised (as every attack loss is). Rounding sequence, fp32, every FMA explicit:
+ *     e_c = p[c,t] - q[k,c];   d_k = sqrt( fma(e_2, e_2, fma(e_1, e_1, e_0*e_0)) + eps )  (correctly rounded sqrt);   k* by `d < best`, k ascending
+ *     s_c = ((sgn(p - left) - sgn(right - p)) + sgn(p - up)) - sgn(down - p)            (differences rounded once; the sum is a small integer)
+ *     c_tv = (float)((double)w_tv / N3),  c_nps = (float)((double)w_nps / N3)
+ *     r_c = fma(c_tv, s_c, c_nps * (e_c / d_k*))        both weights non-zero
+ *         = c_nps * (e_c / d_k*)                        w_tv == 0 (the TV gradient work is skipped)
+ *         = c_tv * s_c                                  w_nps == 0
+ * NaN rule: a NaN texel gives a NaN distance to every colour; a NaN distance is taken by the minimum and kept, so that texel's three gradient
+ * elements and the NPS sum are NaN (sgn(NaN) = 0, torch's rule: the TV gradient of its neighbours stays finite).
+ *   patch    dev  [3,ph,pw] float32
+ *   palette  dev  [K,3] float32, or NULL with K = 0 when w_nps == 0 (the NPS value is then 0)
+ *   grad     dev  [3,ph,pw] float32 or NULL (values only): accumulate = 0 writes r, accumulate = 1 writes grad + r — ONE rounded add of exactly
+ *             the r the write form produces
+ *   part     dev  float64 [vaa_patch_reg_parts(ph,pw)][2] out: per workgroup (256 consecutive texels) {sum of the right / down |differences|
+ *             its texels own, sum of their min distances}, un-normalised, accumulated in a fixed order (the thread's own terms in channel order,
+ *             a butterfly over the wave, the waves in order): the same arguments give the same bits. TV = sum(part[:,0]) / N3 and
+ *             NPS = sum(part[:,1]) / N3 are folded by the caller when it wants them; the launch has no atomics and no hand-over.
+ * VAA_E_INVALID before any launch: NULL patch or part, a non-finite weight, K > 64, K < 1 (or a NULL palette) while w_nps != 0.
+ */
+size_t vaa_patch_reg_parts(int ph, int pw);
+int vaa_patch_reg(const float* patch, int ph, int pw, const float* palette, int K, float w_tv, float w_nps, float* grad, int accumulate,
+                  double* part, void* stream);
+
+/*
  * K3 — replaces HF Llama's `.loss` (via modeling_prismatic.py:404-415) + OpenVLAAttacker.weighted_loss
  * (UADA.py:381-406, UADA_ddp.py:99-124, UPA.py:367-387) and their autograd backward to the logits.
  *   logits   dev  f32|bf16, layout FULL [B,S,V] or ROWS [R,V]. For ROWS pass S = R (the number of rows, which must equal the number

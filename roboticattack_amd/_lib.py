@@ -47,6 +47,8 @@ EXPORTS = (
     "vaa_patch_jitter_fwd",
     "vaa_patch_jitter_ws_bytes",
     "vaa_patch_jitter_bwd",
+    "vaa_patch_reg_parts",
+    "vaa_patch_reg",
     "vaa_patch_apply_fwd_multi",
     "vaa_patch_grad_gather_multi",
     "vaa_loss_rowmap_bytes",
@@ -179,6 +181,10 @@ def lib() -> C.CDLL:
     L.vaa_patch_jitter_ws_bytes.argtypes = [i32, i32, i32]
     L.vaa_patch_jitter_bwd.restype = i32
     L.vaa_patch_jitter_bwd.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, sz, vp]
+    L.vaa_patch_reg_parts.restype = sz
+    L.vaa_patch_reg_parts.argtypes = [i32, i32]
+    L.vaa_patch_reg.restype = i32
+    L.vaa_patch_reg.argtypes = [vp, i32, i32, vp, i32, f32, f32, vp, i32, vp, vp]
     L.vaa_patch_apply_fwd_multi.restype = i32
     L.vaa_patch_apply_fwd_multi.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, vp, vp]
     L.vaa_patch_grad_gather_multi.restype = i32

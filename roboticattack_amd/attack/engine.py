@@ -13,7 +13,7 @@ import pickle
 import numpy as np
 import torch
 
-from .. import _lib, ops
+from .. import _lib, ops, palette as _palette
 from ..action_tokenizer import ActionTokenizer
 from ..constants import MEAN0, MEAN1, STD0, STD1
 from ..transform import RandomPatchTransform
@@ -101,6 +101,54 @@ class AttackBase:
         self.optimizer = optimizer
         self.use_rows = hasattr(vla, "forward_rows")  # LM head on labelled rows only (no [B,S,32064] logits)
         self.n_img_tokens = vla.vision_backbone.featurizer.patch_embed.num_patches
+        self.tv_weight = self.nps_weight = 0.0  # the patch regulariser (K6) is off until set_patch_reg turns it on
+        self._reg_palette_host = self._reg_palette = self._reg_part = None
+
+    # ---- smoothness / printability terms of the patch (K6: total variation + non-printability score) ----
+    def set_patch_reg(self, tv_weight: float = 0.0, nps_weight: float = 0.0, palette=None):
+        """An EXTENSION (the reference has no such term): every training step adds the gradient of tv_weight*TV(patch) + nps_weight*NPS(patch, palette)
+        — always minimised — to the patch gradient (add_patch_reg). `palette`: [K,3] RGB in [0,1], K <= 64; None = the built-in 27-colour grid
+        (palette.default_palette: a placeholder for a measured printer palette). Both weights 0 (the default) leaves every step as it is."""
+        tv_weight, nps_weight = float(tv_weight), float(nps_weight)
+        if not (np.isfinite(tv_weight) and np.isfinite(nps_weight)) or tv_weight < 0 or nps_weight < 0:
+            raise ValueError(f"tv_weight / nps_weight must be finite and >= 0, got {tv_weight}, {nps_weight}")
+        self.tv_weight, self.nps_weight = tv_weight, nps_weight
+        self._reg_palette_host = _palette.check_palette(palette) if palette is not None else _palette.default_palette()
+        self._reg_palette = self._reg_part = None
+
+    @property
+    def patch_reg_on(self) -> bool:
+        return self.tv_weight != 0.0 or self.nps_weight != 0.0
+
+    def _reg_palette_on(self, device):
+        if self._reg_palette is None or self._reg_palette.device != device:
+            self._reg_palette = torch.from_numpy(self._reg_palette_host).to(device)
+        return self._reg_palette
+
+    def add_patch_reg(self, patch, scale: float = 1.0):
+        """Right after `total.backward()`: patch.grad += scale * d(tv_weight*TV + nps_weight*NPS)/d patch, in place, ONE launch (in front of UPA's L1
+        clip, the PGD sign and the data-parallel exchange); the launch's partial sums of the two values are kept for the log (patch_reg_log).
+        Both weights 0: nothing happens — no launch, no allocation."""
+        if not self.patch_reg_on:
+            return
+        if patch.grad is None:
+            raise ValueError("add_patch_reg: patch.grad is not materialised (the fused single-patch paths are off while a weight is non-zero)")
+        _, self._reg_part = ops.patch_reg_grad(patch.detach(), self._reg_palette_on(patch.device), self.tv_weight * scale, self.nps_weight * scale,
+                                               grad=patch.grad, accumulate=True, part=self._reg_part)
+
+    def patch_reg_log(self, prefix: str, patch=None) -> dict:
+        """{prefix_tv: TV, prefix_nps: NPS} for a log, {} while the regulariser is off. `patch` None: the values of the last add_patch_reg, folded
+        from the partial sums that launch left (call it behind the outer iteration's read-back); a patch: the values-only launch on it."""
+        if not self.patch_reg_on:
+            return {}
+        if patch is not None:
+            _, part = ops.patch_reg_grad(patch.detach(), self._reg_palette_on(patch.device), self.tv_weight, self.nps_weight, want_grad=False)
+        else:
+            part, patch = self._reg_part, self.patch
+        if part is None:
+            return {}
+        tv, nps = (float(v) for v in torch.stack(ops.patch_reg_values(part, patch.numel())).cpu())
+        return {f"{prefix}_patch_tv": tv, f"{prefix}_patch_nps": nps}
 
     # ---- the model + loss leg of a step ----
     def model_loss(self, input_ids, attention_mask, pix, labels, mode, w=5.0, alpha=0.8, beta=0.2, scale=1.0, need_grad=True, full_ce=True, read_scalars=True):
@@ -182,10 +230,11 @@ class AttackBase:
     def fused_ddp_available(self) -> bool:
         """K1 (tile-major) -> model -> K3 statistics (+ gradient slice) -> K2' tiles + scatter -> ONE epilogue launch (K2's final sum, K3's
         fold, the DDP message) needs a model that exposes its patch-embed weights and its hidden rows, and one patch per batch (no resize_patch,
-        no colorjitter: their per-image patches go through the per-image forms of K1 / K2')."""
+        no colorjitter: their per-image patches go through the per-image forms of K1 / K2'), and no patch regulariser (K6 adds to a materialised
+        patch.grad, which this path never builds)."""
         t = self.randomPatchTransform
         return (os.environ.get("VAA_FUSED_EPILOGUE", "1") != "0" and self.use_rows and hasattr(self.vla, "hidden_rows")
-                and t.embed_with is not None and not t.resize_patch and not t.colorjitter)
+                and t.embed_with is not None and not t.resize_patch and not t.colorjitter and not self.patch_reg_on)
 
     @staticmethod
     def _fused_head(R, h, W) -> bool:
@@ -270,7 +319,8 @@ class AttackBase:
         L1 clip (UPA's clip needs the whole gradient's norm first). Works behind both boundaries: K2' (a model that exposes its patch-embed
         weights) and K2 on a black-box model's pixel gradient."""
         t = self.randomPatchTransform
-        ok = os.environ.get("VAA_FUSED_EPILOGUE", "1") != "0" and not t.resize_patch and not t.colorjitter and not optimizer.l1_clip
+        ok = (os.environ.get("VAA_FUSED_EPILOGUE", "1") != "0" and not t.resize_patch and not t.colorjitter and not optimizer.l1_clip
+              and not self.patch_reg_on)  # (K6 adds to patch.grad, which the fused update never materialises)
         return {} if ok else None
 
     def fused_update(self, sink, patch, optimizer, scalars):

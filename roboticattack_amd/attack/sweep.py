@@ -199,6 +199,8 @@ def check(attacker, kind: SweepKind, groups):
         refuse("resize_patch=True is not supported (one patch size per group only)")
     if attacker.randomPatchTransform.colorjitter:
         refuse("colorjitter is not supported (one shared patch per group only)")
+    if attacker.patch_reg_on:
+        refuse("tv_weight / nps_weight are not supported (the sweeps' K4 lives inside the segmented epilogue: patch.grad is never materialised)")
     if not attacker.fused_ddp_available():
         refuse("needs the fused path (a model that exposes its patch-embed weights and hidden rows, VAA_FUSED_EPILOGUE != 0)")
     if P * bs > SWEEP_MAX_IMAGES:

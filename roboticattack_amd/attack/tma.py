@@ -66,6 +66,7 @@ class OpenVLAAttacker(AttackBase):
         pix = self._images(pixel_values, patch, geometry, colorjitter, grad_sink=sink)
         total, scalars, pred = self.model_loss(input_ids, attention_mask, pix, newlabels, ops.LOSS_CE, scale=1.0 / accumulate_steps)
         total.backward()
+        self.add_patch_reg(patch, scale=1.0 / accumulate_steps)  # K6: + the TV / NPS gradient, scaled like the loss, in front of the PGD sign
         fused = sink is not None and "partials" in sink
         if fused:
             self.fused_update(sink, patch, optimizer, scalars)
@@ -127,6 +128,7 @@ class OpenVLAAttacker(AttackBase):
             self.last_train_log = {"TRAIN_attack_loss(CE)": loss, "TRAIN_patch_gradient": float(host[-1, 9]),
                                    "TRAIN_LR": optimizer.param_groups[0]["lr"], "TRAIN_inner_avg_loss": inner_avg_loss,
                                    "TRAIN_inner_relatived_distance": inner_rel}
+            self.last_train_log.update(self.patch_reg_log("TRAIN"))
             if wandb_enabled(args):
                 wandb.log(self.last_train_log, step=i)
             self.train_CE_loss.append(loss)
@@ -188,6 +190,7 @@ class OpenVLAAttacker(AttackBase):
         ASR = success / val_num_sample
         val_rel /= val_num_sample
         self.last_val_log = {"VAL_avg_CE_loss": avg_CE, "VAL_avg_L1_loss": avg_L1, "VAL_ASR": ASR, "VAL_inner_relatived_distance": val_rel}
+        self.last_val_log.update(self.patch_reg_log("VAL", patch))
         if len(maskidx) == 1 and maskidx[0] == 6:
             s02, n0, s12, n1, so2, no = asr6
             self.last_val_log.update({"ASR_02other": s02 / n0 if n0 else 0, "ASR_12other": s12 / n1 if n1 else 0,

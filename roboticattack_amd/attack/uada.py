@@ -38,6 +38,7 @@ class OpenVLAAttacker(AttackBase):
                                                                   colorjitter=self.randomPatchTransform.colorjitter, **({"grad_sink": sink} if sink is not None else {}))
         total, scalars, pred = self.model_loss(input_ids, attention_mask, pix, labels, self.loss_mode, w=self.mse_weight)
         total.backward()
+        self.add_patch_reg(patch)  # K6: + the TV / NPS gradient (a no-op while both weights are 0)
         scalars_out[k, :8] = scalars
         if sink is not None and "partials" in sink:
             self.fused_update(sink, patch, optimizer, scalars)  # K2's final sum + K4 (AdamW + clamp(0,1)) in one launch
@@ -98,6 +99,7 @@ class OpenVLAAttacker(AttackBase):
             train_relative_distance = self.calculate_relative_distance(cont_pred, cont_gt, maskidx, train_relative_distance)
             train_logdata = {"TRAIN_attack_loss(CE)": celoss, "TRAIN_patch_gradient": log_patch_grad,
                              "TRAIN_LR": optimizer.param_groups[0]["lr"], "TRAIN_attack_loss (MSE_Distance)": total, "TRAIN_UAD": UAD}
+            train_logdata.update(self.patch_reg_log("TRAIN"))  # the last inner step's TV / NPS (nothing while the regulariser is off)
             for key, value in train_relative_distance.items():
                 train_logdata[f"train_rd_{key}"] = sum(value) / len(value)
             self.last_train_log = train_logdata
@@ -141,6 +143,7 @@ class OpenVLAAttacker(AttackBase):
         avg_UAD /= val_num_sample
         avg_CE_loss /= val_num_sample
         log_data = {"VAL_MSE_Distance": avg_MSE_Distance, "VAL_UAD": val_UAD}
+        log_data.update(self.patch_reg_log("VAL", patch))
         for key, value in relative_distance.items():
             log_data[f"val_rd_{key}"] = sum(value) / len(value)
         self.last_val_log = log_data

@@ -60,7 +60,7 @@ class OpenVLAAttacker(AttackBase):
     def __init__(self, vla_path, dataset_name, save_dir="", resize_patch=False, patch_size=[3, 50, 50], lr=0.01, bs=1, warmup=20,
                  num_iter=10000, maskidx=[], innerLoop=1, geometry=True, use_wandb=True, MSE_weights=1,
                  model_factory=None, dataset_factory=None, device=None, attack_type="UADA", alpha=0.8, belta=0.2, target_action=0.0, maskidx_sweep=None,
-                 target_sweep=None, upa_sweep=None, colorjitter=False):
+                 target_sweep=None, upa_sweep=None, colorjitter=False, tv_weight=0.0, nps_weight=0.0, nps_palette=None):
         """`attack_type`, `alpha`, `belta`, `target_action` are EXTENSIONS (the reference ships DDP for UADA only):
         "UPA" = UPA.py's reverse-direction loss + L1 grad clip, "TMA" = TMA.py's target-token CE, same data-parallel loop.
         `maskidx_sweep`, `target_sweep` (attack_type="TMA" only), `upa_sweep` (attack_type="UPA" only) are EXTENSIONS, at most one per run (sweep.KINDS):
@@ -68,7 +68,9 @@ class OpenVLAAttacker(AttackBase):
         group sees the same frames, draws and schedule, and group p ends where a standalone run with entry p in place of `maskidx` / `maskidx` and
         `target_action` / `alpha` and `belta` (then unused) and the same seed ends (DESIGN.md §maskidx sweep). None keeps the loop as it is.
         `colorjitter` is an EXTENSION (True or three strengths): every training step pastes a per-image brightness / contrast / saturation variant
-        of the patch through the per-image forms of K1 / K2'; validation evaluates the patch as it is saved. Not available with a sweep."""
+        of the patch through the per-image forms of K1 / K2'; validation evaluates the patch as it is saved. Not available with a sweep.
+        `tv_weight`, `nps_weight`, `nps_palette` are EXTENSIONS (AttackBase.set_patch_reg): the total-variation and non-printability terms of the
+        patch; every rank adds their gradient before the exchange, so the rank mean carries it once. Not available with a sweep."""
         rank, world, local = vdist.env_rank_world()
         if device is None:
             device = vdist.local_device()
@@ -88,6 +90,8 @@ class OpenVLAAttacker(AttackBase):
             raise ValueError(f"attack_type must be UADA, UPA or TMA, got {attack_type!r}")
         self.attack_type, self.alpha, self.belta, self.target_action = attack_type, alpha, belta, target_action
         self.randomPatchTransform.colorjitter = colorjitter
+        if tv_weight or nps_weight or nps_palette is not None:
+            self.set_patch_reg(tv_weight, nps_weight, nps_palette)
         # at most one kind of sweep; the parameters are checked in KINDS' order, so a refusal of an earlier one comes first
         self.sweep_kind = self.sweep_groups = None
         given = dict(maskidx_sweep=maskidx_sweep, target_sweep=target_sweep, upa_sweep=upa_sweep)
@@ -154,6 +158,7 @@ class OpenVLAAttacker(AttackBase):
                 total, sc, _ = self.model_loss(input_ids, attention_mask, pix, labels, self._loss_mode(), w=float(self.MSE_weights),
                                                alpha=self.alpha, beta=self.belta, full_ce=full_ce, read_scalars=full_ce)
                 total.backward()  # K2 inside
+                self.add_patch_reg(patch)  # K6: + the TV / NPS gradient on every rank, before the exchange (a no-op while both weights are 0)
                 return lambda: sync.allreduce_step(patch.grad, sc, pick)
 
             s_sum, device_failure = self._inner_loop(optimizer, sync, world_size, step)
@@ -282,6 +287,7 @@ class OpenVLAAttacker(AttackBase):
         logs = [{"TRAIN_attack_loss(CE)": float(sg[0]), "TRAIN_patch_gradient": float(st[1]), "TRAIN_LR": lr,
                  "TRAIN_attack_loss (MSE_Distance)": float(sg[1]), "TRAIN_UAD": float(sg[2])} for sg, st in zip(s.reshape(-1, 4), stats)]
         if tags is None:
+            logs[0].update(self.patch_reg_log("TRAIN"))
             self.last_train_log = logs[0]
             if rank == 0 and self.use_wandb and wandb is not None:
                 wandb.log(logs[0], step=i)
@@ -367,6 +373,8 @@ class OpenVLAAttacker(AttackBase):
         g_UAD = vdist.allreduce_scalar(avg_UAD, "AVG", self.device)
         g_CE = vdist.allreduce_scalar(avg_CE, "AVG", self.device)
         log = {"VAL_MSE_Distance": g_MSE, "VAL_UAD": g_UAD}
+        if tag is None:
+            log.update(self.patch_reg_log("VAL", patch))
         if rank == 0:
             pre = "" if tag is None else f"{tag}/"
             best = self.MSE_Distance_best if tag is None else self.MSE_Distance_best[tag]

@@ -63,6 +63,7 @@ class OpenVLAAttacker(AttackBase):
         total, scalars, pred = self.model_loss(input_ids, attention_mask, pix, labels, mode, alpha=self.alpha, beta=self.belta, scale=scale, full_ce=False,
                                                read_scalars=read_scalars)
         total.backward()
+        self.add_patch_reg(patch)  # K6: + the TV / NPS gradient, in front of the L1 clip (a no-op while both weights are 0)
         if do_step:
             stats = optimizer.step()  # K4: L1 clip 1e-3 -> AdamW -> clamp
             if read_scalars:
@@ -114,6 +115,7 @@ class OpenVLAAttacker(AttackBase):
             self.last_train_log = {"TRAIN_attack_loss(CE)": loss, "TRAIN_patch_gradient": float(host[-1, 9]),
                                    "TRAIN_LR": optimizer.param_groups[0]["lr"], "TRAIN_ANGLE_LOSS": angle_loss,
                                    "TRAIN_DISTANCE_LOSS": distance_loss}
+            self.last_train_log.update(self.patch_reg_log("TRAIN"))
             if wandb_enabled(args):
                 wandb.log(self.last_train_log, step=i)
             self.train_CE_loss.append(loss)
@@ -148,6 +150,7 @@ class OpenVLAAttacker(AttackBase):
         avg_dist /= val_num_sample
         avg_res /= val_num_sample
         self.last_val_log = {"reverse_direction_loss": avg_res, "avg_angle_loss": avg_angle, "avg_distance_loss": avg_dist}
+        self.last_val_log.update(self.patch_reg_log("VAL", patch))
         if wandb_enabled(args):
             wandb.log(self.last_val_log, step=i)
         if avg_res < self.reverse_direction_loss:

@@ -3,7 +3,8 @@
 Flag names, types and defaults are the reference's (UADA_wrapper.py:87-121, UADA_wrapper_ddp.py:87-119,
 TMA_wrapper.py:89-124, UPA_wrapper.py:90-127). Added flags (all optional, defaults keep reference behaviour where the
 environment allows): --vla_path (local checkpoint dir, or random:openvla-7b / random:tiny / surrogate), --data (synthetic),
---colorjitter / --colorjitter_strength (photometric draw on the patch in training steps; off by default).
+--colorjitter / --colorjitter_strength (photometric draw on the patch in training steps; off by default),
+--tv_weight / --nps_weight / --nps_palette (total-variation and non-printability terms of the patch; off by default).
 """
 from __future__ import annotations
 
@@ -30,6 +31,14 @@ def three_floats(arg):
 def colorjitter_arg(args):
     """--colorjitter / --colorjitter_strength as the attackers take them: False, or the three strengths."""
     return tuple(args.colorjitter_strength) if args.colorjitter else False
+
+
+def patch_reg_args(args):
+    """--tv_weight / --nps_weight / --nps_palette as AttackBase.set_patch_reg (and the data-parallel attacker's constructor) take them:
+    (tv_weight, nps_weight, palette [K,3] | None = the built-in grid). The file is read here, so a bad palette stops the run before the model loads."""
+    from .palette import load_palette
+
+    return float(args.tv_weight), float(args.nps_weight), (load_palette(args.nps_palette) if args.nps_palette else None)
 
 
 def str2bool(value):
@@ -95,6 +104,11 @@ def add_common(parser: argparse.ArgumentParser, *, lr, maskidx, iters, warmup, i
                         help="training steps paste a per-image brightness / contrast / saturation variant of the patch")
     parser.add_argument("--colorjitter_strength", type=three_floats, default=(0.2, 0.2, 0.2),
                         help="brightness,contrast,saturation strengths s: factors ~ U(1-s, 1+s)")
+    parser.add_argument("--tv_weight", type=float, default=0.0, help="weight of the patch's total variation (smoothness) in every training step")
+    parser.add_argument("--nps_weight", type=float, default=0.0, help="weight of the patch's non-printability score in every training step")
+    parser.add_argument("--nps_palette", type=str, default=None,
+                        help="text file of printable colours, one `r g b` in [0,1] per line, '#' comments, at most 64 rows "
+                             "(default: the built-in 27-colour grid {0.15,0.5,0.85}^3, a placeholder for a measured printer palette)")
 
 
 def resolve_device(index: int):

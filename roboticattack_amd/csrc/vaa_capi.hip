@@ -140,7 +140,7 @@ const char* vaa_last_error(void) { return vaa::g_err; }
 
 int vaa_async_error(void) { return vaa::async_error_poll("vaa_async_error", true); }
 
-int vaa_version(void) { return 101; /* 0.1.1: vaa_patch_jitter_* */ }
+int vaa_version(void) { return 102; /* 0.1.2: vaa_patch_reg */ }
 
 int vaa_device_check(void) {
     int n = 0;

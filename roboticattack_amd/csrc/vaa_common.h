@@ -285,6 +285,20 @@ __device__ __forceinline__ T wave_sum(T v) {
     return v;
 }
 
+// Sum of v over a workgroup of kWaves waves, the same bits in every thread: butterfly inside a wave, then the waves in order (sl: kWaves doubles
+// of LDS; every thread of the workgroup must call it).
+template <int kWaves>
+__device__ __forceinline__ double block_sum(double v, double* sl) {
+    v = wave_sum(v);
+    __syncthreads();  // the previous sum's slots are no longer read
+    if ((threadIdx.x & 63) == 0) sl[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = 0.0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) t += sl[w];
+    return t;
+}
+
 __device__ __forceinline__ int wave_min_i(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));

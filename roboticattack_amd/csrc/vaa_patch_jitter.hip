@@ -77,18 +77,6 @@ __device__ __forceinline__ void stages(const JitterArgs& a, int N, int t, const 
     }
 }
 
-// Sum of v over the workgroup, the same bits in every thread: butterfly inside a wave, then the waves in order.
-__device__ __forceinline__ double block_sum(double v, double* sl) {
-    v = wave_sum(v);
-    __syncthreads();  // the previous sum's slots are no longer read
-    if ((threadIdx.x & 63) == 0) sl[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < kJitWaves; ++w) t += sl[w];
-    return t;
-}
-
 // m of image b's factors: mean over the texels of gray(clamp(beta*p))
 __device__ __forceinline__ float mean_gray(const JitterArgs& a, int N, const Factors& k, double* sl) {
     double acc = 0.0;
@@ -97,7 +85,7 @@ __device__ __forceinline__ float mean_gray(const JitterArgs& a, int N, const Fac
         brightness(a, N, t, k, pre1, y1);
         acc += (double)gray3(y1);
     }
-    return (float)(block_sum(acc, sl) / (double)N);
+    return (float)(block_sum<kJitWaves>(acc, sl) / (double)N);
 }
 
 // image b's descriptor must state the base patch's own size (workgroup-uniform); anything else is reported and the image left alone
@@ -163,7 +151,7 @@ __global__ __launch_bounds__(kJitThreads) void patch_jitter_bwd_kernel(JitterArg
         contrast_grad(k, s, g3, g2);
         acc += (double)((g2[0] + g2[1]) + g2[2]);
     }
-    const float gmean = (float)(block_sum(acc, sl) / (double)N);
+    const float gmean = (float)(block_sum<kJitWaves>(acc, sl) / (double)N);
     const float wc[3] = {0.299f, 0.587f, 0.114f};
     for (int t = threadIdx.x; t < N; t += kJitThreads) {
         Stages s;

@@ -345,6 +345,43 @@ def patch_jitter_bwd(gpacked, patch, factors, pdesc):
     return g
 
 
+def patch_reg_grad(patch, palette, w_tv: float, w_nps: float, grad=None, accumulate: bool = False, part=None, want_grad: bool = True):
+    """K6 (include/vaa.h states the arithmetic): the gradient r of w_tv*TV(patch) + w_nps*NPS(patch, palette) and the per-workgroup partial sums
+    of the two values, ONE launch. patch [3,ph,pw] f32; palette [K,3] f32 (K <= 64), or None when w_nps == 0. `grad` None: a new tensor receives
+    r; given: r is written to it, or with `accumulate` added to it in place (one rounded add of the same r). `want_grad=False`: values only.
+    -> (grad | None, part f64 [parts,2]); TV / NPS are folded from `part` by patch_reg_values when somebody wants them."""
+    _need(patch, torch.float32, "patch")
+    if patch.dim() != 3 or int(patch.shape[0]) != 3:
+        raise _lib.VaaError(f"patch: expected shape (3, ph, pw), got {tuple(patch.shape)}")
+    ph, pw = int(patch.shape[1]), int(patch.shape[2])
+    K = 0
+    if palette is not None:
+        K = int(palette.shape[0])
+        _need(palette, torch.float32, "palette", (K, 3))
+    L = _lib.lib()
+    parts = int(L.vaa_patch_reg_parts(ph, pw))
+    if part is None:
+        part = torch.empty((parts, 2), dtype=torch.float64, device=patch.device)
+    _need(part, torch.float64, "part", (parts, 2))
+    if not want_grad:
+        grad = None
+    elif grad is None:
+        grad, accumulate = torch.empty_like(patch), False
+    else:
+        _need(grad, torch.float32, "grad", tuple(patch.shape))
+    with _timed("K6_patch_reg"):
+        rc = L.vaa_patch_reg(patch.data_ptr(), ph, pw, _ptr(palette), K, float(w_tv), float(w_nps), _ptr(grad), int(bool(accumulate)), part.data_ptr(),
+                             _stream())
+    _lib.check(rc, "vaa_patch_reg")
+    return grad, part
+
+
+def patch_reg_values(part, n3: int):
+    """(TV, NPS) as device fp64 scalars from K6's partial sums: part[:,0].sum()/n3, part[:,1].sum()/n3 (n3 = 3*ph*pw). Nothing is read back."""
+    s = part.sum(dim=0) / float(n3)
+    return s[0], s[1]
+
+
 def patch_apply_fwd_multi(img_u8, packed, pdesc, max_hw, xy, theta, geometry: bool, mask_mode: int = MASK_LT_M20, want_keep: bool = True,
                           mean6=None, std6=None):
     """K1 with one patch per image (packed/pdesc from patch_resize_fwd or patch_jitter_fwd). max_hw = (max h, max w) over the batch (host ints)."""

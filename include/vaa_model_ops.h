@@ -51,6 +51,28 @@ int vaa_model_attention_bwd(const uint16_t* q, const int64_t* q_str, const uint1
                             const float* lse, float* dsum, uint16_t* dq, const int64_t* dq_str, uint16_t* dk, const int64_t* dk_str,
                             uint16_t* dv, const int64_t* dv_str, const float* rope_cos, const float* rope_sin, const int32_t* cu_seqlens, int B,
                             int H, int T, int hd, int causal, float scale, void* stream);
+/* One greedy decode step of one Llama layer: single-query softmax attention over a KV cache, for all B rows in ONE launch (inference only).
+ * Arguments
+ *   q, k_new, v_new  bf16 [B,H,hd] views, UN-rotated, given by element strides {batch, head} (e.g. the three slices of the step's packed
+ *                    QKV GEMM output [B,3,H,hd]); last dim contiguous.
+ *   kcache, vcache   bf16 [B,Tmax,H,hd] views given by element strides {batch, token, head}; read AND written.
+ *   pos              device int32 [B]: row b's current position (its cache holds keys 0 .. pos[b]-1); rows may differ.
+ *   cos_t, sin_t     float32 [Tmax, hd/2], the tables vaa_model_rope takes.
+ *   o                bf16 [B,H,hd] view given by element strides {batch, head}.
+ *   hd in {16, 128}; every stride a multiple of 8 elements and every tensor base 16-byte aligned (anything else: VAA_E_UNSUPPORTED before any
+ *   launch). NULL pointers, B < 0, H <= 0, Tmax <= 0 or a scale that is not finite and > 0: VAA_E_INVALID. B == 0: VAA_OK, nothing done.
+ * Per (b, h): q and k_new are rotated at position pos[b] with vaa_model_rope's own arithmetic (same device function: the same bits, each
+ *   rounded to bf16 once); the rotated k_new and v_new are stored into cache slot pos[b]; the query attends over keys 0 .. pos[b] inclusive
+ *   (the new key straight from registers); the softmax runs in fp32 with the running max taken before the scaling; o is rounded to bf16 once.
+ * Out-of-range rule: a row with pos[b] < 0 or pos[b] >= Tmax is skipped — its o is written as zeros, its cache is neither read nor written,
+ *   and the device-failure word is raised (vaa_async_error() reports it; later library calls return VAA_E_LAUNCH until it is polled). No value
+ *   of pos makes the kernel touch memory outside the views.
+ * Determinism: no atomics and no hand-over between workgroups; the partial softmax states of a (b, h) pair are folded in a fixed order that
+ *   depends on pos[b] alone, so the same arguments give the same bits and a row's result does not depend on the rest of the batch. */
+int vaa_model_attention_decode(const uint16_t* q, const int64_t* q_str, const uint16_t* k_new, const int64_t* k_str, const uint16_t* v_new,
+                               const int64_t* v_str, uint16_t* kcache, const int64_t* kc_str, uint16_t* vcache, const int64_t* vc_str,
+                               const int32_t* pos, const float* cos_t, const float* sin_t, uint16_t* o, const int64_t* o_str, int B, int H,
+                               int Tmax, int hd, float scale, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,8 @@ SEG_UPA_MAX_GROUPS = 32  # VAA_SEG_UPA_MAX_GROUPS: groups of one vaa_loss_rows_f
 OPT_ADAMW_HF, OPT_PGD_SIGN = 0, 1
 
 MODEL_OP_EXPORTS = ("vaa_model_rope", "vaa_model_swiglu_fwd", "vaa_model_swiglu_bwd", "vaa_model_rmsnorm_fwd", "vaa_model_rmsnorm_bwd",
-                    "vaa_model_attention_fwd", "vaa_model_attention_bwd", "vaa_model_layernorm_fwd", "vaa_model_layernorm_bwd", "vaa_model_scale_add")
+                    "vaa_model_attention_fwd", "vaa_model_attention_bwd", "vaa_model_layernorm_fwd", "vaa_model_layernorm_bwd", "vaa_model_scale_add",
+                    "vaa_model_attention_decode")
 
 EXPORTS = (
     "vaa_last_error",
@@ -288,6 +289,8 @@ def lib() -> C.CDLL:
     L.vaa_model_attention_fwd.argtypes = [vp, i64p, vp, i64p, vp, i64p, vp, i64p, vp, vp, i32, i32, i32, i32, i32, f32, vp]
     L.vaa_model_attention_bwd.restype = i32
     L.vaa_model_attention_bwd.argtypes = [vp, i64p, vp, i64p, vp, i64p, vp, i64p, vp, i64p, vp, vp, vp, i64p, vp, i64p, vp, i64p, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]
+    L.vaa_model_attention_decode.restype = i32
+    L.vaa_model_attention_decode.argtypes = [vp, i64p, vp, i64p, vp, i64p, vp, i64p, vp, i64p, vp, vp, vp, vp, i64p, i32, i32, i32, i32, f32, vp]
     _lib = L
     return L
 

@@ -51,9 +51,10 @@ int async_error_poll(const char* what, bool clear) {
     if (!w) return VAA_OK;
     const unsigned bits = clear ? __atomic_exchange_n(w, 0u, __ATOMIC_ACQ_REL) : __atomic_load_n(w, __ATOMIC_ACQUIRE);
     if (bits == 0u) return VAA_OK;
-    set_error("%s: a kernel of this process reported a device-side failure (bits 0x%x%s%s): its outputs are NaN-poisoned%s", what, bits,
+    set_error("%s: a kernel of this process reported a device-side failure (bits 0x%x%s%s%s): its outputs are NaN-poisoned%s", what, bits,
               (bits & VAA_ASYNC_K3_HANDOVER_TIMEOUT) ? ": the one-launch K3 hand-over timed out — unset VAA_K3_ONE_PASS" : "",
               (bits & VAA_ASYNC_JITTER_PDESC) ? ": vaa_patch_jitter_* met a pdesc entry whose size is not (ph, pw) and left that image unwritten" : "",
+              (bits & VAA_ASYNC_DECODE_POS) ? ": vaa_model_attention_decode met a pos outside [0, Tmax), zeroed that row's o and left its cache alone" : "",
               clear ? "" : "; library calls keep failing until vaa_async_error() is polled");
     return VAA_E_LAUNCH;
 }

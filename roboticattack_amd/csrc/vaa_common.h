@@ -24,6 +24,7 @@ unsigned* async_error_word();        // pinned, device-mapped word kernels OR fa
 int async_error_poll(const char* what, bool clear);
 constexpr unsigned VAA_ASYNC_K3_HANDOVER_TIMEOUT = 1u;
 constexpr unsigned VAA_ASYNC_JITTER_PDESC = 2u;  // vaa_patch_jitter_*: a descriptor entry whose size is not the base patch's (that image is left alone)
+constexpr unsigned VAA_ASYNC_DECODE_POS = 4u;    // vaa_model_attention_decode: a row whose pos is outside [0, Tmax) (its o is zero, its cache untouched)
 // vaa_patch_grad.hip: gpatch[e] = sum_p partial[p][e] (p < nparts, e < n) in a fixed order with fp64 accumulation
 int launch_partial_reduce(const float* partial, float* gpatch, int n, int nparts, hipStream_t st, const char* who);
 
@@ -276,6 +277,29 @@ __device__ __forceinline__ bool partial_reduce_block(const float* __restrict__ p
         }
     }
     return false;
+}
+
+// HF rotate_half on 8 + 8 bf16: lo = x[i .. i+7], hi = x[i+hd/2 .. i+hd/2+7], c0|c1 / s0|s1 = the 8 table entries cos/sin[t, i .. i+7].
+//   ol = lo*cos - hi*sin*sgn,  oh = hi*cos + lo*sin*sgn, each rounded to bf16 once.
+// The one source of the rotation's arithmetic: vaa_model_rope and vaa_model_attention_decode both call it, so their bits agree.
+__device__ __forceinline__ void rope_rotate8(const uint4& lo, const uint4& hi, const float4& c0, const float4& c1, const float4& s0, const float4& s1,
+                                             float sgn, uint4& ol, uint4& oh) {
+    const float cs[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+    const float sn[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+    const uint32_t lw[4] = {lo.x, lo.y, lo.z, lo.w}, hw[4] = {hi.x, hi.y, hi.z, hi.w};
+    uint32_t l4[4], h4[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float x1a = __uint_as_float(lw[q] << 16), x1b = __uint_as_float(lw[q] & 0xffff0000u);
+        const float x2a = __uint_as_float(hw[q] << 16), x2b = __uint_as_float(hw[q] & 0xffff0000u);
+        const float sa = sn[2 * q] * sgn, sb2 = sn[2 * q + 1] * sgn;
+        const float o1a = x1a * cs[2 * q] - x2a * sa, o1b = x1b * cs[2 * q + 1] - x2b * sb2;
+        const float o2a = x2a * cs[2 * q] + x1a * sa, o2b = x2b * cs[2 * q + 1] + x1b * sb2;
+        l4[q] = f32_to_bf16_bits(o1a) | (f32_to_bf16_bits(o1b) << 16);
+        h4[q] = f32_to_bf16_bits(o2a) | (f32_to_bf16_bits(o2b) << 16);
+    }
+    ol = make_uint4(l4[0], l4[1], l4[2], l4[3]);
+    oh = make_uint4(h4[0], h4[1], h4[2], h4[3]);
 }
 
 template <typename T>

@@ -38,23 +38,11 @@ __global__ __launch_bounds__(256) void rope_kernel(const RopeArgs a) {
         const uint4 lo = *reinterpret_cast<const uint4*>(xp), hi = *reinterpret_cast<const uint4*>(xp + half);
         const float4 c0 = *reinterpret_cast<const float4*>(a.cos + (long)t * half + iv * 8), c1 = *reinterpret_cast<const float4*>(a.cos + (long)t * half + iv * 8 + 4);
         const float4 s0 = *reinterpret_cast<const float4*>(a.sin + (long)t * half + iv * 8), s1 = *reinterpret_cast<const float4*>(a.sin + (long)t * half + iv * 8 + 4);
-        const float cs[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-        const float sn[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
-        const uint32_t lw[4] = {lo.x, lo.y, lo.z, lo.w}, hw[4] = {hi.x, hi.y, hi.z, hi.w};
-        uint32_t ol[4], oh[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float x1a = __uint_as_float(lw[q] << 16), x1b = __uint_as_float(lw[q] & 0xffff0000u);
-            const float x2a = __uint_as_float(hw[q] << 16), x2b = __uint_as_float(hw[q] & 0xffff0000u);
-            const float sa = sn[2 * q] * a.sgn, sb2 = sn[2 * q + 1] * a.sgn;
-            const float o1a = x1a * cs[2 * q] - x2a * sa, o1b = x1b * cs[2 * q + 1] - x2b * sb2;
-            const float o2a = x2a * cs[2 * q] + x1a * sa, o2b = x2b * cs[2 * q + 1] + x1b * sb2;
-            ol[q] = f32_to_bf16_bits(o1a) | (f32_to_bf16_bits(o1b) << 16);
-            oh[q] = f32_to_bf16_bits(o2a) | (f32_to_bf16_bits(o2b) << 16);
-        }
+        uint4 ol, oh;
+        rope_rotate8(lo, hi, c0, c1, s0, s1, a.sgn, ol, oh);
         uint16_t* op = a.out + row * a.hd + iv * 8;
-        *reinterpret_cast<uint4*>(op) = make_uint4(ol[0], ol[1], ol[2], ol[3]);
-        *reinterpret_cast<uint4*>(op + half) = make_uint4(oh[0], oh[1], oh[2], oh[3]);
+        *reinterpret_cast<uint4*>(op) = ol;
+        *reinterpret_cast<uint4*>(op + half) = oh;
     }
 }
 

@@ -336,3 +336,55 @@ class PackedAttentionFn(torch.autograd.Function):
     def backward(ctx, dout):
         qkv, o, lse = ctx.saved_tensors
         return attention_bwd(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], o, lse, dout, ctx.causal, ctx.scale, packed_grad=True), None, None
+
+
+def _str2(x: torch.Tensor):
+    """Element strides {batch, head} of a [B,H,hd] view as a C int64[2]."""
+    import ctypes
+
+    if x.stride(2) != 1:
+        raise ValueError("attention_decode operands need a contiguous head dimension")
+    return (ctypes.c_int64 * 2)(x.stride(0), x.stride(1))
+
+
+def _attention_decode_stock(q, k_new, v_new, kcache, vcache, pos, cos, sin, scale):
+    """The stock PyTorch formulation of attention_decode (and its A/B yardstick): rotate_half on q and k at pos, index_put into the caches, SDPA
+    over the whole cache under a `key <= pos` mask. A row with pos outside [0, Tmax) gets o = 0 and keeps its cache (no host sync: the slot
+    index is clamped and the row's old contents are written back)."""
+    from .openvla_model import _rope
+
+    B, H, hd = q.shape
+    Tmax = kcache.shape[1]
+    p = pos.to(torch.int64)
+    valid = (p >= 0) & (p < Tmax)
+    pc = p.clamp(0, Tmax - 1)
+    c = torch.cat([cos, cos], -1).index_select(0, pc)[:, None, :].to(q.dtype)  # [B,1,hd]
+    s = torch.cat([sin, sin], -1).index_select(0, pc)[:, None, :].to(q.dtype)
+    qr, kr = _rope(q, k_new, c, s)
+    bidx = torch.arange(B, device=q.device)
+    keep = valid[:, None, None]
+    kcache.index_put_((bidx, pc), torch.where(keep, kr.to(kcache.dtype), kcache[bidx, pc]))
+    vcache.index_put_((bidx, pc), torch.where(keep, v_new.to(vcache.dtype), vcache[bidx, pc]))
+    mask = torch.arange(Tmax, device=q.device)[None, :] <= pc[:, None]  # [B,Tmax]
+    o = torch.nn.functional.scaled_dot_product_attention(qr[:, :, None, :], kcache.permute(0, 2, 1, 3), vcache.permute(0, 2, 1, 3),
+                                                         attn_mask=mask[:, None, None, :], scale=float(scale))
+    return torch.where(keep, o[:, :, 0, :], torch.zeros((), dtype=o.dtype, device=o.device))
+
+
+def attention_decode(q, k_new, v_new, kcache, vcache, pos, cos, sin, scale=None):
+    """One decode step of one Llama layer for all B rows (include/vaa_model_ops.h: vaa_model_attention_decode). q, k_new, v_new: [B,H,hd]
+    UN-rotated views (any batch / head strides); kcache, vcache: [B,Tmax,H,hd], updated in place at slot pos[b]; pos: int32 [B] on the
+    device; cos, sin: float32 [Tmax, hd/2]. Returns o [B,H,hd]. bf16 ROCm tensors run the kernel (a head width it does not cover is an error,
+    not a quiet detour); everything else, and VAA_NO_FUSED_ATTENTION=1, runs the stock formulation."""
+    B, H, hd = q.shape
+    scale = float(hd) ** -0.5 if scale is None else float(scale)
+    if not (enabled(q) and not os.environ.get("VAA_NO_FUSED_ATTENTION")):
+        return _attention_decode_stock(q, k_new, v_new, kcache, vcache, pos, cos, sin, scale)
+    if pos.dtype != torch.int32 or not pos.is_contiguous():
+        pos = pos.to(torch.int32).contiguous()
+    o = torch.empty((B, H, hd), dtype=torch.bfloat16, device=q.device)
+    rc = _lib.lib().vaa_model_attention_decode(q.data_ptr(), _str2(q), k_new.data_ptr(), _str2(k_new), v_new.data_ptr(), _str2(v_new),
+                                               kcache.data_ptr(), _str3(kcache), vcache.data_ptr(), _str3(vcache), pos.data_ptr(), cos.data_ptr(),
+                                               sin.data_ptr(), o.data_ptr(), _str2(o), B, H, kcache.shape[1], hd, scale, _stream())
+    _lib.check(rc, "vaa_model_attention_decode")
+    return o

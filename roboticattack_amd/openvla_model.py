@@ -319,6 +319,77 @@ class LlamaLayer(nn.Module):
             x = x + self.down_proj(F.silu(self.gate_proj(h)) * self.up_proj(h))
         return x[0] if rows is not None else x
 
+    # ---- inference only: KV-cached greedy decoding (predict.py). New code next to `forward`, which never materialises the rotated K. ----
+    def _infer_fused(self, x) -> bool:
+        from . import model_ops
+
+        D = x.shape[-1]
+        return model_ops.enabled(x) and (D // self.heads) % 16 == 0 and D % 8 == 0 and D <= 8192
+
+    def _infer_norm(self, norm, x, fused):
+        from . import model_ops
+
+        return model_ops.ResidualRMSNormFn.apply(x, norm.weight, norm.eps)[1] if fused else norm(x)
+
+    def _infer_qkv(self, h, fused):
+        """[B,T,3,H,hd]: one GEMM over the row-concatenated weights on the fused path, the three stock projections otherwise."""
+        B, T, D = h.shape
+        if fused:
+            qkv = F.linear(h, self._wcat(("q_proj", "k_proj", "v_proj"))[0])
+        else:
+            qkv = torch.stack([self.q_proj(h), self.k_proj(h), self.v_proj(h)], dim=2)
+        return qkv.view(B, T, 3, self.heads, D // self.heads)
+
+    def _infer_tail(self, x, a, fused):
+        """o_proj + residual, RMSNorm, SwiGLU MLP + residual on [B,T,D]."""
+        from . import model_ops
+
+        B, T, D = x.shape
+        x = torch.addmm(x.reshape(-1, D), a.reshape(-1, D), self.o_proj.weight.t()).view(B, T, D)
+        h = self._infer_norm(self.post_attention_layernorm, x, fused)
+        if fused and (B * T * self.gate_proj.out_features) % 8 == 0:
+            y = model_ops.SwiGLUFn.apply(self.gate_proj(h), self.up_proj(h))
+            return torch.addmm(x.reshape(-1, D), y.reshape(-1, y.shape[-1]), self.down_proj.weight.t()).view(B, T, D)
+        return x + self.down_proj(F.silu(self.gate_proj(h)) * self.up_proj(h))
+
+    @torch.no_grad()
+    def prefill(self, x, rope_tab, cache):
+        """The layer on the whole right-padded prompt x [B,T,D]; the rotated K and V of its T positions go into cache = (kcache, vcache), each
+        [B,Tmax,H,hd]. rope_tab = (cos, sin) float32 [Tmax, hd/2]. Causal attention on right-padded rows is HF's mask on the real tokens; the
+        pad slots hold garbage that the decode steps overwrite before any query sees it."""
+        from . import model_ops
+
+        B, T, D = x.shape
+        hd = D // self.heads
+        fused = self._infer_fused(x)
+        qkv = self._infer_qkv(self._infer_norm(self.input_layernorm, x, fused), fused)
+        cos, sin = rope_tab[0][:T], rope_tab[1][:T]
+        if fused:
+            q, k = model_ops.RopeFn.apply(qkv[:, :, 0], cos, sin), model_ops.RopeFn.apply(qkv[:, :, 1], cos, sin)  # [B,T,H,hd]
+        else:
+            c, s = (torch.cat([t, t], -1).to(x.dtype)[None, :, None, :] for t in (cos, sin))
+            q, k = _rope(qkv[:, :, 0], qkv[:, :, 1], c, s)
+        v = qkv[:, :, 2]
+        if fused and model_ops.attention_enabled(q):
+            a = model_ops.attention_fwd(q, k, v, True)[0]
+        else:
+            a = F.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), is_causal=True).transpose(1, 2)
+        cache[0][:, :T] = k
+        cache[1][:, :T] = v
+        return self._infer_tail(x, a.reshape(B, T, D), fused)
+
+    @torch.no_grad()
+    def decode_step(self, x, pos, rope_tab, cache):
+        """The layer on one new token per row: x [B,1,D], pos int32 [B] (row b's position; its cache holds keys 0 .. pos[b]-1). RMSNorm, the
+        QKV GEMM on [B,1,D], model_ops.attention_decode (rotation, cache append and attention in one launch), o_proj, residual, MLP."""
+        from . import model_ops
+
+        B, _, D = x.shape
+        fused = self._infer_fused(x)
+        qkv = self._infer_qkv(self._infer_norm(self.input_layernorm, x, fused), fused)[:, 0]  # [B,3,H,hd]
+        a = model_ops.attention_decode(qkv[:, 0], qkv[:, 1], qkv[:, 2], cache[0], cache[1], pos, rope_tab[0], rope_tab[1])
+        return self._infer_tail(x, a.reshape(B, 1, D), fused)
+
 
 class SeqPack:
     """Right-padded batch -> packed token axis for the Llama stack: the padding rows (8 of 300 tokens per sample on BridgeData-like
@@ -545,6 +616,18 @@ class OpenVLAShaped(nn.Module):
         logits = self.lm_head(self.hidden_states(input_ids, pixel_values)).float()
         loss = hf_causal_ce(logits, labels) if labels is not None else None
         return types.SimpleNamespace(loss=loss, logits=logits)
+
+    @torch.no_grad()
+    def predict_action(self, input_ids, attention_mask, pixel_values, unnorm_stats=None, action_dim=7):
+        """Greedy action decoding for a right-padded batch, the semantics of the reference's predict_action (modeling_prismatic.py:506-536):
+        29871 is put behind every row whose last real token is not 29871, `action_dim` tokens are decoded greedily (full-vocabulary argmax, the
+        lowest index wins a tie) through a KV cache allocated for this call, and mapped to bin centres in [-1, 1]; with `unnorm_stats`
+        (q01, q99, mask) the masked dimensions become 0.5*(a+1)*(q99-q01)+q01. Returns (tokens int64 [B,action_dim] on the model's device,
+        actions float64 [B,action_dim] on the CPU). VAA_PREDICT_NO_CACHE=1 decodes with action_dim full forward calls instead; see predict.py."""
+        from . import predict
+
+        tokens, _ = predict.greedy_decode(self, input_ids, attention_mask, pixel_values, action_dim)
+        return tokens, predict.tokens_to_actions(tokens, unnorm_stats)
 
 
 def enable_tuned_gemms() -> bool:

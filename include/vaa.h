@@ -531,6 +531,30 @@ int vaa_patch_update(float* patch, const float* g, float* m, float* v, int n, in
 int vaa_patch_apply_eval(const uint8_t* img_u8, const float* patch, const int32_t* xy, const float* theta, const int32_t* geometry,
                          int B, int ph, int pw, uint8_t* out_u8, void* stream);
 
+/*
+ * K7 — the evaluation's image front end behind the eval-time paste: replaces, per camera frame, the centre crop of get_vla_action
+ * (experiments/robot/openvla_utils.py:132-155: convert_image_dtype(float32), crop_and_resize :81-124, clip_by_value,
+ * convert_image_dtype(uint8, saturate=True)) and the processor call behind it (:166: to [0,1], one normalisation per vision tower, six channels,
+ * bfloat16). One launch per batch; a frame's result does not depend on the batch around it.
+ *   img_u8   dev  [B,224,224,3] uint8 HWC (4-byte aligned)
+ *   crop_scale    0 = no crop (the frame's own bytes are normalised); else the AREA share of the centre crop, in (0, 1] (the reference: 0.9)
+ *   mean6/std6 host [6] float32, as vaa_patch_apply_fwd
+ *   out_bf16 dev  [B,6,224,224] bfloat16 bits (16-byte aligned): the model's pixel_values
+ * VAA_E_INVALID before any launch: crop_scale negative, above 1 or NaN; B < 0; a null pointer or a misaligned one (B > 0). B == 0 returns VAA_OK
+ * and launches nothing.
+ * The arithmetic is the contract: TensorFlow's CPU CropAndResize (bilinear, extrapolation value 0) followed by convert_image_dtype, restated
+ * with every operation a separately rounded fp32 operation (no FMA). N = 224. On the host:
+ *     s = min(max(sqrtf(crop_scale), 0), 1);   y1 = x1 = (1 - s) / 2;   y2 = x2 = y1 + s;   scale = ((y2 - y1) * 223) / 223
+ * Per output row y (columns alike, with x, lx, left = floor, right = ceil):
+ *     in_y = y1*223 + y*scale;   t = floorf(in_y);   b = ceilf(in_y);   ly = in_y - t;     in_y or in_x outside [0, 223]: value 0 in all channels
+ * Per channel, with f(u8) = (float)u8 * (1.0f / 255.0f) of the four source bytes tl, tr (row t) and bl, br (row b):
+ *     top = tl + (tr - tl)*lx;   bot = bl + (br - bl)*lx;   v = top + (bot - top)*ly;   v = min(max(v, 0), 1)
+ *     q = min(255, (int)(v * 255.5f))                      (truncation, as convert_image_dtype(saturate=True) does)
+ * and q is normalised exactly as vaa_patch_apply_fwd normalises a frame byte: x = (float)q / 255.0f, (x - mean[c]) / std[c] with true divisions,
+ * round-to-nearest-even to bfloat16, for c and c + 3. With crop_scale == 0, q is the source byte itself.
+ */
+int vaa_eval_preprocess(const uint8_t* img_u8, int B, float crop_scale, const float* mean6, const float* std6, uint16_t* out_bf16, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

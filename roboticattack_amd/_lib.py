@@ -36,6 +36,7 @@ EXPORTS = (
     "vaa_loss_fwd_bwd_ex",
     "vaa_patch_update",
     "vaa_patch_apply_eval",
+    "vaa_eval_preprocess",
     "vaa_patch_embed_grad_ws_bytes",
     "vaa_patch_embed_grad_gather",
     "vaa_patch_embed_packed_elems",
@@ -208,6 +209,8 @@ def lib() -> C.CDLL:
     L.vaa_patch_update.argtypes = [vp, vp, vp, vp, i32, i32, f32, f32, f32, f32, i32, f32, f32, vp, vp]
     L.vaa_patch_apply_eval.restype = i32
     L.vaa_patch_apply_eval.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
+    L.vaa_eval_preprocess.restype = i32
+    L.vaa_eval_preprocess.argtypes = [vp, i32, f32, C.POINTER(f32), C.POINTER(f32), vp, vp]
     L.vaa_patch_apply_fwd_tiles.restype = i32
     L.vaa_patch_apply_fwd_tiles.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, vp, vp, vp, vp]
     L.vaa_patch_embed_grad_gather_multi_tiles.restype = i32

@@ -159,3 +159,56 @@ def maybe_wandb_init(args, name, rank=0):
 
 def new_exp_id() -> str:
     return str(uuid.uuid4())
+
+
+# ---- VLAAttacker/eval_patch.py: open-loop evaluation of a finished patch ----
+def two_ints(arg):
+    vals = tuple(map(int, arg.split(",")))
+    if len(vals) != 2 or min(vals) < 1:
+        raise argparse.ArgumentTypeError("two comma-separated positive integers expected (GX,GY)")
+    return vals
+
+
+def target_arg(arg):
+    """`maskidx:value`, e.g. `0:0.5` or `0,1,2:0` -> (maskidx list, target value): TMA's --maskidx / --targetAction pair."""
+    try:
+        idx, value = arg.split(":")
+        return list_of_ints(idx), float(value)
+    except ValueError:
+        raise argparse.ArgumentTypeError("maskidx:value expected, e.g. 0:0.5 or 0,1,2:0")
+
+
+def add_eval(parser: argparse.ArgumentParser):
+    parser.add_argument("--patch", required=True, type=str, help="a patch.pt written by a wrapper run (fp32 [3,ph,pw])")
+    parser.add_argument("--vla_path", default=None, type=str, help="local OpenVLA checkpoint dir, or random:openvla-7b | random:tiny")
+    parser.add_argument("--dataset", default="bridge_orig", type=str)
+    parser.add_argument("--device", default=0, type=int)
+    parser.add_argument("--bs", default=8, type=int, help="(frame, placement) rows per evaluated batch")
+    parser.add_argument("--frames", default=16, type=int, help="number of synthetic BridgeData-shaped frames and prompts")
+    parser.add_argument("--seed", default=7, type=int)
+    parser.add_argument("--center_crop", type=str2bool, nargs="?", const=True, default=True,
+                        help="centre crop to 0.9 of the area and resize back (mandatory for the fine-tuned LIBERO checkpoints)")
+    parser.add_argument("--crop_scale", default=0.9, type=float)
+    # the reference script's placement flags (run_libero_eval_args_geo_batch.py:333-337); angle / shear default to simulation_random_patch's
+    parser.add_argument("--geometry", type=str2bool, nargs="?", const=True, default=True)
+    parser.add_argument("--angle", default=1, type=float, help="rotation in degrees")
+    parser.add_argument("--shx", default=0.1, type=float)
+    parser.add_argument("--shy", default=0.1, type=float)
+    parser.add_argument("--x", default=2, type=int)
+    parser.add_argument("--y", default=2, type=int)
+    parser.add_argument("--grid", default=None, type=two_ints, help="GX,GY: a grid of positions over the valid range at that angle and shear")
+    parser.add_argument("--target", default=None, type=target_arg, help="maskidx:value — also report how often the patched token hits that action")
+    parser.add_argument("--out", default=None, type=str, help="write the report as JSON (tokens included)")
+
+
+def eval_placements(args, ph: int, pw: int):
+    """One (geometry, angle, shx, shy, x, y) from the flags, or with --grid GX,GY the GX x GY positions spread evenly over the valid range
+    [0, 224 - pw] x [0, 224 - ph], row-major (y outer); an axis with one point keeps --x / --y."""
+    from .constants import IMG
+
+    if min(args.x, args.y) < 0 or args.x > IMG - pw or args.y > IMG - ph:
+        raise ValueError(f"position ({args.x}, {args.y}) leaves the frame for a {ph}x{pw} patch")
+    gx, gy = args.grid if args.grid else (1, 1)
+    xs = [args.x] if gx == 1 else [int(round(v)) for v in np.linspace(0, IMG - pw, gx)]
+    ys = [args.y] if gy == 1 else [int(round(v)) for v in np.linspace(0, IMG - ph, gy)]
+    return [(bool(args.geometry), args.angle, args.shx, args.shy, x, y) for y in ys for x in xs]

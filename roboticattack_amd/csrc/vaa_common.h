@@ -91,6 +91,30 @@ __device__ __forceinline__ uint32_t f32_to_bf16_bits(float f) {
     return u >> 16;
 }
 
+// Host and device share the arithmetic of the camera-pixel LUT: IEEE fp32 true divisions, RNE bf16 cast
+// (host code of the library is compiled with -ffp-contract=off as well).
+__host__ __device__ inline uint32_t bf16_rne(float f) {
+    uint32_t u;
+    __builtin_memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x0040u;
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return u >> 16;
+}
+
+// value v in [0,1] of channel c -> packed {bf16 first normalisation, bf16 second normalisation} (UADA.py:56-57)
+__host__ __device__ inline uint32_t norm_pack(float v, const Norm6& n, int c) {
+    float o0 = (v - n.mean[c]) / n.stdv[c];
+    float o1 = (v - n.mean[c + 3]) / n.stdv[c + 3];
+    return bf16_rne(o0) | (bf16_rne(o1) << 16);
+}
+
+// The 3x256 table of a frame byte's normalised values, lut[c*256 + u8] = norm_pack(u8 / 255, nrm, c): built once per workgroup in LDS by all
+// of its `nthreads` threads (the caller places the barrier). The one fill behind K1 (planar and tile-major) and K7: one source, same bits.
+__device__ __forceinline__ void fill_norm_lut(uint32_t* lut, const Norm6& nrm, int tid, int nthreads) {
+#pragma unroll
+    for (int e = tid; e < 768; e += nthreads) lut[e] = norm_pack((float)(e & 255) / 255.0f, nrm, e >> 8);
+}
+
 // F.affine_grid(align_corners=False) base coordinate of pixel index i along a 224-long axis:
 // torch.linspace(-1, 1, 224)[i] * 223 / 224, with linspace's two-sided evaluation (one FMA each side).
 __device__ __forceinline__ float base_coord(int i) {

@@ -44,21 +44,7 @@ constexpr int kItemsPerImg = VAA_IMG * kItemsPerRow;      // 3136
 constexpr int kFwdThreads = 256;
 constexpr int kMaxRows = 20;                              // rows one workgroup's 256 items can touch (256/14 + 2)
 
-// Host and device share the arithmetic of the camera-pixel LUT: IEEE fp32 true divisions, RNE bf16 cast
-// (host code of this file is compiled with -ffp-contract=off as well).
-__host__ __device__ inline uint32_t bf16_rne(float f) {
-    uint32_t u;
-    __builtin_memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x0040u;
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return u >> 16;
-}
-
-__host__ __device__ inline uint32_t norm_pack(float v, const Norm6& n, int c) {
-    float o0 = (v - n.mean[c]) / n.stdv[c];
-    float o1 = (v - n.mean[c + 3]) / n.stdv[c + 3];
-    return bf16_rne(o0) | (bf16_rne(o1) << 16);
-}
+// (bf16_rne / norm_pack / fill_norm_lut, the arithmetic of the camera-pixel LUT, live in vaa_common.h: K7 normalises with the same table)
 
 // Conservative COLUMN span of output row i of image b: pixels [jlo, jhi] may have a source point that touches the patch; jhi < jlo
 // (normalised to [0, -1]) when the row is clear. Every role of both K1 kernels derives its ownership from this one function.
@@ -145,8 +131,7 @@ __global__ __launch_bounds__(kFwdThreads) void patch_apply_fwd_kernel(const FwdA
         }
     }
     // camera-pixel LUT: same IEEE arithmetic as the host (true divisions, RNE), 3 entries per thread
-#pragma unroll
-    for (int e = tid; e < 768; e += kFwdThreads) lut[e] = norm_pack((float)(e & 255) / 255.0f, a.nrm, e >> 8);
+    fill_norm_lut(lut, a.nrm, tid, kFwdThreads);
     // (building this table once on the host and carrying it in the kernel-argument segment was measured: 16.4 vs 15.5 us at bs=64 —
     // bulk reads from the kernarg segment are slower than nine correctly-rounded divisions per thread)
 
@@ -380,8 +365,7 @@ __global__ __launch_bounds__(kFwdThreads) void patch_apply_tiles_kernel(const Fw
     } else {
         b = (int)blockIdx.x / fsplit;
     }
-#pragma unroll
-    for (int e = tid; e < 768; e += kFwdThreads) lut[e] = norm_pack((float)(e & 255) / 255.0f, a.nrm, e >> 8);
+    fill_norm_lut(lut, a.nrm, tid, kFwdThreads);
 
     if (bg) {
         // ------------------------------------------------------------------ background role: tile row (b, ty)

@@ -1173,3 +1173,20 @@ def patch_apply_eval(img_u8, patch, xy, theta, geometry):
                                              int(patch.shape[1]), int(patch.shape[2]), out.data_ptr(), _stream())
     _lib.check(rc, "vaa_patch_apply_eval")
     return out
+
+
+# ------------------------------------------------------------------------------------------------------
+# evaluation front end (get_vla_action's centre crop + the processor)
+# ------------------------------------------------------------------------------------------------------
+def eval_preprocess(img_u8, crop_scale: float = 0.0, mean6=None, std6=None):
+    """K7. uint8 frames [B,224,224,3] -> the model's pixel_values, bf16 [B,6,224,224]: centre crop to `crop_scale` of the area and bilinear
+    resize back (crop_scale = 0: no crop), uint8 conversion, both normalisations (include/vaa.h states the arithmetic)."""
+    B = img_u8.shape[0]
+    _need(img_u8, torch.uint8, "img_u8", (B, IMG, IMG, 3))
+    out = torch.empty((B, 6, IMG, IMG), dtype=torch.bfloat16, device=img_u8.device)
+    mean_c = _MEAN if mean6 is None else _lib.f32x(mean6)
+    std_c = _STD if std6 is None else _lib.f32x(std6)
+    with _timed("K7_eval_preprocess", B=B):
+        rc = _lib.lib().vaa_eval_preprocess(img_u8.data_ptr(), B, float(crop_scale), mean_c, std_c, out.data_ptr(), _stream())
+    _lib.check(rc, "vaa_eval_preprocess")
+    return out

@@ -111,3 +111,13 @@ def synth_logits(seed: int, batch: int, seq: int, vocab: int, scale: float = 2.0
         action_boost
     )
     return torch.from_numpy(z)
+
+
+def synth_eval_batch(seed: int, batch: int, kind: str = "smooth", **kw):
+    """What an open-loop evaluation consumes: (frames u8 [B,224,224,3], input_ids, attention_mask) with the PROMPT part of synth_batch's rows only
+    ([BOS, prompt tokens...], right-padded with 32000) — the action tokens and EOS behind it are what predict_action decodes."""
+    input_ids, _, attention_mask = synth_text_batch(seed + 7919, batch, **kw)
+    lens = attention_mask.sum(1) - 8
+    keep = torch.arange(input_ids.shape[1])[None, :] < lens[:, None]
+    ids = torch.where(keep, input_ids, torch.full_like(input_ids, PAD_ID))[:, : int(lens.max())]
+    return synth_images(seed, batch, kind), ids, ids.ne(PAD_ID)

@@ -298,6 +298,15 @@ class RandomPatchTransform:
         geo = torch.from_numpy(np.asarray(geometry).astype(np.int32)).to(self.device)
         return ops.patch_apply_eval(img, patch.detach().to(self.device, torch.float32).contiguous(), xy, torch.from_numpy(theta).to(self.device), geo)
 
+    def eval_pixel_values(self, frames_u8, mean, std, center_crop=False, crop_scale=0.9, out_dtype=torch.bfloat16):
+        """The evaluation's image front end behind the paste (experiments/robot/openvla_utils.py:132-166): uint8 frames [B,224,224,3] (numpy or
+        a device tensor, e.g. simulation_patch_batch's output) -> pixel_values [B,6,224,224]. center_crop=True crops the centre to `crop_scale`
+        of the area and resizes back bilinearly before the uint8 conversion (mandatory for the fine-tuned LIBERO checkpoints); one launch (K7)."""
+        mean6, std6 = _six(mean, std)
+        img = self.stage_images(frames_u8 if isinstance(frames_u8, torch.Tensor) else torch.as_tensor(np.asarray(frames_u8)))
+        out = ops.eval_preprocess(img, float(crop_scale) if center_crop else 0.0, mean6, std6)
+        return out if out_dtype == torch.bfloat16 else out.to(out_dtype)
+
     def im_process(self, images, mean, std, out_dtype=torch.bfloat16):
         """:190-197 — normalise the clean frames only (K1 with a 1x1 sentinel patch that is never kept)."""
         mean6, std6 = _six(mean, std)

@@ -1,0 +1,197 @@
+"""The open-loop evaluation's batch at the 7B shape (random:openvla-7b, prompts of 20-36 tokens, a 50x50 patch, centre crop 0.9) for bs = 1 and 8:
+
+    front   K7 (vaa_eval_preprocess) against the same preprocessing written with stock PyTorch ops (a gather-based bilinear with the op order of
+            include/vaa.h; checked against K7 bit for bit before anything is timed): per-dispatch us of K7 from vaa_prof_*, event-bracketed us of
+            both, K7's share of the 8 TB/s HBM peak on its 752,640 bytes per frame (150,528 in + 602,112 out)
+    batch   ms per evaluated batch, split into K5 (paste), K7 and predict_action (device events around each; predict_action ends with its token
+            read-back), median of 5
+
+    python tools/eval_bench.py [--bs 1,8] [--iters 5] [--warmup 2] [--out file.json]
+
+Each part runs in a fresh child process under `timeout`, one after the other; the first child that fails ends the run. One JSON line per result.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+BYTES_PER_FRAME = 224 * 224 * 3 + 6 * 224 * 224 * 2
+HBM_PEAK = 8.0e12
+CROP = 0.9
+
+
+def stock_preprocess(frames_u8, crop_scale, mean6, std6):
+    """vaa_eval_preprocess with stock PyTorch ops on the frames' device: every line one separately rounded fp32 elementwise op or a gather."""
+    import numpy as np
+    import torch
+
+    f32 = np.float32
+    s = np.minimum(np.maximum(np.sqrt(f32(crop_scale)), f32(0.0)), f32(1.0))
+    y1 = (f32(1.0) - s) / f32(2.0)
+    y2 = y1 + s
+    scale = ((y2 - y1) * f32(223)) / f32(223)
+    dev = frames_u8.device
+    in_c = torch.arange(224, dtype=torch.float32, device=dev) * float(scale) + float(y1 * f32(223))
+    lo, hi = in_c.floor(), in_c.ceil()
+    w = in_c - lo
+    li, hi_i = lo.long(), hi.long()
+    f = frames_u8.to(torch.float32) * float(f32(1.0) / f32(255.0))
+    t, b = f[:, li], f[:, hi_i]
+    tl, tr, bl, br = t[:, :, li], t[:, :, hi_i], b[:, :, li], b[:, :, hi_i]
+    lx, ly = w[None, None, :, None], w[None, :, None, None]
+    top = tl + (tr - tl) * lx
+    bot = bl + (br - bl) * lx
+    v = (top + (bot - top) * ly).clamp(0.0, 1.0)
+    q = (v * 255.5).to(torch.int32).clamp_max(255)
+    # a true division needs a device tensor as the divisor: by a Python scalar, PyTorch's GPU kernel multiplies by the reciprocal instead
+    x = (q.to(torch.float32) / torch.tensor(255.0, device=dev)).permute(0, 3, 1, 2).repeat(1, 2, 1, 1)
+    mean = torch.tensor(mean6, dtype=torch.float32, device=dev)[None, :, None, None]
+    std = torch.tensor(std6, dtype=torch.float32, device=dev)[None, :, None, None]
+    return ((x - mean) / std).to(torch.bfloat16)
+
+
+def _median(v):
+    v = sorted(v)
+    return v[len(v) // 2]
+
+
+def _event_us(fn, reps):
+    import torch
+
+    pairs = []
+    for _ in range(reps):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        fn()
+        e.record()
+        pairs.append((s, e))
+    torch.cuda.synchronize()
+    return [s.elapsed_time(e) * 1e3 for s, e in pairs]
+
+
+def child_front(batches, reps: int) -> int:
+    import torch
+
+    from roboticattack_amd import ops, synthetic
+    from roboticattack_amd.constants import MEAN6, STD6
+
+    dev = torch.device("cuda:0")
+    for bs in batches:
+        frames = torch.from_numpy(synthetic.synth_images(40 + bs, bs, "smooth")).to(dev)
+        k7 = ops.eval_preprocess(frames, CROP, MEAN6, STD6)
+        stock = stock_preprocess(frames, CROP, MEAN6, STD6)
+        torch.cuda.synchronize()
+        same = torch.equal(k7.view(torch.int16), stock.view(torch.int16))
+        if not same:
+            bad = k7.view(torch.int16) != stock.view(torch.int16)
+            print(json.dumps(dict(part="front", bs=bs, failed="stock formulation differs from K7 in %d of %d elements" % (int(bad.sum()), bad.numel()))))
+            return 1
+        for _ in range(5):  # warm-up of both
+            ops.eval_preprocess(frames, CROP, MEAN6, STD6)
+            stock_preprocess(frames, CROP, MEAN6, STD6)
+        torch.cuda.synchronize()
+        ops.prof_start(reps)
+        for _ in range(reps):
+            ops.eval_preprocess(frames, CROP, MEAN6, STD6)
+        torch.cuda.synchronize()
+        disp = [us for _, us in ops.prof_collect()]
+        rounds = {"k7": [], "stock": []}
+        for _ in range(3):  # alternate the two in one process
+            rounds["k7"] += _event_us(lambda: ops.eval_preprocess(frames, CROP, MEAN6, STD6), reps)
+            rounds["stock"] += _event_us(lambda: stock_preprocess(frames, CROP, MEAN6, STD6), reps)
+        d = _median(disp)
+        print(json.dumps(dict(part="front", bs=bs, bit_exact_vs_stock=True, k7_dispatch_us_median=round(d, 2), k7_dispatch_us_min=round(min(disp), 2),
+                              k7_bytes=BYTES_PER_FRAME * bs, k7_tb_per_s=round(BYTES_PER_FRAME * bs / (d * 1e-6) / 1e12, 3),
+                              k7_share_of_8tb_s=round(BYTES_PER_FRAME * bs / (d * 1e-6) / HBM_PEAK, 4),
+                              k7_event_us_median=round(_median(rounds["k7"]), 2), stock_event_us_median=round(_median(rounds["stock"]), 2),
+                              stock_over_k7=round(_median(rounds["stock"]) / _median(rounds["k7"]), 2), reps=reps)), flush=True)
+    return 0
+
+
+def child_batch(batches, iters: int, warmup: int) -> int:
+    import numpy as np
+    import torch
+
+    from roboticattack_amd import ops, synthetic
+    from roboticattack_amd.constants import MEAN6, STD6
+    from roboticattack_amd.openvla_model import build_openvla, openvla_7b_cfg
+    from roboticattack_amd.transform import RandomPatchTransform
+
+    dev = torch.device("cuda:0")
+    model = build_openvla(openvla_7b_cfg(), device=dev, dtype=torch.bfloat16)
+    t = RandomPatchTransform(dev)
+    mean, std = [MEAN6[:3], MEAN6[3:]], [STD6[:3], STD6[3:]]
+    patch = torch.from_numpy(np.random.RandomState(0).rand(3, 50, 50).astype(np.float32)).to(dev)
+    for bs in batches:
+        frames, ids, mask = synthetic.synth_eval_batch(100 + bs, bs)
+        frames, ids, mask = torch.from_numpy(frames).to(dev), ids.to(dev), mask.to(dev)
+        place = ([True] * bs, [10.0] * bs, [0.1] * bs, [-0.1] * bs, [(37 + 11 * b, 60 + 7 * b) for b in range(bs)])
+
+        def one():
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            t0 = time.perf_counter()
+            ev[0].record()
+            pasted = t.simulation_patch_batch(frames, patch, *place)
+            ev[1].record()
+            pix = t.eval_pixel_values(pasted, mean, std, center_crop=True, crop_scale=CROP)
+            ev[2].record()
+            tokens, _ = model.predict_action(ids, mask, pix)  # returns after the tokens reached the host
+            ev[3].record()
+            torch.cuda.synchronize()
+            wall = (time.perf_counter() - t0) * 1e3
+            return wall, ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2]), ev[2].elapsed_time(ev[3]), tokens
+
+        for _ in range(warmup):
+            one()
+        runs = [one() for _ in range(iters)]
+        ops.async_error_check()
+        print(json.dumps(dict(part="batch", bs=bs, ms_batch_median=round(_median([r[0] for r in runs]), 3), ms_k5_median=round(_median([r[1] for r in runs]), 4),
+                              ms_k7_median=round(_median([r[2] for r in runs]), 4), ms_predict_median=round(_median([r[3] for r in runs]), 3),
+                              ms_batch_min=round(min(r[0] for r in runs), 3), ms_batch_max=round(max(r[0] for r in runs), 3), iters=iters,
+                              tokens_row0=runs[-1][4][0].tolist())), flush=True)
+    return 0
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=50, help="K7 / stock repetitions per round of the front part")
+    ap.add_argument("--bs", default="1,8")
+    ap.add_argument("--parts", default="front,batch")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--timeout", type=int, default=300, help="seconds per child process")
+    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    batches = [int(b) for b in a.bs.split(",")]
+    if a.child == "front":
+        return child_front(batches, a.reps)
+    if a.child == "batch":
+        return child_batch(batches, a.iters, a.warmup)
+    results = []
+    for part in a.parts.split(","):
+        cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", part, "--iters", str(a.iters),
+               "--warmup", str(a.warmup), "--reps", str(a.reps), "--bs", a.bs]
+        p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True)
+        sys.stdout.write(p.stdout)
+        results += [json.loads(line) for line in p.stdout.splitlines() if line.startswith("{")]
+        if p.returncode != 0:  # nothing more is started on the GPU after a failure
+            sys.stderr.write(p.stderr[-4000:])
+            print(json.dumps(dict(part=part, failed=p.returncode)))
+            return 1
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(dict(results=results), f, indent=1)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

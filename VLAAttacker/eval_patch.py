@@ -20,7 +20,9 @@ from roboticattack_amd.transform import RandomPatchTransform  # noqa: E402
 def arg_parser(argv=None):
     parser = argparse.ArgumentParser(description=__doc__)
     cli.add_eval(parser)
-    return parser.parse_args(argv)
+    args = parser.parse_args(argv)
+    cli.check_eval_quant(parser, args)
+    return args
 
 
 def main(argv=None):
@@ -32,11 +34,18 @@ def main(argv=None):
         raise ValueError(f"{args.patch}: expected a [3,ph,pw] tensor")
     placements = cli.eval_placements(args, int(patch.shape[1]), int(patch.shape[2]))
     vla, path = cli.resolve_model(args, device)
+    vla_q4 = None
+    if args.load_in_4bit:  # a second model whose Llama projections are 4-bit codes; towers, projector, embeddings and head are copies
+        import copy
+
+        from roboticattack_amd.quant import quantize_llm
+
+        vla_q4 = quantize_llm(copy.deepcopy(vla), args.bnb_4bit_quant_type)
     frames, input_ids, attention_mask = synthetic.synth_eval_batch(args.seed, args.frames)
     target = (args.target[0], args.target[1]) if args.target else None
     report = evaluate_patch(vla, RandomPatchTransform(device), frames, input_ids, attention_mask, patch.float(), placements,
                             center_crop=args.center_crop, crop_scale=args.crop_scale, mean=[MEAN6[:3], MEAN6[3:]], std=[STD6[:3], STD6[3:]],
-                            target=target, bs=args.bs)
+                            target=target, bs=args.bs, quant_model=vla_q4)
     torch.cuda.synchronize()
     ops.async_error_check()
     for (geo, angle, shx, shy, x, y), r in zip(report["placements"], report["per_placement"]):
@@ -46,6 +55,10 @@ def main(argv=None):
     o = report["overall"]
     print(f"overall ({len(placements)} placements x {args.frames} frames, model {path}): any_flip={o['any_flip_rate']:.3f} "
           f"mean_nad={float(o['nad'].mean()):.4f}")
+    if vla_q4 is not None:
+        q, ca = report["quantised"], report["clean_agreement"]
+        print(f"4-bit ({q['quant_type']}) model: any_flip={q['overall']['any_flip_rate']:.3f} mean_nad={float(q['overall']['nad'].mean()):.4f}; "
+              f"clean actions equal to the bf16 model's on {ca['frames']:.3f} of the frames, {ca['tokens']:.3f} of the tokens")
     out = to_jsonable(dict(report, patch=args.patch, vla_path=path, frames=args.frames, center_crop=bool(args.center_crop),
                            crop_scale=args.crop_scale))
     if args.out:

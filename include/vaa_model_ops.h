@@ -73,6 +73,31 @@ int vaa_model_attention_decode(const uint16_t* q, const int64_t* q_str, const ui
                                const int64_t* v_str, uint16_t* kcache, const int64_t* kc_str, uint16_t* vcache, const int64_t* vc_str,
                                const int32_t* pos, const float* cos_t, const float* sin_t, uint16_t* o, const int64_t* o_str, int B, int H,
                                int Tmax, int hd, float scale, void* stream);
+/* ---- 4-bit block-quantised weights (inference only): the Llama projections of a model converted by quant.quantize_llm ----
+ * THE FORMAT (this header defines it; it follows the layout of bitsandbytes' Linear4bit without double quantisation, but no copy of
+ * bitsandbytes was available to compare a single value with):
+ *   W        bf16 [N, K] row-major, K % 64 == 0 (anything else: VAA_E_UNSUPPORTED). A block is 64 consecutive elements of one row.
+ *   absmax   float32 [N, K/64]: absmax[n, j] = max |W[n, 64 j .. 64 j + 63]| (exact: bf16 converts to fp32 exactly).
+ *   table    16 float32 values, an ARGUMENT of every call (a HOST pointer, read before the call returns; nothing is compiled in).
+ *   code     q[n, k] = the index i whose table[i] is nearest to the fp32 quotient W[n, k] / absmax[n, k / 64] (IEEE fp32 division, distances
+ *            compared exactly); a tie goes to the smaller index; every element of a block whose absmax is 0 gets the smallest index i with
+ *            table[i] == 0.
+ *   codes    uint8 [N, K/2]: byte [n, i] = q[n, 2 i] << 4 | q[n, 2 i + 1] (the even element in the HIGH nibble).
+ *   wq       the dequantised weight: wq[n, k] = bf16(table[q[n, k]] * absmax[n, k / 64]) — ONE fp32 product, rounded to bf16 once
+ *            (round-to-nearest-even). Every consumer below sees exactly these wq, so a prefill through vaa_model_q4_dequant + a GEMM and a
+ *            decode step through vaa_model_q4_gemv evaluate the same model.
+ *   The quantiser itself is host-side (roboticattack_amd/quant.py: quantize_q4, on the CPU or the GPU with the same codes).
+ * Both entry points: NULL pointers (res excepted), N < 1 or K < 64: VAA_E_INVALID; K % 64 != 0, or a device base address (codes, absmax, out /
+ * x, res, y) that is not 16-byte aligned: VAA_E_UNSUPPORTED before any launch. */
+/* out_bf16 [N, K] = wq. */
+int vaa_model_q4_dequant(const uint8_t* codes, const float* absmax, const float* table, int N, int K, uint16_t* out_bf16, void* stream);
+/* y[m, n] = bf16(res[m, n] + sum_k x[m, k] * wq[n, k]): x bf16 [M, K] contiguous, res (may be NULL) and y bf16 [M, N] contiguous; fp32
+ * accumulation on the matrix cores, one rounding. 1 <= M <= 16 (M > 16: VAA_E_UNSUPPORTED — dequantise and run a GEMM; M < 0: VAA_E_INVALID;
+ * M == 0: VAA_OK, nothing done). One launch; every code byte is read once.
+ * Determinism: no atomics, no hand-over between workgroups, no waiting on memory another wave writes; the split over K inside a workgroup is
+ * folded in a fixed order, so the same arguments give the same bits, and row m of y depends on row m of x (and res) alone. */
+int vaa_model_q4_gemv(const uint16_t* x, int M, const uint8_t* codes, const float* absmax, const float* table, int N, int K,
+                      const uint16_t* res, uint16_t* y, void* stream);
 #ifdef __cplusplus
 }
 #endif

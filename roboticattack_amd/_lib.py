@@ -22,7 +22,7 @@ OPT_ADAMW_HF, OPT_PGD_SIGN = 0, 1
 
 MODEL_OP_EXPORTS = ("vaa_model_rope", "vaa_model_swiglu_fwd", "vaa_model_swiglu_bwd", "vaa_model_rmsnorm_fwd", "vaa_model_rmsnorm_bwd",
                     "vaa_model_attention_fwd", "vaa_model_attention_bwd", "vaa_model_layernorm_fwd", "vaa_model_layernorm_bwd", "vaa_model_scale_add",
-                    "vaa_model_attention_decode")
+                    "vaa_model_attention_decode", "vaa_model_q4_dequant", "vaa_model_q4_gemv")
 
 EXPORTS = (
     "vaa_last_error",
@@ -294,6 +294,10 @@ def lib() -> C.CDLL:
     L.vaa_model_attention_bwd.argtypes = [vp, i64p, vp, i64p, vp, i64p, vp, i64p, vp, i64p, vp, vp, vp, i64p, vp, i64p, vp, i64p, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]
     L.vaa_model_attention_decode.restype = i32
     L.vaa_model_attention_decode.argtypes = [vp, i64p, vp, i64p, vp, i64p, vp, i64p, vp, i64p, vp, vp, vp, vp, i64p, i32, i32, i32, i32, f32, vp]
+    L.vaa_model_q4_dequant.restype = i32
+    L.vaa_model_q4_dequant.argtypes = [vp, vp, C.POINTER(f32), i32, i32, vp, vp]
+    L.vaa_model_q4_gemv.restype = i32
+    L.vaa_model_q4_gemv.argtypes = [vp, i32, vp, vp, C.POINTER(f32), i32, i32, vp, vp, vp]
     _lib = L
     return L
 

@@ -71,13 +71,16 @@ def summarise(tokens_clean: torch.Tensor, tokens_patched: torch.Tensor, unnorm_s
 
 @torch.no_grad()
 def evaluate_patch(model, transform, frames_u8, input_ids, attention_mask, patch, placements, *, center_crop=True, crop_scale=0.9, mean, std,
-                   unnorm_stats=None, action_dim=7, target=None, bs=8) -> dict:
+                   unnorm_stats=None, action_dim=7, target=None, bs=8, quant_model=None) -> dict:
     """Clean and patched greedy actions of `model` on F recorded frames with their prompts (right-padded input_ids / attention_mask [F,L]).
     placements: list of (geometry, angle, shx, shy, x, y), the per-frame arguments of simulation_patch_batch. The clean actions are decoded
     once per frame and reused for every placement; the patched rows are the P*F (placement, frame) pairs in placement-major order, run in
     batches of at most `bs` rows (K5 paste -> K7 crop / normalise -> predict_action). Nothing but token ids travels to the host: predict_action's
     own read-back and one copy of the collected ids at the end.
-    Returns {"tokens_clean" [F,A], "tokens_patched" [P,F,A], "placements", **summarise(...)}."""
+    Returns {"tokens_clean" [F,A], "tokens_patched" [P,F,A], "placements", **summarise(...)}.
+    quant_model (the same model converted by quant.quantize_llm): every batch is decoded on it as well, from the same pixel values; the report
+    gains "quantised" (the same four entries for that model, "quant_type") and "clean_agreement" (see clean_agreement) — without the latter the
+    two models' patched rates cannot be compared."""
     if bs < 1:
         raise ValueError("bs must be at least 1")
     dev = transform.device
@@ -89,8 +92,10 @@ def evaluate_patch(model, transform, frames_u8, input_ids, attention_mask, patch
     patch = patch.detach().to(dev, torch.float32).contiguous()
     placements = [(bool(g), float(a), float(sx), float(sy), int(x), int(y)) for g, a, sx, sy, x, y in placements]
 
+    models = [model] + ([quant_model] if quant_model is not None else [])
+
     def decode(pix, rows):
-        return model.predict_action(ids[rows], mask[rows], pix, unnorm_stats=unnorm_stats, action_dim=action_dim)[0]
+        return torch.stack([m.predict_action(ids[rows], mask[rows], pix, unnorm_stats=unnorm_stats, action_dim=action_dim)[0] for m in models], 1)
 
     clean = []
     for i in range(0, F, bs):
@@ -103,10 +108,24 @@ def evaluate_patch(model, transform, frames_u8, input_ids, attention_mask, patch
         geo, ang, shx, shy, pos = zip(*[(g, a, sx, sy, (x, y)) for g, a, sx, sy, x, y in (placements[r // F] for r in pairs)])
         pasted = transform.simulation_patch_batch(frames[rows], patch, geo, ang, shx, shy, pos)
         patched.append(decode(transform.eval_pixel_values(pasted, mean, std, center_crop, crop_scale), rows))
-    tokens_clean = torch.cat(clean).cpu()
-    tokens_patched = (torch.cat(patched).cpu() if patched else torch.empty((0, action_dim), dtype=torch.int64)).view(P, F, -1)
-    return {"tokens_clean": tokens_clean, "tokens_patched": tokens_patched, "placements": placements,
-            **summarise(tokens_clean, tokens_patched, unnorm_stats, target)}
+    clean = torch.cat(clean).cpu()  # [F, models, A]
+    patched = torch.cat(patched).cpu() if patched else torch.empty((0, len(models), action_dim), dtype=torch.int64)
+
+    def report(i):
+        tokens_clean, tokens_patched = clean[:, i].contiguous(), patched[:, i].reshape(P, F, action_dim)
+        return {"tokens_clean": tokens_clean, "tokens_patched": tokens_patched, **summarise(tokens_clean, tokens_patched, unnorm_stats, target)}
+
+    out = {"placements": placements, **report(0)}
+    if quant_model is not None:
+        out["quantised"] = dict(report(1), quant_type=getattr(quant_model, "q4", None))
+        out["clean_agreement"] = clean_agreement(out["tokens_clean"], out["quantised"]["tokens_clean"])
+    return out
+
+
+def clean_agreement(tokens_a: torch.Tensor, tokens_b: torch.Tensor) -> dict:
+    """Two models' clean tokens int64 [F,A] -> {"frames": share of frames whose whole action is the same, "tokens": share of equal tokens}."""
+    same = torch.as_tensor(tokens_a).cpu() == torch.as_tensor(tokens_b).cpu()
+    return {"frames": float(same.all(1).double().mean()), "tokens": float(same.double().mean())}
 
 
 def to_jsonable(report: dict):

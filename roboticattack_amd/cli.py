@@ -199,6 +199,18 @@ def add_eval(parser: argparse.ArgumentParser):
     parser.add_argument("--grid", default=None, type=two_ints, help="GX,GY: a grid of positions over the valid range at that angle and shear")
     parser.add_argument("--target", default=None, type=target_arg, help="maskidx:value — also report how often the patched token hits that action")
     parser.add_argument("--out", default=None, type=str, help="write the report as JSON (tokens included)")
+    # the reference's quantised deployment (run_libero_eval_args_geo_batch.py:312-313 -> from_pretrained, openvla_utils.py:43-51)
+    parser.add_argument("--load_in_8bit", type=str2bool, nargs="?", const=True, default=False, help="accepted and refused: LLM.int8 is not built")
+    parser.add_argument("--load_in_4bit", type=str2bool, nargs="?", const=True, default=False,
+                        help="also evaluate the model with its Llama projections quantised to 4 bits (quant.quantize_llm) and report both")
+    parser.add_argument("--bnb_4bit_quant_type", default="fp4", choices=("fp4", "nf4"), help="the 4-bit table (transformers' BitsAndBytesConfig default: fp4)")
+
+
+def check_eval_quant(parser: argparse.ArgumentParser, args):
+    """--load_in_8bit is parsed so that the reference's command lines are understood, and refused: LLM.int8's activation quantisation and
+    outlier split do not exist here."""
+    if args.load_in_8bit:
+        parser.error("--load_in_8bit is not supported (LLM.int8 is not built here); --load_in_4bit evaluates the 4-bit deployment")
 
 
 def eval_placements(args, ph: int, pw: int):

@@ -186,6 +186,8 @@ def _rope(q, k, cos, sin):
 
 
 class LlamaLayer(nn.Module):
+    q4 = None  # the table name once quant.quantize_llm has replaced the seven projections by Q4Linear modules (inference only from then on)
+
     def __init__(self, c: OpenVLACfg):
         super().__init__()
         d = c.llm_dim
@@ -246,6 +248,10 @@ class LlamaLayer(nn.Module):
         for those rows only and [R,D] is returned (last layer of `forward_rows`: no other position reaches the loss)."""
         from . import model_ops
 
+        if self.q4:
+            from . import quant
+
+            quant.refuse_training("LlamaLayer.forward")
         B, T, D = x.shape
         hd = D // self.heads
         fused = rope_tab is not None and model_ops.enabled(x) and hd % 16 == 0 and D % 8 == 0 and D <= 8192
@@ -359,6 +365,10 @@ class LlamaLayer(nn.Module):
         pad slots hold garbage that the decode steps overwrite before any query sees it."""
         from . import model_ops
 
+        if self.q4:  # the 4-bit route (quant.py): dequant + GEMM on the same graph
+            from . import quant
+
+            return quant.layer_prefill(self, x, rope_tab, cache)
         B, T, D = x.shape
         hd = D // self.heads
         fused = self._infer_fused(x)
@@ -384,6 +394,10 @@ class LlamaLayer(nn.Module):
         QKV GEMM on [B,1,D], model_ops.attention_decode (rotation, cache append and attention in one launch), o_proj, residual, MLP."""
         from . import model_ops
 
+        if self.q4:  # the 4-bit route (quant.py): the projections through vaa_model_q4_gemv
+            from . import quant
+
+            return quant.layer_decode(self, x, pos, rope_tab, cache)
         B, _, D = x.shape
         fused = self._infer_fused(x)
         qkv = self._infer_qkv(self._infer_norm(self.input_layernorm, x, fused), fused)[:, 0]  # [B,3,H,hd]
@@ -429,6 +443,14 @@ class SeqPack:
 
 
 class OpenVLAShaped(nn.Module):
+    q4 = None  # the table name once quant.quantize_llm has converted the Llama stack (predict_action / evaluate_patch only from then on)
+
+    def _refuse_if_quantised(self, what):
+        if self.q4:
+            from . import quant
+
+            quant.refuse_training(what)
+
     def __init__(self, cfg: OpenVLACfg | None = None):
         super().__init__()
         self.cfg = c = cfg or openvla_7b_cfg()
@@ -536,6 +558,7 @@ class OpenVLAShaped(nn.Module):
         `rows` (flat position indices into the PADDED [B*T] layout) only those positions of the LAST layer are evaluated and
         [R,D] is returned. `pack` (SeqPack): the Llama stack runs on the packed token axis ([1, sum T_b, D] is returned unless
         `rows` is given)."""
+        self._refuse_if_quantised("hidden_states")
         if patch_embeds is not None:
             in0, in1, kw = patch_embeds[0], patch_embeds[1], True
         else:
@@ -600,6 +623,7 @@ class OpenVLAShaped(nn.Module):
         """Logits [R,V] of the labelled rows only, in (b,k) row-major order of labels[b,k+1] != -100 (VAA_LAYOUT_ROWS):
         row (b,k) is model position S-L+k = 256+k, the position whose next-token target is labels[b,k+1].
         Pass `row_index=label_row_index(labels)` to keep the step free of host synchronisation."""
+        self._refuse_if_quantised("forward_rows")
         if row_index is None:
             row_index = self.label_row_index(labels)
         return self.lm_head(self.hidden_states(input_ids, pixel_values, rows=row_index, patch_embeds=patch_embeds, pack=pack))  # [R, D] -> [R, V]
@@ -613,6 +637,7 @@ class OpenVLAShaped(nn.Module):
         """Drop-in contract of PrismaticForConditionalGeneration.forward: full fp32 logits and HF's mean CE."""
         from .surrogate import hf_causal_ce
 
+        self._refuse_if_quantised("forward")
         logits = self.lm_head(self.hidden_states(input_ids, pixel_values)).float()
         loss = hf_causal_ce(logits, labels) if labels is not None else None
         return types.SimpleNamespace(loss=loss, logits=logits)

@@ -20,8 +20,10 @@ from roboticattack_amd.transform import RandomPatchTransform  # noqa: E402
 def arg_parser(argv=None):
     parser = argparse.ArgumentParser(description=__doc__)
     cli.add_eval(parser)
+    cli.add_eval_frame_flags(parser)
     args = parser.parse_args(argv)
     cli.check_eval_quant(parser, args)
+    cli.check_eval_frames(parser, args)
     return args
 
 
@@ -41,11 +43,20 @@ def main(argv=None):
         from roboticattack_amd.quant import quantize_llm
 
         vla_q4 = quantize_llm(copy.deepcopy(vla), args.bnb_4bit_quant_type)
-    frames, input_ids, attention_mask = synthetic.synth_eval_batch(args.seed, args.frames)
+    source = {}
+    if args.frames_data is None:
+        frames, input_ids, attention_mask = synthetic.synth_eval_batch(args.seed, args.frames)
+    else:  # recorded frames; their prompts, or the synthetic batch's
+        frames, input_ids, attention_mask = args.frames_data
+        args.frames = int(frames.shape[0])
+        if input_ids is None:
+            _, input_ids, attention_mask = synthetic.synth_eval_batch(args.seed, args.frames)
+        source = dict(frames_file=args.frames_file, source_size=[int(frames.shape[1]), int(frames.shape[2])], frame_resize=args.frame_resize,
+                      rotate180=bool(args.rotate180))
     target = (args.target[0], args.target[1]) if args.target else None
     report = evaluate_patch(vla, RandomPatchTransform(device), frames, input_ids, attention_mask, patch.float(), placements,
                             center_crop=args.center_crop, crop_scale=args.crop_scale, mean=[MEAN6[:3], MEAN6[3:]], std=[STD6[:3], STD6[3:]],
-                            target=target, bs=args.bs, quant_model=vla_q4)
+                            target=target, bs=args.bs, quant_model=vla_q4, resize=args.frame_resize, rot180=bool(args.rotate180))
     torch.cuda.synchronize()
     ops.async_error_check()
     for (geo, angle, shx, shy, x, y), r in zip(report["placements"], report["per_placement"]):
@@ -60,7 +71,7 @@ def main(argv=None):
         print(f"4-bit ({q['quant_type']}) model: any_flip={q['overall']['any_flip_rate']:.3f} mean_nad={float(q['overall']['nad'].mean()):.4f}; "
               f"clean actions equal to the bf16 model's on {ca['frames']:.3f} of the frames, {ca['tokens']:.3f} of the tokens")
     out = to_jsonable(dict(report, patch=args.patch, vla_path=path, frames=args.frames, center_crop=bool(args.center_crop),
-                           crop_scale=args.crop_scale))
+                           crop_scale=args.crop_scale, **source))
     if args.out:
         with open(args.out, "w") as f:
             json.dump(out, f)

@@ -555,6 +555,47 @@ int vaa_patch_apply_eval(const uint8_t* img_u8, const float* patch, const int32_
  */
 int vaa_eval_preprocess(const uint8_t* img_u8, int B, float crop_scale, const float* mean6, const float* std6, uint16_t* out_bf16, void* stream);
 
+/*
+ * K8 — the resize of a simulator's camera frames to 224x224 in front of the eval-time paste: replaces, per camera frame,
+ * `tf.image.resize(img, (224,224), method="lanczos3", antialias=True)` followed by round, clip_by_value(0, 255) and the uint8 cast
+ * (experiments/robot/libero/libero_utils.py:44-45, experiments/robot/bridge/bridgev2_utils.py:112) and, with rot180, LIBERO's `img[::-1, ::-1]`
+ * in front of it (libero_utils.py:56). One launch per batch; a frame's bytes do not depend on the batch around it; same arguments, same bits.
+ *   src_u8   dev  [B,H,W,3] uint8 HWC (4-byte aligned), 8 <= H, W <= 2048
+ *   rot180   0 or 1: the source is read as src[b, H-1-r, W-1-j] wherever the rules below say src[b, r, j] (no extra pass)
+ *   start_x, w_x, Tx / start_y, w_y, Ty   host: the separable filter per axis (x: along W, y: along H), for each of the 224 output indices i
+ *            start[i]  int32: the first source index; w[i*T + t] float32, t < T: the weight of source index start[i] + t (zero-padded to T).
+ *            1 <= T <= VAA_FRAME_RESIZE_MAX_TAPS; every start[i] >= 0 and start[i] + T - 1 <= axis length - 1; every weight finite.
+ *   taps_dev dev  the same four tables on the device, vaa_frame_resize_taps_bytes(Tx, Ty) bytes (4-byte aligned), packed in the order
+ *            int32 start_x[224], int32 start_y[224], float32 w_x[224*Tx], float32 w_y[224*Ty]. The host tables are what is validated, the
+ *            device copy is what the kernel reads; the kernel clamps every source index to the axis, so a device copy that differs from
+ *            the validated tables cannot read outside src.
+ *   dst_u8   dev  [B,224,224,3] uint8 HWC (16-byte aligned): the layout vaa_patch_apply_eval takes
+ * Before any launch: B < 0 or (B > 0) a NULL pointer, rot180 not 0 / 1, T < 1, a start outside the axis or a non-finite weight: VAA_E_INVALID;
+ * B == 0: VAA_OK, nothing is read or written; H or W outside [8, 2048], T > VAA_FRAME_RESIZE_MAX_TAPS, a misaligned base: VAA_E_UNSUPPORTED.
+ *
+ * The arithmetic is the contract: fp32 throughout, every operation separately rounded (no FMA), the horizontal pass first, the taps of a
+ * pass accumulated in ascending source index starting from 0.0f. With p(r, j, c) = (float)src[b, r, j, c] (after rot180):
+ *     h(r, x, c) = (..((0 + w_x[x][0] * p(r, sx, c)) + w_x[x][1] * p(r, sx + 1, c)) + ..) + w_x[x][Tx-1] * p(r, sx + Tx - 1, c),  sx = start_x[x]
+ *     v(y, x, c) = (..((0 + w_y[y][0] * h(sy, x, c)) + w_y[y][1] * h(sy + 1, x, c)) + ..) + w_y[y][Ty-1] * h(sy + Ty - 1, x, c),  sy = start_y[y]
+ *     dst[b, y, x, c] = (uint8) min(max(rintf(v), 0), 255)             (rintf: round half to even, as tf.round)
+ *
+ * The tables are the caller's; the ones the evaluation uses (resize.lanczos3_taps) follow TensorFlow's ScaleAndTranslate rule for
+ * lanczos3 with antialias. THE RULE IS WRITTEN HERE FROM MEMORY: TensorFlow cannot be run on this platform, so neither the span, nor the
+ * normalisation, nor the rounding of the weights could be compared with it — this header is the definition. Per axis, in -> out = 224,
+ * everything in fp64:
+ *     scale = in / out;   kernel_scale = max(scale, 1);   T = 2*ceil(3*kernel_scale) + 1
+ *     sample point of output index i (pixel-edge coordinates):  s = (i + 0.5) * scale
+ *     span: lo = max(ceil(s - 3*kernel_scale - 0.5), 0),  hi = min(floor(s + 3*kernel_scale - 0.5), in - 1)     (at most T indices)
+ *     raw weight of source index j in [lo, hi]:  L((j + 0.5 - s) / kernel_scale),   L(x) = sinc(x) * sinc(x / 3) on |x| < 3, else 0,
+ *         sinc(x) = sin(pi*x) / (pi*x), sinc(0) = 1
+ *     the raw weights of a span are divided by their sum (added in ascending j), then rounded to fp32
+ *     start = max(min(lo, in - T), 0): the window of T indices is shifted into the axis at its end; positions outside [lo, hi] hold 0
+ */
+#define VAA_FRAME_RESIZE_MAX_TAPS 57 /* 2*ceil(3*2048/224) + 1 */
+size_t vaa_frame_resize_taps_bytes(int Tx, int Ty);
+int vaa_frame_resize(const uint8_t* src_u8, int B, int H, int W, int rot180, const int32_t* start_x, const float* w_x, int Tx,
+                     const int32_t* start_y, const float* w_y, int Ty, const void* taps_dev, uint8_t* dst_u8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ LAYOUT_FULL, LAYOUT_ROWS = 0, 1
 GRAD_FULL, GRAD_SLICE = 0, 1
 SEG_UPA_MAX_GROUPS = 32  # VAA_SEG_UPA_MAX_GROUPS: groups of one vaa_loss_rows_fwd_bwd_seg_upa call
 OPT_ADAMW_HF, OPT_PGD_SIGN = 0, 1
+FRAME_RESIZE_MAX_TAPS = 57  # VAA_FRAME_RESIZE_MAX_TAPS
 
 MODEL_OP_EXPORTS = ("vaa_model_rope", "vaa_model_swiglu_fwd", "vaa_model_swiglu_bwd", "vaa_model_rmsnorm_fwd", "vaa_model_rmsnorm_bwd",
                     "vaa_model_attention_fwd", "vaa_model_attention_bwd", "vaa_model_layernorm_fwd", "vaa_model_layernorm_bwd", "vaa_model_scale_add",
@@ -37,6 +38,8 @@ EXPORTS = (
     "vaa_patch_update",
     "vaa_patch_apply_eval",
     "vaa_eval_preprocess",
+    "vaa_frame_resize_taps_bytes",
+    "vaa_frame_resize",
     "vaa_patch_embed_grad_ws_bytes",
     "vaa_patch_embed_grad_gather",
     "vaa_patch_embed_packed_elems",
@@ -211,6 +214,10 @@ def lib() -> C.CDLL:
     L.vaa_patch_apply_eval.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
     L.vaa_eval_preprocess.restype = i32
     L.vaa_eval_preprocess.argtypes = [vp, i32, f32, C.POINTER(f32), C.POINTER(f32), vp, vp]
+    L.vaa_frame_resize_taps_bytes.restype = sz
+    L.vaa_frame_resize_taps_bytes.argtypes = [i32, i32]
+    L.vaa_frame_resize.restype = i32
+    L.vaa_frame_resize.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp]
     L.vaa_patch_apply_fwd_tiles.restype = i32
     L.vaa_patch_apply_fwd_tiles.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, vp, vp, vp, vp]
     L.vaa_patch_embed_grad_gather_multi_tiles.restype = i32

@@ -71,7 +71,7 @@ def summarise(tokens_clean: torch.Tensor, tokens_patched: torch.Tensor, unnorm_s
 
 @torch.no_grad()
 def evaluate_patch(model, transform, frames_u8, input_ids, attention_mask, patch, placements, *, center_crop=True, crop_scale=0.9, mean, std,
-                   unnorm_stats=None, action_dim=7, target=None, bs=8, quant_model=None) -> dict:
+                   unnorm_stats=None, action_dim=7, target=None, bs=8, quant_model=None, resize=None, rot180=False) -> dict:
     """Clean and patched greedy actions of `model` on F recorded frames with their prompts (right-padded input_ids / attention_mask [F,L]).
     placements: list of (geometry, angle, shx, shy, x, y), the per-frame arguments of simulation_patch_batch. The clean actions are decoded
     once per frame and reused for every placement; the patched rows are the P*F (placement, frame) pairs in placement-major order, run in
@@ -80,10 +80,19 @@ def evaluate_patch(model, transform, frames_u8, input_ids, attention_mask, patch
     Returns {"tokens_clean" [F,A], "tokens_patched" [P,F,A], "placements", **summarise(...)}.
     quant_model (the same model converted by quant.quantize_llm): every batch is decoded on it as well, from the same pixel values; the report
     gains "quantised" (the same four entries for that model, "quant_type") and "clean_agreement" (see clean_agreement) — without the latter the
-    two models' patched rates cannot be compared."""
+    two models' patched rates cannot be compared.
+    resize="lanczos3": frames_u8 are a simulator's camera frames [F,H,W,3] of any size; each is resized to 224x224 once (K8,
+    transform.eval_frames; rot180=True rotates it by 180 degrees first, as the LIBERO evaluation does), before the clean pass, and everything
+    above runs on the resized frames. Without it the frames must be 224x224 and are used as they are."""
     if bs < 1:
         raise ValueError("bs must be at least 1")
+    if resize not in (None, "lanczos3"):
+        raise ValueError(f"resize must be None or 'lanczos3', got {resize!r}")
+    if resize is None and rot180:
+        raise ValueError("rot180 is part of the frame resize: pass resize='lanczos3'")
     dev = transform.device
+    if resize is not None:
+        frames_u8 = transform.eval_frames(frames_u8, rot180)
     frames = transform.stage_images(frames_u8 if isinstance(frames_u8, torch.Tensor) else torch.as_tensor(np.asarray(frames_u8)))
     ids, mask = input_ids.to(dev), attention_mask.to(dev)
     F, P = int(frames.shape[0]), len(placements)

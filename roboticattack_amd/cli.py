@@ -213,6 +213,59 @@ def check_eval_quant(parser: argparse.ArgumentParser, args):
         parser.error("--load_in_8bit is not supported (LLM.int8 is not built here); --load_in_4bit evaluates the 4-bit deployment")
 
 
+def add_eval_frame_flags(parser: argparse.ArgumentParser):
+    """Recorded camera frames instead of the synthetic ones, and what the reference's simulators do to a frame before the paste
+    (experiments/robot/libero/libero_utils.py:44-58, experiments/robot/bridge/bridgev2_utils.py:112)."""
+    parser.add_argument("--frames_file", default=None, type=str,
+                        help="an .npz with `frames` uint8 [F,H,W,3] and optionally `input_ids` / `attention_mask` int64 [F,T] (right-padded); "
+                             "without the prompts, those of the synthetic batch of --seed are used")
+    parser.add_argument("--frame_resize", default=None, choices=("lanczos3",),
+                        help="resize the file's frames to 224x224 as the simulators' wrappers do (lanczos3 with antialias, round, clip)")
+    parser.add_argument("--rotate180", type=str2bool, nargs="?", const=True, default=False,
+                        help="rotate every frame by 180 degrees in front of the resize (the LIBERO evaluation does)")
+
+
+def load_frames_file(path: str):
+    """--frames_file -> (frames uint8 [F,H,W,3] numpy, input_ids | None, attention_mask | None); the prompts are int64 tensors [F,T]."""
+    with np.load(path) as z:
+        if "frames" not in z.files:
+            raise ValueError(f"{path}: no `frames` array")
+        frames = np.ascontiguousarray(z["frames"])
+        ids = torch.from_numpy(z["input_ids"].astype(np.int64)) if "input_ids" in z.files else None
+        mask = torch.from_numpy(z["attention_mask"].astype(np.int64)) if "attention_mask" in z.files else None
+    if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[-1] != 3 or frames.shape[0] < 1:
+        raise ValueError(f"{path}: `frames` must be uint8 [F,H,W,3], got {frames.dtype} {frames.shape}")
+    if (ids is None) != (mask is None):
+        raise ValueError(f"{path}: `input_ids` and `attention_mask` come together or not at all")
+    if ids is not None and (ids.dim() != 2 or ids.shape != mask.shape or ids.shape[0] != frames.shape[0]):
+        raise ValueError(f"{path}: prompts {tuple(ids.shape)} / {tuple(mask.shape)} do not match {frames.shape[0]} frames")
+    return frames, ids, mask
+
+
+def check_eval_frames(parser: argparse.ArgumentParser, args):
+    """Reads --frames_file (into args.frames_data) so that a file the command cannot use stops the run before the model loads: frames that
+    are not 224x224 need --frame_resize. Without --frames_file the two other flags have nothing to act on."""
+    from .constants import IMG
+
+    args.frames_data = None
+    if args.frames_file is None:
+        if args.frame_resize is not None or args.rotate180:
+            parser.error("--frame_resize / --rotate180 act on the frames of --frames_file")
+        return
+    try:
+        args.frames_data = load_frames_file(args.frames_file)
+    except (OSError, ValueError, KeyError) as e:
+        parser.error(f"--frames_file: {e}")
+    h, w = args.frames_data[0].shape[1:3]
+    if args.frame_resize is None:
+        if (h, w) != (IMG, IMG):
+            parser.error(f"--frames_file {args.frames_file}: the frames are {h}x{w}, not {IMG}x{IMG}: pass --frame_resize lanczos3")
+        if args.rotate180:
+            parser.error("--rotate180 is part of the frame resize: pass --frame_resize lanczos3")
+    elif not (8 <= h <= 2048 and 8 <= w <= 2048):
+        parser.error(f"--frames_file {args.frames_file}: {h}x{w} frames are outside what --frame_resize takes (8 to 2048 per side)")
+
+
 def eval_placements(args, ph: int, pw: int):
     """One (geometry, angle, shx, shy, x, y) from the flags, or with --grid GX,GY the GX x GY positions spread evenly over the valid range
     [0, 224 - pw] x [0, 224 - ph], row-major (y outer); an axis with one point keeps --x / --y."""

@@ -1190,3 +1190,44 @@ def eval_preprocess(img_u8, crop_scale: float = 0.0, mean6=None, std6=None):
         rc = _lib.lib().vaa_eval_preprocess(img_u8.data_ptr(), B, float(crop_scale), mean_c, std_c, out.data_ptr(), _stream())
     _lib.check(rc, "vaa_eval_preprocess")
     return out
+
+
+# ------------------------------------------------------------------------------------------------------
+# camera frames -> 224x224 in front of the eval-time paste (tf.image.resize lanczos3 + round + clip + uint8)
+# ------------------------------------------------------------------------------------------------------
+_resize_taps: dict = {}
+
+
+def _frame_taps(H: int, W: int, device):
+    """The tap tables of an H x W source, computed once per (H, W, device): the host arrays the library validates and their packed device copy."""
+    import numpy as np
+
+    from . import resize
+
+    key = (H, W, device.index if device.index is not None else torch.cuda.current_device())
+    hit = _resize_taps.get(key)
+    if hit is None:
+        sx, wx, sy, wy = (np.ascontiguousarray(t) for t in resize.frame_taps(H, W))
+        dev = torch.from_numpy(resize.pack_taps(sx, wx, sy, wy)).to(device)
+        hit = _resize_taps[key] = (sx, wx, sy, wy, dev)
+    return hit
+
+
+def resize_frames(frames_u8, rot180: bool = False):
+    """K8. uint8 frames [B,H,W,3] (8 <= H, W <= 2048) -> uint8 [B,224,224,3]: the lanczos3 resize with antialias, round half to even, clip
+    (include/vaa.h states the arithmetic and the tap rule). rot180: the frames are read as frames[:, ::-1, ::-1] (LIBERO), in the same launch."""
+    if not isinstance(frames_u8, torch.Tensor) or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
+        raise _lib.VaaError("frames_u8: expected a uint8 tensor [B,H,W,3] on a ROCm device (there is no CPU fallback)")
+    _need(frames_u8, torch.uint8, "frames_u8")
+    B, H, W = (int(v) for v in frames_u8.shape[:3])
+    from . import resize
+
+    if not (resize.MIN_SIDE <= H <= resize.MAX_SIDE and resize.MIN_SIDE <= W <= resize.MAX_SIDE):
+        raise _lib.VaaError(f"frames_u8: {H}x{W} frames outside [{resize.MIN_SIDE}, {resize.MAX_SIDE}] per side")
+    sx, wx, sy, wy, taps = _frame_taps(H, W, frames_u8.device)
+    out = torch.empty((B, IMG, IMG, 3), dtype=torch.uint8, device=frames_u8.device)
+    with _timed("K8_frame_resize", B=B, H=H, W=W):
+        rc = _lib.lib().vaa_frame_resize(frames_u8.data_ptr(), B, H, W, int(bool(rot180)), sx.ctypes.data, wx.ctypes.data, int(wx.shape[1]),
+                                         sy.ctypes.data, wy.ctypes.data, int(wy.shape[1]), taps.data_ptr(), out.data_ptr(), _stream())
+    _lib.check(rc, "vaa_frame_resize")
+    return out

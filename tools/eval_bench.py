@@ -6,7 +6,11 @@
     batch   ms per evaluated batch, split into K5 (paste), K7 and predict_action (device events around each; predict_action ends with its token
             read-back), median of 5
 
-    python tools/eval_bench.py [--bs 1,8] [--iters 5] [--warmup 2] [--out file.json]
+    k8      K8 (vaa_frame_resize, the lanczos3 resize of camera frames to 224x224) at 256x256 and 480x640 against the same filter in stock
+            PyTorch ops (two fp32 matmuls with the dense tap matrices, then round, clip and cast; the differing bytes are counted before
+            anything is timed): per-dispatch us of K8 from vaa_prof_* (median of 50), event-bracketed us of both in alternating rounds
+
+    python tools/eval_bench.py [--bs 1,8] [--iters 5] [--warmup 2] [--parts front,batch,k8] [--out file.json]
 
 Each part runs in a fresh child process under `timeout`, one after the other; the first child that fails ends the run. One JSON line per result.
 """
@@ -116,6 +120,74 @@ def child_front(batches, reps: int) -> int:
     return 0
 
 
+K8_SIZES = ((256, 256), (480, 640))
+
+
+def stock_resize(frames_u8, mx, my):
+    """vaa_frame_resize's filter with stock PyTorch ops: the horizontal pass as one fp32 matmul with the dense [224,W] tap matrix, the vertical
+    pass as one with the dense [224,H] matrix, then round (half to even), clip and cast. The matmuls add a span's taps in their own order."""
+    import torch
+
+    x = frames_u8.permute(0, 3, 1, 2).to(torch.float32)        # [B,3,H,W]
+    v = my @ (x @ mx.t())                                      # [B,3,224,224]
+    return v.round().clamp(0.0, 255.0).to(frames_u8.dtype).permute(0, 2, 3, 1).contiguous()
+
+
+def _dense(start, w, n_in, dev):
+    import torch
+
+    m = torch.zeros((224, n_in), dtype=torch.float32)
+    for i in range(224):
+        m[i, int(start[i]): int(start[i]) + w.shape[1]] = torch.from_numpy(w[i])
+    return m.to(dev)
+
+
+def child_k8(batches, reps: int) -> int:
+    import numpy as np
+    import torch
+
+    from roboticattack_amd import ops, resize
+
+    dev = torch.device("cuda:0")
+    for H, W in K8_SIZES:
+        sx, wx, sy, wy = resize.frame_taps(H, W)
+        mx, my = _dense(sx, wx, W, dev), _dense(sy, wy, H, dev)
+        for bs in batches:
+            rs = np.random.RandomState(1000 * H + bs)
+            ramp = np.linspace(0, 255, W)[None, None, :, None] * 0.7 + np.linspace(0, 255, H)[None, :, None, None] * 0.3
+            frames = torch.from_numpy(np.clip(ramp + rs.uniform(-30, 30, (bs, H, W, 3)), 0, 255).astype(np.uint8)).to(dev)
+            k8 = ops.resize_frames(frames)
+            stock = stock_resize(frames, mx, my)
+            torch.cuda.synchronize()
+            ops.async_error_check()
+            differ = int((k8 != stock).sum())
+            off_by_more = int(((k8.to(torch.int16) - stock.to(torch.int16)).abs() > 1).sum())
+            if off_by_more or differ > k8.numel() // 1000:  # a summation-order difference moves a byte only at a .5 tie, and by one
+                print(json.dumps(dict(part="k8", H=H, W=W, bs=bs, failed="stock formulation differs from K8 in %d of %d bytes (%d by more than 1)"
+                                      % (differ, k8.numel(), off_by_more))))
+                return 1
+            for _ in range(5):  # warm-up of both
+                ops.resize_frames(frames)
+                stock_resize(frames, mx, my)
+            torch.cuda.synchronize()
+            ops.prof_start(reps)
+            for _ in range(reps):
+                ops.resize_frames(frames)
+            torch.cuda.synchronize()
+            disp = [us for _, us in ops.prof_collect()]
+            rounds = {"k8": [], "stock": []}
+            for _ in range(3):  # alternate the two in one process
+                rounds["k8"] += _event_us(lambda: ops.resize_frames(frames), reps)
+                rounds["stock"] += _event_us(lambda: stock_resize(frames, mx, my), reps)
+            nbytes = bs * (H * W * 3 + 224 * 224 * 3)
+            d = _median(disp)
+            print(json.dumps(dict(part="k8", H=H, W=W, bs=bs, taps=[int(wx.shape[1]), int(wy.shape[1])], bytes_differing_from_stock=differ,
+                                  bytes_out=k8.numel(), k8_dispatch_us_median=round(d, 2), k8_dispatch_us_min=round(min(disp), 2), k8_bytes=nbytes,
+                                  k8_event_us_median=round(_median(rounds["k8"]), 2), stock_event_us_median=round(_median(rounds["stock"]), 2),
+                                  stock_over_k8=round(_median(rounds["stock"]) / _median(rounds["k8"]), 2), reps=reps)), flush=True)
+    return 0
+
+
 def child_batch(batches, iters: int, warmup: int) -> int:
     import numpy as np
     import torch
@@ -164,7 +236,7 @@ def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--reps", type=int, default=50, help="K7 / stock repetitions per round of the front part")
+    ap.add_argument("--reps", type=int, default=50, help="kernel / stock repetitions per round of the front and k8 parts")
     ap.add_argument("--bs", default="1,8")
     ap.add_argument("--parts", default="front,batch")
     ap.add_argument("--out", default=None)
@@ -176,6 +248,8 @@ def main() -> int:
         return child_front(batches, a.reps)
     if a.child == "batch":
         return child_batch(batches, a.iters, a.warmup)
+    if a.child == "k8":
+        return child_k8(batches, a.reps)
     results = []
     for part in a.parts.split(","):
         cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", part, "--iters", str(a.iters),

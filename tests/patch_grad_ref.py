@@ -1,0 +1,649 @@
+"""fp64 reference of the patch-gradient kernels (K2, K2', the K0 adjoint) with a bound per output element.
+
+Plain numpy / torch-CPU; calls no HIP code and takes no value from the C oracle's gradient routines. The keep mask is an INPUT (K1's
+mask as the C oracle states it, pinned to the reference goldens): the reference never derives it.
+
+COORDINATES (sample()): formed in fp32 exactly as roboticattack_amd/csrc/vaa_common.h documents torch's CPU chain —
+    base     linspace's two-sided evaluation, one FMA per side, then (lin * 223) / 224
+    grid     base @ theta^T as a product, one FMA, then a plain add of the translation
+    ix, iy   the unnormalise step (g + 1) * 112 - 0.5 as one FMA, the border clamp to [0, 223], floor
+An fp32 FMA of fp32 inputs is np.float32(float64(a) * float64(b) + float64(c)) wherever the fp64 expression is exact (then the cast is the
+one rounding). That holds for the base coordinate (an 8-bit integer times a 24-bit step, plus 1: 38 bits) and for the unnormalise step (a
+24-bit value that is a multiple of 2^-24 or larger, times 112, minus 0.5: under 40 bits). It does NOT hold for the grid's FMA when the two
+terms differ widely in magnitude (theta entries like 1e-7): fma32() therefore forms the exact product, adds with TwoSum and moves a sum
+that sits exactly on an fp32 rounding midpoint off it in the direction of the residual before the cast — correctly rounded for every input.
+test_patch_grad_ref_host.py checks the grid against F.affine_grid (fp32, CPU) bit for bit.
+The fractions w, n are taken as those fp32 values; corner weights (1-n)(1-w), (1-n)w, n(1-w), nw, the 1/std scaling, the tower sum, the
+products and every sum are fp64.
+
+BOUNDS. u = 2^-24 (fp32 unit roundoff). For texel e with contributions k = (pixel, corner) of weight w_k >= 0 from kept pixels:
+    A_k   = |t0_k| / std0 + |t1_k| / std1, the absolute tower terms of the pixel's effective gradient G_k = t0/std0 + t1/std1
+    S_e   = sum_k A_k w_k
+  K2 (patch_grad_scatter_kernel):
+    T1  7 u S_e          fl(1/std) (1), the two fp32 products (1) and their fp32 sum (1) of G; fl(1-w), fl(1-n), the corner product
+                         and fl(G * w) (1 each): seven (1 + d) factors per contribution, first order
+    T2  n_e q / 2        each contribution is rounded to an integer multiple of q = 2^(E + 1 - 30); E = floor(log2(largest |G| the
+                         workgroup sees)) is at most that of the batch maximum (per image for the per-image forms, which reset E)
+    T3  min(n_e, B) q    shift_round re-scales of the tile when E grows: exponents strictly increase, so their half-quanta sum to less
+                         than one final quantum per workgroup tile; at most min(n_e, B) workgroup tiles hold contributions to a texel
+    T4  u (S_e + dG_e)   the fp32 rounding of each workgroup's partial tile (a partial is at most the absolute sum of its contributions)
+    T5  u |value_e|      the final fp32 rounding after the fixed-order fp64 sum of the partial tiles
+  K2' (embed_dgrad_tiles*_kernel, then the same scatter), per tile pixel t = sum_d dy_d w_d (bf16 x bf16 products are exact in fp32):
+    T6  dt = D u sum_d |dy_d w_d|      fp32 MFMA accumulation of D terms, any order
+        round_bf16: the reference rounds its own fp64 t to bf16 (RNE). The kernel's bf16(acc) can differ only where a bf16 rounding
+        midpoint lies within dt of t; there the bound is dt + one bf16 ulp at |t| + dt (half an ulp on either side of the midpoint plus
+        the accumulated error), elsewhere 0: the rounded values are equal.
+    The fp32 `* 1/std` and the tower add are the first three factors of T1. dG_e = sum_k w_k (dt0_k / std0 + dt1_k / std1) carries T6
+    through the scatter with the weights.
+  K0 adjoint (patch_resize_bwd_kernel): the kernel's tap weights are torch's fp32 CPU weights (the forward is bit-exact against it), the
+    reference's are fp64. With per-axis weight matrices Wy, Wx (taken from F.interpolate of an identity, fp32 and fp64):
+    T7  (|Wy32 - Wy64| (x) Wx64 + Wy32 (x) |Wx32 - Wx64|)^T |gy|    the weight difference — the DOMINANT term (fp32 tap centres carry an
+                         absolute error of ~2^-17 at 224 pixels, so weights differ by ~1e-5 absolutely, however small the weight)
+    T8  k u A^T|gy|, k = n_cov + B + 3    fl(wx * wy), fl(. * g) (2), the fp32 running sum over the n_cov outputs that cover the element,
+                         the fp32 sum over the images of a group (<= B) and the final rounding (1). The filter weights are non-negative,
+                         so A^T|gy| is the same fp64 autograd run on |gy|.
+  A texel that no kept pixel reaches has n_e = 0: value 0, bound 0 — it must come out exactly 0.
+  SAFETY = 2 multiplies the derived sum, once (second-order terms, the 1-ulp slack of E at a power of two).
+"""
+from __future__ import annotations
+
+import collections
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+IMG = 224
+NPIX = IMG * IMG
+U = 2.0 ** -24
+SAFETY = 2.0
+CBITS = 30
+STD6 = np.array([0.228515625, 0.2236328125, 0.224609375, 0.5, 0.5, 0.5], np.float32)
+MEAN6 = np.array([0.484375, 0.455078125, 0.40625, 0.5, 0.5, 0.5], np.float32)
+
+Ref = collections.namedtuple("Ref", "value bound meta")  # meta: dict(kind, B, ph, pw, pdesc, band_rows)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# fp32 coordinate chain
+# ---------------------------------------------------------------------------------------------------------------------------------
+def fma32(a, b, c):
+    """Correctly rounded fp32 fma(a, b, c) of fp32 arrays (see the module docstring)."""
+    a, b, c = (np.asarray(v, np.float32).astype(np.float64) for v in (a, b, c))
+    p = a * b  # exact: 48 bits
+    s = p + c
+    bb = s - p
+    e = (p - (s - bb)) + (c - bb)  # TwoSum residual: p + c == s + e exactly
+    r = s.astype(np.float32)
+    r64 = r.astype(np.float64)
+    toward = np.where(s > r64, np.float32(np.inf), np.float32(-np.inf)).astype(np.float32)
+    other = np.nextafter(r, toward).astype(np.float64)
+    tie = (s != r64) & (2.0 * s == r64 + other) & (e != 0.0)
+    if np.any(tie):
+        s = np.where(tie, np.nextafter(s, np.where(e > 0, np.inf, -np.inf)), s)
+        r = s.astype(np.float32)
+    return r
+
+
+def base_coords():
+    i = np.arange(IMG, dtype=np.float64)
+    step = np.float64(np.float32(2.0) / np.float32(223.0))
+    lin = np.where(i < IMG // 2, i * step - 1.0, -(IMG - 1 - i) * step + 1.0).astype(np.float32)  # exact in fp64: one rounding
+    return (lin * np.float32(223.0)) / np.float32(224.0)
+
+
+_BASE = base_coords()
+
+
+def grid32(theta6):
+    """F.affine_grid(theta, align_corners=False) of one image: (gx, gy) fp32 [224,224], row i, column j."""
+    th = np.asarray(theta6, np.float32).reshape(6)
+    bx, by = _BASE[None, :], _BASE[:, None]
+    gx = fma32(by, th[1], bx * th[0]) + th[2]
+    gy = fma32(by, th[4], bx * th[3]) + th[5]
+    return gx.astype(np.float32), gy.astype(np.float32)
+
+
+def sample(theta6, geometry=True):
+    """(x0, y0 int32, w, n fp32) [224*224] of one image: the floor of the clamped source position and its fractions."""
+    if not geometry:
+        jj, ii = np.meshgrid(np.arange(IMG, dtype=np.int32), np.arange(IMG, dtype=np.int32))
+        z = np.zeros(NPIX, np.float32)
+        return jj.ravel(), ii.ravel(), z, z
+    gx, gy = grid32(theta6)
+    out = []
+    for g in (gx, gy):
+        v = ((g + np.float32(1.0)).astype(np.float64) * 112.0 - 0.5).astype(np.float32)  # one FMA: the fp64 expression is exact
+        v = np.minimum(np.float32(223.0), np.maximum(v, np.float32(0.0)))
+        f = np.floor(v)
+        out.append((f.astype(np.int32).ravel(), (v - f).astype(np.float32).ravel()))
+    return out[0][0], out[1][0], out[0][1], out[1][1]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the launcher's schedule (csrc/vaa_patch_grad.hip: grad_sched, band_rows_for, launch_scatter_reduce / _multi), restated for the messages
+# ---------------------------------------------------------------------------------------------------------------------------------
+def band_rows(B, ph, pw, multi=False):
+    gx = B if (multi or B < 512) else 512
+    if not multi and 3 * ph * pw * 8 <= 64 * 1024:
+        bands = 8 if B <= 32 else (4 if B <= 128 else 1)
+        return (ph + bands - 1) // bands
+    rows = min(ph, (144 * 1024) // (pw * 8))
+    want = (128 + 3 * gx - 1) // (3 * gx)
+    return min(max((ph + want - 1) // want, 8), rows)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# records: one per (image, frame pixel) that is kept in some channel and has a corner on its image's patch
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _sizes(B, ph, pw, pdesc):
+    if pdesc is None:
+        return np.tile(np.array([ph, pw, 0], np.int64), (B, 1))
+    return np.asarray(pdesc, np.int64)[:, :3]
+
+
+def _records(B, keep, xy, theta, geometry, sz, pix_fn):
+    """pix_fn(b, idx) -> (T0, T1, D0, D1) [len(idx), 3] fp64: the towers' pixel gradients before 1/std and their error bounds."""
+    cols = collections.defaultdict(list)
+    keep = np.asarray(keep).reshape(B, 3, NPIX)
+    for b in range(B):
+        x0, y0, w, n = sample(theta[b] if geometry else None, geometry)
+        px, py = int(xy[b][0]), int(xy[b][1])
+        h, wd = int(sz[b][0]), int(sz[b][1])
+        u0, v0 = x0 - px, y0 - py
+        near = (u0 >= -1) & (u0 < wd) & (v0 >= -1) & (v0 < h) & (keep[b].max(axis=0) != 0)
+        idx = np.nonzero(near)[0]
+        T0, T1, D0, D1 = pix_fn(b, idx)
+        k = keep[b][:, idx].T.astype(bool)
+        for name, v in (("b", np.full(len(idx), b, np.int64)), ("p", idx), ("x0", x0[idx]), ("y0", y0[idx]), ("w", w[idx]), ("n", n[idx]),
+                        ("T0", np.where(k, T0, 0.0)), ("T1", np.where(k, T1, 0.0)), ("D0", np.where(k, D0, 0.0)), ("D1", np.where(k, D1, 0.0)), ("k", k)):
+            cols[name].append(v)
+    return {k: np.concatenate(v) for k, v in cols.items()}
+
+
+def _scatter(rec, xy, sz, total, inv_std=None, q_img=None, lose_row=None):
+    """Dense sums over the records' contributions -> dict(val, S, dG, cnt, qsum) [total] (value only when q_img is None)."""
+    s = (1.0 / STD6.astype(np.float64)) if inv_std is None else np.asarray(inv_std, np.float64)  # [6]
+    b = rec["b"]
+    s0, s1 = s[None, :3], s[None, 3:]
+    G = rec["T0"] * s0 + rec["T1"] * s1
+    A = np.abs(rec["T0"]) * s0 + np.abs(rec["T1"]) * s1
+    Ge = rec["D0"] * s0 + rec["D1"] * s1
+    px, py = np.asarray(xy, np.int64)[b, 0], np.asarray(xy, np.int64)[b, 1]
+    h, wd, off = sz[b, 0], sz[b, 1], sz[b, 2]
+    w, n = rec["w"].astype(np.float64), rec["n"].astype(np.float64)
+    out = {k: np.zeros(total) for k in ("val", "S", "dG", "cnt", "qsum", "R")}
+    for du, dv in ((0, 0), (1, 0), (0, 1), (1, 1)):
+        wt = (n if dv else 1.0 - n) * (w if du else 1.0 - w)
+        u, v = rec["x0"] - px + du, rec["y0"] - py + dv
+        on = (u >= 0) & (u < wd) & (v >= 0) & (v < h) & (rec["x0"] + du < IMG) & (rec["y0"] + dv < IMG)
+        ok = on & (wt > 0.0)
+        if lose_row is not None:
+            ok &= v != lose_row
+        for c in range(3):
+            m = ok & rec["k"][:, c]
+            t = (off + c * h * wd + v * wd + u)[m]
+            out["val"] += np.bincount(t, G[m, c] * wt[m], total)
+            if q_img is not None:
+                out["S"] += np.bincount(t, A[m, c] * wt[m], total)
+                out["dG"] += np.bincount(t, Ge[m, c] * wt[m], total)
+                out["cnt"] += np.bincount(t, None, total)
+                out["qsum"] += np.bincount(t, q_img[b[m]], total)
+                mr = on & rec["k"][:, c]  # R: the absolute gradient of every pixel with a corner ON the texel, whatever its weight
+                out["R"] += np.bincount((off + c * h * wd + v * wd + u)[mr], A[mr, c], total)
+    return out
+
+
+def _quantum(rec, B, multi):
+    """q = 2^(E + 1 - 30) per image: E from the batch maximum of |G| (its upper bound), or per image for the per-image forms."""
+    s = 1.0 / STD6.astype(np.float64)
+    Gmax = ((np.abs(rec["T0"]) + rec["D0"]) * s[:3] + (np.abs(rec["T1"]) + rec["D1"]) * s[3:]).max(axis=1) * (1.0 + 4 * U) if len(rec["b"]) else np.zeros(0)
+    m = np.zeros(B)
+    np.maximum.at(m, rec["b"], Gmax)
+    if not multi:
+        m[:] = m.max() if B else 0.0
+    E = np.maximum(np.floor(np.log2(np.maximum(m, 2.0 ** -126))), -96.0)
+    return np.where(m > 0, 2.0 ** (E + 1 - CBITS), 0.0)
+
+
+def _finish(rec, B, xy, sz, total, multi, meta):
+    q = _quantum(rec, B, multi)
+    o = _scatter(rec, xy, sz, total, q_img=q)
+    if multi:
+        qt = np.zeros(total)
+        for b in range(B):
+            h, wd, off = (int(v) for v in sz[b])
+            qt[off : off + 3 * h * wd] = q[b]
+        resc = np.where(o["cnt"] > 0, qt, 0.0)
+    else:
+        resc = np.minimum(o["cnt"], B) * (q[0] if B else 0.0)
+    bound = SAFETY * (7 * U * o["S"] + o["dG"] + 0.5 * o["qsum"] + resc + U * (o["S"] + o["dG"]) + U * np.abs(o["val"]))
+    meta = dict(meta, rec=rec, xy=np.asarray(xy), sz=sz, total=total, S=o["S"], cnt=o["cnt"], R=o["R"])
+    return Ref(o["val"], bound, meta)
+
+
+def per_image(ref):
+    """The reference of a single-patch case image by image: value and bound [B, 3*ph*pw] of every image's own contribution. With fewer than 512
+    images a workgroup row owns ONE image, so these are the partial tiles a deferred reduce leaves (E, the quantum and the fp32 rounding of a
+    partial are per image) — the finest result the kernels expose, a few contributions per texel instead of the batch's hundreds."""
+    m = ref.meta
+    B, n = m["B"], 3 * m["ph"] * m["pw"]
+    assert m["pdesc"] is None and B < 512
+    sz = m["sz"].copy()
+    sz[:, 2] = np.arange(B) * n
+    pdesc = np.concatenate([sz, np.zeros((B, 1), np.int64)], axis=1)
+    return _finish(m["rec"], B, m["xy"], sz, B * n, True, dict(kind=m["kind"], B=B, ph=m["ph"], pw=m["pw"], pdesc=pdesc, band_rows=m["band_rows"]))
+
+
+def bf16_fault_pixel(ref):
+    """The record for the `two bf16 ulps` fault: |G| in the median band like median_pixel; among those the one whose fault stands out most
+    against the bound of a texel it reaches (a pixel whose texels also collect values that sit on a bf16 rounding midpoint is legitimately
+    uncertain by more than the fault)."""
+    rec, xy, sz = ref.meta["rec"], ref.meta["xy"], ref.meta["sz"]
+    s = 1.0 / STD6.astype(np.float64)
+    g = np.abs(rec["T0"] * s[:3] + rec["T1"] * s[3:]).max(axis=1)
+    lo, hi = np.percentile(g[g > 0], [45, 55])
+    cand = np.nonzero((g >= lo) & (g <= hi))[0]
+    b = rec["b"][cand]
+    c = np.argmax(rec["k"][cand], axis=1)
+    t0 = rec["T0"][cand, c]
+    delta = 2 * bf16_rne(t0)[1] * s[c]
+    w, n = rec["w"][cand].astype(np.float64), rec["n"][cand].astype(np.float64)
+    h, wd, off = sz[b, 0], sz[b, 1], sz[b, 2]
+    best = np.zeros(len(cand))
+    for du, dv in ((0, 0), (1, 0), (0, 1), (1, 1)):
+        wt = (n if dv else 1.0 - n) * (w if du else 1.0 - w)
+        u, v = rec["x0"][cand] - xy[b, 0] + du, rec["y0"][cand] - xy[b, 1] + dv
+        on = (u >= 0) & (u < wd) & (v >= 0) & (v < h) & (rec["x0"][cand] + du < IMG) & (rec["y0"][cand] + dv < IMG) & (wt > 0)
+        idx = np.where(on, off + c * h * wd + v * wd + u, 0)
+        best = np.maximum(best, np.where(on, delta * wt / np.maximum(ref.bound[idx], 1e-300), 0.0))
+    return int(cand[np.argmax(best)])
+
+
+def _bf16_bits_to_f64(bits):
+    return (np.asarray(bits, np.uint16).astype(np.uint32) << 16).view(np.float32).astype(np.float64)
+
+
+def k2(gout_bf16, keep, xy, theta, geometry, ph, pw, pdesc=None):
+    """K2: gout_bf16 uint16 bits [B,6,224,224], keep 0/1 [B,3,50176] -> Ref(value, bound) [3*ph*pw] (or packed, with pdesc)."""
+    g = np.asarray(gout_bf16, np.uint16).reshape(-1, 6, NPIX)
+    B = g.shape[0]
+    sz = _sizes(B, ph, pw, pdesc)
+    total = 3 * ph * pw if pdesc is None else int(max(sz[:, 2] + (3 * sz[:, 0] * sz[:, 1] + 3) // 4 * 4))  # make_pdesc's packed length
+
+    def pix(b, idx):
+        t = _bf16_bits_to_f64(g[b][:, idx])
+        z = np.zeros((len(idx), 3))
+        return t[:3].T, t[3:].T, z, z
+
+    rec = _records(B, keep, xy, theta, geometry, sz, pix)
+    return _finish(rec, B, xy, sz, total, pdesc is not None, dict(kind="k2", B=B, ph=ph, pw=pw, pdesc=pdesc, band_rows=band_rows(B, ph, pw, pdesc is not None)))
+
+
+def bf16_rne(x):
+    """fp64 -> nearest bf16 (ties to even), as fp64; and the bf16 ulp at x."""
+    x = np.asarray(x, np.float64)
+    _m, ex = np.frexp(np.where(x == 0, 1.0, x))
+    q = np.ldexp(1.0, ex - 8)  # |x| in [2^(ex-1), 2^ex): 8 significant bits
+    return np.where(x == 0, 0.0, np.rint(x / q) * q), q
+
+
+def tile_grads(dy, w, tiles_b, round_bf16):
+    """t = dy[b, tile] @ w in fp64 for the listed tiles of every image, and its bound (T6). dy [B,256,D], w [D,588] hold bf16 values.
+    -> list over images of (t [nt,588], dt [nt,588])."""
+    dy, w = np.asarray(dy, np.float64), np.asarray(w, np.float64)
+    D = w.shape[0]
+    out = []
+    for b, tl in enumerate(tiles_b):
+        t = dy[b, tl] @ w
+        dt = D * U * (np.abs(dy[b, tl]) @ np.abs(w))
+        if round_bf16:
+            r, _q = bf16_rne(t)
+            lo, _ = bf16_rne(t - dt * (1 + 2.0 ** -20))
+            hi, _ = bf16_rne(t + dt * (1 + 2.0 ** -20))
+            _r2, q2 = bf16_rne(np.abs(t) + dt)
+            t, dt = r, np.where(lo != hi, dt + q2, 0.0)
+        out.append((t, dt))
+    return out
+
+
+def kept_tiles(keep):
+    """[B,256] bool: tile ty*16+tx holds a kept pixel in some channel."""
+    k = np.asarray(keep).reshape(-1, 3, 16, 14, 16, 14)
+    return k.max(axis=(1, 3, 5)).reshape(-1, 256) != 0
+
+
+def k2e(dy0, dy1, w0, w1, keep, xy, theta, geometry, ph, pw, round_bf16, pdesc=None):
+    """K2': dy_k [B,256,D_k], w_k [D_k,588] (bf16 values as floats) -> Ref. t = dY W only on the tiles that carry a kept pixel."""
+    B = np.asarray(dy0).shape[0]
+    flags = kept_tiles(keep)
+    tl = [np.nonzero(flags[b])[0] for b in range(B)]
+    tg = [tile_grads(dy0, w0, tl, round_bf16), tile_grads(dy1, w1, tl, round_bf16)]
+    sz = _sizes(B, ph, pw, pdesc)
+    total = 3 * ph * pw if pdesc is None else int(max(sz[:, 2] + (3 * sz[:, 0] * sz[:, 1] + 3) // 4 * 4))  # make_pdesc's packed length
+
+    def pix(b, idx):
+        i, j = idx // IMG, idx % IMG
+        slot = np.full(256, -1)
+        slot[tl[b]] = np.arange(len(tl[b]))
+        row = slot[(i // 14) * 16 + j // 14]
+        el = (i % 14) * 14 + j % 14
+        res = []
+        for k in range(2):
+            t, dt = tg[k][b]
+            res.append(np.stack([t[row, c * 196 + el] for c in range(3)], 1))
+            res.append(np.stack([dt[row, c * 196 + el] for c in range(3)], 1))
+        return res[0], res[2], res[1], res[3]
+
+    rec = _records(B, keep, xy, theta, geometry, sz, pix)
+    return _finish(rec, B, xy, sz, total, pdesc is not None,
+                   dict(kind="k2e", B=B, ph=ph, pw=pw, pdesc=pdesc, band_rows=band_rows(B, ph, pw, pdesc is not None), tiles=tl))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# faults for the perturbation self-test: the value a kernel with ONE defect would return, from the records of a finished reference
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _sub(rec, m):
+    return {k: v[m] for k, v in rec.items()}
+
+
+def median_pixel(ref):
+    """Index of a record whose largest |G| over the channels sits at the batch median (45..55 %), with every corner on the patch; among
+    those the one with the most unequal fractions |w - n| (a transposed pair of weights must change something)."""
+    rec, xy, sz = ref.meta["rec"], ref.meta["xy"], ref.meta["sz"]
+    s = 1.0 / STD6.astype(np.float64)
+    g = np.abs(rec["T0"] * s[:3] + rec["T1"] * s[3:]).max(axis=1)
+    b = rec["b"]
+    u, v = rec["x0"] - xy[b, 0], rec["y0"] - xy[b, 1]
+    w, n = rec["w"].astype(np.float64), rec["n"].astype(np.float64)
+    inx, iny = lambda uu: (uu >= 0) & (uu < sz[b, 1]), lambda vv: (vv >= 0) & (vv < sz[b, 0])
+    # the north-east or south-west corner on the patch with a weight that changes when w and n trade places ((1-n)(1-w) and nw do not)
+    asym = ((inx(u + 1) & iny(v) & (rec["x0"] + 1 < IMG)) | (inx(u) & iny(v + 1) & (rec["y0"] + 1 < IMG))) & (w != n) & (g > 0)
+    inner = inx(u) & inx(u + 1) & iny(v) & iny(v + 1)
+    pool = asym & inner if np.any(asym & inner) else asym
+    if not np.any(pool):  # the un-warped paste has no fractions at all: any contributing pixel
+        pool = inx(u) & iny(v) & (g > 0)
+    lo, med, hi = np.percentile(g[g > 0], [45, 50, 55])
+    cand = np.nonzero(pool & (g >= lo) & (g <= hi))[0]
+    if len(cand) == 0:  # a handful of contributions in all (1x1 patches): the candidate nearest the median
+        cand = np.nonzero(pool)[0]
+        return int(cand[np.argmin(np.abs(g[cand] - med))])
+    return int(cand[np.argmax(np.abs(w[cand] - n[cand]))])
+
+
+def faulted(ref, kind, at=None, image=None, row=None):
+    """ref.value with one defect: drop | shift_x | shift_y | transpose (record `at`), swap_std | twice (image), lose_row (texel row)."""
+    rec, xy, sz, total = ref.meta["rec"], ref.meta["xy"], ref.meta["sz"], ref.meta["total"]
+    sc = lambda r, **kw: _scatter(r, xy, sz, total, **kw)["val"]
+    if kind == "lose_row":
+        return sc(rec, lose_row=row)
+    if kind in ("swap_std", "twice"):
+        one = _sub(rec, rec["b"] == image)
+        if kind == "twice":
+            return ref.value + sc(one)
+        s = 1.0 / STD6.astype(np.float64)
+        return ref.value - sc(one) + sc(one, inv_std=np.concatenate([s[3:], s[:3]]))
+    if kind == "zero_tile":  # the 14x14 tile of record `at`, in its image
+        tile = lambda p: (p // IMG // 14) * 16 + (p % IMG) // 14
+        return ref.value - sc(_sub(rec, (rec["b"] == rec["b"][at]) & (tile(rec["p"]) == tile(rec["p"][at]))))
+    one = _sub(rec, np.arange(len(rec["b"])) == at)
+    new = {k: v.copy() for k, v in one.items()}
+    if kind == "bf16_2ulp":  # tower 0's tile pixel, in the record's first kept channel
+        c = int(np.argmax(one["k"][0]))
+        new["T0"][0, c] += 2 * bf16_rne(one["T0"][0, c])[1]
+        return ref.value - sc(one) + sc(new)
+    if kind == "drop":
+        return ref.value - sc(one)
+    if kind == "shift_x":
+        new["x0"] = one["x0"] + 1
+    elif kind == "shift_y":
+        new["y0"] = one["y0"] + 1
+    elif kind == "transpose":
+        new["w"], new["n"] = one["n"], one["w"]
+    else:
+        raise ValueError(kind)
+    return ref.value - sc(one) + sc(new)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# K0 adjoint
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _aa(x, h, w):
+    return F.interpolate(x, size=(h, w), mode="bilinear", antialias=True, align_corners=False)
+
+
+def axis_weights(n_in, n_out, dtype):
+    """[n_out, n_in] antialias-bilinear weights of one axis as torch's CPU kernel forms them in `dtype` (identity when unchanged)."""
+    if n_in == n_out:
+        return np.eye(n_in)
+    eye = torch.eye(n_in, dtype=dtype).view(1, 1, n_in, n_in)  # resized along its rows only: out[o, x] = sum_y W[o, y] eye[y, x] = W[o, x]
+    return _aa(eye, n_out, n_in)[0, 0].double().numpy()
+
+
+def resize_bwd(gy, pdesc, ph, pw):
+    """K0 adjoint: gy packed [total] -> Ref(value, bound) [3*ph*pw]: fp64 autograd through torch's antialias bilinear interpolate."""
+    gy = np.asarray(gy, np.float64)
+    pdesc = np.asarray(pdesc, np.int64)
+    B = len(pdesc)
+
+    def adj(g):
+        x = torch.zeros(1, 3, ph, pw, dtype=torch.float64, requires_grad=True)
+        acc = 0
+        for (h, w, off, _z) in pdesc:
+            acc = acc + (_aa(x, int(h), int(w))[0] * torch.from_numpy(g[off : off + 3 * h * w]).view(3, int(h), int(w))).sum()
+        acc.backward()
+        return x.grad[0].numpy().copy()
+
+    val, absv = adj(gy), adj(np.abs(gy))
+    t7, ncov = np.zeros((3, ph, pw)), np.zeros((ph, pw))
+    for (h, w, off, _z) in pdesc:
+        h, w = int(h), int(w)
+        wy64, wx64, wy32, wx32 = axis_weights(ph, h, torch.float64), axis_weights(pw, w, torch.float64), axis_weights(ph, h, torch.float32), axis_weights(pw, w, torch.float32)
+        g = np.abs(gy[off : off + 3 * h * w]).reshape(3, h, w)
+        t7 += np.einsum("oy,cop,px->cyx", np.abs(wy32 - wy64), g, wx64) + np.einsum("oy,cop,px->cyx", wy32, g, np.abs(wx32 - wx64))
+        ncov = np.maximum(ncov, np.outer((wy32 > 0).sum(0), (wx32 > 0).sum(0)))
+    bound = SAFETY * (t7 + (ncov[None] + B + 3) * U * (absv + t7))
+    return Ref(val.ravel(), bound.ravel(), dict(kind="k0", B=B, ph=ph, pw=pw, pdesc=None, band_rows=ph))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# compare
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _where(ref, e):
+    m = ref.meta
+    img = ""
+    h, w, off = m["ph"], m["pw"], 0
+    if m.get("pdesc") is not None:
+        pd = np.asarray(m["pdesc"], np.int64)
+        b = int(np.nonzero((pd[:, 2] <= e) & (e < pd[:, 2] + 3 * pd[:, 0] * pd[:, 1]))[0][0])
+        h, w, off = (int(v) for v in pd[b, :3])
+        img = f" image {b} ({h}x{w})"
+    c, r = divmod(e - off, h * w)
+    v, u = divmod(r, w)
+    br = m["band_rows"]
+    return f"channel {c} texel (row {v}, col {u}){img}, band {v // br} (rows {v // br * br}..{min(h, (v // br + 1) * br) - 1})"
+
+
+def compare(ref, got, tag=""):
+    """Worst |got - value| / bound over the elements (0 / 0 counts as 0; any error against a zero bound is infinite). Fails, naming the
+    worst element, when it exceeds 1."""
+    got = np.asarray(got.detach().double().cpu() if isinstance(got, torch.Tensor) else got, np.float64).ravel()
+    assert got.shape == ref.value.shape, f"{tag}: {got.shape} values for {ref.value.shape}"
+    err = np.abs(got - ref.value)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(err == 0, 0.0, np.where(ref.bound > 0, err / ref.bound, np.inf))
+    ratio = np.where(np.isfinite(got), ratio, np.inf)
+    e = int(np.argmax(ratio))
+    worst = float(ratio[e])
+    assert worst <= 1.0, (f"{tag}: {int((ratio > 1).sum())} of {ratio.size} elements outside their bound; worst at {_where(ref, e)}: got {got[e]:.9g}, "
+                          f"reference {ref.value[e]:.9g}, error {err[e]:.3g} = {worst:.3g} x bound {ref.bound[e]:.3g}")
+    return worst
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# CASES (shared by the host and the GPU tests). Placements of every case mix: interior, the four frame edges and a corner (border
+# padding clamps onto edge texels), identity theta, rotation / shear at the reference's extremes (+-30 deg, +-0.2) and the general affines
+# of test_k1_general_affine_with_translation.
+# ---------------------------------------------------------------------------------------------------------------------------------
+_GENERAL = np.array([[[1.3, 0.1, 0.2], [-0.2, 0.8, -0.1]], [[0.5, 0, 0.5], [0, 0.5, 0.5]], [[2.0, 0, -0.9], [0, 2.0, -0.9]],
+                     [[0.0, 1.0, 0.0], [-1.0, 0.0, 0.0]], [[1e-7, 1.0, 0.0], [1.0, 1e-7, 0.0]], [[1, 0, 3.0], [0, 1, 3.0]]], np.float32)
+
+
+def _rot_shear(deg, shx, shy):
+    t = np.deg2rad(deg)
+    r = np.array([[np.cos(t), -np.sin(t), 0], [np.sin(t), np.cos(t), 0], [0, 0, 1]], np.float32)
+    return np.dot(np.array([[1, shx, 0], [shy, 1, 0], [0, 0, 1]], np.float32), r)[:2]
+
+
+def placements(B, sizes, seed):
+    """xy int32 [B,2], theta fp32 [B,2,3]: image b takes placement b % 8 and transform b % 13 of the lists below, so every batch of 2 or
+    more images mixes them; sizes [B,2] = (h, w) of each image's patch."""
+    rs = np.random.RandomState(seed)
+    xy, th = np.zeros((B, 2), np.int32), np.zeros((B, 2, 3), np.float32)
+    for b in range(B):
+        h, w = int(sizes[b][0]), int(sizes[b][1])
+        fx, fy = IMG - w, IMG - h
+        xy[b] = [(rs.randint(0, fx + 1), rs.randint(0, fy + 1)), (0, fy // 2), (fx, fy // 3), (fx // 2, 0), (fx // 3, fy), (0, 0), (fx, fy),
+                 (rs.randint(0, fx + 1), rs.randint(0, fy + 1))][b % 8]
+        k = b % 13  # identity, then the extremes and the general affines in turn, then two random draws
+        ext = [(30, 0.2, -0.2), (-30, -0.2, 0.2), (30, -0.2, -0.2), (-30, 0.2, 0.2)]
+        if k == 0:
+            th[b] = np.eye(3, dtype=np.float32)[:2]
+        elif k <= 8:
+            th[b] = _rot_shear(*ext[k // 2]) if k % 2 else _GENERAL[k // 2 - 1]
+        elif k <= 10:
+            th[b] = _GENERAL[k - 5]
+        else:
+            th[b] = _rot_shear(rs.uniform(-30, 30), rs.uniform(-0.2, 0.2), rs.uniform(-0.2, 0.2))
+    return xy, th
+
+
+Case = collections.namedtuple("Case", "B ph pw geo mask sizes D0 D1 note", defaults=(1, 0, None, 0, 0, ""))
+
+# K2 scatter forms. The comment of each case is the launcher condition (launch_scatter_reduce / grad_sched / band_rows_for) that selects it.
+K2_CASES = {
+    # 3*52*52*8 = 64,896 B <= 65,536: three channels per workgroup; B <= 32: 8 bands of ceil(52/8) = 7 rows, the last of 3
+    "c3_52": Case(5, 52, 52),
+    # 3*53*53*8 = 67,416 B > 65,536: one channel per workgroup (grid.y = 3); band_rows_for(53, 53, 15): want 9 bands -> 8-row bands (6 of 8, one of 5)
+    "c1_53": Case(5, 53, 53),
+    "b32": Case(32, 22, 22),    # B <= 32: 8 bands; 22 rows -> 3-row bands, 7 of 3 and a ONE-row last band
+    "b33": Case(33, 22, 22),    # 32 < B <= 128: 4 bands of 6 rows (6, 6, 6, 4)
+    "b128": Case(128, 10, 12),  # B = 128: 4 bands of 3 rows (3, 3, 3, 1)
+    "b129": Case(129, 10, 12),  # B > 128: 1 band
+    "rows50": Case(6, 50, 50),  # 8 bands of 7 rows: 7 x 7 + a ONE-row last band
+    "one": Case(4, 1, 1),       # ph < band count: band_rows = 1, one band
+    "rows3": Case(4, 3, 40),    # ph = 3 < 8 bands: band_rows = 1, three one-row bands
+    "lds139": Case(3, 139, 139),  # one plane 154,568 B > 147,456 B of LDS: rows limited to 132, band_rows_for(.., 9): 15 bands -> 10-row bands
+    "lds224": Case(2, 224, 224),  # 224 x 224: LDS holds 82 rows; band_rows_for(.., 6): 22 bands -> 11-row bands (20 of 11, one of 4)
+    "rect": Case(6, 37, 61),    # non-square, 3 channels per workgroup, 8 bands of 5 rows (7 of 5, one of 2)
+    "paste": Case(6, 50, 50, 0, 0),     # geometry 0 (un-warped paste), mask `canvas < -20`
+    "paste_ne": Case(6, 50, 50, 0, 1),  # geometry 0 with the `canvas != -100` mask (check_patch_call: that mask with geometry 0 only)
+    "paste53": Case(3, 53, 53, 0, 1),   # the same through the one-channel-per-workgroup kernel
+    "b520": Case(520, 8, 8),    # B > 512: gx = 512, workgroup rows 0..7 own two images each (b and b + 512); one band
+    # _multi: one workgroup per (image, channel, band); band_rows_for(139, 139, 3 * 5 = 15): 9 bands wanted -> 16-row bands: the 139-row image
+    # has 9 bands, 61 rows 4, 30 rows 2, 8 and 1 rows ONE band (v_lo >= ph: the other bands' workgroups idle)
+    "multi": Case(5, 139, 139, sizes=[(139, 139), (61, 61), (30, 100), (8, 8), (1, 1)]),
+    "multi_paste": Case(3, 70, 90, 0, 1, sizes=[(70, 90), (22, 31), (50, 50)]),
+}
+
+# K2' tile-kernel forms (launch_embed_tiles): eff = pad8(B) when ny == 1, else B * ny; split while eff <= 64: nch = 5 / 3 / 2 for eff <= 24 / 40 / 64
+# and NB = ceil(ceil(37 / nch) / 8) = 1 / 2 / 3; else unsplit (nch = 3, NB = 2). tiles_bound(50 x 50) = 64 -> ny = 1.
+K2E_CASES = {
+    "split_nb1": Case(3, 50, 50, D0=64, D1=192),    # eff = 8 <= 24: split, 5 column groups, NB = 1; D/64 = 1 and 3 (odd against kEmbedGroup = 2), D0 != D1
+    "split_nb2": Case(33, 50, 50, D0=192, D1=64),   # eff = 40: split, nch = 3, NB = 2
+    "split_nb3": Case(41, 50, 50, D0=64, D1=128),   # eff = 48: split, nch = 2, NB = 3 (one 64-wide chunk per weight group)
+    "unsplit": Case(65, 50, 50, D0=128, D1=64),     # eff = 72 > 64: both towers per workgroup
+    "ny2": Case(2, 61, 61, D0=64, D1=128),          # tiles_bound = 9 * 9 = 81 -> ny = 2, eff = 4: split
+    "ny4": Case(2, 100, 100, D0=128, D1=64),        # tiles_bound = 13 * 13 = 169 -> ny = 4, eff = 8: split
+    "paste": Case(3, 22, 31, 0, 1, D0=64, D1=64),   # geometry 0, `!= -100` mask
+    "prod": Case(8, 50, 50, D0=1024, D1=1152),      # production widths, eff = 8: split NB = 1, 16 / 18 chunks
+    "wide": Case(2, 50, 50, D0=1216, D1=64),        # 64 * (1216 + 8) * 2 = 156,672 B > 150 KiB: the global-memory variant (embed_dgrad_tiles_kernel)
+    "multi": Case(4, 139, 139, D0=64, D1=128, sizes=[(139, 139), (61, 61), (30, 100), (8, 8)]),  # tiles_bound(139) = 17^2 -> ny = 4, eff = 16: split
+}
+
+K0_CASES = {  # the size lists of test_patch_resize_kernel_vs_torch_cpu
+    "r100": (100, 100, [(61, 61), (139, 139), (100, 100), (100, 61), (139, 100), (1, 1), (224, 224)]),
+    "r50": (50, 50, [(30, 69), (50, 50), (19, 19), (69, 69)]),
+    "r37x61": (37, 61, [(22, 84), (51, 37)]),
+}
+CASES = {"k2": K2_CASES, "k2e": K2E_CASES, "k0": K0_CASES}
+
+
+def make_pdesc(sizes, align=4):
+    sizes = np.asarray(sizes, np.int32).reshape(-1, 2)
+    pdesc, off = np.zeros((len(sizes), 4), np.int32), 0
+    for b, (h, w) in enumerate(sizes):
+        pdesc[b] = (h, w, off, 0)
+        off += (3 * int(h) * int(w) + align - 1) // align * align
+    return pdesc, off
+
+
+_INPUTS = {}
+
+
+def case_inputs(family, name):
+    """Seeded inputs of a case, built once per session: dict(imgs, patch | packed, pdesc, sizes, xy, theta, g (bf16 tensor) | dy, w)."""
+    key = (family, name)
+    if key in _INPUTS:
+        return _INPUTS[key]
+    from roboticattack_amd import synthetic
+
+    c = CASES[family][name]
+    seed = sum(ord(ch) for ch in family + name)
+    rs = np.random.RandomState(seed)
+    sizes = np.asarray(c.sizes if c.sizes else [(c.ph, c.pw)] * c.B, np.int32)
+    xy, th = placements(c.B, sizes, seed)
+    d = dict(case=c, sizes=sizes, xy=xy, theta=th, imgs=synthetic.synth_images(seed, c.B, "noise"), pdesc=None)
+    if c.sizes:
+        d["pdesc"], total = make_pdesc(sizes)
+        d["patch"] = rs.rand(total).astype(np.float32)
+    else:
+        d["patch"] = rs.rand(3, c.ph, c.pw).astype(np.float32)
+    if family == "k2":
+        g = synthetic.synth_upstream_grad(seed, 1).repeat(min(c.B, 8), 1, 1, 1)
+        for b in range(1, g.shape[0]):  # a different gradient per image without 520 normal draws: rolled, and scaled over two octaves
+            g[b] = torch.roll(g[0], shifts=(b, 7 * b + 1), dims=(0, 2)) * (0.5 + 0.25 * b)
+        d["g"] = g.repeat((c.B + g.shape[0] - 1) // g.shape[0], 1, 1, 1)[: c.B].contiguous()
+    else:
+        gen = torch.Generator().manual_seed(seed)
+        d["w"] = [(torch.randn(D, 588, generator=gen) * 0.05).to(torch.bfloat16) for D in (c.D0, c.D1)]  # [D,588], column c*196 + y*14 + x
+        d["dy"] = [(torch.randn(c.B, 256, D, generator=gen) * 0.1).to(torch.bfloat16) for D in (c.D0, c.D1)]
+    _INPUTS[key] = d
+    return d
+
+
+def oracle_keep(d):
+    """K1's keep bits of a case as the C oracle states them: 0/1 [B,3,50176]."""
+    from oracle import c_oracle
+
+    c = d["case"]
+    if "keep" not in d:
+        if d["pdesc"] is None:
+            d["keep"] = c_oracle.patch_apply_fwd(d["imgs"], d["patch"], d["xy"], d["theta"], c.geo, c.mask, want_f32=False, want_bf16=False)[2]
+        else:
+            d["keep"] = c_oracle.patch_apply_fwd_multi(d["imgs"], d["patch"], d["pdesc"], d["xy"], d["theta"], c.geo, c.mask, want_f32=False, want_bf16=False)[2]
+    return d["keep"]
+
+
+_REFS = {}
+
+
+def case_ref(family, name, round_bf16=True):
+    """The reference of a case, computed once per session and shared (never modified by its users)."""
+    key = (family, name, round_bf16)
+    if key not in _REFS:
+        if family == "k0":
+            ph, pw, sizes = K0_CASES[name]
+            pdesc, total = make_pdesc(sizes)
+            gy = torch.rand(total, generator=torch.Generator().manual_seed(ph + pw)).numpy()
+            _REFS[key] = (resize_bwd(gy, pdesc, ph, pw), gy, pdesc)
+            return _REFS[key]
+        d = case_inputs(family, name)
+        c, keep = d["case"], oracle_keep(d)
+        if family == "k2":
+            bits = d["g"].view(torch.int16).numpy().view(np.uint16)
+            _REFS[key] = k2(bits, keep, d["xy"], d["theta"], c.geo, c.ph, c.pw, d["pdesc"])
+        else:
+            f = lambda t: t.double().numpy()
+            _REFS[key] = k2e(f(d["dy"][0]), f(d["dy"][1]), f(d["w"][0]), f(d["w"][1]), keep, d["xy"], d["theta"], c.geo, c.ph, c.pw, round_bf16, d["pdesc"])
+    return _REFS[key]

@@ -43,6 +43,12 @@ def main(argv=None):
         from roboticattack_amd.quant import quantize_llm
 
         vla_q4 = quantize_llm(copy.deepcopy(vla), args.bnb_4bit_quant_type)
+    elif args.llm_int8:  # likewise with int8 codes, per-call int8 activations and bf16 outlier columns (this project's statement of LLM.int8)
+        import copy
+
+        from roboticattack_amd.quant import quantize_llm
+
+        vla_q4 = quantize_llm(copy.deepcopy(vla), "int8", threshold=args.llm_int8_threshold)
     source = {}
     if args.frames_data is None:
         frames, input_ids, attention_mask = synthetic.synth_eval_batch(args.seed, args.frames)
@@ -68,7 +74,8 @@ def main(argv=None):
           f"mean_nad={float(o['nad'].mean()):.4f}")
     if vla_q4 is not None:
         q, ca = report["quantised"], report["clean_agreement"]
-        print(f"4-bit ({q['quant_type']}) model: any_flip={q['overall']['any_flip_rate']:.3f} mean_nad={float(q['overall']['nad'].mean()):.4f}; "
+        name = f"8-bit (int8, threshold {args.llm_int8_threshold:g})" if q["quant_type"] == "int8" else f"4-bit ({q['quant_type']})"
+        print(f"{name} model: any_flip={q['overall']['any_flip_rate']:.3f} mean_nad={float(q['overall']['nad'].mean()):.4f}; "
               f"clean actions equal to the bf16 model's on {ca['frames']:.3f} of the frames, {ca['tokens']:.3f} of the tokens")
     out = to_jsonable(dict(report, patch=args.patch, vla_path=path, frames=args.frames, center_crop=bool(args.center_crop),
                            crop_scale=args.crop_scale, **source))

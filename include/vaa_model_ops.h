@@ -98,6 +98,43 @@ int vaa_model_q4_dequant(const uint8_t* codes, const float* absmax, const float*
  * folded in a fixed order, so the same arguments give the same bits, and row m of y depends on row m of x (and res) alone. */
 int vaa_model_q4_gemv(const uint16_t* x, int M, const uint8_t* codes, const float* absmax, const float* table, int N, int K,
                       const uint16_t* res, uint16_t* y, void* stream);
+/* ---- 8-bit weights and activations with bf16 outlier columns (inference only): a model converted by quant.quantize_llm(model, "int8") ----
+ * THE FORMAT AND THE ARITHMETIC (this header defines them; they follow LLM.int8 — Dettmers et al. 2022, what transformers' load_in_8bit gets
+ * from bitsandbytes — vector-wise absmax scales, integer products, a threshold split — but bitsandbytes does not exist on this platform and not
+ * one value was compared with it: this is this project's statement of the method). Every fp32 operation below is a separately rounded IEEE
+ * operation (no fused multiply-add, correctly rounded division); rint is round-to-nearest-even.
+ *   Weights W bf16 [N, K] row-major, K % 64 == 0, 64 <= K <= 133120 (127^2 K < 2^31: the int32 sum cannot overflow):
+ *     wscale   float32 [N]: wscale[n] = max_k |W[n, k]| (exact).
+ *     q        int8 [N, K] row-major: q[n, k] = clamp(rint(127 W[n, k] / wscale[n]), -127, 127), the product exact and the quotient formed in fp64
+ *              (a quotient of two bf16 numbers that is not a half-integer is further than 2^-18 from one, so the fp64 rounding never makes a
+ *              tie: this is rint of the exact quotient); a zero row has zero codes. The quantiser is host-side (quant.quantize_q8).
+ *     wdq      the dequantised weight: wdq[n, k] = bf16((float(q[n, k]) * wscale[n]) / 127).
+ *   Activations x bf16 [M, K], per call, threshold t >= 0 (fp32; t == 0: no outlier split):
+ *     outlier  column k is an outlier when t > 0 and max_m |x[m, k]| >= t — the maximum over ALL M rows of the call: a row's result depends on
+ *              the other rows of its call unless t == 0.
+ *     ascale   float32 [M]: ascale[m] = max over the non-outlier k of |x[m, k]| (0 when every column is an outlier).
+ *     xq       int8 [M, K]: 0 on outlier columns and in a row with ascale[m] == 0; elsewhere, with inv = 127 / ascale[m] (one division per
+ *              row), xq[m, k] = clamp(rint(x[m, k] * inv), -127, 127).
+ *     outliers int32 [K + 1] in caller-owned memory: outliers[0] = the count, outliers[1 .. count] = the outlier columns in ascending order;
+ *              the rest of the K + 1 words is scratch and holds no defined value afterwards.
+ *   Result, for every m < M, n < N:
+ *     acc      = sum_k xq[m, k] q[n, k], exact in int32.
+ *     o        = the sum over the outlier columns k, ascending, starting from 0, of x[m, k] * wdq[n, k]: o = o + (x * wdq).
+ *     y[m, n]  = bf16((((float(acc) * (ascale[m] * wscale[n])) / 16129) + o) + res[m, n]); float(acc) rounds to nearest even; without res the
+ *              last addition is not made.
+ * Both entry points: M == 0: VAA_OK, nothing done. NULL pointers (res excepted), M < 0, N < 1, K < 64, a threshold that is negative or not
+ * finite: VAA_E_INVALID; K % 64 != 0, K > 133120, or a base address of x, xq, q, res, y that is not 16-byte aligned (ascale, wscale, outliers:
+ * 4-byte): VAA_E_UNSUPPORTED before any launch. Nothing outside xq, ascale, the K + 1 words of outliers and y is written. No atomics, no
+ * hand-over between workgroups: the same arguments give the same bits. */
+/* x -> xq, ascale, outliers. Any M >= 1. M <= 16: one launch (every workgroup owns one row and forms the column maxima of all M rows itself);
+ * more rows: three launches on the stream (column flags, the rows, the ordered list). */
+int vaa_model_q8_act_quant(const uint16_t* x, int M, int K, float threshold, int8_t* xq, float* ascale, int32_t* outliers, void* stream);
+/* y from what vaa_model_q8_act_quant wrote (x is read on the outlier columns only). form 0: M <= 16 runs the split-K form (one launch, every
+ * weight byte read once by one lane of one workgroup), more rows the tiled integer GEMM (a workgroup owns 128 rows n x 64 rows m: the weights
+ * are read ceil(M / 64) times). form 1 forces the split-K form (M > 16: VAA_E_UNSUPPORTED), form 2 the GEMM; any other form: VAA_E_INVALID.
+ * Both forms end in the same device function, so they give the same bits for the same call. */
+int vaa_model_q8_matmul(const int8_t* xq, const float* ascale, const int32_t* outliers, const uint16_t* x, int M, const int8_t* q,
+                        const float* wscale, int N, int K, const uint16_t* res, uint16_t* y, int form, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -23,7 +23,7 @@ FRAME_RESIZE_MAX_TAPS = 57  # VAA_FRAME_RESIZE_MAX_TAPS
 
 MODEL_OP_EXPORTS = ("vaa_model_rope", "vaa_model_swiglu_fwd", "vaa_model_swiglu_bwd", "vaa_model_rmsnorm_fwd", "vaa_model_rmsnorm_bwd",
                     "vaa_model_attention_fwd", "vaa_model_attention_bwd", "vaa_model_layernorm_fwd", "vaa_model_layernorm_bwd", "vaa_model_scale_add",
-                    "vaa_model_attention_decode", "vaa_model_q4_dequant", "vaa_model_q4_gemv")
+                    "vaa_model_attention_decode", "vaa_model_q8_act_quant", "vaa_model_q8_matmul", "vaa_model_q4_dequant", "vaa_model_q4_gemv")
 
 EXPORTS = (
     "vaa_last_error",
@@ -305,6 +305,10 @@ def lib() -> C.CDLL:
     L.vaa_model_q4_dequant.argtypes = [vp, vp, C.POINTER(f32), i32, i32, vp, vp]
     L.vaa_model_q4_gemv.restype = i32
     L.vaa_model_q4_gemv.argtypes = [vp, i32, vp, vp, C.POINTER(f32), i32, i32, vp, vp, vp]
+    L.vaa_model_q8_act_quant.restype = i32
+    L.vaa_model_q8_act_quant.argtypes = [vp, i32, i32, f32, vp, vp, vp, vp]
+    L.vaa_model_q8_matmul.restype = i32
+    L.vaa_model_q8_matmul.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp]
     _lib = L
     return L
 

@@ -200,17 +200,31 @@ def add_eval(parser: argparse.ArgumentParser):
     parser.add_argument("--target", default=None, type=target_arg, help="maskidx:value — also report how often the patched token hits that action")
     parser.add_argument("--out", default=None, type=str, help="write the report as JSON (tokens included)")
     # the reference's quantised deployment (run_libero_eval_args_geo_batch.py:312-313 -> from_pretrained, openvla_utils.py:43-51)
-    parser.add_argument("--load_in_8bit", type=str2bool, nargs="?", const=True, default=False, help="accepted and refused: LLM.int8 is not built")
+    parser.add_argument("--load_in_8bit", type=str2bool, nargs="?", const=True, default=False,
+                        help="accepted and refused: no bitsandbytes-pinned LLM.int8 exists here; --llm_int8 runs this project's statement of it")
+    parser.add_argument("--llm_int8", type=str2bool, nargs="?", const=True, default=False,
+                        help="also evaluate the model with its Llama projections as int8 codes, per-call int8 activations and bf16 outlier columns "
+                             "(quant.quantize_llm(model, 'int8')) and report both: this project's statement of LLM.int8 (include/vaa_model_ops.h), "
+                             "not one pinned against bitsandbytes")
+    parser.add_argument("--llm_int8_threshold", default=6.0, type=float,
+                        help="a column whose largest |activation| over the rows of a call reaches this is carried in bf16 (transformers' "
+                             "llm_int8_threshold; 0: no outlier split)")
     parser.add_argument("--load_in_4bit", type=str2bool, nargs="?", const=True, default=False,
                         help="also evaluate the model with its Llama projections quantised to 4 bits (quant.quantize_llm) and report both")
     parser.add_argument("--bnb_4bit_quant_type", default="fp4", choices=("fp4", "nf4"), help="the 4-bit table (transformers' BitsAndBytesConfig default: fp4)")
 
 
 def check_eval_quant(parser: argparse.ArgumentParser, args):
-    """--load_in_8bit is parsed so that the reference's command lines are understood, and refused: LLM.int8's activation quantisation and
-    outlier split do not exist here."""
+    """--load_in_8bit is parsed so that the reference's command lines are understood, and refused: what it asks for is bitsandbytes' LLM.int8,
+    and no value here was ever compared with bitsandbytes. --llm_int8 asks for this project's statement of the method (DESIGN.md section 4);
+    together with --load_in_4bit it is an error, as the reference asserts for its two flags."""
     if args.load_in_8bit:
-        parser.error("--load_in_8bit is not supported (LLM.int8 is not built here); --load_in_4bit evaluates the 4-bit deployment")
+        parser.error("--load_in_8bit is not supported (bitsandbytes' LLM.int8 cannot be pinned here); --llm_int8 evaluates this project's "
+                     "statement of the int8 deployment, --load_in_4bit the 4-bit one")
+    if args.llm_int8 and args.load_in_4bit:
+        parser.error("--llm_int8 and --load_in_4bit exclude each other: one quantised model per run")
+    if not 0.0 <= args.llm_int8_threshold < float("inf"):
+        parser.error("--llm_int8_threshold must be finite and >= 0")
 
 
 def add_eval_frame_flags(parser: argparse.ArgumentParser):

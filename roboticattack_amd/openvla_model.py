@@ -186,7 +186,7 @@ def _rope(q, k, cos, sin):
 
 
 class LlamaLayer(nn.Module):
-    q4 = None  # the table name once quant.quantize_llm has replaced the seven projections by Q4Linear modules (inference only from then on)
+    q4 = None  # the table name (or "int8") once quant.quantize_llm has replaced the seven projections by Q4Linear / Q8Linear modules (inference only from then on)
 
     def __init__(self, c: OpenVLACfg):
         super().__init__()
@@ -251,7 +251,7 @@ class LlamaLayer(nn.Module):
         if self.q4:
             from . import quant
 
-            quant.refuse_training("LlamaLayer.forward")
+            quant.refuse_training("LlamaLayer.forward", self.q4)
         B, T, D = x.shape
         hd = D // self.heads
         fused = rope_tab is not None and model_ops.enabled(x) and hd % 16 == 0 and D % 8 == 0 and D <= 8192
@@ -443,13 +443,13 @@ class SeqPack:
 
 
 class OpenVLAShaped(nn.Module):
-    q4 = None  # the table name once quant.quantize_llm has converted the Llama stack (predict_action / evaluate_patch only from then on)
+    q4 = None  # the table name (or "int8") once quant.quantize_llm has converted the Llama stack (predict_action / evaluate_patch only from then on)
 
     def _refuse_if_quantised(self, what):
         if self.q4:
             from . import quant
 
-            quant.refuse_training(what)
+            quant.refuse_training(what, self.q4)
 
     def __init__(self, cfg: OpenVLACfg | None = None):
         super().__init__()

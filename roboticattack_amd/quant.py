@@ -9,6 +9,13 @@ model, the training entry points refuse it.
   layer_prefill / layer_decode  the second route of LlamaLayer.prefill / decode_step: vaa_model_q4_gemv for at most GEMV_MAX_ROWS rows in a
                                 decode step, vaa_model_q4_dequant into one shared scratch + the stock GEMM otherwise and always in prefill
 Neither table could be compared with bitsandbytes in this image; the fp4 entries are stated from memory.
+
+The 8-bit route (`load_in_8bit` in the reference: LLM.int8) lives here as well — csrc/vaa_quant8.hip, stated in the same header, likewise not
+compared with bitsandbytes:
+  quantize_q8 / dequantize_q8   int8 codes with one fp32 scale per row, and the dequantised weight
+  q8_linear                     vaa_model_q8_act_quant + vaa_model_q8_matmul on a GPU, q8_linear_torch (the same arithmetic in torch) elsewhere
+  Q8Linear / Q8LinearRows       codes + wscale as buffers and the outlier threshold of the layer's calls
+  quantize_llm(model, "int8")   the same seven projections -> Q8Linear; layer_prefill / layer_decode serve both kinds through _proj
 """
 from __future__ import annotations
 
@@ -236,49 +243,256 @@ def q4_linear(x2: torch.Tensor, lin: Q4Linear, res: torch.Tensor | None = None, 
     return F.linear(x2, w) if res is None else torch.addmm(res, x2, w.t())
 
 
-QUANT_ERROR = ("this model's Llama projections were quantised to 4 bits by quantize_llm: it is inference only (predict_action / evaluate_patch); "
+# ---- the 8-bit format (include/vaa_model_ops.h, "8-bit weights and activations with bf16 outlier columns"; csrc/vaa_quant8.hip) ----
+INT8 = "int8"
+Q8_MAX_K = 133120        # 127^2 K < 2^31
+Q8_GEMV_MAX_ROWS = 16    # vaa_model_q8_matmul: at most this many rows take the split-K form, more the tiled integer GEMM
+Q8_TORCH_ROUTE = False   # tests: run q8_linear's torch formulation on the GPU as well
+
+
+def _div32(a: torch.Tensor, b) -> torch.Tensor:
+    """The correctly rounded fp32 quotient on every device: the fp64 quotient rounded to fp32 (53 >= 2*24 + 2 bits)."""
+    b = b.to(torch.float64) if isinstance(b, torch.Tensor) else float(b)
+    return (a.to(torch.float64) / b).to(torch.float32)
+
+
+@torch.no_grad()
+def quantize_q8(w: torch.Tensor, rows_per_pass: int = 1024):
+    """W [N,K] (bf16 or fp32 holding bf16 values; K % 64 == 0) -> (codes int8 [N,K], wscale float32 [N]) in the format of
+    include/vaa_model_ops.h, on W's device, the same codes on every device: wscale = the row's absmax, code = rint(127 W / wscale) with the
+    product exact and the quotient formed in fp64 (never within rounding distance of a tie), clamped to +-127; a zero row gives zero codes."""
+    if w.dim() != 2 or w.shape[1] % 64 != 0 or not 64 <= w.shape[1] <= Q8_MAX_K:
+        raise ValueError(f"quantize_q8: W must be [N,K] with K a multiple of 64 in 64 .. {Q8_MAX_K}, got {tuple(w.shape)}")
+    N, K = w.shape
+    codes = torch.empty((N, K), dtype=torch.int8, device=w.device)
+    wscale = torch.empty((N,), dtype=torch.float32, device=w.device)
+    for r0 in range(0, N, rows_per_pass):
+        wf = w[r0:r0 + rows_per_pass].to(torch.float32)
+        ws = wf.abs().amax(-1)
+        wscale[r0:r0 + rows_per_pass] = ws
+        wd = ws.to(torch.float64)[:, None]
+        quot = torch.where(wd > 0, 127.0 * wf.to(torch.float64) / wd, torch.zeros((), dtype=torch.float64, device=w.device))
+        codes[r0:r0 + rows_per_pass] = torch.round(quot).clamp_(-127, 127).to(torch.int8)  # torch.round: half to even
+    return codes, wscale
+
+
+@torch.no_grad()
+def dequantize_q8(codes: torch.Tensor, wscale: torch.Tensor) -> torch.Tensor:
+    """(codes int8 [N,K], wscale [N]) -> wdq bf16 [N,K] = bf16((float(q) * wscale) / 127): one fp32 product, one fp32 division, one rounding."""
+    return _div32(codes.to(torch.float32) * wscale.to(torch.float32)[:, None], 127.0).to(torch.bfloat16)
+
+
+@torch.no_grad()
+def q8_act_quant_torch(x2: torch.Tensor, threshold: float):
+    """The activation rule in torch (any device): (xq float32 [M,K] holding the integers, ascale float32 [M], outlier mask bool [K])."""
+    xf = x2.to(torch.float32)
+    ax = xf.abs()
+    outl = ax.amax(0) >= threshold if threshold > 0 else torch.zeros(xf.shape[1], dtype=torch.bool, device=xf.device)
+    ascale = ax.masked_fill(outl[None, :], 0.0).amax(1)
+    inv = torch.where(ascale > 0, _div32(torch.full_like(ascale, 127.0), ascale.clamp_min(1e-45)), torch.zeros_like(ascale))
+    xq = torch.round(xf * inv[:, None]).clamp_(-127, 127)
+    xq = xq.masked_fill(outl[None, :] | (ascale == 0)[:, None], 0.0)
+    return xq, ascale, outl
+
+
+@torch.no_grad()
+def q8_linear_torch(x2: torch.Tensor, codes: torch.Tensor, wscale: torch.Tensor, res: torch.Tensor | None, threshold: float) -> torch.Tensor:
+    """The arithmetic of vaa_model_q8_act_quant + vaa_model_q8_matmul in torch, step by step as the header states it: the integer sum through
+    an fp64 product (exact: below 2^31), every fp32 step an elementwise torch operation, the divisions through _div32."""
+    xq, ascale, outl = q8_act_quant_torch(x2, threshold)
+    xf = x2.to(torch.float32)
+    acc = (xq.to(torch.float64) @ codes.to(torch.float64).t()).to(torch.float32)  # float(acc): round to nearest even
+    y = _div32(acc * (ascale[:, None] * wscale[None, :]), 16129.0)
+    o = torch.zeros_like(y)
+    for k in outl.nonzero().flatten().tolist():  # ascending
+        wdq = _div32(codes[:, k].to(torch.float32) * wscale, 127.0).to(torch.bfloat16).to(torch.float32)
+        prod = xf[:, k:k + 1] * wdq[None, :]
+        o = o + prod
+    y = y + o
+    if res is not None:
+        y = y + res.to(torch.float32)
+    return y.to(torch.bfloat16)
+
+
+class Q8Scratch:
+    """The per-call buffers of vaa_model_q8_act_quant (xq, ascale, the K + 1 outlier words), shared by every layer of a converted model and
+    grown on demand; calls on one stream are ordered, so the next projection may overwrite them."""
+
+    def __init__(self):
+        self._xq = self._as = self._out = None
+
+    def get(self, M: int, K: int, device):
+        if self._xq is None or self._xq.device != device or self._xq.numel() < M * K:
+            self._xq = torch.empty(M * K, dtype=torch.int8, device=device)
+        if self._as is None or self._as.device != device or self._as.numel() < M:
+            self._as = torch.empty(M, dtype=torch.float32, device=device)
+        if self._out is None or self._out.device != device or self._out.numel() < K + 1:
+            self._out = torch.empty(K + 1, dtype=torch.int32, device=device)
+        return self._xq[:M * K].view(M, K), self._as[:M], self._out[:K + 1]
+
+
+def q8_act_quant(x2: torch.Tensor, threshold: float, scratch: Q8Scratch | None = None):
+    """vaa_model_q8_act_quant on contiguous bf16 x2 [M,K] (a GPU is required): (xq int8 [M,K], ascale float32 [M], outliers int32 [K+1] =
+    the count, then the outlier columns in ascending order)."""
+    M, K = x2.shape
+    if x2.dtype != torch.bfloat16 or not x2.is_contiguous():
+        raise ValueError("q8_act_quant: x must be contiguous bf16 [M,K]")
+    xq, ascale, outl = (scratch or Q8Scratch()).get(M, K, x2.device)
+    rc = _lib.lib().vaa_model_q8_act_quant(x2.data_ptr(), M, K, float(threshold), xq.data_ptr(), ascale.data_ptr(), outl.data_ptr(), _stream())
+    _lib.check(rc, "vaa_model_q8_act_quant")
+    return xq, ascale, outl
+
+
+def q8_matmul(xq, ascale, outl, x2, codes, wscale, res=None) -> torch.Tensor:
+    """vaa_model_q8_matmul on what q8_act_quant returned: y bf16 [M,N]; at most Q8_GEMV_MAX_ROWS rows take the split-K form."""
+    M, K = x2.shape
+    N = codes.shape[0]
+    if codes.shape[1] != K or codes.dtype != torch.int8 or not (codes.is_contiguous() and wscale.is_contiguous()):
+        raise ValueError("q8_matmul: codes / wscale must be contiguous int8 [N,K] / float32 [N]")
+    if res is not None and (res.shape != (M, N) or res.dtype != torch.bfloat16 or not res.is_contiguous()):
+        raise ValueError("q8_matmul: res must be contiguous bf16 [M,N]")
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=x2.device)
+    rc = _lib.lib().vaa_model_q8_matmul(xq.data_ptr(), ascale.data_ptr(), outl.data_ptr(), x2.data_ptr(), M, codes.data_ptr(), wscale.data_ptr(), N, K,
+                                        res.data_ptr() if res is not None else None, y.data_ptr(), 1 if M <= Q8_GEMV_MAX_ROWS else 2, _stream())
+    _lib.check(rc, "vaa_model_q8_matmul")
+    return y
+
+
+class Q8Linear(nn.Module):
+    """A frozen bias-free linear layer held as int8 codes: buffers `codes` int8 [out,in] and `wscale` float32 [out], and the outlier
+    threshold of its calls. There is no `weight`; `dequantize()` forms wdq."""
+
+    quant_type = INT8
+
+    def __init__(self, codes: torch.Tensor, wscale: torch.Tensor, threshold: float = 6.0):
+        super().__init__()
+        if not threshold >= 0 or threshold == float("inf"):
+            raise ValueError("Q8Linear: the threshold must be finite and >= 0")
+        self.threshold = float(threshold)
+        self.register_buffer("codes", codes)
+        self.register_buffer("wscale", wscale)
+
+    @classmethod
+    def from_weight(cls, w: torch.Tensor, threshold: float = 6.0) -> "Q8Linear":
+        return cls(*quantize_q8(w), threshold)
+
+    @property
+    def out_features(self) -> int:
+        return int(self.codes.shape[0])
+
+    @property
+    def in_features(self) -> int:
+        return int(self.codes.shape[1])
+
+    def dequantize(self) -> torch.Tensor:
+        return dequantize_q8(self.codes, self.wscale)
+
+    def extra_repr(self) -> str:
+        return f"in_features={self.in_features}, out_features={self.out_features}, quant_type={self.quant_type}, threshold={self.threshold:g}"
+
+    @torch.no_grad()
+    def forward(self, x, res=None, scratch=None):
+        """q8_linear on the last axis of x (inference only): ALL leading axes form the rows of one call."""
+        y = q8_linear(x.reshape(-1, x.shape[-1]), self, None if res is None else res.reshape(-1, self.out_features), None, scratch)
+        return y.view(*x.shape[:-1], self.out_features)
+
+
+class Q8LinearRows(Q8Linear):
+    """Rows [row0, row0 + rows) of a fused Q8Linear (q / k / v of the row-concatenated qkv codes, gate / up likewise): the projection as a
+    module of its own without a second copy of its codes. A scale belongs to one row, so the slice is exactly the projection's own codes."""
+
+    def __init__(self, parent: Q8Linear, row0: int, rows: int):
+        nn.Module.__init__(self)
+        self.threshold = parent.threshold
+        self._src = (parent,)  # in a tuple: the parent is registered once, on the layer
+        self.row0, self.rows = int(row0), int(rows)
+
+    @property
+    def codes(self):
+        return self._src[0].codes[self.row0:self.row0 + self.rows]
+
+    @property
+    def wscale(self):
+        return self._src[0].wscale[self.row0:self.row0 + self.rows]
+
+
+def q8_linear(x2: torch.Tensor, lin: Q8Linear, res: torch.Tensor | None = None, threshold: float | None = None,
+              scratch: Q8Scratch | None = None) -> torch.Tensor:
+    """The LLM.int8 product of include/vaa_model_ops.h for x2 [M,K]: the rows are quantised per call, multiplied as integers, rescaled by
+    ascale[m] * wscale[n], and the columns where ANY of the M rows reaches `threshold` (default: the layer's) are carried in bf16 — so a
+    row's result depends on the other rows of its call unless the threshold is 0. bf16 on a GPU: vaa_model_q8_act_quant +
+    vaa_model_q8_matmul. Elsewhere (CPU plumbing tests): q8_linear_torch, the same arithmetic in torch."""
+    t = lin.threshold if threshold is None else float(threshold)
+    if _on_gpu(x2) and x2.dtype == torch.bfloat16 and not Q8_TORCH_ROUTE:
+        if x2.shape[0] == 0:
+            return torch.empty((0, lin.out_features), dtype=torch.bfloat16, device=x2.device)
+        x2 = x2.contiguous()
+        xq, ascale, outl = q8_act_quant(x2, t, scratch)
+        return q8_matmul(xq, ascale, outl, x2, lin.codes, lin.wscale, None if res is None else res.contiguous())
+    return q8_linear_torch(x2, lin.codes, lin.wscale, res, t).to(x2.dtype)
+
+
+QUANT_ERROR = ("this model's Llama projections were quantised to {bits} by quantize_llm: it is inference only (predict_action / evaluate_patch); "
                "{what} needs the bf16 weights — build a second, unquantised model for training or for the no-cache decoding route")
 
 
-def refuse_training(what: str):
-    raise RuntimeError(QUANT_ERROR.format(what=what))
+def refuse_training(what: str, quant_type=None):
+    raise RuntimeError(QUANT_ERROR.format(what=what, bits="int8" if quant_type == INT8 else "4 bits"))
 
 
 PROJECTIONS = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
 
 
 @torch.no_grad()
-def quantize_llm(model, quant_type: str = "fp4"):
+def quantize_llm(model, quant_type: str = "fp4", threshold: float = 6.0):
     """Replace, in place, the seven projections of every LlamaLayer by Q4Linear modules and drop their bf16 weights (and the layer's cached
     transposed / concatenated copies). q / k / v share one row-concatenated Q4Linear (`qkv_q4`), gate / up likewise (`gate_up_q4`): the
-    decode step runs each group as one launch. Vision towers, projector, embeddings and lm_head are left as they are. Returns the model."""
-    table_values(quant_type)
+    decode step runs each group as one launch. Vision towers, projector, embeddings and lm_head are left as they are. Returns the model.
+    quant_type "int8": the same seven projections become Q8Linear modules (fused groups `qkv_q8`, `gate_up_q8`) whose calls split outlier
+    columns at `threshold` (transformers' llm_int8_threshold; 0: no split); `model.q4` then reads "int8"."""
+    int8 = quant_type == INT8
+    if not int8:
+        table_values(quant_type)
+    elif not threshold >= 0 or threshold == float("inf"):
+        raise ValueError("quantize_llm: the int8 threshold must be finite and >= 0")
     if getattr(model, "q4", None):
         raise ValueError("quantize_llm: the model is quantised already")
     cfg = model.cfg
-    scratch = Q4Scratch(cfg.llm_mlp * cfg.llm_dim)
+    scratch = Q8Scratch() if int8 else Q4Scratch(cfg.llm_mlp * cfg.llm_dim)
+    suffix, rows_cls = ("_q8", Q8LinearRows) if int8 else ("_q4", Q4LinearRows)
     for layer in model.layers:
         def take(names):
             w = torch.cat([getattr(layer, n).weight.detach() for n in names], 0) if len(names) > 1 else getattr(layer, names[0]).weight.detach()
             rows = [getattr(layer, n).weight.shape[0] for n in names]
             for n in names:
                 delattr(layer, n)
-            return Q4Linear.from_weight(w, quant_type), rows
+            return (Q8Linear.from_weight(w, threshold) if int8 else Q4Linear.from_weight(w, quant_type)), rows
 
         layer._wt_cache.clear()
-        for fused, names in (("qkv_q4", ("q_proj", "k_proj", "v_proj")), ("gate_up_q4", ("gate_proj", "up_proj"))):
+        for fused, names in (("qkv" + suffix, ("q_proj", "k_proj", "v_proj")), ("gate_up" + suffix, ("gate_proj", "up_proj"))):
             parent, rows = take(names)
             setattr(layer, fused, parent)
             r0 = 0
             for n, r in zip(names, rows):
-                setattr(layer, n, Q4LinearRows(parent, r0, r))
+                setattr(layer, n, rows_cls(parent, r0, r))
                 r0 += r
         for n in ("o_proj", "down_proj"):
             setattr(layer, n, take((n,))[0])
         layer.q4 = quant_type
-        layer._q4_scratch = scratch
+        if int8:
+            layer._q8_scratch = scratch
+        else:
+            layer._q4_scratch = scratch
     model.q4 = quant_type
     return model
+
+
+def _proj(layer, x2, name, res, gemv):
+    """One projection (or fused group: "qkv", "gate_up") of a converted layer on x2 [M,K]: q8_linear on an int8 layer (its two matmul forms
+    are chosen by M alone), q4_linear otherwise."""
+    if layer.q4 == INT8:
+        return q8_linear(x2, getattr(layer, name + "_q8" if name in ("qkv", "gate_up") else name), res, None, layer._q8_scratch)
+    return q4_linear(x2, getattr(layer, name + "_q4" if name in ("qkv", "gate_up") else name), res, layer._q4_scratch, gemv)
 
 
 # ---- the second inference route of LlamaLayer (openvla_model.py dispatches here when layer.q4 is set) ----
@@ -287,23 +501,22 @@ def _tail(layer, x, a, fused, gemv):
     from . import model_ops
 
     B, T, D = x.shape
-    sc = layer._q4_scratch
-    x2 = q4_linear(a.reshape(-1, D), layer.o_proj, x.reshape(-1, D), sc, gemv)
+    x2 = _proj(layer, a.reshape(-1, D), "o_proj", x.reshape(-1, D), gemv)
     h = layer._infer_norm(layer.post_attention_layernorm, x2.view(B, T, D), fused).reshape(-1, D)
-    gu = q4_linear(h, layer.gate_up_q4, None, sc, gemv)
+    gu = _proj(layer, h, "gate_up", None, gemv)
     mlp = gu.shape[1] // 2
     g, u = gu[:, :mlp], gu[:, mlp:]
     if fused and (B * T * mlp) % 8 == 0:
         y = model_ops.SwiGLUFn.apply(g, u)
     else:
         y = F.silu(g) * u
-    return q4_linear(y.contiguous(), layer.down_proj, x2, sc, gemv).view(B, T, D)
+    return _proj(layer, y.contiguous(), "down_proj", x2, gemv).view(B, T, D)
 
 
 def _qkv(layer, x, fused, gemv):
     B, T, D = x.shape
     h = layer._infer_norm(layer.input_layernorm, x, fused).reshape(-1, D)
-    return q4_linear(h, layer.qkv_q4, None, layer._q4_scratch, gemv).view(B, T, 3, layer.heads, D // layer.heads)
+    return _proj(layer, h, "qkv", None, gemv).view(B, T, 3, layer.heads, D // layer.heads)
 
 
 @torch.no_grad()

@@ -596,6 +596,44 @@ size_t vaa_frame_resize_taps_bytes(int Tx, int Ty);
 int vaa_frame_resize(const uint8_t* src_u8, int B, int H, int W, int rot180, const int32_t* start_x, const float* w_x, int Tx,
                      const int32_t* start_y, const float* w_y, int Ty, const void* taps_dev, uint8_t* dst_u8, void* stream);
 
+/*
+ * K9 — the evaluation's crop (K7's geometry) sampled inside a training step: crop + bilinear resize back to 224x224 of K1's planar pixel
+ * values with one box per image, and the adjoint that carries the model's pixel gradient back in front of K2. It acts on the normalised
+ * bf16 planes, not on the uint8 frame: normalisation is affine per channel and the bilinear taps sum to 1, so cropping after it equals
+ * normalising after the crop up to rounding. One launch per call; an image's result does not depend on the batch around it; same arguments,
+ * same bits (the adjoint is a gather per source element, no atomics).
+ *   x_bf16 / gout_bf16   dev  [B,6,224,224] bfloat16 bits (16-byte aligned)
+ *   boxes_host, boxes_dev     [B,4] float32 {y1, x1, y2, x2} in crop_and_resize's normalised coordinates, on the host and (16-byte aligned)
+ *            on the device. The host copy is what is validated, the device copy is what the kernels read; the kernels clamp every index
+ *            to the frame, so a device copy that differs from the validated boxes cannot read or write outside the tensors.
+ *   out_bf16 / gx_bf16   dev  [B,6,224,224] bfloat16 bits (16-byte aligned). Every element is written (the caller never zeroes gx).
+ * VAA_E_INVALID before any launch: B < 0; with B > 0 a NULL pointer, a misaligned device base, or a box with a coordinate that is not
+ * finite or breaks 0 <= y1 < y2 <= 1, y2 - y1 >= 0.5 (fp32 difference) or the same along x. B == 0 returns VAA_OK and launches nothing.
+ *
+ * The forward arithmetic is the contract: fp32, every operation separately rounded (no FMA), K7's own expressions per image and axis
+ * (columns alike, with x1, x2, x, lx, left = floor, right = ceil):
+ *     org_y = y1*223;   scale_y = ((y2 - y1)*223)/223
+ *     in_y = min(max(org_y + y*scale_y, 0), 223);   t = floorf(in_y);   b = ceilf(in_y);   ly = in_y - t
+ * The clamp stands where K7 has "outside [0, 223] -> 0"; with a valid box it can only fire through rounding when y2 == 1. Per channel c < 6,
+ * with the four source values widened to fp32, tl, tr from row t and bl, br from row b (columns left, right):
+ *     top = tl + (tr - tl)*lx;   bot = bl + (br - bl)*lx;   v = top + (bot - top)*ly;   out[b,c,y,x] = bf16(v)  (round to nearest even)
+ * The box {0,0,1,1} returns its input bit for bit for finite inputs (a negative zero comes back as +0: x + 0*0).
+ *
+ * The adjoint is the exact transpose of those taps. With t, b, ly of output row y as above, the weight of y on source row r is
+ *     wy(y, r) = [t(y) == r]*(1 - ly(y)) + [b(y) == r]*ly(y)        (a row that is both gets (1 - 0) + 0 = 1)
+ * and wx(x, j) alike. An output index TOUCHES a source index when its t or its b equals it; its weight is then never 0. Then
+ *     gx[b,c,r,j] = bf16( sum_y wy(y, r) * ( sum_x wx(x, j) * gout[b,c,y,x] ) )
+ * over the touching y and x only, both sums starting from 0.0f with ascending indices, every product and every add a separately rounded fp32
+ * operation, one rounding to bf16 at the end. A source element that no output touches is written as +0. Which outputs touch an index is
+ * decided by evaluating the forward's own t and b for each candidate (the candidates of j are the six indices from
+ * floor((j - org)/scale) - 2: a side of at least 0.5 puts every touching output among them), never by a second formula.
+ *
+ * What K9 does not model: K5's uint8 quantisation of the patch, K7's uint8 truncation of the cropped frame, and the
+ * order of interpolation and bf16 rounding (K9 interpolates values K1 has already rounded).
+ */
+int vaa_crop_resize_fwd(const uint16_t* x_bf16, const float* boxes_host, const float* boxes_dev, int B, uint16_t* out_bf16, void* stream);
+int vaa_crop_resize_bwd(const uint16_t* gout_bf16, const float* boxes_host, const float* boxes_dev, int B, uint16_t* gx_bf16, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,8 @@ EXPORTS = (
     "vaa_eval_preprocess",
     "vaa_frame_resize_taps_bytes",
     "vaa_frame_resize",
+    "vaa_crop_resize_fwd",
+    "vaa_crop_resize_bwd",
     "vaa_patch_embed_grad_ws_bytes",
     "vaa_patch_embed_grad_gather",
     "vaa_patch_embed_packed_elems",
@@ -218,6 +220,10 @@ def lib() -> C.CDLL:
     L.vaa_frame_resize_taps_bytes.argtypes = [i32, i32]
     L.vaa_frame_resize.restype = i32
     L.vaa_frame_resize.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp]
+    L.vaa_crop_resize_fwd.restype = i32
+    L.vaa_crop_resize_fwd.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.vaa_crop_resize_bwd.restype = i32
+    L.vaa_crop_resize_bwd.argtypes = [vp, vp, vp, i32, vp, vp]
     L.vaa_patch_apply_fwd_tiles.restype = i32
     L.vaa_patch_apply_fwd_tiles.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, vp, vp, vp, vp]
     L.vaa_patch_embed_grad_gather_multi_tiles.restype = i32

@@ -4,6 +4,7 @@ Flag names, types and defaults are the reference's (UADA_wrapper.py:87-121, UADA
 TMA_wrapper.py:89-124, UPA_wrapper.py:90-127). Added flags (all optional, defaults keep reference behaviour where the
 environment allows): --vla_path (local checkpoint dir, or random:openvla-7b / random:tiny / surrogate), --data (synthetic),
 --colorjitter / --colorjitter_strength (photometric draw on the patch in training steps; off by default),
+--train_crop / --train_crop_scale (the evaluation's crop inside the training steps; off by default),
 --tv_weight / --nps_weight / --nps_palette (total-variation and non-printability terms of the patch; off by default).
 """
 from __future__ import annotations
@@ -31,6 +32,11 @@ def three_floats(arg):
 def colorjitter_arg(args):
     """--colorjitter / --colorjitter_strength as the attackers take them: False, or the three strengths."""
     return tuple(args.colorjitter_strength) if args.colorjitter else False
+
+
+def train_crop_args(args):
+    """--train_crop / --train_crop_scale as the attackers take them: dict(train_crop=None | "center" | "random", train_crop_scale=area share)."""
+    return {"train_crop": None if args.train_crop == "none" else args.train_crop, "train_crop_scale": float(args.train_crop_scale)}
 
 
 def patch_reg_args(args):
@@ -104,6 +110,10 @@ def add_common(parser: argparse.ArgumentParser, *, lr, maskidx, iters, warmup, i
                         help="training steps paste a per-image brightness / contrast / saturation variant of the patch")
     parser.add_argument("--colorjitter_strength", type=three_floats, default=(0.2, 0.2, 0.2),
                         help="brightness,contrast,saturation strengths s: factors ~ U(1-s, 1+s)")
+    parser.add_argument("--train_crop", choices=("none", "center", "random"), default="none",
+                        help="training steps crop the pasted frames as the evaluation does (center: its centre box; random: the same side at a "
+                             "random offset per image) and resize back; validation passes use the centre box")
+    parser.add_argument("--train_crop_scale", type=float, default=0.9, help="the crop's share of the area, in [0.25, 1] (the evaluation: 0.9)")
     parser.add_argument("--tv_weight", type=float, default=0.0, help="weight of the patch's total variation (smoothness) in every training step")
     parser.add_argument("--nps_weight", type=float, default=0.0, help="weight of the patch's non-printability score in every training step")
     parser.add_argument("--nps_palette", type=str, default=None,

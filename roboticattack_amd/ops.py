@@ -1193,6 +1193,61 @@ def eval_preprocess(img_u8, crop_scale: float = 0.0, mean6=None, std6=None):
 
 
 # ------------------------------------------------------------------------------------------------------
+# K9: the evaluation's crop inside a training step (crop + bilinear resize of K1's pixel values, and the adjoint)
+# ------------------------------------------------------------------------------------------------------
+def _crop_boxes(boxes, B: int, device):
+    """boxes [B,4] {y1, x1, y2, x2}: a host float32 array (copied to the device here) or a (host array, device tensor) pair. The host copy is
+    what the library validates, the device copy what the kernels read (include/vaa.h)."""
+    import numpy as np
+
+    host, dev = boxes if isinstance(boxes, tuple) else (boxes, None)
+    host = np.ascontiguousarray(np.asarray(host, dtype=np.float32))
+    if host.shape != (B, 4):
+        raise _lib.VaaError(f"boxes: expected shape {(B, 4)}, got {host.shape}")
+    if dev is None:
+        dev = torch.from_numpy(host).to(device, non_blocking=True)
+    return host, _need(dev, torch.float32, "boxes (device copy)", (B, 4))
+
+
+def _crop_call(name, fn, t, boxes):
+    B = t.shape[0] if isinstance(t, torch.Tensor) and t.dim() == 4 else 0
+    _need(t, torch.bfloat16, name, (B, 6, IMG, IMG))
+    host, dev = _crop_boxes(boxes, B, t.device)
+    out = torch.empty_like(t)
+    with _timed(fn, B=B):
+        rc = getattr(_lib.lib(), fn)(t.data_ptr(), host.ctypes.data, dev.data_ptr(), B, out.data_ptr(), _stream())
+    _lib.check(rc, fn)
+    return out
+
+
+def crop_resize_fwd(pixel_values, boxes):
+    """K9. pixel_values bf16 [B,6,224,224] (K1's planar output) -> the same planes cropped to each image's box {y1, x1, y2, x2} (normalised
+    coordinates, sides in [0.5, 1]) and resized back bilinearly: K7's geometry on the normalised values (include/vaa.h states the arithmetic)."""
+    return _crop_call("pixel_values", "vaa_crop_resize_fwd", pixel_values, boxes)
+
+
+def crop_resize_bwd(gout, boxes):
+    """K9's adjoint: the gradient of crop_resize_fwd's output -> the gradient of its input, the exact transpose of the forward's taps."""
+    return _crop_call("gout", "vaa_crop_resize_bwd", gout, boxes)
+
+
+class CropResize(torch.autograd.Function):
+    """Differentiable K9 between K1 (PatchApply*) and the model: (pixel_values, boxes) -> pixel_values. `boxes`: host float32 [B,4]."""
+
+    @staticmethod
+    def forward(ctx, pixel_values, boxes):
+        x = pixel_values.contiguous() if isinstance(pixel_values, torch.Tensor) else pixel_values
+        B = x.shape[0] if isinstance(x, torch.Tensor) and x.dim() == 4 else 0
+        _need(x, torch.bfloat16, "pixel_values", (B, 6, IMG, IMG))
+        ctx.boxes = _crop_boxes(boxes, B, x.device)
+        return crop_resize_fwd(x, ctx.boxes)
+
+    @staticmethod
+    def backward(ctx, gout):
+        return crop_resize_bwd(gout.to(torch.bfloat16).contiguous(), ctx.boxes), None
+
+
+# ------------------------------------------------------------------------------------------------------
 # camera frames -> 224x224 in front of the eval-time paste (tf.image.resize lanczos3 + round + clip + uint8)
 # ------------------------------------------------------------------------------------------------------
 _resize_taps: dict = {}

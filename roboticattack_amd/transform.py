@@ -13,6 +13,8 @@ Differences a caller can observe (all documented in DESIGN.md):
   * Appendix A defects: D1 (IndentationError) n/a; D2 (resize_patch UnboundLocalError) resolved as "scale the BASE
     patch per image"; D3 (`colorjitter=` kwarg, dead in the reference) given a meaning here: a per-image brightness / contrast /
     saturation draw on the patch (include/vaa.h states the arithmetic; `_draw_jitter` the draws). Off by default: zero extra RNG calls.
+  * `train_crop` (an EXTENSION, off by default: no extra RNG call, no extra launch): the pasted frames go through the evaluation's crop
+    (K7's geometry, `eval_pixel_values(center_crop=True)`) inside the training step — K9 on K1's pixel values, `_crop_boxes` the draws.
 """
 from __future__ import annotations
 
@@ -25,6 +27,40 @@ from . import ops
 from .constants import IMG, MAX_ANGLE_DEG, MAX_SHEAR, P_IDENTITY
 
 JITTER_STRENGTH = (0.2, 0.2, 0.2)  # colorjitter=True: brightness, contrast, saturation factors ~ U(1 - s, 1 + s)
+TRAIN_CROP_MODES = (None, "center", "random")
+TRAIN_CROP_SCALE = 0.9  # the evaluation's centre crop keeps this share of the area (experiments/robot/openvla_utils.py:143)
+
+
+def train_crop_arg(mode, scale=TRAIN_CROP_SCALE):
+    """`train_crop` / `train_crop_scale` as the callers pass them -> (None | "center" | "random", area share in [0.25, 1])."""
+    mode = None if mode in (None, False, "none") else mode
+    if mode not in TRAIN_CROP_MODES:
+        raise ValueError(f"train_crop must be None, 'center' or 'random', got {mode!r}")
+    scale = float(scale)
+    if not 0.25 <= scale <= 1.0:  # NaN fails both
+        raise ValueError(f"train_crop_scale is the crop's share of the area and must be in [0.25, 1] (K9 takes box sides from 0.5), got {scale!r}")
+    return mode, scale
+
+
+def center_crop_box(scale):
+    """K7's box for an area share `scale`, in fp32 as vaa_eval_preprocess computes it: s = sqrt(scale), y1 = x1 = (1 - s)/2, y2 = x2 = y1 + s."""
+    one = np.float32(1.0)
+    s = np.minimum(np.maximum(np.sqrt(np.float32(scale)), np.float32(0.0)), one)
+    y1 = (one - s) / np.float32(2.0)
+    y2 = y1 + s
+    return np.array([y1, y1, y2, y2], np.float32)
+
+
+def _fit_side(lo, s):
+    """[lo, lo + s] in fp32 as K9 accepts it: inside [0, 1], and a side that is still >= 0.5 after the fp32 subtraction."""
+    lo = np.float32(lo)
+    hi = np.float32(min(np.float32(lo + s), np.float32(1.0)))
+    while np.float32(hi - lo) < np.float32(0.5):  # s == 0.5 and a rounding: widen by one ulp on the side that has room
+        if hi < np.float32(1.0):
+            hi = np.nextafter(hi, np.float32(2.0))
+        else:
+            lo = np.nextafter(lo, np.float32(-1.0))
+    return lo, hi
 
 
 def jitter_strength(colorjitter):
@@ -48,7 +84,7 @@ def _six(mean, std):
 
 
 class RandomPatchTransform:
-    def __init__(self, device, resize_patch: bool = False):
+    def __init__(self, device, resize_patch: bool = False, train_crop=None, train_crop_scale: float = TRAIN_CROP_SCALE):
         self.device = torch.device(device)
         self.angle = MAX_ANGLE_DEG  # appply_random_transform.py:11
         self.shx = MAX_SHEAR  # :12
@@ -61,6 +97,35 @@ class RandomPatchTransform:
         self.last_params = None  # (xy, theta) of the most recent call, host numpy (tests / logging)
         self.last_sizes = None   # resize_patch=True: per-image (h, w) of the most recent call
         self.last_jitter = None  # colorjitter: per-image (brightness, contrast, saturation) factors of the most recent call, float32 [B,3]
+        # train_crop: None | "center" | "random" (set_train_crop; set by the attackers like colorjitter: those steps stay off the fused paths)
+        self.set_train_crop(train_crop, train_crop_scale)
+        self.last_crop = None    # train_crop: per-image boxes {y1, x1, y2, x2} of the most recent call, float32 [B,4]
+
+    def set_train_crop(self, mode, scale=TRAIN_CROP_SCALE):
+        """Every paste of a training step is followed by the evaluation's crop (K9, ops.CropResize): "center" = K7's box for the area share
+        `scale`, "random" = the same side at a per-image random offset (OpenVLA's fine-tuning augmentation); None switches it off."""
+        self.train_crop, self.train_crop_scale = train_crop_arg(mode, scale)
+
+    def _crop_boxes(self, batch, patch):
+        """The boxes of one call. A differentiable call (a training step) uses `train_crop`; any other call (the validation passes inside the
+        loops) the centre box, which is what the evaluation will do. "center" makes no RNG call; "random" makes 2 per image after every other
+        draw of the call, image-major: y1 = random.uniform(0, 1 - s), then x1."""
+        box = center_crop_box(self.train_crop_scale)
+        boxes = np.tile(box, (batch, 1))
+        if self.train_crop == "random" and patch.requires_grad and torch.is_grad_enabled():
+            s = box[2] - box[0]
+            for b in range(batch):
+                y1, y2 = _fit_side(random.uniform(0.0, 1.0 - float(s)), s)
+                x1, x2 = _fit_side(random.uniform(0.0, 1.0 - float(s)), s)
+                boxes[b] = (y1, x1, y2, x2)
+        self.last_crop = boxes
+        return boxes
+
+    def _finish(self, out, patch, out_dtype):
+        """The tail of every paste that returns pixel values: [K9 with the call's boxes ->] the caller's dtype."""
+        if self.train_crop is not None:
+            out = ops.CropResize.apply(out, self._crop_boxes(int(out.shape[0]), patch))
+        return out if out_dtype == torch.bfloat16 else out.to(out_dtype)
 
     # ---- small tensor helpers kept for API compatibility (:16-24) ----
     def normalize(self, images, mean, std):
@@ -156,7 +221,10 @@ class RandomPatchTransform:
         patch gradient — the caller adds them with ops.step_epilogue (into the DDP message and / or straight through the optimiser).
         draws: (xy, theta) host arrays from `draw_params` to use instead of drawing (a maskidx sweep hands every group the same draws).
         colorjitter (True: strengths 0.2 each; or three strengths): every image pastes its own brightness / contrast / saturation variant of the
-        patch (`_apply_jittered`); False makes no extra RNG call."""
+        patch (`_apply_jittered`); False makes no extra RNG call.
+        With `train_crop` set the result is ops.CropResize of K1's pixel values (the planar K1 -> K9 path; no grad_sink)."""
+        if self.train_crop is not None and grad_sink is not None:
+            raise ValueError("grad_sink is not available with train_crop (the pixel gradient goes through the crop adjoint first)")
         mean6, std6 = _six(mean, std)
         img = self.stage_images(images)
         B = img.shape[0]
@@ -177,7 +245,7 @@ class RandomPatchTransform:
         if emb is not None:
             return ops.PatchEmbeds(ops.PatchApplyEmbed.apply(patch, img, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6, *emb, grad_sink))
         out = ops.PatchApply.apply(patch, img, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6, grad_sink)
-        return out if out_dtype == torch.bfloat16 else out.to(out_dtype)
+        return self._finish(out, patch, out_dtype)
 
     def draw_params(self, batch, ph, pw, geometry):
         """The host draws of one apply_random_patch_batch call on `batch` frames (the same RNG consumption), for `draws=` / apply_sweep_batch."""
@@ -193,14 +261,17 @@ class RandomPatchTransform:
         Bp = int(img.shape[0]) // P
         if self.embed_with is None:
             raise ValueError("apply_sweep_batch needs a model that exposes its patch-embed weights")
+        if self.train_crop is not None:
+            raise ValueError("apply_sweep_batch is not available with train_crop (K2' cannot take the cropped gradient)")
         xy_n, th_n = draws if draws is not None else self._draw(Bp, ph, pw, geometry)
         xy, theta = self._to_dev(np.tile(xy_n, (P, 1)), np.tile(th_n, (P, 1)))
         emb = self.embed_with.patch_embed_params()
         return ops.PatchEmbeds(ops.PatchApplySweepEmbed.apply(patches, img, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6, *emb, grad_sink))
 
     def _embed_params(self, patch, out_dtype):
-        """Patch-embed weights for the path that never materialises the pixel gradient — only for differentiable bf16 calls."""
-        if self.embed_with is None or not patch.requires_grad or out_dtype != torch.bfloat16 or not torch.is_grad_enabled():
+        """Patch-embed weights for the path that never materialises the pixel gradient — only for differentiable bf16 calls, and never with
+        train_crop: K2' evaluates only the tiles under the uncropped patch and cannot be fed the cropped gradient."""
+        if self.train_crop is not None or self.embed_with is None or not patch.requires_grad or out_dtype != torch.bfloat16 or not torch.is_grad_enabled():
             return None
         return self.embed_with.patch_embed_params()
 
@@ -229,7 +300,7 @@ class RandomPatchTransform:
         if emb is not None:
             return ops.PatchEmbeds(ops.PatchApplyResizedEmbed.apply(patch, img, sizes, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6, *emb))
         out = ops.PatchApplyResized.apply(patch, img, sizes, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6)
-        return out if out_dtype == torch.bfloat16 else out.to(out_dtype)
+        return self._finish(out, patch, out_dtype)
 
     def _draw_jitter(self, batch, strength):
         """3 * batch calls random.uniform(1 - s_k, 1 + s_k): image-major, in order brightness, contrast, saturation."""
@@ -251,7 +322,7 @@ class RandomPatchTransform:
         if emb is not None:
             return ops.PatchEmbeds(ops.PatchApplyJitteredEmbed.apply(patch, img, factors, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6, *emb))
         out = ops.PatchApplyJittered.apply(patch, img, factors, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6)
-        return out if out_dtype == torch.bfloat16 else out.to(out_dtype)
+        return self._finish(out, patch, out_dtype)
 
     def _paste(self, images, patch, mean, std, out_dtype):
         mean6, std6 = _six(mean, std)
@@ -262,7 +333,7 @@ class RandomPatchTransform:
         if emb is not None:
             return ops.PatchEmbeds(ops.PatchApplyEmbed.apply(patch, img, xy, theta, False, ops.MASK_NE_M100, mean6, std6, *emb)), xy
         out = ops.PatchApply.apply(patch, img, xy, theta, False, ops.MASK_NE_M100, mean6, std6)
-        return (out if out_dtype == torch.bfloat16 else out.to(out_dtype)), xy
+        return self._finish(out, patch, out_dtype), xy
 
     def random_paste_patch(self, images, patch, mean, std, out_dtype=torch.bfloat16):
         """:138-158 — paste without warp, mask rule `canvas != -100`."""

@@ -10,7 +10,12 @@
             PyTorch ops (two fp32 matmuls with the dense tap matrices, then round, clip and cast; the differing bytes are counted before
             anything is timed): per-dispatch us of K8 from vaa_prof_* (median of 50), event-bracketed us of both in alternating rounds
 
-    python tools/eval_bench.py [--bs 1,8] [--iters 5] [--warmup 2] [--parts front,batch,k8] [--out file.json]
+    k9      K9 (vaa_crop_resize_fwd / _bwd, the evaluation's crop inside a training step) with the centre box at 0.9: per-dispatch us of the
+            forward and the adjoint from vaa_prof_* (median of 50) and the share of 8 TB/s on the 1,204,224 bytes each launch must move per
+            image (602,112 in + 602,112 out); run it with --bs 8,64. Behind it the un-fused UADA inner step (UADA's own inner_step on
+            random:openvla-7b, geometry on) at the first --bs with train_crop off and "center": ms per step, median of --iters
+
+    python tools/eval_bench.py [--bs 1,8] [--iters 5] [--warmup 2] [--parts front,batch,k8,k9] [--out file.json]
 
 Each part runs in a fresh child process under `timeout`, one after the other; the first child that fails ends the run. One JSON line per result.
 """
@@ -232,6 +237,70 @@ def child_batch(batches, iters: int, warmup: int) -> int:
     return 0
 
 
+K9_BYTES_PER_IMAGE = 2 * 6 * 224 * 224 * 2
+
+
+def child_k9(batches, reps: int, iters: int, warmup: int) -> int:
+    import numpy as np
+    import torch
+
+    from roboticattack_amd import ops, synthetic
+    from roboticattack_amd.transform import center_crop_box
+
+    dev = torch.device("cuda:0")
+    for bs in batches:
+        x = (torch.randn(bs, 6, 224, 224, generator=torch.Generator().manual_seed(bs)) * 1.2).to(torch.bfloat16).to(dev)
+        boxes = np.tile(center_crop_box(CROP), (bs, 1))
+        pair = (boxes, torch.from_numpy(boxes).to(dev))  # the host copy and its device copy, staged once
+        for _ in range(5):
+            ops.crop_resize_fwd(x, pair)
+            ops.crop_resize_bwd(x, pair)
+        torch.cuda.synchronize()
+        ops.prof_start(2 * reps)
+        for _ in range(reps):
+            ops.crop_resize_fwd(x, pair)
+            ops.crop_resize_bwd(x, pair)
+        torch.cuda.synchronize()
+        disp = ops.prof_collect()
+        row = dict(part="k9", bs=bs, bytes=K9_BYTES_PER_IMAGE * bs, reps=reps)
+        for key, name in (("fwd", "crop_resize_fwd_kernel"), ("bwd", "crop_resize_bwd_kernel")):
+            us = [u for n, u in disp if name in n]
+            d = _median(us)
+            row.update({f"{key}_dispatch_us_median": round(d, 2), f"{key}_dispatch_us_min": round(min(us), 2),
+                        f"{key}_share_of_8tb_s": round(K9_BYTES_PER_IMAGE * bs / (d * 1e-6) / HBM_PEAK, 4)})
+        print(json.dumps(row), flush=True)
+
+    # the un-fused UADA step with and without the crop
+    from roboticattack_amd.attack.uada import OpenVLAAttacker
+    from roboticattack_amd.attack.uada_ddp import default_model_factory
+    from roboticattack_amd.attack.engine import to_dev
+    from roboticattack_amd.optim import PatchOptimizer
+
+    bs = batches[0]
+    att = OpenVLAAttacker(default_model_factory("random:openvla-7b", dev), None, "", optimizer="adamW")
+    data = synthetic.synth_batch(123, bs, "smooth")
+    pixel_values, labels, attention_mask, input_ids = to_dev(data, dev)
+    labels = att.mask_labels(labels, [0])
+    for mode in (None, "center", None, "center"):  # alternating, in one process
+        att.randomPatchTransform.set_train_crop(mode, CROP)
+        torch.manual_seed(0)
+        patch = torch.rand(3, 50, 50).to(dev).requires_grad_(True)
+        opt = PatchOptimizer(patch, 1e-3, "adamW")
+        scal = torch.zeros((1, 10), dtype=torch.float32, device=dev)
+        ms = []
+        for i in range(warmup + iters):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            att.inner_step(patch, opt, pixel_values, input_ids, attention_mask, labels, True, scal, 0)
+            torch.cuda.synchronize()
+            if i >= warmup:
+                ms.append((time.perf_counter() - t0) * 1e3)
+        ops.async_error_check()
+        print(json.dumps(dict(part="k9_step", attack="uada", bs=bs, train_crop=mode or "none", step_ms_median=round(_median(ms), 3),
+                              step_ms_min=round(min(ms), 3), iters=iters)), flush=True)
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
@@ -250,6 +319,8 @@ def main() -> int:
         return child_batch(batches, a.iters, a.warmup)
     if a.child == "k8":
         return child_k8(batches, a.reps)
+    if a.child == "k9":
+        return child_k9(batches, a.reps, a.iters, a.warmup)
     results = []
     for part in a.parts.split(","):
         cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", part, "--iters", str(a.iters),

@@ -126,7 +126,7 @@ def evaluate_patch(model, transform, frames_u8, input_ids, attention_mask, patch
 
     out = {"placements": placements, **report(0)}
     if quant_model is not None:
-        out["quantised"] = dict(report(1), quant_type=getattr(quant_model, "q4", None))
+        out["quantised"] = dict(report(1), quant_type=getattr(quant_model, "quant_type", None))
         out["clean_agreement"] = clean_agreement(out["tokens_clean"], out["quantised"]["tokens_clean"])
     return out
 

@@ -185,8 +185,35 @@ def _rope(q, k, cos, sin):
     return q * cos + rot(q) * sin, k * cos + rot(k) * sin
 
 
+class Bf16Projections:
+    """The bf16 kind of a layer's inference projections (quant.py holds the 4-bit and the int8 kind): what LlamaLayer.prefill / decode_step
+    call on 2-D rows. `gemv` is the quantised kinds' switch and means nothing here."""
+
+    def __init__(self, layer):
+        self.layer = layer
+
+    def qkv(self, h2, fused, gemv):
+        """[M,3D]: one GEMM over the row-concatenated weights on the fused path, the three stock projections otherwise."""
+        L = self.layer
+        if fused:
+            return F.linear(h2, L._wcat(("q_proj", "k_proj", "v_proj"))[0])
+        return torch.stack([L.q_proj(h2), L.k_proj(h2), L.v_proj(h2)], dim=1).view(h2.shape[0], -1)
+
+    def o(self, a2, res, gemv):
+        return torch.addmm(res, a2, self.layer.o_proj.weight.t())
+
+    def gate_up(self, h2, fused, gemv):
+        return self.layer.gate_proj(h2), self.layer.up_proj(h2)
+
+    def down(self, y2, res, fused_mlp, gemv):
+        """The residual in the GEMM's epilogue behind the SwiGLU kernel; the stock route adds it to the rounded product."""
+        if fused_mlp:
+            return torch.addmm(res, y2, self.layer.down_proj.weight.t())
+        return res + self.layer.down_proj(y2)
+
+
 class LlamaLayer(nn.Module):
-    q4 = None  # the table name (or "int8") once quant.quantize_llm has replaced the seven projections by Q4Linear / Q8Linear modules (inference only from then on)
+    quant_type = None  # the table name (or "int8") once quant.quantize_llm has replaced the seven projections by Q4Linear / Q8Linear modules (inference only from then on)
 
     def __init__(self, c: OpenVLACfg):
         super().__init__()
@@ -202,6 +229,7 @@ class LlamaLayer(nn.Module):
         self.up_proj = nn.Linear(d, c.llm_mlp, bias=False)
         self.down_proj = nn.Linear(c.llm_mlp, d, bias=False)
         self._wt_cache = {}
+        self.projections = Bf16Projections(self)  # quant.quantize_llm installs the kind of its codes
 
     def _wt(self, name):
         """Resident transposed copy of a frozen projection ([in,out] contiguous) for the TN-layout dgrad (model_ops.FrozenLinearsFn)."""
@@ -248,10 +276,10 @@ class LlamaLayer(nn.Module):
         for those rows only and [R,D] is returned (last layer of `forward_rows`: no other position reaches the loss)."""
         from . import model_ops
 
-        if self.q4:
+        if self.quant_type:
             from . import quant
 
-            quant.refuse_training("LlamaLayer.forward", self.q4)
+            quant.refuse_training("LlamaLayer.forward", self.quant_type)
         B, T, D = x.shape
         hd = D // self.heads
         fused = rope_tab is not None and model_ops.enabled(x) and hd % 16 == 0 and D % 8 == 0 and D <= 8192
@@ -325,7 +353,10 @@ class LlamaLayer(nn.Module):
             x = x + self.down_proj(F.silu(self.gate_proj(h)) * self.up_proj(h))
         return x[0] if rows is not None else x
 
-    # ---- inference only: KV-cached greedy decoding (predict.py). New code next to `forward`, which never materialises the rotated K. ----
+    # ---- inference only: KV-cached greedy decoding (predict.py). ONE graph for bf16, 4-bit and int8 weights: norm, qkv, attention (prefill:
+    # RoPE + attention + cache write; decode step: attention_decode), o_proj + residual, norm, gate and up, SwiGLU, down_proj + residual. How a
+    # projection is formed is all that differs, and sits behind self.projections (Bf16Projections above, quant.Q4Projections / Q8Projections);
+    # `gemv` tells the 4-bit kind that the rows are a decode step's. `forward` is the training path and never materialises the rotated K. ----
     def _infer_fused(self, x) -> bool:
         from . import model_ops
 
@@ -337,26 +368,24 @@ class LlamaLayer(nn.Module):
 
         return model_ops.ResidualRMSNormFn.apply(x, norm.weight, norm.eps)[1] if fused else norm(x)
 
-    def _infer_qkv(self, h, fused):
-        """[B,T,3,H,hd]: one GEMM over the row-concatenated weights on the fused path, the three stock projections otherwise."""
-        B, T, D = h.shape
-        if fused:
-            qkv = F.linear(h, self._wcat(("q_proj", "k_proj", "v_proj"))[0])
-        else:
-            qkv = torch.stack([self.q_proj(h), self.k_proj(h), self.v_proj(h)], dim=2)
-        return qkv.view(B, T, 3, self.heads, D // self.heads)
+    def _infer_norm_qkv(self, x, fused, gemv):
+        """RMSNorm and the q/k/v projections of x [B,T,D]: [B,T,3,H,hd]."""
+        B, T, D = x.shape
+        h = self._infer_norm(self.input_layernorm, x, fused).reshape(-1, D)
+        return self.projections.qkv(h, fused, gemv).view(B, T, 3, self.heads, D // self.heads)
 
-    def _infer_tail(self, x, a, fused):
-        """o_proj + residual, RMSNorm, SwiGLU MLP + residual on [B,T,D]."""
+    def _infer_o_mlp(self, x, a, fused, gemv):
+        """o_proj + residual, RMSNorm, SwiGLU MLP + residual on [B,T,D]; the residuals are the projections' `res`."""
         from . import model_ops
 
         B, T, D = x.shape
-        x = torch.addmm(x.reshape(-1, D), a.reshape(-1, D), self.o_proj.weight.t()).view(B, T, D)
-        h = self._infer_norm(self.post_attention_layernorm, x, fused)
-        if fused and (B * T * self.gate_proj.out_features) % 8 == 0:
-            y = model_ops.SwiGLUFn.apply(self.gate_proj(h), self.up_proj(h))
-            return torch.addmm(x.reshape(-1, D), y.reshape(-1, y.shape[-1]), self.down_proj.weight.t()).view(B, T, D)
-        return x + self.down_proj(F.silu(self.gate_proj(h)) * self.up_proj(h))
+        proj = self.projections
+        x2 = proj.o(a.reshape(-1, D), x.reshape(-1, D), gemv)
+        h = self._infer_norm(self.post_attention_layernorm, x2.view(B, T, D), fused).reshape(-1, D)
+        g, u = proj.gate_up(h, fused, gemv)
+        fused_mlp = fused and (B * T * g.shape[1]) % 8 == 0
+        y = model_ops.SwiGLUFn.apply(g, u) if fused_mlp else F.silu(g) * u
+        return proj.down(y, x2, fused_mlp, gemv).view(B, T, D)
 
     @torch.no_grad()
     def prefill(self, x, rope_tab, cache):
@@ -365,14 +394,9 @@ class LlamaLayer(nn.Module):
         pad slots hold garbage that the decode steps overwrite before any query sees it."""
         from . import model_ops
 
-        if self.q4:  # the 4-bit route (quant.py): dequant + GEMM on the same graph
-            from . import quant
-
-            return quant.layer_prefill(self, x, rope_tab, cache)
         B, T, D = x.shape
-        hd = D // self.heads
         fused = self._infer_fused(x)
-        qkv = self._infer_qkv(self._infer_norm(self.input_layernorm, x, fused), fused)
+        qkv = self._infer_norm_qkv(x, fused, gemv=False)  # T is a whole prompt: a 4-bit layer takes dequant + GEMM
         cos, sin = rope_tab[0][:T], rope_tab[1][:T]
         if fused:
             q, k = model_ops.RopeFn.apply(qkv[:, :, 0], cos, sin), model_ops.RopeFn.apply(qkv[:, :, 1], cos, sin)  # [B,T,H,hd]
@@ -386,23 +410,20 @@ class LlamaLayer(nn.Module):
             a = F.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), is_causal=True).transpose(1, 2)
         cache[0][:, :T] = k
         cache[1][:, :T] = v
-        return self._infer_tail(x, a.reshape(B, T, D), fused)
+        return self._infer_o_mlp(x, a.reshape(B, T, D), fused, gemv=False)
 
     @torch.no_grad()
     def decode_step(self, x, pos, rope_tab, cache):
         """The layer on one new token per row: x [B,1,D], pos int32 [B] (row b's position; its cache holds keys 0 .. pos[b]-1). RMSNorm, the
-        QKV GEMM on [B,1,D], model_ops.attention_decode (rotation, cache append and attention in one launch), o_proj, residual, MLP."""
+        q/k/v projection of [B,1,D] (a 4-bit layer: ONE vaa_model_q4_gemv over the row-concatenated codes while B <= quant.GEMV_MAX_ROWS),
+        model_ops.attention_decode (rotation, cache append and attention in one launch), o_proj, residual, MLP."""
         from . import model_ops
 
-        if self.q4:  # the 4-bit route (quant.py): the projections through vaa_model_q4_gemv
-            from . import quant
-
-            return quant.layer_decode(self, x, pos, rope_tab, cache)
         B, _, D = x.shape
         fused = self._infer_fused(x)
-        qkv = self._infer_qkv(self._infer_norm(self.input_layernorm, x, fused), fused)[:, 0]  # [B,3,H,hd]
+        qkv = self._infer_norm_qkv(x, fused, gemv=True)[:, 0]  # [B,3,H,hd]
         a = model_ops.attention_decode(qkv[:, 0], qkv[:, 1], qkv[:, 2], cache[0], cache[1], pos, rope_tab[0], rope_tab[1])
-        return self._infer_tail(x, a.reshape(B, 1, D), fused)
+        return self._infer_o_mlp(x, a.reshape(B, 1, D), fused, gemv=True)
 
 
 class SeqPack:
@@ -443,13 +464,13 @@ class SeqPack:
 
 
 class OpenVLAShaped(nn.Module):
-    q4 = None  # the table name (or "int8") once quant.quantize_llm has converted the Llama stack (predict_action / evaluate_patch only from then on)
+    quant_type = None  # the table name (or "int8") once quant.quantize_llm has converted the Llama stack (predict_action / evaluate_patch only from then on)
 
     def _refuse_if_quantised(self, what):
-        if self.q4:
+        if self.quant_type:
             from . import quant
 
-            quant.refuse_training(what, self.q4)
+            quant.refuse_training(what, self.quant_type)
 
     def __init__(self, cfg: OpenVLACfg | None = None):
         super().__init__()

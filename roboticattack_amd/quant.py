@@ -4,18 +4,22 @@ built here because bitsandbytes does not exist on this platform. Inference only:
 model, the training entry points refuse it.
 
   quantize_q4 / dequantize_q4   the quantiser and its inverse in torch (CPU and GPU give the same codes: every comparison is exact)
-  Q4Linear                      codes + absmax as buffers, the table, no `weight`
-  quantize_llm                  the seven projections of every LlamaLayer -> Q4Linear; towers, projector, embeddings and lm_head stay bf16
-  layer_prefill / layer_decode  the second route of LlamaLayer.prefill / decode_step: vaa_model_q4_gemv for at most GEMV_MAX_ROWS rows in a
-                                decode step, vaa_model_q4_dequant into one shared scratch + the stock GEMM otherwise and always in prefill
+  q4_linear                     vaa_model_q4_gemv for at most GEMV_MAX_ROWS rows of a decode step, vaa_model_q4_dequant into one shared scratch +
+                                the stock GEMM otherwise and always in prefill
+  Q4Linear / Q4LinearRows       codes + absmax as buffers, the table, no `weight`; the rows of a fused parent as a module of their own
 Neither table could be compared with bitsandbytes in this image; the fp4 entries are stated from memory.
 
-The 8-bit route (`load_in_8bit` in the reference: LLM.int8) lives here as well — csrc/vaa_quant8.hip, stated in the same header, likewise not
+The 8-bit format (`load_in_8bit` in the reference: LLM.int8) lives here as well — csrc/vaa_quant8.hip, stated in the same header, likewise not
 compared with bitsandbytes:
   quantize_q8 / dequantize_q8   int8 codes with one fp32 scale per row, and the dequantised weight
   q8_linear                     vaa_model_q8_act_quant + vaa_model_q8_matmul on a GPU, q8_linear_torch (the same arithmetic in torch) elsewhere
   Q8Linear / Q8LinearRows       codes + wscale as buffers and the outlier threshold of the layer's calls
-  quantize_llm(model, "int8")   the same seven projections -> Q8Linear; layer_prefill / layer_decode serve both kinds through _proj
+
+Both formats share one host shape (QuantLinear, the row views of a fused parent) and one place in the model:
+  quantize_llm                  the seven projections of every LlamaLayer -> Q4Linear or Q8Linear ("int8"); towers, projector, embeddings and
+                                lm_head stay bf16. Sets `quant_type` on the model and its layers and installs QuantProjections on each layer
+  QuantProjections              the quantised kinds of the projections in LlamaLayer.prefill / decode_step. The inference graph is stated there,
+                                once, for bf16, 4-bit and int8 weights; a kind only says how a projection is formed
 """
 from __future__ import annotations
 
@@ -114,15 +118,47 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-def _on_gpu(t: torch.Tensor) -> bool:
-    return t.is_cuda
+class QuantLinear(nn.Module):
+    """What Q4Linear and Q8Linear share: a frozen bias-free linear layer held as a buffer `codes` [out, ...] and its scales, without a
+    `weight` (`dequantize()` forms it), called through its format's product on 2-D rows (`linear2d`: q4_linear / q8_linear)."""
+
+    @property
+    def out_features(self) -> int:
+        return int(self.codes.shape[0])
+
+    def extra_repr(self) -> str:
+        return f"in_features={self.in_features}, out_features={self.out_features}, quant_type={self.quant_type}"
+
+    @torch.no_grad()
+    def forward(self, x, res=None, scratch=None, gemv=True):
+        """linear2d on the last axis of x (inference only): ALL leading axes form the rows of one call."""
+        y = self.linear2d(x.reshape(-1, x.shape[-1]), None if res is None else res.reshape(-1, self.out_features), scratch, gemv)
+        return y.view(*x.shape[:-1], self.out_features)
+
+
+class _FusedRows:
+    """Rows [row0, row0 + rows) of a fused QuantLinear (q / k / v of the row-concatenated qkv codes, gate / up likewise): the projection as a
+    module of its own without a second copy of its codes. A subclass names the parent's buffers that it slices and the settings it takes over."""
+
+    def __init_subclass__(cls, buffers=(), settings=(), **kw):
+        super().__init_subclass__(**kw)
+        cls._settings = settings
+        for name in buffers:
+            setattr(cls, name, property(lambda self, name=name: getattr(self._src[0], name)[self.row0:self.row0 + self.rows]))
+
+    def __init__(self, parent: QuantLinear, row0: int, rows: int):
+        nn.Module.__init__(self)
+        for name in self._settings:
+            setattr(self, name, getattr(parent, name))
+        self._src = (parent,)  # in a tuple: the parent is registered once, on the layer
+        self.row0, self.rows = int(row0), int(rows)
 
 
 def q4_dequant(codes: torch.Tensor, absmax: torch.Tensor, table, out: torch.Tensor | None = None) -> torch.Tensor:
     """The dequantised weight [N,K] bf16 through vaa_model_q4_dequant on a GPU (into `out`, a contiguous buffer of at least N*K bf16, when
     given), through dequantize_q4 elsewhere."""
     N, K = codes.shape[0], codes.shape[1] * 2
-    if not _on_gpu(codes):
+    if not codes.is_cuda:
         w = dequantize_q4(codes, absmax, table)
         return w if out is None else out.reshape(-1)[:N * K].view(N, K).copy_(w)
     if not (codes.is_contiguous() and absmax.is_contiguous()):
@@ -148,7 +184,7 @@ def q4_gemv(x: torch.Tensor, codes: torch.Tensor, absmax: torch.Tensor, table, r
     return y
 
 
-class Q4Linear(nn.Module):
+class Q4Linear(QuantLinear):
     """A frozen bias-free linear layer held as 4-bit codes: buffers `codes` uint8 [out,in/2] and `absmax` float32 [out,in/64], the table's
     name and values. There is no `weight`; `dequantize()` forms it."""
 
@@ -164,43 +200,19 @@ class Q4Linear(nn.Module):
         return cls(*quantize_q4(w, quant_type), quant_type)
 
     @property
-    def out_features(self) -> int:
-        return int(self.codes.shape[0])
-
-    @property
     def in_features(self) -> int:
         return int(self.codes.shape[1]) * 2
 
     def dequantize(self) -> torch.Tensor:
         return dequantize_q4(self.codes, self.absmax, self.table)
 
-    def extra_repr(self) -> str:
-        return f"in_features={self.in_features}, out_features={self.out_features}, quant_type={self.quant_type}"
-
-    @torch.no_grad()
-    def forward(self, x, res=None, scratch=None, gemv=True):
-        """bf16(res + x @ wq^T) on the last axis of x (inference only)."""
-        y = q4_linear(x.reshape(-1, x.shape[-1]), self, None if res is None else res.reshape(-1, self.out_features), scratch, gemv)
-        return y.view(*x.shape[:-1], self.out_features)
+    def linear2d(self, x2, res=None, scratch=None, gemv=True):
+        """bf16(res + x2 @ wq^T): q4_linear."""
+        return q4_linear(x2, self, res, scratch, gemv)
 
 
-class Q4LinearRows(Q4Linear):
-    """Rows [row0, row0 + rows) of a fused Q4Linear (q / k / v of the row-concatenated qkv codes, gate / up likewise): the projection as a
-    module of its own without a second copy of its codes. Blocks never cross a row, so the slice is exactly the projection's own codes."""
-
-    def __init__(self, parent: Q4Linear, row0: int, rows: int):
-        nn.Module.__init__(self)
-        self.quant_type, self.table = parent.quant_type, parent.table
-        self._src = (parent,)  # in a tuple: the parent is registered once, on the layer
-        self.row0, self.rows = int(row0), int(rows)
-
-    @property
-    def codes(self):
-        return self._src[0].codes[self.row0:self.row0 + self.rows]
-
-    @property
-    def absmax(self):
-        return self._src[0].absmax[self.row0:self.row0 + self.rows]
+class Q4LinearRows(_FusedRows, Q4Linear, buffers=("codes", "absmax"), settings=("quant_type", "table")):
+    """Rows of a fused Q4Linear. Blocks never cross a row, so the slice is exactly the projection's own codes."""
 
 
 class Q4Scratch:
@@ -224,7 +236,7 @@ def q4_linear(x2: torch.Tensor, lin: Q4Linear, res: torch.Tensor | None = None, 
     M, K = x2.shape
     N = lin.out_features
     codes, absmax = lin.codes, lin.absmax
-    if _on_gpu(x2) and x2.dtype == torch.bfloat16:
+    if x2.is_cuda and x2.dtype == torch.bfloat16:
         if gemv and 1 <= M <= GEMV_MAX_ROWS:
             return q4_gemv(x2.contiguous(), codes, absmax, lin.table, None if res is None else res.contiguous())
         buf = scratch.get(x2.device) if scratch is not None else torch.empty(N * K, dtype=torch.bfloat16, device=x2.device)
@@ -358,7 +370,7 @@ def q8_matmul(xq, ascale, outl, x2, codes, wscale, res=None) -> torch.Tensor:
     return y
 
 
-class Q8Linear(nn.Module):
+class Q8Linear(QuantLinear):
     """A frozen bias-free linear layer held as int8 codes: buffers `codes` int8 [out,in] and `wscale` float32 [out], and the outlier
     threshold of its calls. There is no `weight`; `dequantize()` forms wdq."""
 
@@ -377,10 +389,6 @@ class Q8Linear(nn.Module):
         return cls(*quantize_q8(w), threshold)
 
     @property
-    def out_features(self) -> int:
-        return int(self.codes.shape[0])
-
-    @property
     def in_features(self) -> int:
         return int(self.codes.shape[1])
 
@@ -388,32 +396,15 @@ class Q8Linear(nn.Module):
         return dequantize_q8(self.codes, self.wscale)
 
     def extra_repr(self) -> str:
-        return f"in_features={self.in_features}, out_features={self.out_features}, quant_type={self.quant_type}, threshold={self.threshold:g}"
+        return f"{super().extra_repr()}, threshold={self.threshold:g}"
 
-    @torch.no_grad()
-    def forward(self, x, res=None, scratch=None):
-        """q8_linear on the last axis of x (inference only): ALL leading axes form the rows of one call."""
-        y = q8_linear(x.reshape(-1, x.shape[-1]), self, None if res is None else res.reshape(-1, self.out_features), None, scratch)
-        return y.view(*x.shape[:-1], self.out_features)
+    def linear2d(self, x2, res=None, scratch=None, gemv=True):
+        """q8_linear at the layer's threshold; `gemv` means nothing here: the matmul's form is chosen by the row count alone."""
+        return q8_linear(x2, self, res, None, scratch)
 
 
-class Q8LinearRows(Q8Linear):
-    """Rows [row0, row0 + rows) of a fused Q8Linear (q / k / v of the row-concatenated qkv codes, gate / up likewise): the projection as a
-    module of its own without a second copy of its codes. A scale belongs to one row, so the slice is exactly the projection's own codes."""
-
-    def __init__(self, parent: Q8Linear, row0: int, rows: int):
-        nn.Module.__init__(self)
-        self.threshold = parent.threshold
-        self._src = (parent,)  # in a tuple: the parent is registered once, on the layer
-        self.row0, self.rows = int(row0), int(rows)
-
-    @property
-    def codes(self):
-        return self._src[0].codes[self.row0:self.row0 + self.rows]
-
-    @property
-    def wscale(self):
-        return self._src[0].wscale[self.row0:self.row0 + self.rows]
+class Q8LinearRows(_FusedRows, Q8Linear, buffers=("codes", "wscale"), settings=("threshold",)):
+    """Rows of a fused Q8Linear. A scale belongs to one row, so the slice is exactly the projection's own codes."""
 
 
 def q8_linear(x2: torch.Tensor, lin: Q8Linear, res: torch.Tensor | None = None, threshold: float | None = None,
@@ -423,7 +414,7 @@ def q8_linear(x2: torch.Tensor, lin: Q8Linear, res: torch.Tensor | None = None, 
     row's result depends on the other rows of its call unless the threshold is 0. bf16 on a GPU: vaa_model_q8_act_quant +
     vaa_model_q8_matmul. Elsewhere (CPU plumbing tests): q8_linear_torch, the same arithmetic in torch."""
     t = lin.threshold if threshold is None else float(threshold)
-    if _on_gpu(x2) and x2.dtype == torch.bfloat16 and not Q8_TORCH_ROUTE:
+    if x2.is_cuda and x2.dtype == torch.bfloat16 and not Q8_TORCH_ROUTE:
         if x2.shape[0] == 0:
             return torch.empty((0, lin.out_features), dtype=torch.bfloat16, device=x2.device)
         x2 = x2.contiguous()
@@ -449,13 +440,13 @@ def quantize_llm(model, quant_type: str = "fp4", threshold: float = 6.0):
     transposed / concatenated copies). q / k / v share one row-concatenated Q4Linear (`qkv_q4`), gate / up likewise (`gate_up_q4`): the
     decode step runs each group as one launch. Vision towers, projector, embeddings and lm_head are left as they are. Returns the model.
     quant_type "int8": the same seven projections become Q8Linear modules (fused groups `qkv_q8`, `gate_up_q8`) whose calls split outlier
-    columns at `threshold` (transformers' llm_int8_threshold; 0: no split); `model.q4` then reads "int8"."""
+    columns at `threshold` (transformers' llm_int8_threshold; 0: no split); `model.quant_type` then reads "int8"."""
     int8 = quant_type == INT8
     if not int8:
         table_values(quant_type)
     elif not threshold >= 0 or threshold == float("inf"):
         raise ValueError("quantize_llm: the int8 threshold must be finite and >= 0")
-    if getattr(model, "q4", None):
+    if getattr(model, "quant_type", None):
         raise ValueError("quantize_llm: the model is quantised already")
     cfg = model.cfg
     scratch = Q8Scratch() if int8 else Q4Scratch(cfg.llm_mlp * cfg.llm_dim)
@@ -478,83 +469,37 @@ def quantize_llm(model, quant_type: str = "fp4", threshold: float = 6.0):
                 r0 += r
         for n in ("o_proj", "down_proj"):
             setattr(layer, n, take((n,))[0])
-        layer.q4 = quant_type
-        if int8:
-            layer._q8_scratch = scratch
-        else:
-            layer._q4_scratch = scratch
-    model.q4 = quant_type
+        layer.quant_type = quant_type
+        layer._quant_scratch = scratch  # a Q4Scratch or a Q8Scratch, shared by all layers
+        layer.projections = QuantProjections(layer, suffix)
+    model.quant_type = quant_type
     return model
 
 
-def _proj(layer, x2, name, res, gemv):
-    """One projection (or fused group: "qkv", "gate_up") of a converted layer on x2 [M,K]: q8_linear on an int8 layer (its two matmul forms
-    are chosen by M alone), q4_linear otherwise."""
-    if layer.q4 == INT8:
-        return q8_linear(x2, getattr(layer, name + "_q8" if name in ("qkv", "gate_up") else name), res, None, layer._q8_scratch)
-    return q4_linear(x2, getattr(layer, name + "_q4" if name in ("qkv", "gate_up") else name), res, layer._q4_scratch, gemv)
+class QuantProjections:
+    """The 4-bit and the int8 kind of a converted layer's inference projections (openvla_model.Bf16Projections is the bf16 kind): the fused
+    groups `qkv_q4` / `gate_up_q4` (or `_q8`) and o_proj / down_proj, each through its format's product on 2-D rows with the residual as
+    `res` and the model's shared scratch. 4-bit honours `gemv` (False in prefill, True in a decode step); int8 chooses by the row count."""
 
+    def __init__(self, layer, suffix: str):
+        self.layer, self.suffix = layer, suffix
 
-# ---- the second inference route of LlamaLayer (openvla_model.py dispatches here when layer.q4 is set) ----
-def _tail(layer, x, a, fused, gemv):
-    """o_proj + residual, RMSNorm, SwiGLU MLP + residual on [B,T,D], every projection through q4_linear (residuals as `res`)."""
-    from . import model_ops
+    def _linear(self, name, x2, res, gemv):
+        return getattr(self.layer, name).linear2d(x2, res, self.layer._quant_scratch, gemv)
 
-    B, T, D = x.shape
-    x2 = _proj(layer, a.reshape(-1, D), "o_proj", x.reshape(-1, D), gemv)
-    h = layer._infer_norm(layer.post_attention_layernorm, x2.view(B, T, D), fused).reshape(-1, D)
-    gu = _proj(layer, h, "gate_up", None, gemv)
-    mlp = gu.shape[1] // 2
-    g, u = gu[:, :mlp], gu[:, mlp:]
-    if fused and (B * T * mlp) % 8 == 0:
-        y = model_ops.SwiGLUFn.apply(g, u)
-    else:
-        y = F.silu(g) * u
-    return _proj(layer, y.contiguous(), "down_proj", x2, gemv).view(B, T, D)
+    def qkv(self, h2, fused, gemv):
+        return self._linear("qkv" + self.suffix, h2, None, gemv)
 
+    def o(self, a2, res, gemv):
+        return self._linear("o_proj", a2, res, gemv)
 
-def _qkv(layer, x, fused, gemv):
-    B, T, D = x.shape
-    h = layer._infer_norm(layer.input_layernorm, x, fused).reshape(-1, D)
-    return _proj(layer, h, "qkv", None, gemv).view(B, T, 3, layer.heads, D // layer.heads)
+    def gate_up(self, h2, fused, gemv):
+        gu = self._linear("gate_up" + self.suffix, h2, None, gemv)
+        mlp = gu.shape[1] // 2
+        return gu[:, :mlp], gu[:, mlp:]
 
-
-@torch.no_grad()
-def layer_prefill(layer, x, rope_tab, cache):
-    """LlamaLayer.prefill on a quantised layer: the same graph, the projections as vaa_model_q4_dequant + GEMM (always: T is a whole prompt)."""
-    from . import model_ops
-    from .openvla_model import _rope
-
-    B, T, D = x.shape
-    fused = layer._infer_fused(x)
-    qkv = _qkv(layer, x, fused, gemv=False)
-    cos, sin = rope_tab[0][:T], rope_tab[1][:T]
-    if fused:
-        q, k = model_ops.RopeFn.apply(qkv[:, :, 0], cos, sin), model_ops.RopeFn.apply(qkv[:, :, 1], cos, sin)
-    else:
-        c, s = (torch.cat([t, t], -1).to(x.dtype)[None, :, None, :] for t in (cos, sin))
-        q, k = _rope(qkv[:, :, 0], qkv[:, :, 1], c, s)
-    v = qkv[:, :, 2]
-    if fused and model_ops.attention_enabled(q):
-        a = model_ops.attention_fwd(q, k, v, True)[0]
-    else:
-        a = F.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), is_causal=True).transpose(1, 2)
-    cache[0][:, :T] = k
-    cache[1][:, :T] = v
-    return _tail(layer, x, a.reshape(B, T, D), fused, gemv=False)
-
-
-@torch.no_grad()
-def layer_decode(layer, x, pos, rope_tab, cache):
-    """LlamaLayer.decode_step on a quantised layer: q/k/v as ONE vaa_model_q4_gemv over the row-concatenated codes, attention_decode, o_proj and
-    down_proj with the residual as the kernel's `res`, gate/up as one launch. More than GEMV_MAX_ROWS rows take dequant + GEMM."""
-    from . import model_ops
-
-    B, _, D = x.shape
-    fused = layer._infer_fused(x)
-    qkv = _qkv(layer, x, fused, gemv=True)[:, 0]  # [B,3,H,hd]
-    a = model_ops.attention_decode(qkv[:, 0], qkv[:, 1], qkv[:, 2], cache[0], cache[1], pos, rope_tab[0], rope_tab[1])
-    return _tail(layer, x, a.reshape(B, 1, D), fused, gemv=True)
+    def down(self, y2, res, fused_mlp, gemv):
+        return self._linear("down_proj", y2.contiguous(), res, gemv)
 
 
 def llm_weight_bytes(model) -> int:

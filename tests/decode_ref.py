@@ -190,3 +190,157 @@ def same_prefix(ta, tb):
     """[B,S] bool: the two decodings chose the same tokens at every EARLIER step of the row (their step-s logits answer the same question)."""
     eq = (ta == tb).long()
     return torch.cat([torch.ones_like(eq[:, :1]), eq.cumprod(1)[:, :-1]], 1).bool()
+
+
+# ---------------------------------------------------------------- one layer's inference graph, written out ----------------------------------------------------------------
+# LlamaLayer.prefill / decode_step restated in a straight line from the public pieces, without the layer's projection kinds: a projection is
+# `linear(name, x2, res)` with name in "qkv" -> [M,3D], "o_proj" -> [M,D], "gate_up" -> (g, u), "down_proj" -> [M,D], supplied by
+# layer_linear below. Both sides run the same operations on the same inputs, so the tests compare with torch.equal.
+LAYER_KINDS = (("bf16", None), ("nf4", None), ("fp4", None), ("int8", 6.0), ("int8", 0.0))
+LAYER_T, LAYER_TMAX = 12, 20
+LAYER_POS = {3: (5, 9, 12), 1: (12,)}  # different per row; 12 is the first slot behind the prompt
+LAYER_BIG_COLUMN = 5  # x carries 64 times the other columns' scale here: RMSNorm maps it to about sqrt(64) = 8 >= the int8 threshold 6
+
+
+def layer_kind_id(k):
+    return k[0] if k[1] is None else "%s_thr%g" % k
+
+
+def layer_fused(layer, x):
+    from roboticattack_amd import model_ops
+
+    D = x.shape[-1]
+    return model_ops.enabled(x) and (D // layer.heads) % 16 == 0 and D % 8 == 0 and D <= 8192
+
+
+def layer_linear(layer, kind, fused, gemv):
+    """The projections of `layer` (layer 0 of a tiny model, converted to `kind`) for one phase of the written-out graph."""
+    import torch.nn.functional as F
+
+    from roboticattack_amd import quant
+
+    def bf16(name, x2, res):
+        if name == "qkv":
+            if fused:
+                return F.linear(x2, torch.cat([layer.q_proj.weight, layer.k_proj.weight, layer.v_proj.weight], 0))
+            return torch.stack([layer.q_proj(x2), layer.k_proj(x2), layer.v_proj(x2)], dim=1).view(x2.shape[0], -1)
+        if name == "gate_up":
+            return layer.gate_proj(x2), layer.up_proj(x2)
+        w = getattr(layer, name).weight
+        if name == "o_proj" or fused:
+            return torch.addmm(res, x2, w.t())
+        return res + F.linear(x2, w)  # down_proj on the stock route: two roundings
+
+    def quantised(name, x2, res):
+        lin = getattr(layer, name + ("_q8" if kind == "int8" else "_q4") if name in ("qkv", "gate_up") else name)
+        if name == "down_proj":
+            x2 = x2.contiguous()
+        if kind == "int8":
+            y = quant.q8_linear(x2, lin, res, None, layer._quant_scratch)
+        else:
+            y = quant.q4_linear(x2, lin, res, layer._quant_scratch, gemv)
+        return (y[:, :y.shape[1] // 2], y[:, y.shape[1] // 2:]) if name == "gate_up" else y
+
+    return bf16 if kind == "bf16" else quantised
+
+
+@torch.no_grad()
+def ref_layer_prefill(layer, linear, x, rope_tab, cache):
+    import torch.nn.functional as F
+
+    from roboticattack_amd import model_ops
+    from roboticattack_amd.openvla_model import _rope as rope_qk
+
+    B, T, D = x.shape
+    H = layer.heads
+    fused = layer_fused(layer, x)
+    n1, n2 = layer.input_layernorm, layer.post_attention_layernorm
+    h = (model_ops.ResidualRMSNormFn.apply(x, n1.weight, n1.eps)[1] if fused else n1(x)).reshape(-1, D)
+    qkv = linear("qkv", h, None).view(B, T, 3, H, D // H)
+    cos, sin = rope_tab[0][:T], rope_tab[1][:T]
+    if fused:
+        q, k = model_ops.RopeFn.apply(qkv[:, :, 0], cos, sin), model_ops.RopeFn.apply(qkv[:, :, 1], cos, sin)
+    else:
+        c, s = (torch.cat([t, t], -1).to(x.dtype)[None, :, None, :] for t in (cos, sin))
+        q, k = rope_qk(qkv[:, :, 0], qkv[:, :, 1], c, s)
+    v = qkv[:, :, 2]
+    if fused and model_ops.attention_enabled(q):
+        a = model_ops.attention_fwd(q, k, v, True)[0]
+    else:
+        a = F.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), is_causal=True).transpose(1, 2)
+    cache[0][:, :T] = k
+    cache[1][:, :T] = v
+    x2 = linear("o_proj", a.reshape(-1, D), x.reshape(-1, D))
+    h = (model_ops.ResidualRMSNormFn.apply(x2.view(B, T, D), n2.weight, n2.eps)[1] if fused else n2(x2.view(B, T, D))).reshape(-1, D)
+    g, u = linear("gate_up", h, None)
+    y = model_ops.SwiGLUFn.apply(g, u) if fused and (B * T * g.shape[1]) % 8 == 0 else F.silu(g) * u
+    return linear("down_proj", y, x2).view(B, T, D)
+
+
+@torch.no_grad()
+def ref_layer_decode_step(layer, linear, x, pos, rope_tab, cache):
+    import torch.nn.functional as F
+
+    from roboticattack_amd import model_ops
+
+    B, _, D = x.shape
+    H = layer.heads
+    fused = layer_fused(layer, x)
+    n1, n2 = layer.input_layernorm, layer.post_attention_layernorm
+    h = (model_ops.ResidualRMSNormFn.apply(x, n1.weight, n1.eps)[1] if fused else n1(x)).reshape(-1, D)
+    qkv = linear("qkv", h, None).view(B, 3, H, D // H)
+    a = model_ops.attention_decode(qkv[:, 0], qkv[:, 1], qkv[:, 2], cache[0], cache[1], pos, rope_tab[0], rope_tab[1])
+    x2 = linear("o_proj", a.reshape(-1, D), x.reshape(-1, D))
+    h = (model_ops.ResidualRMSNormFn.apply(x2.view(B, 1, D), n2.weight, n2.eps)[1] if fused else n2(x2.view(B, 1, D))).reshape(-1, D)
+    g, u = linear("gate_up", h, None)
+    y = model_ops.SwiGLUFn.apply(g, u) if fused and (B * g.shape[1]) % 8 == 0 else F.silu(g) * u
+    return linear("down_proj", y, x2).view(B, 1, D)
+
+
+_LAYERS = {}
+
+
+def layer_of_kind(kind, threshold, device="cpu", seed=3):
+    """Layer 0 of tiny_model(seed, bf16), converted to `kind`; built once per process and device and left unchanged."""
+    from roboticattack_amd import quant
+
+    key = (kind, threshold, str(device))
+    if key not in _LAYERS:
+        m = tiny_model(seed, BF, device)
+        if kind == "int8":
+            quant.quantize_llm(m, kind, threshold=threshold)
+        elif kind != "bf16":
+            quant.quantize_llm(m, kind)
+        _LAYERS[key] = m.layers[0]
+    return _LAYERS[key]
+
+
+def layer_inputs(B, device="cpu", seed=3):
+    """(x bf16 [B,12,64], x1 bf16 [B,1,64], pos int32 [B], rope_tab): rows of one seeded draw with LAYER_BIG_COLUMN scaled up."""
+    g = torch.Generator().manual_seed(seed)
+    scale = torch.ones(64)
+    scale[LAYER_BIG_COLUMN] = 64.0
+    x = (torch.randn((3, LAYER_T, 64), generator=g) * scale).to(BF)[:B]
+    x1 = (torch.randn((3, 1, 64), generator=g) * scale).to(BF)[:B]
+    cos, sin = rope_tables(LAYER_TMAX, 16)
+    return x.to(device), x1.to(device), torch.tensor(LAYER_POS[B], dtype=torch.int32, device=device), (cos.to(device), sin.to(device))
+
+
+def layer_outlier_columns(layer, x, threshold=6.0):
+    """How many columns of the q/k/v projection's input quant.q8_linear carries in bf16 at `threshold`."""
+    from roboticattack_amd import quant
+
+    return int(quant.q8_act_quant_torch(layer.input_layernorm(x).reshape(-1, x.shape[-1]), threshold)[2].sum())
+
+
+def layer_graph_pairs(layer, kind, x, x1, pos, rope_tab):
+    """[(what, the layer's result, the written-out statement's)] for one prefill and one decode step behind it: hidden states and caches."""
+    B, _, D = x.shape
+    H = layer.heads
+    caches = [tuple(torch.zeros((B, LAYER_TMAX, H, D // H), dtype=x.dtype, device=x.device) for _ in range(2)) for _ in range(2)]
+    fused = layer_fused(layer, x)
+    y = layer.prefill(x, rope_tab, caches[0])
+    yr = ref_layer_prefill(layer, layer_linear(layer, kind, fused, False), x, rope_tab, caches[1])
+    z = layer.decode_step(x1, pos, rope_tab, caches[0])
+    zr = ref_layer_decode_step(layer, layer_linear(layer, kind, fused, True), x1, pos, rope_tab, caches[1])
+    return [("prefill", y, yr), ("decode step", z, zr), ("k cache", caches[0][0], caches[1][0]), ("v cache", caches[0][1], caches[1][1])]

@@ -203,7 +203,7 @@ def test_quantize_llm_int8_on_the_tiny_model():
     before = quant.llm_weight_bytes(model)
     others = {n: p.detach().clone() for n, p in model.named_parameters() if not n.startswith("layers.") or "layernorm" in n}
     ref_w = {(i, n): R.dequantise_w(*R.quantise_w(getattr(l, n).weight.float().numpy())) for i, l in enumerate(model.layers) for n in quant.PROJECTIONS}
-    assert quant.quantize_llm(model, "int8", threshold=6.0) is model and model.q4 == "int8"
+    assert quant.quantize_llm(model, "int8", threshold=6.0) is model and model.quant_type == "int8"
     for i, layer in enumerate(model.layers):
         for n in quant.PROJECTIONS:
             lin = getattr(layer, n)
@@ -211,7 +211,7 @@ def test_quantize_llm_int8_on_the_tiny_model():
             assert lin.codes.dtype == torch.int8 and lin.wscale.dtype == torch.float32
             assert np.array_equal(lin.dequantize().float().numpy(), ref_w[(i, n)])  # each projection's own codes, fused or not
         assert isinstance(layer.q_proj, quant.Q8LinearRows) and layer.qkv_q8.out_features == 3 * d and layer.gate_up_q8.out_features == 2 * mlp
-        assert not layer._wt_cache and layer.q4 == "int8"
+        assert not layer._wt_cache and layer.quant_type == "int8"
         assert sum(b.numel() * b.element_size() for b in layer.buffers()) == per_layer + rows_per_layer * 4  # codes + scales, held once
     after = quant.llm_weight_bytes(model)
     assert after == cfg.llm_layers * (per_layer + rows_per_layer * 4 + 2 * d * 2) and after < before

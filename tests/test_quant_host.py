@@ -179,14 +179,14 @@ def test_quantize_llm_on_the_tiny_model(name):
     others = {n: p.detach().clone() for n, p in model.named_parameters() if not n.startswith("layers.") or "layernorm" in n}
     wq = {(i, n): quant_ref.dequantise(*quant_ref.quantise(getattr(l, n).weight.float().numpy(), quant_ref.TABLES[name]), quant_ref.TABLES[name])
           for i, l in enumerate(model.layers) for n in quant.PROJECTIONS}
-    assert quant.quantize_llm(model, name) is model and model.q4 == name
+    assert quant.quantize_llm(model, name) is model and model.quant_type == name
     for i, layer in enumerate(model.layers):
         for n in quant.PROJECTIONS:
             lin = getattr(layer, n)
             assert isinstance(lin, quant.Q4Linear) and not hasattr(lin, "weight") and not list(lin.parameters())
             assert lin.codes.dtype == torch.uint8 and lin.absmax.dtype == torch.float32
             assert np.array_equal(lin.dequantize().float().numpy(), wq[(i, n)])  # each projection's own codes, fused or not
-        assert not layer._wt_cache and layer.q4 == name
+        assert not layer._wt_cache and layer.quant_type == name
         assert sorted(n for n, _ in layer.named_parameters()) == ["input_layernorm.weight", "post_attention_layernorm.weight"]
         assert sum(b.numel() * b.element_size() for b in layer.buffers()) == per_layer // 2 + per_layer // 64 * 4  # codes + scales, held once
     # no bf16 copy is left: the Llama stack's parameters are its norms, everything else keeps its bytes and its values

@@ -634,6 +634,62 @@ int vaa_frame_resize(const uint8_t* src_u8, int B, int H, int W, int rot180, con
 int vaa_crop_resize_fwd(const uint16_t* x_bf16, const float* boxes_host, const float* boxes_dev, int B, uint16_t* out_bf16, void* stream);
 int vaa_crop_resize_bwd(const uint16_t* gout_bf16, const float* boxes_host, const float* boxes_dev, int B, uint16_t* gx_bf16, void* stream);
 
+/*
+ * K10 — scene-lighting jitter of the pasted frame inside a training step: brightness, contrast, saturation and hue of the WHOLE frame (patch
+ * and surroundings together), one factor row per image, on K1 / K9's planar pixel values, and its adjoint. It is the photometric half of
+ * OpenVLA's `image_aug` (prismatic/vla/datasets/datasets.py:126-138: random brightness 0.2, contrast and saturation 0.8-1.2, hue 0.05, behind the
+ * 0.9 random crop, which is K9). TensorFlow / dlimp do not exist on this platform: what follows is THIS PROJECT'S OWN STATEMENT of that
+ * augmentation (additive brightness, a contrast mean per channel, a YIQ hue rotation) and is not pinned against tf.image; as for K0c and K9
+ * this header is the definition.
+ *   x_bf16 / gout_bf16   dev  [B,6,224,224] bfloat16 bits (16-byte aligned). Channels 0-2 (mean6 / std6 entries 0-2) and 3-5 (entries 3-5) are
+ *            two RGB images — the two towers' normalisations of one frame — processed independently with the same factors.
+ *   factors_host, factors_dev  [B,12] float32 {delta, kappa, sigma, R[0][0..2], R[1][0..2], R[2][0..2]} on the host and (16-byte aligned) on the
+ *            device. The host copy is what is validated, the device copy is what the kernels read; no address depends on a factor, so a
+ *            device copy that differs from the validated one changes values only.
+ *   mean6, std6          host [6] float32, the normalisation K1 applied
+ *   out_bf16 / gx_bf16   dev  [B,6,224,224] bfloat16 bits (16-byte aligned). Every element is written (the caller never zeroes gx).
+ *   ws, ws_bytes         dev  scratch of at least vaa_scene_jitter_ws_bytes(B) bytes, 8-byte aligned: the per-part partial sums
+ * VAA_E_INVALID before any launch: B < 0 (or beyond the grid: B > (2^31 - 1)/28); with B > 0 a NULL pointer, a misaligned device base, a mean
+ * or std that is not finite, std_c <= 0, a factor that is not finite, kappa < 0 or sigma < 0. VAA_E_WORKSPACE before any launch: ws NULL,
+ * misaligned or too small. B == 0 returns VAA_OK and launches nothing.
+ *
+ * R is the hue rotation by h turns, built by the caller in fp64 and rounded to fp32:
+ *     R(h) = I + Tinv * (rot(2*pi*h) - I) * T,     rot(a) = [[1, 0, 0], [0, cos a, -sin a], [0, sin a, cos a]]
+ *     T = [[0.299, 0.587, 0.114], [0.596, -0.274, -0.322], [0.211, -0.523, 0.312]]   (RGB -> YIQ; Tinv its fp64 inverse)
+ * It is exactly the identity for h = 0 (rot - I is exactly 0), and every row sums to 1 (T maps gray to (1, 0, 0), which rot leaves alone).
+ *
+ * The forward arithmetic is the contract. Per image and tower, with N = 224*224, fp32, every a*b + c below ONE FMA on a rounded c:
+ *     p_c    = fma(x_c, std_c, mean_c)                                               back to pixel space
+ *     pre1_c = p_c + delta;                             y1_c = clamp(pre1_c, 0, 1)   brightness
+ *     m_c    = fp32( (sum over the pixels of y1_c) / N )                             one mean PER CHANNEL; the sum and the division in fp64
+ *     pre2_c = fma(kappa, y1_c, (1 - kappa)*m_c);       y2_c = clamp(pre2_c, 0, 1)   contrast
+ *     gray   = fma(0.114, y2_B, fma(0.587, y2_G, 0.299*y2_R))                        K0c's
+ *     pre3_c = fma(sigma, y2_c, (1 - sigma)*gray);      y3_c = clamp(pre3_c, 0, 1)   saturation
+ *     pre4_c = fma(R[c][2], y3_B, fma(R[c][1], y3_G, R[c][0]*y3_R));  y4_c = clamp(pre4_c, 0, 1)   hue
+ *     out_c  = bf16( (y4_c - mean_c) / std_c )                                       true division, round to nearest even
+ * 1 - kappa and 1 - sigma are fp32 differences. clamp is torch.clamp (x < 0 ? 0 : x > 1 ? 1 : x): a NaN in x stays a NaN, and makes m_c — so
+ * that whole plane of that image — a NaN. The sum for m_c has a fixed order: a plane is 14 parts of 448 runs of 8 consecutive elements; a run
+ * is added in ascending order, the 448 runs of a part by a butterfly over 64 runs (xor 32, 16, ..., 1) and then the 7 groups of 64 in
+ * ascending order, the 14 parts in ascending order, all in fp64. The identity factors (0, 1, 1, I) give out_c = bf16((clamp(p_c) - mean_c)/std_c).
+ *
+ * The adjoint is the exact derivative with torch.clamp's gate at each of the four clamps (the gradient passes where 0 <= pre <= 1, bounds
+ * included, never for a NaN), the gates recomputed from x and the factors (nothing of the forward is kept; the means are summed again):
+ *     G4_c = gate(pre4_c) ? gout_c * fp32(1/std_c) : 0                               1/std_c rounded from fp64, as K2 applies it
+ *     G3_d = gate(pre3_d) ? fma(R[2][d], G4_B, fma(R[1][d], G4_G, R[0][d]*G4_R)) : 0 the transposed matrix
+ *     G2_c = gate(pre2_c) ? fma(sigma, G3_c, ((1 - sigma)*w_c) * ((G3_R + G3_G) + G3_B)) : 0        w = (0.299, 0.587, 0.114)
+ *     s_c  = fp32( (sum over the pixels of G2_c) / N )                               the whole-image term of the contrast mean, per channel,
+ *                                                                                    summed in the order of m_c
+ *     G1_c = gate(pre1_c) ? fma(kappa, G2_c, (1 - kappa)*s_c) : 0
+ *     gx_c = bf16( G1_c * std_c )
+ * Launches: forward 2 (part sums of y1; apply), adjoint 3 (part sums of y1; part sums of G2; apply), each B*2*14 workgroups whatever the
+ * factors. No atomics; an image's result does not depend on the batch around it; the same arguments give the same bits.
+ */
+size_t vaa_scene_jitter_ws_bytes(int B);
+int vaa_scene_jitter_fwd(const uint16_t* x_bf16, const float* factors_host, const float* factors_dev, const float* mean6, const float* std6, int B,
+                         uint16_t* out_bf16, void* ws, size_t ws_bytes, void* stream);
+int vaa_scene_jitter_bwd(const uint16_t* gout_bf16, const uint16_t* x_bf16, const float* factors_host, const float* factors_dev, const float* mean6,
+                         const float* std6, int B, uint16_t* gx_bf16, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,7 @@ TMA_wrapper.py:89-124, UPA_wrapper.py:90-127). Added flags (all optional, defaul
 environment allows): --vla_path (local checkpoint dir, or random:openvla-7b / random:tiny / surrogate), --data (synthetic),
 --colorjitter / --colorjitter_strength (photometric draw on the patch in training steps; off by default),
 --train_crop / --train_crop_scale (the evaluation's crop inside the training steps; off by default),
+--scene_jitter / --scene_jitter_strength (brightness / contrast / saturation / hue draw of the whole pasted frame in training steps; off by default),
 --tv_weight / --nps_weight / --nps_palette (total-variation and non-printability terms of the patch; off by default).
 """
 from __future__ import annotations
@@ -37,6 +38,22 @@ def colorjitter_arg(args):
 def train_crop_args(args):
     """--train_crop / --train_crop_scale as the attackers take them: dict(train_crop=None | "center" | "random", train_crop_scale=area share)."""
     return {"train_crop": None if args.train_crop == "none" else args.train_crop, "train_crop_scale": float(args.train_crop_scale)}
+
+
+def four_floats(s: str):
+    """'0.2,0.2,0.2,0.05' -> (0.2, 0.2, 0.2, 0.05) (the --scene_jitter_strength value)."""
+    try:
+        v = tuple(float(x) for x in s.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"four comma-separated numbers expected, got {s!r}")
+    if len(v) != 4 or not all(0.0 <= x <= 1.0 for x in v[:3]) or not 0.0 <= v[3] <= 0.5:
+        raise argparse.ArgumentTypeError(f"four strengths expected (brightness, contrast, saturation in [0, 1], hue in [0, 0.5]), got {s!r}")
+    return v
+
+
+def scene_jitter_arg(args):
+    """--scene_jitter / --scene_jitter_strength as the attackers take them: dict(scene_jitter=False | the four strengths)."""
+    return {"scene_jitter": tuple(args.scene_jitter_strength) if args.scene_jitter else False}
 
 
 def patch_reg_args(args):
@@ -114,6 +131,11 @@ def add_common(parser: argparse.ArgumentParser, *, lr, maskidx, iters, warmup, i
                         help="training steps crop the pasted frames as the evaluation does (center: its centre box; random: the same side at a "
                              "random offset per image) and resize back; validation passes use the centre box")
     parser.add_argument("--train_crop_scale", type=float, default=0.9, help="the crop's share of the area, in [0.25, 1] (the evaluation: 0.9)")
+    parser.add_argument("--scene_jitter", type=str2bool, nargs="?", const=True, default=False,
+                        help="training steps end in a per-image brightness / contrast / saturation / hue draw of the whole pasted frame "
+                             "(OpenVLA's image_aug, behind --train_crop); validation passes get none")
+    parser.add_argument("--scene_jitter_strength", type=four_floats, default=(0.2, 0.2, 0.2, 0.05),
+                        help="B,C,S,H: brightness delta ~ U(-B, B), contrast / saturation factors ~ U(1-s, 1+s), hue ~ U(-H, H) turns")
     parser.add_argument("--tv_weight", type=float, default=0.0, help="weight of the patch's total variation (smoothness) in every training step")
     parser.add_argument("--nps_weight", type=float, default=0.0, help="weight of the patch's non-printability score in every training step")
     parser.add_argument("--nps_palette", type=str, default=None,

@@ -1248,6 +1248,96 @@ class CropResize(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------------
+# K10: scene-lighting jitter of the pasted frame (brightness, contrast, saturation, hue of the pixel values, and the adjoint)
+# ------------------------------------------------------------------------------------------------------
+HUE_T = ((0.299, 0.587, 0.114), (0.596, -0.274, -0.322), (0.211, -0.523, 0.312))  # RGB -> YIQ (include/vaa.h, K10)
+
+
+def scene_factors(delta, kappa, sigma, hue):
+    """Per-image draws -> K10's factor rows, float32 [B,12] = {delta, kappa, sigma, R(hue) row-major}. R(h) = I + Tinv (rot(2 pi h) - I) T in fp64,
+    rounded to fp32: exactly the identity for h = 0 (include/vaa.h)."""
+    import numpy as np
+
+    d, k, s, h = (np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in (delta, kappa, sigma, hue))
+    B = max(d.size, k.size, s.size, h.size)
+    d, k, s, h = (np.broadcast_to(v, (B,)) for v in (d, k, s, h))
+    T = np.array(HUE_T, np.float64)
+    Tinv = np.linalg.inv(T)
+    out = np.empty((B, 12), np.float32)
+    for b in range(B):
+        a = 2.0 * np.pi * h[b]
+        c, sn = np.cos(a), np.sin(a)
+        rot_m_i = np.array([[0.0, 0.0, 0.0], [0.0, c - 1.0, -sn], [0.0, sn, c - 1.0]])
+        R = np.eye(3) + Tinv @ rot_m_i @ T
+        out[b, 0], out[b, 1], out[b, 2] = d[b], k[b], s[b]
+        out[b, 3:] = R.reshape(9)
+    return out
+
+
+def _scene_factors(factors, B: int, device):
+    """factors [B,12]: a host float32 array (copied to the device here) or a (host array, device tensor) pair. The host copy is what the
+    library validates, the device copy what the kernels read (include/vaa.h)."""
+    import numpy as np
+
+    host, dev = factors if isinstance(factors, tuple) else (factors, None)
+    host = np.ascontiguousarray(np.asarray(host, dtype=np.float32))
+    if host.shape != (B, 12):
+        raise _lib.VaaError(f"factors: expected shape {(B, 12)}, got {host.shape}")
+    if dev is None:
+        dev = torch.from_numpy(host).to(device, non_blocking=True)
+    return host, _need(dev, torch.float32, "factors (device copy)", (B, 12))
+
+
+def _scene_call(fn, tensors, names, factors, mean6, std6):
+    t = tensors[0]
+    B = t.shape[0] if isinstance(t, torch.Tensor) and t.dim() == 4 else 0
+    for v, name in zip(tensors, names):
+        _need(v, torch.bfloat16, name, (B, 6, IMG, IMG))
+    host, dev = _scene_factors(factors, B, t.device)
+    mean_c = _MEAN if mean6 is None else _lib.f32x(mean6)
+    std_c = _STD if std6 is None else _lib.f32x(std6)
+    L = _lib.lib()
+    ws = _workspace(t.device, L.vaa_scene_jitter_ws_bytes(B), "scene")
+    out = torch.empty_like(t)
+    with _timed(fn, B=B):
+        rc = getattr(L, fn)(*(v.data_ptr() for v in tensors), host.ctypes.data, dev.data_ptr(), mean_c, std_c, B, out.data_ptr(), ws.data_ptr(),
+                            ws.numel(), _stream())
+    _lib.check(rc, fn)
+    return out
+
+
+def scene_jitter_fwd(pixel_values, factors, mean6=None, std6=None):
+    """K10. pixel_values bf16 [B,6,224,224] (K1 / K9's planar output) -> the same frames under each image's brightness / contrast / saturation /
+    hue factors (`scene_factors`), both towers alike (include/vaa.h states the arithmetic)."""
+    return _scene_call("vaa_scene_jitter_fwd", (pixel_values,), ("pixel_values",), factors, mean6, std6)
+
+
+def scene_jitter_bwd(gout, pixel_values, factors, mean6=None, std6=None):
+    """K10's adjoint: the gradient of scene_jitter_fwd's output -> the gradient of its input, the exact derivative with torch.clamp's gates
+    (recomputed from `pixel_values` and the factors), the whole-image term of the contrast mean included."""
+    return _scene_call("vaa_scene_jitter_bwd", (gout, pixel_values), ("gout", "pixel_values"), factors, mean6, std6)
+
+
+class SceneJitter(torch.autograd.Function):
+    """Differentiable K10 between K1 / K9 and the model: (pixel_values, factors, mean6, std6) -> pixel_values. `factors`: host float32 [B,12]."""
+
+    @staticmethod
+    def forward(ctx, pixel_values, factors, mean6=None, std6=None):
+        x = pixel_values.contiguous() if isinstance(pixel_values, torch.Tensor) else pixel_values
+        B = x.shape[0] if isinstance(x, torch.Tensor) and x.dim() == 4 else 0
+        _need(x, torch.bfloat16, "pixel_values", (B, 6, IMG, IMG))
+        ctx.factors = _scene_factors(factors, B, x.device)
+        ctx.norm = (mean6, std6)
+        ctx.save_for_backward(x)
+        return scene_jitter_fwd(x, ctx.factors, mean6, std6)
+
+    @staticmethod
+    def backward(ctx, gout):
+        (x,) = ctx.saved_tensors
+        return scene_jitter_bwd(gout.to(torch.bfloat16).contiguous(), x, ctx.factors, *ctx.norm), None, None, None
+
+
+# ------------------------------------------------------------------------------------------------------
 # camera frames -> 224x224 in front of the eval-time paste (tf.image.resize lanczos3 + round + clip + uint8)
 # ------------------------------------------------------------------------------------------------------
 _resize_taps: dict = {}

@@ -15,6 +15,9 @@ Differences a caller can observe (all documented in DESIGN.md):
     saturation draw on the patch (include/vaa.h states the arithmetic; `_draw_jitter` the draws). Off by default: zero extra RNG calls.
   * `train_crop` (an EXTENSION, off by default: no extra RNG call, no extra launch): the pasted frames go through the evaluation's crop
     (K7's geometry, `eval_pixel_values(center_crop=True)`) inside the training step — K9 on K1's pixel values, `_crop_boxes` the draws.
+  * `scene_jitter` (an EXTENSION, off by default: no extra RNG call, no extra launch): the pasted (and cropped) frames of a training step get a
+    per-image brightness / contrast / saturation / hue draw of the WHOLE frame — K10 behind K9, the photometric half of OpenVLA's `image_aug`
+    (include/vaa.h states the arithmetic; `_scene_draw` the draws).
 """
 from __future__ import annotations
 
@@ -27,6 +30,7 @@ from . import ops
 from .constants import IMG, MAX_ANGLE_DEG, MAX_SHEAR, P_IDENTITY
 
 JITTER_STRENGTH = (0.2, 0.2, 0.2)  # colorjitter=True: brightness, contrast, saturation factors ~ U(1 - s, 1 + s)
+SCENE_JITTER_STRENGTH = (0.2, 0.2, 0.2, 0.05)  # scene_jitter=True: OpenVLA's image_aug (prismatic/vla/datasets/datasets.py:126-138)
 TRAIN_CROP_MODES = (None, "center", "random")
 TRAIN_CROP_SCALE = 0.9  # the evaluation's centre crop keeps this share of the area (experiments/robot/openvla_utils.py:143)
 
@@ -75,6 +79,20 @@ def jitter_strength(colorjitter):
     return s
 
 
+def scene_strength(scene_jitter):
+    """`scene_jitter` as the callers pass it -> None (off) or the four strengths (True: OpenVLA's; a 4-tuple sets them): brightness delta ~
+    U(-s0, s0), contrast and saturation factors ~ U(1 - s, 1 + s), hue ~ U(-s3, s3) turns."""
+    if scene_jitter is None or scene_jitter is False:
+        return None
+    if scene_jitter is True:
+        return SCENE_JITTER_STRENGTH
+    s = tuple(float(v) for v in scene_jitter)
+    if len(s) != 4 or not all(0.0 <= v <= 1.0 for v in s[:3]) or not 0.0 <= s[3] <= 0.5:
+        raise ValueError("scene_jitter must be a bool or four strengths (brightness, contrast, saturation in [0, 1], hue in [0, 0.5]), "
+                         f"got {scene_jitter!r}")
+    return s
+
+
 def _six(mean, std):
     m = [float(v) for t in mean for v in (t.tolist() if hasattr(t, "tolist") else t)]
     s = [float(v) for t in std for v in (t.tolist() if hasattr(t, "tolist") else t)]
@@ -100,6 +118,8 @@ class RandomPatchTransform:
         # train_crop: None | "center" | "random" (set_train_crop; set by the attackers like colorjitter: those steps stay off the fused paths)
         self.set_train_crop(train_crop, train_crop_scale)
         self.last_crop = None    # train_crop: per-image boxes {y1, x1, y2, x2} of the most recent call, float32 [B,4]
+        self.scene_jitter = None  # None | four strengths (set_scene_jitter; set by the attackers: those steps stay off the fused paths)
+        self.last_scene = None   # scene_jitter: K10's factor rows {delta, kappa, sigma, R} of the most recent training call, float32 [B,12]
 
     def set_train_crop(self, mode, scale=TRAIN_CROP_SCALE):
         """Every paste of a training step is followed by the evaluation's crop (K9, ops.CropResize): "center" = K7's box for the area share
@@ -121,10 +141,29 @@ class RandomPatchTransform:
         self.last_crop = boxes
         return boxes
 
-    def _finish(self, out, patch, out_dtype):
-        """The tail of every paste that returns pixel values: [K9 with the call's boxes ->] the caller's dtype."""
+    def set_scene_jitter(self, strength):
+        """Every paste of a training step is followed (behind K9) by a per-image brightness / contrast / saturation / hue draw of the whole
+        frame (K10, ops.SceneJitter): True = OpenVLA's strengths (0.2, 0.2, 0.2, 0.05), four strengths set them, None / False switch it off."""
+        self.scene_jitter = scene_strength(strength)
+
+    def _scene_draw(self, batch):
+        """4 * batch calls random.uniform, image-major, after every other draw of the call: delta ~ U(-s0, s0), kappa ~ U(1 - s1, 1 + s1),
+        sigma ~ U(1 - s2, 1 + s2), h ~ U(-s3, s3)."""
+        s = self.scene_jitter
+        d = np.empty((batch, 4), np.float64)
+        for b in range(batch):
+            d[b] = (random.uniform(-s[0], s[0]), random.uniform(1.0 - s[1], 1.0 + s[1]), random.uniform(1.0 - s[2], 1.0 + s[2]),
+                    random.uniform(-s[3], s[3]))
+        self.last_scene = ops.scene_factors(d[:, 0], d[:, 1], d[:, 2], d[:, 3])
+        return self.last_scene
+
+    def _finish(self, out, patch, out_dtype, mean6=None, std6=None):
+        """The tail of every paste that returns pixel values: [K9 with the call's boxes ->] [K10 with the call's factors ->] the caller's dtype.
+        K10 runs in a differentiable call only (a training step): the validation passes inside the loops see the frame as it is."""
         if self.train_crop is not None:
             out = ops.CropResize.apply(out, self._crop_boxes(int(out.shape[0]), patch))
+        if self.scene_jitter is not None and patch.requires_grad and torch.is_grad_enabled():
+            out = ops.SceneJitter.apply(out, self._scene_draw(int(out.shape[0])), mean6, std6)
         return out if out_dtype == torch.bfloat16 else out.to(out_dtype)
 
     # ---- small tensor helpers kept for API compatibility (:16-24) ----
@@ -222,9 +261,12 @@ class RandomPatchTransform:
         draws: (xy, theta) host arrays from `draw_params` to use instead of drawing (a maskidx sweep hands every group the same draws).
         colorjitter (True: strengths 0.2 each; or three strengths): every image pastes its own brightness / contrast / saturation variant of the
         patch (`_apply_jittered`); False makes no extra RNG call.
-        With `train_crop` set the result is ops.CropResize of K1's pixel values (the planar K1 -> K9 path; no grad_sink)."""
+        With `train_crop` set the result is ops.CropResize of K1's pixel values (the planar K1 -> K9 path; no grad_sink); with `scene_jitter`
+        set a training call ends in ops.SceneJitter (K10, behind K9; no grad_sink either)."""
         if self.train_crop is not None and grad_sink is not None:
             raise ValueError("grad_sink is not available with train_crop (the pixel gradient goes through the crop adjoint first)")
+        if self.scene_jitter is not None and grad_sink is not None:
+            raise ValueError("grad_sink is not available with scene_jitter (the pixel gradient goes through the scene-jitter adjoint first)")
         mean6, std6 = _six(mean, std)
         img = self.stage_images(images)
         B = img.shape[0]
@@ -245,7 +287,7 @@ class RandomPatchTransform:
         if emb is not None:
             return ops.PatchEmbeds(ops.PatchApplyEmbed.apply(patch, img, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6, *emb, grad_sink))
         out = ops.PatchApply.apply(patch, img, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6, grad_sink)
-        return self._finish(out, patch, out_dtype)
+        return self._finish(out, patch, out_dtype, mean6, std6)
 
     def draw_params(self, batch, ph, pw, geometry):
         """The host draws of one apply_random_patch_batch call on `batch` frames (the same RNG consumption), for `draws=` / apply_sweep_batch."""
@@ -263,6 +305,8 @@ class RandomPatchTransform:
             raise ValueError("apply_sweep_batch needs a model that exposes its patch-embed weights")
         if self.train_crop is not None:
             raise ValueError("apply_sweep_batch is not available with train_crop (K2' cannot take the cropped gradient)")
+        if self.scene_jitter is not None:
+            raise ValueError("apply_sweep_batch is not available with scene_jitter (K2' cannot take the pixel gradient behind K10)")
         xy_n, th_n = draws if draws is not None else self._draw(Bp, ph, pw, geometry)
         xy, theta = self._to_dev(np.tile(xy_n, (P, 1)), np.tile(th_n, (P, 1)))
         emb = self.embed_with.patch_embed_params()
@@ -270,8 +314,8 @@ class RandomPatchTransform:
 
     def _embed_params(self, patch, out_dtype):
         """Patch-embed weights for the path that never materialises the pixel gradient — only for differentiable bf16 calls, and never with
-        train_crop: K2' evaluates only the tiles under the uncropped patch and cannot be fed the cropped gradient."""
-        if self.train_crop is not None or self.embed_with is None or not patch.requires_grad or out_dtype != torch.bfloat16 or not torch.is_grad_enabled():
+        train_crop or scene_jitter: K2' evaluates only the tiles under the uncropped patch and cannot be fed the gradient behind K9 / K10."""
+        if self.train_crop is not None or self.scene_jitter is not None or self.embed_with is None or not patch.requires_grad or out_dtype != torch.bfloat16 or not torch.is_grad_enabled():
             return None
         return self.embed_with.patch_embed_params()
 
@@ -300,7 +344,7 @@ class RandomPatchTransform:
         if emb is not None:
             return ops.PatchEmbeds(ops.PatchApplyResizedEmbed.apply(patch, img, sizes, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6, *emb))
         out = ops.PatchApplyResized.apply(patch, img, sizes, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6)
-        return self._finish(out, patch, out_dtype)
+        return self._finish(out, patch, out_dtype, mean6, std6)
 
     def _draw_jitter(self, batch, strength):
         """3 * batch calls random.uniform(1 - s_k, 1 + s_k): image-major, in order brightness, contrast, saturation."""
@@ -322,7 +366,7 @@ class RandomPatchTransform:
         if emb is not None:
             return ops.PatchEmbeds(ops.PatchApplyJitteredEmbed.apply(patch, img, factors, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6, *emb))
         out = ops.PatchApplyJittered.apply(patch, img, factors, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6)
-        return self._finish(out, patch, out_dtype)
+        return self._finish(out, patch, out_dtype, mean6, std6)
 
     def _paste(self, images, patch, mean, std, out_dtype):
         mean6, std6 = _six(mean, std)
@@ -333,7 +377,7 @@ class RandomPatchTransform:
         if emb is not None:
             return ops.PatchEmbeds(ops.PatchApplyEmbed.apply(patch, img, xy, theta, False, ops.MASK_NE_M100, mean6, std6, *emb)), xy
         out = ops.PatchApply.apply(patch, img, xy, theta, False, ops.MASK_NE_M100, mean6, std6)
-        return self._finish(out, patch, out_dtype), xy
+        return self._finish(out, patch, out_dtype, mean6, std6), xy
 
     def random_paste_patch(self, images, patch, mean, std, out_dtype=torch.bfloat16):
         """:138-158 — paste without warp, mask rule `canvas != -100`."""

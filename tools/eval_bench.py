@@ -15,7 +15,13 @@
             image (602,112 in + 602,112 out); run it with --bs 8,64. Behind it the un-fused UADA inner step (UADA's own inner_step on
             random:openvla-7b, geometry on) at the first --bs with train_crop off and "center": ms per step, median of --iters
 
-    python tools/eval_bench.py [--bs 1,8] [--iters 5] [--warmup 2] [--parts front,batch,k8,k9] [--out file.json]
+    k10     K10 (vaa_scene_jitter_fwd / _bwd, the scene-lighting jitter of the pasted frame) with OpenVLA's strengths: per-dispatch us of every
+            launch from vaa_prof_* (median of --reps after a warm-up; the forward is 2 launches, the adjoint 3) and their sums, min and max
+            reported; the same arithmetic in stock PyTorch ops on the same tensors (forward, and forward + autograd backward: event-bracketed
+            us, median); and the algorithmic bytes (forward: x read once + out written once; adjoint: gout and x read, gx written) over
+            8 TB/s; run it with --bs 8,64. Behind it the un-fused UADA inner step at the first --bs with scene_jitter off and on
+
+    python tools/eval_bench.py [--bs 1,8] [--iters 5] [--warmup 2] [--parts front,batch,k8,k9,k10] [--out file.json]
 
 Each part runs in a fresh child process under `timeout`, one after the other; the first child that fails ends the run. One JSON line per result.
 """
@@ -301,6 +307,120 @@ def child_k9(batches, reps: int, iters: int, warmup: int) -> int:
     return 0
 
 
+def stock_scene_jitter(x, F, mean6, std6):
+    """vaa_scene_jitter_fwd's arithmetic with stock PyTorch ops on x's device (fp32 from the bf16 input, bf16 out), differentiable."""
+    import torch
+
+    B = x.shape[0]
+    mean = torch.tensor(mean6, dtype=torch.float32, device=x.device).view(1, 2, 3, 1)
+    std = torch.tensor(std6, dtype=torch.float32, device=x.device).view(1, 2, 3, 1)
+    w = torch.tensor([0.299, 0.587, 0.114], dtype=torch.float32, device=x.device).view(1, 1, 3, 1)
+    delta, kappa, sigma = (F[:, k].view(B, 1, 1, 1) for k in range(3))
+    R = F[:, 3:].view(B, 3, 3)
+    y1 = torch.clamp(x.float().reshape(B, 2, 3, -1) * std + mean + delta, 0.0, 1.0)
+    y2 = torch.clamp(kappa * y1 + (1.0 - kappa) * y1.mean(dim=3, keepdim=True), 0.0, 1.0)
+    y3 = torch.clamp(sigma * y2 + (1.0 - sigma) * (y2 * w).sum(dim=2, keepdim=True), 0.0, 1.0)
+    y4 = torch.clamp(torch.einsum("bcd,btdn->btcn", R, y3), 0.0, 1.0)
+    return ((y4 - mean) / std).reshape(x.shape).to(torch.bfloat16)
+
+
+K10_FWD_BYTES_PER_IMAGE = 2 * 6 * 224 * 224 * 2
+K10_BWD_BYTES_PER_IMAGE = 3 * 6 * 224 * 224 * 2
+
+
+def child_k10(batches, reps: int, iters: int, warmup: int) -> int:
+    import numpy as np
+    import torch
+
+    from roboticattack_amd import ops, synthetic
+    from roboticattack_amd.constants import MEAN6, STD6
+    from roboticattack_amd.transform import SCENE_JITTER_STRENGTH as S
+
+    dev = torch.device("cuda:0")
+    for bs in batches:
+        gen = torch.Generator().manual_seed(bs)
+        x = (torch.randn(bs, 6, 224, 224, generator=gen) * 1.2).to(torch.bfloat16).to(dev)
+        g = (torch.randn(bs, 6, 224, 224, generator=gen) * 1e-2).to(torch.bfloat16).to(dev)
+        rs = np.random.RandomState(bs)
+        F = ops.scene_factors(rs.uniform(-S[0], S[0], bs), rs.uniform(1 - S[1], 1 + S[1], bs), rs.uniform(1 - S[2], 1 + S[2], bs), rs.uniform(-S[3], S[3], bs))
+        Fd = torch.from_numpy(F).to(dev)
+        pair = (F, Fd)  # the host copy and its device copy, staged once
+        out = ops.scene_jitter_fwd(x, pair, MEAN6, STD6)
+        ref = stock_scene_jitter(x, Fd, MEAN6, STD6)
+        diff = (out.float() - ref.float()).abs()
+        for _ in range(5):
+            ops.scene_jitter_fwd(x, pair, MEAN6, STD6)
+            ops.scene_jitter_bwd(g, x, pair, MEAN6, STD6)
+        torch.cuda.synchronize()
+        ops.prof_start(5 * reps)
+        for _ in range(reps):
+            ops.scene_jitter_fwd(x, pair, MEAN6, STD6)
+            ops.scene_jitter_bwd(g, x, pair, MEAN6, STD6)
+        torch.cuda.synchronize()
+        disp = ops.prof_collect()
+        names = [n for n, _ in disp[:5]]
+        us = np.array([u for _, u in disp]).reshape(reps, 5)
+        row = dict(part="k10", bs=bs, reps=reps, launches=names, max_abs_diff_vs_stock=float(diff.max()), share_differing_vs_stock=float((diff > 0).float().mean()))
+        for key, cols, nbytes in (("fwd", slice(0, 2), K10_FWD_BYTES_PER_IMAGE * bs), ("bwd", slice(2, 5), K10_BWD_BYTES_PER_IMAGE * bs)):
+            tot = us[:, cols].sum(axis=1)
+            row.update({f"{key}_us_median": round(float(np.median(tot)), 2), f"{key}_us_min": round(float(tot.min()), 2), f"{key}_us_max": round(float(tot.max()), 2),
+                        f"{key}_launch_us_median": [round(float(v), 2) for v in np.median(us[:, cols], axis=0)],
+                        f"{key}_bytes": nbytes, f"{key}_us_at_8tb_s": round(nbytes / HBM_PEAK * 1e6, 2),
+                        f"{key}_share_of_8tb_s": round(nbytes / (float(np.median(tot)) * 1e-6) / HBM_PEAK, 4)})
+
+        def stock_fwd():
+            with torch.no_grad():
+                stock_scene_jitter(x, Fd, MEAN6, STD6)
+
+        def stock_both():
+            xl = x.float().requires_grad_(True)
+            stock_scene_jitter(xl, Fd, MEAN6, STD6).backward(g)
+
+        def ours_fwd():
+            ops.scene_jitter_fwd(x, pair, MEAN6, STD6)
+
+        def ours_both():
+            ops.scene_jitter_fwd(x, pair, MEAN6, STD6)
+            ops.scene_jitter_bwd(g, x, pair, MEAN6, STD6)
+
+        for fn in (stock_fwd, stock_both, ours_fwd, ours_both):
+            _event_us(fn, 5)
+        for key, fn in (("stock_fwd", stock_fwd), ("k10_fwd", ours_fwd), ("stock_fwd_bwd", stock_both), ("k10_fwd_bwd", ours_both)):
+            t = _event_us(fn, reps)
+            row.update({f"{key}_event_us_median": round(_median(t), 2), f"{key}_event_us_min": round(min(t), 2), f"{key}_event_us_max": round(max(t), 2)})
+        print(json.dumps(row), flush=True)
+
+    # the un-fused UADA step with and without the scene jitter
+    from roboticattack_amd.attack.uada import OpenVLAAttacker
+    from roboticattack_amd.attack.uada_ddp import default_model_factory
+    from roboticattack_amd.attack.engine import to_dev
+    from roboticattack_amd.optim import PatchOptimizer
+
+    bs = batches[0]
+    att = OpenVLAAttacker(default_model_factory("random:openvla-7b", dev), None, "", optimizer="adamW")
+    data = synthetic.synth_batch(123, bs, "smooth")
+    pixel_values, labels, attention_mask, input_ids = to_dev(data, dev)
+    labels = att.mask_labels(labels, [0])
+    for on in (False, True, False, True):  # alternating, in one process
+        att.randomPatchTransform.set_scene_jitter(on)
+        torch.manual_seed(0)
+        patch = torch.rand(3, 50, 50).to(dev).requires_grad_(True)
+        opt = PatchOptimizer(patch, 1e-3, "adamW")
+        scal = torch.zeros((1, 10), dtype=torch.float32, device=dev)
+        ms = []
+        for i in range(warmup + iters):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            att.inner_step(patch, opt, pixel_values, input_ids, attention_mask, labels, True, scal, 0)
+            torch.cuda.synchronize()
+            if i >= warmup:
+                ms.append((time.perf_counter() - t0) * 1e3)
+        ops.async_error_check()
+        print(json.dumps(dict(part="k10_step", attack="uada", bs=bs, scene_jitter=on, step_ms_median=round(_median(ms), 3),
+                              step_ms_min=round(min(ms), 3), step_ms_max=round(max(ms), 3), iters=iters)), flush=True)
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
@@ -321,6 +441,8 @@ def main() -> int:
         return child_k8(batches, a.reps)
     if a.child == "k9":
         return child_k9(batches, a.reps, a.iters, a.warmup)
+    if a.child == "k10":
+        return child_k10(batches, a.reps, a.iters, a.warmup)
     results = []
     for part in a.parts.split(","):
         cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", part, "--iters", str(a.iters),

@@ -33,7 +33,7 @@ def main(args):
     attacker.patchattack_unconstrained(train_dataloader, val_dataloader, num_iter=args.iter, target_action=args.targetAction * np.ones(7),
                                        patch_size=args.patch_size, alpha=args.lr, accumulate_steps=args.accumulate, maskidx=args.maskidx,
                                        warmup=args.warmup, filterGripTrainTo1=args.filterGripTrainTo1, geometry=args.geometry,
-                                       innerLoop=args.innerLoop, args=args, colorjitter=cli.colorjitter_arg(args), **cli.train_crop_args(args), **cli.scene_jitter_arg(args))
+                                       innerLoop=args.innerLoop, args=args, colorjitter=cli.colorjitter_arg(args), **cli.train_crop_args(args), **cli.scene_jitter_arg(args), **cli.defocus_blur_arg(args))
     print("Attack done!")
 
 

@@ -53,7 +53,7 @@ def main(args):
         "patch_size": args.patch_size, "lr": args.lr, "bs": args.bs, "warmup": args.warmup, "num_iter": args.iter,
         "maskidx": args.maskidx, "innerLoop": args.innerLoop, "geometry": args.geometry,
         "use_wandb": args.wandb_project != "false", "MSE_weights": args.MSE_weights, "colorjitter": cli.colorjitter_arg(args), **cli.train_crop_args(args),
-        **cli.scene_jitter_arg(args),
+        **cli.scene_jitter_arg(args), **cli.defocus_blur_arg(args),
     }
     if args.tv_weight or args.nps_weight:  # extension: total-variation / non-printability terms of the patch
         instance_params.update(zip(("tv_weight", "nps_weight", "nps_palette"), cli.patch_reg_args(args)))

@@ -34,7 +34,7 @@ def main(args):
                                        patch_size=args.patch_size, lr=args.lr, accumulate_steps=args.accumulate, maskidx=args.maskidx,
                                        warmup=args.warmup, filterGripTrainTo1=args.filterGripTrainTo1, geometry=args.geometry,
                                        innerLoop=args.innerLoop, reverse_direction=args.reverse_direction, args=args,
-                                       colorjitter=cli.colorjitter_arg(args), **cli.train_crop_args(args), **cli.scene_jitter_arg(args))
+                                       colorjitter=cli.colorjitter_arg(args), **cli.train_crop_args(args), **cli.scene_jitter_arg(args), **cli.defocus_blur_arg(args))
     print("Attack done!")
 
 

@@ -690,6 +690,38 @@ int vaa_scene_jitter_fwd(const uint16_t* x_bf16, const float* factors_host, cons
 int vaa_scene_jitter_bwd(const uint16_t* gout_bf16, const uint16_t* x_bf16, const float* factors_host, const float* factors_dev, const float* mean6,
                          const float* std6, int B, uint16_t* gx_bf16, void* ws, size_t ws_bytes, void* stream);
 
+/*
+ * K11 — camera defocus blur of the pasted frame inside a training step: a separable 13-tap low-pass with edge replication, one tap row per
+ * image, on K1's planar pixel values (in front of K9 and K10: optics act before the crop), and its adjoint. The blur is linear and its taps
+ * sum to 1, so it commutes with the per-channel affine normalisation up to rounding: like K9 it acts on the normalised bf16 planes and needs
+ * no mean6 / std6. One launch per call; an image's result does not depend on the batch around it; same arguments, same bits (the adjoint is a
+ * gather per source element: no atomics, no workspace).
+ *   x_bf16 / gout_bf16   dev  [B,6,224,224] bfloat16 bits (16-byte aligned)
+ *   taps_host, taps_dev       [B,8] float32 rows {w0, w1, ..., w6, 0} on the host and (16-byte aligned) on the device. The 13-tap kernel of
+ *            image b is w_|t|, t = -6..6, the same along both axes and for all six planes. The host copy is what is validated, the device
+ *            copy is what the kernels read; no address depends on a tap, so a device copy that differs changes values only.
+ *   out_bf16 / gx_bf16   dev  [B,6,224,224] bfloat16 bits (16-byte aligned). Every element is written (the caller never zeroes gx). The
+ *            input and the output must not overlap (checked by address ranges: a workgroup reads rows that its neighbours write).
+ * VAA_E_INVALID before any launch: B < 0, or B > (2^31 - 1)/42 = 51130563 (the grid: one workgroup per image, plane and band of 32 rows); with
+ * B > 0 a NULL pointer, a misaligned device base, overlapping buffers, a tap that is not finite or is below 0, w0 <= 0, row[7] != 0, or
+ * w0 + 2*(w1 + ... + w6), summed in fp64, further than 1e-5 from 1. B == 0 returns VAA_OK and launches nothing.
+ *
+ * The forward arithmetic is the contract: fp32, every product and every add a separately rounded operation (no FMA), both sums from 0.0f with
+ * t ascending. With c(i) = min(max(i, 0), 223) (edge replication: the camera sees more scene beyond the frame, not black), per plane:
+ *     h[y,x]   = sum over t = -6..6 of  w_|t| * x[y, c(x+t)]          kept in fp32
+ *     v[y,x]   = sum over t = -6..6 of  w_|t| * h[c(y+t), x]
+ *     out[y,x] = bf16(v[y,x])                                         round to nearest even
+ * The taps (1,0,0,0,0,0,0,0) return their input bit for bit for finite inputs (a negative zero comes back as +0).
+ *
+ * The adjoint is the exact transpose of V*H, the edge accumulation included:
+ *     a[r,x]  = sum over y ascending, within it t = -6..6 ascending, of  [c(y+t) == r] * w_|t| * g[y,x]          kept in fp32
+ *     gx[r,j] = bf16( sum over x ascending, within it t ascending, of  [c(x+t) == j] * w_|t| * a[r,x] )
+ * over the terms whose bracket is 1, from 0.0f, every product and add separately rounded. An interior index gets at most 13 terms (t = r - y);
+ * index 0 collects from output i every t with i + t <= 0, index 223 every t with i + t >= 223.
+ */
+int vaa_defocus_blur_fwd(const uint16_t* x_bf16, const float* taps_host, const float* taps_dev, int B, uint16_t* out_bf16, void* stream);
+int vaa_defocus_blur_bwd(const uint16_t* gout_bf16, const float* taps_host, const float* taps_dev, int B, uint16_t* gx_bf16, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

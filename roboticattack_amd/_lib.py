@@ -45,6 +45,8 @@ EXPORTS = (
     "vaa_scene_jitter_ws_bytes",
     "vaa_scene_jitter_fwd",
     "vaa_scene_jitter_bwd",
+    "vaa_defocus_blur_fwd",
+    "vaa_defocus_blur_bwd",
     "vaa_patch_embed_grad_ws_bytes",
     "vaa_patch_embed_grad_gather",
     "vaa_patch_embed_packed_elems",
@@ -233,6 +235,10 @@ def lib() -> C.CDLL:
     L.vaa_scene_jitter_fwd.argtypes = [vp, vp, vp, C.POINTER(f32), C.POINTER(f32), i32, vp, vp, sz, vp]
     L.vaa_scene_jitter_bwd.restype = i32
     L.vaa_scene_jitter_bwd.argtypes = [vp, vp, vp, vp, C.POINTER(f32), C.POINTER(f32), i32, vp, vp, sz, vp]
+    L.vaa_defocus_blur_fwd.restype = i32
+    L.vaa_defocus_blur_fwd.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.vaa_defocus_blur_bwd.restype = i32
+    L.vaa_defocus_blur_bwd.argtypes = [vp, vp, vp, i32, vp, vp]
     L.vaa_patch_apply_fwd_tiles.restype = i32
     L.vaa_patch_apply_fwd_tiles.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, vp, vp, vp, vp]
     L.vaa_patch_embed_grad_gather_multi_tiles.restype = i32

@@ -231,12 +231,12 @@ class AttackBase:
         """K1 (tile-major) -> model -> K3 statistics (+ gradient slice) -> K2' tiles + scatter -> ONE epilogue launch (K2's final sum, K3's
         fold, the DDP message) needs a model that exposes its patch-embed weights and its hidden rows, and one patch per batch (no resize_patch,
         no colorjitter: their per-image patches go through the per-image forms of K1 / K2'), and no patch regulariser (K6 adds to a materialised
-        patch.grad, which this path never builds), and no train_crop or scene_jitter (K2' cannot take the gradient behind K9 / K10: the planar
-        K1 -> K9 -> K10 path runs)."""
+        patch.grad, which this path never builds), and no train_crop, scene_jitter or defocus_blur (K2' cannot take the gradient behind K9 / K10 /
+        K11: the planar K1 -> K11 -> K9 -> K10 path runs)."""
         t = self.randomPatchTransform
         return (os.environ.get("VAA_FUSED_EPILOGUE", "1") != "0" and self.use_rows and hasattr(self.vla, "hidden_rows")
                 and t.embed_with is not None and not t.resize_patch and not t.colorjitter and not t.train_crop and not t.scene_jitter
-                and not self.patch_reg_on)
+                and not t.defocus_blur and not self.patch_reg_on)
 
     @staticmethod
     def _fused_head(R, h, W) -> bool:
@@ -322,7 +322,7 @@ class AttackBase:
         weights) and K2 on a black-box model's pixel gradient."""
         t = self.randomPatchTransform
         ok = (os.environ.get("VAA_FUSED_EPILOGUE", "1") != "0" and not t.resize_patch and not t.colorjitter and not t.train_crop
-              and not t.scene_jitter and not optimizer.l1_clip and not self.patch_reg_on)  # (K6 adds to patch.grad, which the fused update never materialises)
+              and not t.scene_jitter and not t.defocus_blur and not optimizer.l1_clip and not self.patch_reg_on)  # (K6 adds to patch.grad, which the fused update never materialises)
         return {} if ok else None
 
     def fused_update(self, sink, patch, optimizer, scalars):

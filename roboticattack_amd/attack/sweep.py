@@ -203,6 +203,8 @@ def check(attacker, kind: SweepKind, groups):
         refuse("train_crop is not supported (the sweeps' K2' cannot take the cropped pixel gradient)")
     if attacker.randomPatchTransform.scene_jitter:
         refuse("scene_jitter is not supported (the sweeps' K2' cannot take the pixel gradient behind K10)")
+    if attacker.randomPatchTransform.defocus_blur:
+        refuse("defocus_blur is not supported (the sweeps' K2' cannot take the pixel gradient behind K11)")
     if attacker.patch_reg_on:
         refuse("tv_weight / nps_weight are not supported (the sweeps' K4 lives inside the segmented epilogue: patch.grad is never materialised)")
     if not attacker.fused_ddp_available():

@@ -61,7 +61,7 @@ class OpenVLAAttacker(AttackBase):
                  num_iter=10000, maskidx=[], innerLoop=1, geometry=True, use_wandb=True, MSE_weights=1,
                  model_factory=None, dataset_factory=None, device=None, attack_type="UADA", alpha=0.8, belta=0.2, target_action=0.0, maskidx_sweep=None,
                  target_sweep=None, upa_sweep=None, colorjitter=False, tv_weight=0.0, nps_weight=0.0, nps_palette=None, train_crop=None,
-                 train_crop_scale=0.9, scene_jitter=False):
+                 train_crop_scale=0.9, scene_jitter=False, defocus_blur=False):
         """`attack_type`, `alpha`, `belta`, `target_action` are EXTENSIONS (the reference ships DDP for UADA only):
         "UPA" = UPA.py's reverse-direction loss + L1 grad clip, "TMA" = TMA.py's target-token CE, same data-parallel loop.
         `maskidx_sweep`, `target_sweep` (attack_type="TMA" only), `upa_sweep` (attack_type="UPA" only) are EXTENSIONS, at most one per run (sweep.KINDS):
@@ -76,6 +76,9 @@ class OpenVLAAttacker(AttackBase):
         frames through the evaluation's crop (K9 on K1's pixel values: the un-fused step); validation uses the centre box. Not available with a sweep.
         `scene_jitter` is an EXTENSION (True = OpenVLA's image_aug strengths (0.2, 0.2, 0.2, 0.05), or four strengths): every training step ends in a
         per-image brightness / contrast / saturation / hue draw of the whole pasted frame (K10, behind K9: the un-fused step); validation gets none.
+        Not available with a sweep.
+        `defocus_blur` is an EXTENSION (True = a maximum sigma of 1.0 pixels, or a maximum sigma in (0, 2.0]): every training step blurs the pasted
+        frame with a per-image Gaussian of sigma ~ U(0, maximum) (K11, in front of K9 and K10: the un-fused step); validation sees the sharp frame.
         Not available with a sweep."""
         rank, world, local = vdist.env_rank_world()
         if device is None:
@@ -98,6 +101,7 @@ class OpenVLAAttacker(AttackBase):
         self.randomPatchTransform.colorjitter = colorjitter
         self.randomPatchTransform.set_train_crop(train_crop, train_crop_scale)
         self.randomPatchTransform.set_scene_jitter(scene_jitter)
+        self.randomPatchTransform.set_defocus_blur(defocus_blur)
         if tv_weight or nps_weight or nps_palette is not None:
             self.set_patch_reg(tv_weight, nps_weight, nps_palette)
         # at most one kind of sweep; the parameters are checked in KINDS' order, so a refusal of an earlier one comes first

@@ -6,6 +6,7 @@ environment allows): --vla_path (local checkpoint dir, or random:openvla-7b / ra
 --colorjitter / --colorjitter_strength (photometric draw on the patch in training steps; off by default),
 --train_crop / --train_crop_scale (the evaluation's crop inside the training steps; off by default),
 --scene_jitter / --scene_jitter_strength (brightness / contrast / saturation / hue draw of the whole pasted frame in training steps; off by default),
+--defocus_blur / --defocus_blur_sigma (per-image Gaussian blur of the whole pasted frame in training steps; off by default),
 --tv_weight / --nps_weight / --nps_palette (total-variation and non-printability terms of the patch; off by default).
 """
 from __future__ import annotations
@@ -54,6 +55,22 @@ def four_floats(s: str):
 def scene_jitter_arg(args):
     """--scene_jitter / --scene_jitter_strength as the attackers take them: dict(scene_jitter=False | the four strengths)."""
     return {"scene_jitter": tuple(args.scene_jitter_strength) if args.scene_jitter else False}
+
+
+def blur_sigma(s: str):
+    """'1.0' -> 1.0 (the --defocus_blur_sigma value: the maximum sigma in pixels, in (0, 2.0])."""
+    try:
+        v = float(s)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"a number expected, got {s!r}")
+    if not 0.0 < v <= 2.0:
+        raise argparse.ArgumentTypeError(f"a maximum sigma in (0, 2.0] pixels expected, got {s!r}")
+    return v
+
+
+def defocus_blur_arg(args):
+    """--defocus_blur / --defocus_blur_sigma as the attackers take them: dict(defocus_blur=False | the maximum sigma)."""
+    return {"defocus_blur": float(args.defocus_blur_sigma) if args.defocus_blur else False}
 
 
 def patch_reg_args(args):
@@ -136,6 +153,10 @@ def add_common(parser: argparse.ArgumentParser, *, lr, maskidx, iters, warmup, i
                              "(OpenVLA's image_aug, behind --train_crop); validation passes get none")
     parser.add_argument("--scene_jitter_strength", type=four_floats, default=(0.2, 0.2, 0.2, 0.05),
                         help="B,C,S,H: brightness delta ~ U(-B, B), contrast / saturation factors ~ U(1-s, 1+s), hue ~ U(-H, H) turns")
+    parser.add_argument("--defocus_blur", type=str2bool, nargs="?", const=True, default=False,
+                        help="training steps blur the whole pasted frame with a per-image Gaussian (camera defocus, in front of --train_crop "
+                             "and --scene_jitter); validation passes see the sharp frame")
+    parser.add_argument("--defocus_blur_sigma", type=blur_sigma, default=1.0, help="maximum sigma in pixels, in (0, 2.0]: sigma ~ U(0, this) per image")
     parser.add_argument("--tv_weight", type=float, default=0.0, help="weight of the patch's total variation (smoothness) in every training step")
     parser.add_argument("--nps_weight", type=float, default=0.0, help="weight of the patch's non-printability score in every training step")
     parser.add_argument("--nps_palette", type=str, default=None,

@@ -1338,6 +1338,88 @@ class SceneJitter(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------------
+# K11: camera defocus blur of the pasted frame (separable 13-tap Gaussian with edge replication on the pixel values, and the adjoint)
+# ------------------------------------------------------------------------------------------------------
+BLUR_MAX_SIGMA = 2.0  # six taps on each side are 3 sigma at 2.0
+BLUR_TAP_FLOOR = 2.0 ** -40  # an un-normalised tap below this is set to 0 (keeps the products out of the subnormals)
+
+
+def blur_taps(sigma):
+    """Per-image sigmas -> K11's tap rows, float32 [B,8] = {w0, ..., w6, 0}; the one place the taps are made. In fp64: e_t = exp(-t^2 / (2 sigma^2))
+    for t = 0..6, any e_t < 2^-40 set to 0, divided by e_0 + 2*sum(e_1..e_6), rounded to fp32. sigma == 0 gives exactly (1, 0, ..., 0)."""
+    import numpy as np
+
+    s = np.atleast_1d(np.asarray(sigma, dtype=np.float64))
+    if s.ndim != 1 or not np.all(np.isfinite(s)) or np.any(s < 0.0) or np.any(s > BLUR_MAX_SIGMA):
+        raise ValueError(f"blur sigma must be finite and in [0, {BLUR_MAX_SIGMA}], got {sigma!r}")
+    t = np.arange(7, dtype=np.float64)
+    e = np.zeros((s.size, 7), np.float64)
+    e[:, 0] = 1.0
+    pos = s > 0.0
+    with np.errstate(divide="ignore", invalid="ignore", under="ignore"):  # a sigma whose square underflows: every e_t but e_0 is 0
+        e[pos] = np.exp(-(t[None, :] ** 2) / (2.0 * s[pos, None] ** 2))
+    e[:, 0] = 1.0
+    e[~(e >= BLUR_TAP_FLOOR)] = 0.0
+    e /= (e[:, :1] + 2.0 * e[:, 1:].sum(axis=1, keepdims=True))
+    out = np.zeros((s.size, 8), np.float32)
+    out[:, :7] = e
+    return out
+
+
+def _blur_taps(taps, B: int, device):
+    """taps [B,8]: a host float32 array (copied to the device here) or a (host array, device tensor) pair. The host copy is what the library
+    validates, the device copy what the kernels read (include/vaa.h)."""
+    import numpy as np
+
+    host, dev = taps if isinstance(taps, tuple) else (taps, None)
+    host = np.ascontiguousarray(np.asarray(host, dtype=np.float32))
+    if host.shape != (B, 8):
+        raise _lib.VaaError(f"taps: expected shape {(B, 8)}, got {host.shape}")
+    if dev is None:
+        dev = torch.from_numpy(host).to(device, non_blocking=True)
+    return host, _need(dev, torch.float32, "taps (device copy)", (B, 8))
+
+
+def _blur_call(name, fn, t, taps):
+    B = t.shape[0] if isinstance(t, torch.Tensor) and t.dim() == 4 else 0
+    _need(t, torch.bfloat16, name, (B, 6, IMG, IMG))
+    host, dev = _blur_taps(taps, B, t.device)
+    out = torch.empty_like(t)
+    with _timed(fn, B=B):
+        rc = getattr(_lib.lib(), fn)(t.data_ptr(), host.ctypes.data, dev.data_ptr(), B, out.data_ptr(), _stream())
+    _lib.check(rc, fn)
+    return out
+
+
+def defocus_blur_fwd(x, taps):
+    """K11. x bf16 [B,6,224,224] (K1's planar output) -> every plane under image b's separable 13-tap kernel `taps[b]` (`blur_taps`), rows then
+    columns, edges replicated, the intermediate kept in fp32 (include/vaa.h states the arithmetic)."""
+    return _blur_call("x", "vaa_defocus_blur_fwd", x, taps)
+
+
+def defocus_blur_bwd(gout, taps):
+    """K11's adjoint: the gradient of defocus_blur_fwd's output -> the gradient of its input, the exact transpose (the edge rows and columns
+    collect the taps the replication folded onto them)."""
+    return _blur_call("gout", "vaa_defocus_blur_bwd", gout, taps)
+
+
+class DefocusBlur(torch.autograd.Function):
+    """Differentiable K11 between K1 (PatchApply*) and K9 / K10 / the model: (pixel_values, taps) -> pixel_values. `taps`: host float32 [B,8]."""
+
+    @staticmethod
+    def forward(ctx, pixel_values, taps):
+        x = pixel_values.contiguous() if isinstance(pixel_values, torch.Tensor) else pixel_values
+        B = x.shape[0] if isinstance(x, torch.Tensor) and x.dim() == 4 else 0
+        _need(x, torch.bfloat16, "pixel_values", (B, 6, IMG, IMG))
+        ctx.taps = _blur_taps(taps, B, x.device)
+        return defocus_blur_fwd(x, ctx.taps)
+
+    @staticmethod
+    def backward(ctx, gout):
+        return defocus_blur_bwd(gout.to(torch.bfloat16).contiguous(), ctx.taps), None
+
+
+# ------------------------------------------------------------------------------------------------------
 # camera frames -> 224x224 in front of the eval-time paste (tf.image.resize lanczos3 + round + clip + uint8)
 # ------------------------------------------------------------------------------------------------------
 _resize_taps: dict = {}

@@ -18,6 +18,9 @@ Differences a caller can observe (all documented in DESIGN.md):
   * `scene_jitter` (an EXTENSION, off by default: no extra RNG call, no extra launch): the pasted (and cropped) frames of a training step get a
     per-image brightness / contrast / saturation / hue draw of the WHOLE frame — K10 behind K9, the photometric half of OpenVLA's `image_aug`
     (include/vaa.h states the arithmetic; `_scene_draw` the draws).
+  * `defocus_blur` (an EXTENSION, off by default: no extra RNG call, no extra launch): the pasted frames of a training step are blurred by a
+    per-image Gaussian of random width — K11 in front of K9 and K10, because optics act before the crop (include/vaa.h states the arithmetic;
+    `_blur_draw` the draws).
 """
 from __future__ import annotations
 
@@ -31,6 +34,7 @@ from .constants import IMG, MAX_ANGLE_DEG, MAX_SHEAR, P_IDENTITY
 
 JITTER_STRENGTH = (0.2, 0.2, 0.2)  # colorjitter=True: brightness, contrast, saturation factors ~ U(1 - s, 1 + s)
 SCENE_JITTER_STRENGTH = (0.2, 0.2, 0.2, 0.05)  # scene_jitter=True: OpenVLA's image_aug (prismatic/vla/datasets/datasets.py:126-138)
+DEFOCUS_BLUR_SIGMA = 1.0  # defocus_blur=True: sigma ~ U(0, 1.0) pixels per image
 TRAIN_CROP_MODES = (None, "center", "random")
 TRAIN_CROP_SCALE = 0.9  # the evaluation's centre crop keeps this share of the area (experiments/robot/openvla_utils.py:143)
 
@@ -93,6 +97,21 @@ def scene_strength(scene_jitter):
     return s
 
 
+def blur_arg(defocus_blur):
+    """`defocus_blur` as the callers pass it -> None (off) or the maximum sigma in pixels (True: DEFOCUS_BLUR_SIGMA; a float in (0, 2.0] sets it)."""
+    if defocus_blur is None or defocus_blur is False:
+        return None
+    if defocus_blur is True:
+        return DEFOCUS_BLUR_SIGMA
+    try:
+        s = float(defocus_blur)
+    except (TypeError, ValueError):
+        s = float("nan")
+    if not 0.0 < s <= ops.BLUR_MAX_SIGMA:  # NaN fails both
+        raise ValueError(f"defocus_blur must be a bool or a maximum sigma in (0, {ops.BLUR_MAX_SIGMA}] pixels, got {defocus_blur!r}")
+    return s
+
+
 def _six(mean, std):
     m = [float(v) for t in mean for v in (t.tolist() if hasattr(t, "tolist") else t)]
     s = [float(v) for t in std for v in (t.tolist() if hasattr(t, "tolist") else t)]
@@ -120,6 +139,8 @@ class RandomPatchTransform:
         self.last_crop = None    # train_crop: per-image boxes {y1, x1, y2, x2} of the most recent call, float32 [B,4]
         self.scene_jitter = None  # None | four strengths (set_scene_jitter; set by the attackers: those steps stay off the fused paths)
         self.last_scene = None   # scene_jitter: K10's factor rows {delta, kappa, sigma, R} of the most recent training call, float32 [B,12]
+        self.defocus_blur = None  # None | maximum sigma (set_defocus_blur; set by the attackers: those steps stay off the fused paths)
+        self.last_blur = None    # defocus_blur: the per-image sigmas of the most recent training call, float32 [B]
 
     def set_train_crop(self, mode, scale=TRAIN_CROP_SCALE):
         """Every paste of a training step is followed by the evaluation's crop (K9, ops.CropResize): "center" = K7's box for the area share
@@ -157,9 +178,23 @@ class RandomPatchTransform:
         self.last_scene = ops.scene_factors(d[:, 0], d[:, 1], d[:, 2], d[:, 3])
         return self.last_scene
 
+    def set_defocus_blur(self, max_sigma):
+        """Every paste of a training step is followed at once (in front of K9 and K10) by a Gaussian blur of the whole frame with a per-image
+        sigma ~ U(0, max_sigma) pixels (K11, ops.DefocusBlur): True = 1.0, a float in (0, 2.0] sets it, None / False switch it off."""
+        self.defocus_blur = blur_arg(max_sigma)
+
+    def _blur_draw(self, batch):
+        """batch calls random.uniform(0, max_sigma), image-major, after the paste's own draws and before the crop's and the scene's."""
+        self.last_blur = np.array([random.uniform(0.0, self.defocus_blur) for _ in range(batch)], np.float32)
+        return ops.blur_taps(self.last_blur)  # from the fp32 sigmas: ops.blur_taps(last_blur) reproduces the call's taps
+
     def _finish(self, out, patch, out_dtype, mean6=None, std6=None):
-        """The tail of every paste that returns pixel values: [K9 with the call's boxes ->] [K10 with the call's factors ->] the caller's dtype.
-        K10 runs in a differentiable call only (a training step): the validation passes inside the loops see the frame as it is."""
+        """The tail of every paste that returns pixel values: [K11 with the call's taps ->] [K9 with the call's boxes ->] [K10 with the call's
+        factors ->] the caller's dtype. K11 and K10 run in a differentiable call only (a training step): the validation passes inside the loops
+        see the frame sharp and as it is lit. Draw order behind the paste's own draws: the blur's sigmas (one per image), then the crop's offsets
+        (two per image), then the scene's factors (four per image), each image-major."""
+        if self.defocus_blur is not None and patch.requires_grad and torch.is_grad_enabled():
+            out = ops.DefocusBlur.apply(out, self._blur_draw(int(out.shape[0])))
         if self.train_crop is not None:
             out = ops.CropResize.apply(out, self._crop_boxes(int(out.shape[0]), patch))
         if self.scene_jitter is not None and patch.requires_grad and torch.is_grad_enabled():
@@ -262,11 +297,14 @@ class RandomPatchTransform:
         colorjitter (True: strengths 0.2 each; or three strengths): every image pastes its own brightness / contrast / saturation variant of the
         patch (`_apply_jittered`); False makes no extra RNG call.
         With `train_crop` set the result is ops.CropResize of K1's pixel values (the planar K1 -> K9 path; no grad_sink); with `scene_jitter`
-        set a training call ends in ops.SceneJitter (K10, behind K9; no grad_sink either)."""
+        set a training call ends in ops.SceneJitter (K10, behind K9; no grad_sink either); with `defocus_blur` set a training call puts
+        ops.DefocusBlur (K11) in front of both (no grad_sink either)."""
         if self.train_crop is not None and grad_sink is not None:
             raise ValueError("grad_sink is not available with train_crop (the pixel gradient goes through the crop adjoint first)")
         if self.scene_jitter is not None and grad_sink is not None:
             raise ValueError("grad_sink is not available with scene_jitter (the pixel gradient goes through the scene-jitter adjoint first)")
+        if self.defocus_blur is not None and grad_sink is not None:
+            raise ValueError("grad_sink is not available with defocus_blur (the pixel gradient goes through the blur adjoint first)")
         mean6, std6 = _six(mean, std)
         img = self.stage_images(images)
         B = img.shape[0]
@@ -307,6 +345,8 @@ class RandomPatchTransform:
             raise ValueError("apply_sweep_batch is not available with train_crop (K2' cannot take the cropped gradient)")
         if self.scene_jitter is not None:
             raise ValueError("apply_sweep_batch is not available with scene_jitter (K2' cannot take the pixel gradient behind K10)")
+        if self.defocus_blur is not None:
+            raise ValueError("apply_sweep_batch is not available with defocus_blur (K2' cannot take the pixel gradient behind K11)")
         xy_n, th_n = draws if draws is not None else self._draw(Bp, ph, pw, geometry)
         xy, theta = self._to_dev(np.tile(xy_n, (P, 1)), np.tile(th_n, (P, 1)))
         emb = self.embed_with.patch_embed_params()
@@ -314,8 +354,9 @@ class RandomPatchTransform:
 
     def _embed_params(self, patch, out_dtype):
         """Patch-embed weights for the path that never materialises the pixel gradient — only for differentiable bf16 calls, and never with
-        train_crop or scene_jitter: K2' evaluates only the tiles under the uncropped patch and cannot be fed the gradient behind K9 / K10."""
-        if self.train_crop is not None or self.scene_jitter is not None or self.embed_with is None or not patch.requires_grad or out_dtype != torch.bfloat16 or not torch.is_grad_enabled():
+        train_crop, scene_jitter or defocus_blur: K2' evaluates only the tiles under the uncropped patch and cannot be fed the gradient behind
+        K9 / K10 / K11."""
+        if self.train_crop is not None or self.scene_jitter is not None or self.defocus_blur is not None or self.embed_with is None or not patch.requires_grad or out_dtype != torch.bfloat16 or not torch.is_grad_enabled():
             return None
         return self.embed_with.patch_embed_params()
 

@@ -21,7 +21,13 @@
             us, median); and the algorithmic bytes (forward: x read once + out written once; adjoint: gout and x read, gx written) over
             8 TB/s; run it with --bs 8,64. Behind it the un-fused UADA inner step at the first --bs with scene_jitter off and on
 
-    python tools/eval_bench.py [--bs 1,8] [--iters 5] [--warmup 2] [--parts front,batch,k8,k9,k10] [--out file.json]
+    k11     K11 (vaa_defocus_blur_fwd / _bwd, the camera defocus blur of the pasted frame) with one sigma ~ U(0, 2) per image: per-dispatch us of
+            the forward and the adjoint from vaa_prof_* (median of --reps after a warm-up, min and max reported); the same arithmetic in stock
+            PyTorch ops on the same tensors (replicate F.pad and two depthwise fp32 convolutions; forward, and forward + autograd backward:
+            event-bracketed us, median, next to K11 bracketed the same way); and the share of 8 TB/s on the 2 x B x 6 x 224 x 224 x 2 bytes
+            each launch must move; run it with --bs 8,64
+
+    python tools/eval_bench.py [--bs 1,8] [--iters 5] [--warmup 2] [--parts front,batch,k8,k9,k10,k11] [--out file.json]
 
 Each part runs in a fresh child process under `timeout`, one after the other; the first child that fails ends the run. One JSON line per result.
 """
@@ -421,6 +427,86 @@ def child_k10(batches, reps: int, iters: int, warmup: int) -> int:
     return 0
 
 
+def stock_defocus_blur(x, taps_dev):
+    """vaa_defocus_blur_fwd's arithmetic with stock PyTorch ops on x's device (fp32 from the bf16 input, bf16 out), differentiable: replicate
+    padding, then one depthwise convolution along the rows and one along the columns, every plane of every image its own group."""
+    import torch
+    import torch.nn.functional as F
+
+    B = x.shape[0]
+    k = torch.cat([taps_dev[:, 1:7].flip(1), taps_dev[:, :7]], dim=1)  # [B,13]: w6..w1, w0, w1..w6
+    k = k[:, None, :].expand(B, 6, 13).reshape(B * 6, 1, 13)
+    p = F.pad(x.float().reshape(1, B * 6, 224, 224), (6, 6, 6, 6), mode="replicate")
+    h = F.conv2d(p, k.view(B * 6, 1, 1, 13), groups=B * 6)
+    v = F.conv2d(h, k.view(B * 6, 1, 13, 1), groups=B * 6)
+    return v.reshape(x.shape).to(torch.bfloat16)
+
+
+K11_BYTES_PER_IMAGE = 2 * 6 * 224 * 224 * 2
+
+
+def child_k11(batches, reps: int) -> int:
+    import numpy as np
+    import torch
+
+    from roboticattack_amd import ops
+
+    dev = torch.device("cuda:0")
+    for bs in batches:
+        gen = torch.Generator().manual_seed(bs)
+        x = (torch.randn(bs, 6, 224, 224, generator=gen) * 1.2).to(torch.bfloat16).to(dev)
+        g = (torch.randn(bs, 6, 224, 224, generator=gen) * 1e-2).to(torch.bfloat16).to(dev)
+        taps = ops.blur_taps(np.random.RandomState(bs).uniform(0.0, 2.0, bs))
+        td = torch.from_numpy(taps).to(dev)
+        pair = (taps, td)  # the host copy and its device copy, staged once
+        out = ops.defocus_blur_fwd(x, pair)
+        diff = (out.float() - stock_defocus_blur(x, td).float()).abs()
+        for _ in range(5):
+            ops.defocus_blur_fwd(x, pair)
+            ops.defocus_blur_bwd(g, pair)
+        torch.cuda.synchronize()
+        ops.prof_start(2 * reps)
+        for _ in range(reps):
+            ops.defocus_blur_fwd(x, pair)
+            ops.defocus_blur_bwd(g, pair)
+        torch.cuda.synchronize()
+        disp = ops.prof_collect()
+        us = np.array([u for _, u in disp]).reshape(reps, 2)
+        nbytes = K11_BYTES_PER_IMAGE * bs
+        row = dict(part="k11", bs=bs, reps=reps, launches=[n for n, _ in disp[:2]], max_abs_diff_vs_stock=float(diff.max()),
+                   share_differing_vs_stock=float((diff > 0).float().mean()), bytes=nbytes, us_at_8tb_s=round(nbytes / HBM_PEAK * 1e6, 2))
+        for key, col in (("fwd", 0), ("bwd", 1)):
+            t = us[:, col]
+            row.update({f"{key}_us_median": round(float(np.median(t)), 2), f"{key}_us_min": round(float(t.min()), 2), f"{key}_us_max": round(float(t.max()), 2),
+                        f"{key}_share_of_8tb_s": round(nbytes / (float(np.median(t)) * 1e-6) / HBM_PEAK, 4)})
+
+        def stock_fwd():
+            with torch.no_grad():
+                stock_defocus_blur(x, td)
+
+        def stock_both():
+            xl = x.float().requires_grad_(True)
+            stock_defocus_blur(xl, td).backward(g)
+
+        def ours_fwd():
+            ops.defocus_blur_fwd(x, pair)
+
+        def ours_both():
+            ops.defocus_blur_fwd(x, pair)
+            ops.defocus_blur_bwd(g, pair)
+
+        for fn in (stock_fwd, stock_both, ours_fwd, ours_both):
+            _event_us(fn, 5)
+        for key, fn in (("stock_fwd", stock_fwd), ("k11_fwd", ours_fwd), ("stock_fwd_bwd", stock_both), ("k11_fwd_bwd", ours_both)):
+            t = _event_us(fn, reps)
+            row.update({f"{key}_event_us_median": round(_median(t), 2), f"{key}_event_us_min": round(min(t), 2), f"{key}_event_us_max": round(max(t), 2)})
+        row["fwd_ratio_stock_over_k11"] = round(row["stock_fwd_event_us_median"] / row["k11_fwd_event_us_median"], 2)
+        row["fwd_bwd_ratio_stock_over_k11"] = round(row["stock_fwd_bwd_event_us_median"] / row["k11_fwd_bwd_event_us_median"], 2)
+        ops.async_error_check()
+        print(json.dumps(row), flush=True)
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
@@ -443,6 +529,8 @@ def main() -> int:
         return child_k9(batches, a.reps, a.iters, a.warmup)
     if a.child == "k10":
         return child_k10(batches, a.reps, a.iters, a.warmup)
+    if a.child == "k11":
+        return child_k11(batches, a.reps)
     results = []
     for part in a.parts.split(","):
         cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", part, "--iters", str(a.iters),

@@ -58,11 +58,12 @@ def main(argv=None):
         if input_ids is None:
             _, input_ids, attention_mask = synthetic.synth_eval_batch(args.seed, args.frames)
         source = dict(frames_file=args.frames_file, source_size=[int(frames.shape[1]), int(frames.shape[2])], frame_resize=args.frame_resize,
-                      rotate180=bool(args.rotate180))
+                      rotate180=bool(args.rotate180), frame_jpeg=int(args.frame_jpeg_quality) if args.frame_jpeg else None)
     target = (args.target[0], args.target[1]) if args.target else None
+    jpeg = dict(jpeg_quality=int(args.frame_jpeg_quality), jpeg_compare=bool(args.frame_jpeg_compare)) if args.frame_jpeg else {}
     report = evaluate_patch(vla, RandomPatchTransform(device), frames, input_ids, attention_mask, patch.float(), placements,
                             center_crop=args.center_crop, crop_scale=args.crop_scale, mean=[MEAN6[:3], MEAN6[3:]], std=[STD6[:3], STD6[3:]],
-                            target=target, bs=args.bs, quant_model=vla_q4, resize=args.frame_resize, rot180=bool(args.rotate180))
+                            target=target, bs=args.bs, quant_model=vla_q4, resize=args.frame_resize, rot180=bool(args.rotate180), **jpeg)
     torch.cuda.synchronize()
     ops.async_error_check()
     for (geo, angle, shx, shy, x, y), r in zip(report["placements"], report["per_placement"]):
@@ -77,6 +78,10 @@ def main(argv=None):
         name = f"8-bit (int8, threshold {args.llm_int8_threshold:g})" if q["quant_type"] == "int8" else f"4-bit ({q['quant_type']})"
         print(f"{name} model: any_flip={q['overall']['any_flip_rate']:.3f} mean_nad={float(q['overall']['nad'].mean()):.4f}; "
               f"clean actions equal to the bf16 model's on {ca['frames']:.3f} of the frames, {ca['tokens']:.3f} of the tokens")
+    if "jpeg_agreement" in report:
+        ja = report["jpeg_agreement"]
+        print(f"JPEG step (quality {args.frame_jpeg_quality}): clean actions equal to those without it on {ja['frames']:.3f} of the frames, "
+              f"{ja['tokens']:.3f} of the tokens")
     out = to_jsonable(dict(report, patch=args.patch, vla_path=path, frames=args.frames, center_crop=bool(args.center_crop),
                            crop_scale=args.crop_scale, **source))
     if args.out:

@@ -722,6 +722,74 @@ int vaa_scene_jitter_bwd(const uint16_t* gout_bf16, const uint16_t* x_bf16, cons
 int vaa_defocus_blur_fwd(const uint16_t* x_bf16, const float* taps_host, const float* taps_dev, int B, uint16_t* out_bf16, void* stream);
 int vaa_defocus_blur_bwd(const uint16_t* gout_bf16, const float* taps_host, const float* taps_dev, int B, uint16_t* gx_bf16, void* stream);
 
+/*
+ * K12 — the JPEG round trip of a simulator's camera frames in front of K8: what the pixels of a frame are after a baseline JPEG encoder
+ * and decoder of the libjpeg family, without the file. The reference's resize_image (experiments/robot/libero/libero_utils.py:42-43)
+ * encodes every frame with tf.io.encode_jpeg and decodes it again before the lanczos3 resize ("as done in RLDS dataset builder"). Huffman
+ * coding, markers and the bit stream are lossless, so only the lossy chain is computed: colour conversion, 4:2:0 subsampling, 8x8 forward
+ * DCT, quantise, dequantise, inverse DCT, chroma upsampling, colour conversion back. No coefficient is ever written to memory.
+ * TensorFlow does not exist on this platform. tf.image.encode_jpeg's defaults are stated FROM MEMORY AND ARE UNVERIFIED: quality 95, chroma
+ * subsampling on (4:2:0), baseline, and decode_image with the default ("slow") integer IDCT and fancy upscaling. They are the settings
+ * that Pillow's save(format="JPEG", quality=95, subsampling=2) followed by a load selects; tests/golden/jpeg_pillow.npz records what
+ * Pillow 12.2 / libjpeg-turbo 3.1 makes of a few frames, and the arithmetic below reproduces every recorded byte.
+ *   src_u8   dev  [B,H,W,3] uint8 HWC (4-byte aligned), 8 <= H, W <= 2048: K8's layout and range
+ *   rot180   0 or 1: the frame that is encoded is src[b, H-1-y, W-1-x] (LIBERO rotates first, then encodes; K8 then runs with rot180 = 0)
+ *   qtab_host, qtab_dev   [2][64] uint16 quantisation tables {luminance, chrominance} in natural (row-major) order, entries 1..255, on the
+ *            host and (2-byte aligned) on the device. The host copy is what is validated, the device copy is what the kernels read; no
+ *            address depends on an entry (a zero in a differing device copy divides by 1).
+ *   dst_u8   dev  [B,H,W,3] uint8 HWC (4-byte aligned). Every byte is written. src and dst must not overlap (checked by address ranges).
+ *   ws, ws_bytes  dev  scratch of at least vaa_jpeg_roundtrip_ws_bytes(B, H, W) = B*2*(8*MY)*(8*MX) bytes, 8-byte aligned: the decoded
+ *            half-resolution chroma planes [B][2][8*MY][8*MX] uint8, MX = ceil(W/16), MY = ceil(H/16). vaa_jpeg_roundtrip_ws_bytes returns 0
+ *            for sizes the call refuses.
+ * VAA_E_INVALID before any launch: B < 0 or beyond the grid (B*MY*ceil(MX/8) > 2^31 - 1); with B > 0 H or W outside [8, 2048], rot180 not
+ * 0 / 1, a NULL or misaligned pointer, overlapping src and dst, a table entry outside 1..255. VAA_E_WORKSPACE before any launch: ws NULL,
+ * misaligned or too small. B == 0 returns VAA_OK and launches nothing. Two launches (chroma; luminance + finish), no atomics; an image's
+ * result does not depend on the batch around it; the same arguments give the same bits.
+ *
+ * The arithmetic is the contract: int32 throughout, >> is the arithmetic shift (floor), FIXn(x) = (int)(x * 2^n + 0.5),
+ * DESCALE(v, n) = (v + 2^(n-1)) >> n. It follows libjpeg's sample converters and its default ("slow integer") DCT pair, restated here
+ * because libjpeg's sources are not part of this project: THIS HEADER IS THE DEFINITION.
+ *
+ * 1. Colour (encoder), per pixel of the (rotated) frame, F = FIX16:
+ *     Y  = ( F(.29900)*R + F(.58700)*G + F(.11400)*B + 32768) >> 16
+ *     Cb = (-F(.16874)*R - F(.33126)*G + F(.50000)*B + (128 << 16) + 32767) >> 16
+ *     Cr = ( F(.50000)*R - F(.41869)*G - F(.08131)*B + (128 << 16) + 32767) >> 16
+ * 2. Padding and 4:2:0 subsampling. The frame is covered by MY x MX MCUs of 16x16 pixels. Y(y, x) beyond the frame is Y(min(y, H-1),
+ *    min(x, W-1)). The half-resolution planes have ch = ceil(H/2) real rows; sample (i, j), i < 8*MY, j < 8*MX, with i' = min(i, ch - 1)
+ *    (the encoder replicates the last SUBSAMPLED row, so with an even H the padding rows average the last two frame rows), is
+ *     C(i, j) = (c(y0, x0) + c(y0, x1) + c(y1, x0) + c(y1, x1) + bias) >> 2,   bias = 1 for even j, 2 for odd j,
+ *     y0 = min(2i', H-1), y1 = min(2i'+1, H-1), x0 = min(2j, W-1), x1 = min(2j+1, W-1)
+ * 3. Forward DCT of every 8x8 block on d = sample - 128, rows first, then columns; the result is 8 x the DCT. With the constants
+ *    c298 = 2446, c390 = 3196, c541 = 4433, c765 = 6270, c899 = 7373, c1175 = 9633, c1501 = 12299, c1847 = 15137, c1961 = 16069, c2053 = 16819,
+ *    c2562 = 20995, c3072 = 25172 (FIX13 of 0.298631336 ... 3.072711026), one eight-point pass on d0..d7 is
+ *     t0 = d0+d7, t7 = d0-d7, t1 = d1+d6, t6 = d1-d6, t2 = d2+d5, t5 = d2-d5, t3 = d3+d4, t4 = d3-d4
+ *     t10 = t0+t3, t13 = t0-t3, t11 = t1+t2, t12 = t1-t2
+ *     o0 = (t10+t11) << 2, o4 = (t10-t11) << 2 in the row pass;   o0 = DESCALE(t10+t11, 2), o4 = DESCALE(t10-t11, 2) in the column pass
+ *     z1 = (t12+t13)*c541;   o2 = DESCALE(z1 + t13*c765, n);   o6 = DESCALE(z1 - t12*c1847, n)       n = 11 (rows), 15 (columns)
+ *     z1 = t4+t7, z2 = t5+t6, z3 = t4+t6, z4 = t5+t7, z5 = (z3+z4)*c1175
+ *     t4 *= c298, t5 *= c2053, t6 *= c3072, t7 *= c1501;   z1 *= -c899, z2 *= -c2562, z3 = z3*(-c1961) + z5, z4 = z4*(-c390) + z5
+ *     o7 = DESCALE(t4+z1+z3, n), o5 = DESCALE(t5+z2+z4, n), o3 = DESCALE(t6+z2+z3, n), o1 = DESCALE(t7+z1+z4, n)
+ * 4. Quantise by division, rounding half away from zero, and dequantise, with q the table entry (luminance for Y, chrominance for Cb, Cr):
+ *     k = sign(o) * ((|o| + 4*q) / (8*q))  (truncating division);    v = k*q
+ * 5. Inverse DCT, columns first (n = 11), then rows (n = 18), one eight-point pass on v0..v7:
+ *     z1 = (v2+v6)*c541;   t2 = z1 - v6*c1847;   t3 = z1 + v2*c765;   t0 = (v0+v4) << 13;   t1 = (v0-v4) << 13
+ *     t10 = t0+t3, t13 = t0-t3, t11 = t1+t2, t12 = t1-t2
+ *     u0 = v7, u1 = v5, u2 = v3, u3 = v1;   z1 = u0+u3, z2 = u1+u2, z3 = u0+u2, z4 = u1+u3, z5 = (z3+z4)*c1175
+ *     u0 *= c298, u1 *= c2053, u2 *= c3072, u3 *= c1501;   z1 *= -c899, z2 *= -c2562, z3 = z3*(-c1961) + z5, z4 = z4*(-c390) + z5
+ *     u0 += z1+z3, u1 += z2+z4, u2 += z2+z3, u3 += z1+z4
+ *     o0, o7 = DESCALE(t10 +- u3, n);  o1, o6 = DESCALE(t11 +- u2, n);  o2, o5 = DESCALE(t12 +- u1, n);  o3, o4 = DESCALE(t13 +- u0, n)
+ *    and the decoded sample is min(max(o + 128, 0), 255).
+ * 6. "Fancy" chroma upsampling of the decoded half-resolution plane D, real size ch x cw = ceil(H/2) x ceil(W/2) (what lies beyond is never
+ *    read: the edges are those of the frame, not of the MCUs), the 3:1 triangle filter vertically, then horizontally. For pixel (y, x) with
+ *    i = y >> 1, j = x >> 1:   i2 = max(i-1, 0) for even y, min(i+1, ch-1) for odd y;   s(j) = 3*D(i, j) + D(i2, j)
+ *     even x:  c = (3*s(j) + s(max(j-1, 0)) + 8) >> 4;        odd x:  c = (3*s(j) + s(min(j+1, cw-1)) + 7) >> 4
+ * 7. Colour (decoder), F = FIX16, cb = Cb - 128, cr = Cr - 128, each result clamped to 0..255:
+ *     R = Y + ((F(1.40200)*cr + 32768) >> 16);   G = Y + ((-F(.34414)*cb + 32768 - F(.71414)*cr) >> 16);   B = Y + ((F(1.77200)*cb + 32768) >> 16)
+ */
+size_t vaa_jpeg_roundtrip_ws_bytes(int B, int H, int W);
+int vaa_jpeg_roundtrip(const uint8_t* src_u8, int B, int H, int W, int rot180, const uint16_t* qtab_host, const uint16_t* qtab_dev,
+                       uint8_t* dst_u8, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,6 +47,8 @@ EXPORTS = (
     "vaa_scene_jitter_bwd",
     "vaa_defocus_blur_fwd",
     "vaa_defocus_blur_bwd",
+    "vaa_jpeg_roundtrip_ws_bytes",
+    "vaa_jpeg_roundtrip",
     "vaa_patch_embed_grad_ws_bytes",
     "vaa_patch_embed_grad_gather",
     "vaa_patch_embed_packed_elems",
@@ -239,6 +241,10 @@ def lib() -> C.CDLL:
     L.vaa_defocus_blur_fwd.argtypes = [vp, vp, vp, i32, vp, vp]
     L.vaa_defocus_blur_bwd.restype = i32
     L.vaa_defocus_blur_bwd.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.vaa_jpeg_roundtrip_ws_bytes.restype = sz
+    L.vaa_jpeg_roundtrip_ws_bytes.argtypes = [i32, i32, i32]
+    L.vaa_jpeg_roundtrip.restype = i32
+    L.vaa_jpeg_roundtrip.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
     L.vaa_patch_apply_fwd_tiles.restype = i32
     L.vaa_patch_apply_fwd_tiles.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, vp, vp, vp, vp]
     L.vaa_patch_embed_grad_gather_multi_tiles.restype = i32

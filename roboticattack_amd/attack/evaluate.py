@@ -71,7 +71,8 @@ def summarise(tokens_clean: torch.Tensor, tokens_patched: torch.Tensor, unnorm_s
 
 @torch.no_grad()
 def evaluate_patch(model, transform, frames_u8, input_ids, attention_mask, patch, placements, *, center_crop=True, crop_scale=0.9, mean, std,
-                   unnorm_stats=None, action_dim=7, target=None, bs=8, quant_model=None, resize=None, rot180=False) -> dict:
+                   unnorm_stats=None, action_dim=7, target=None, bs=8, quant_model=None, resize=None, rot180=False, jpeg_quality=None,
+                   jpeg_compare=False) -> dict:
     """Clean and patched greedy actions of `model` on F recorded frames with their prompts (right-padded input_ids / attention_mask [F,L]).
     placements: list of (geometry, angle, shx, shy, x, y), the per-frame arguments of simulation_patch_batch. The clean actions are decoded
     once per frame and reused for every placement; the patched rows are the P*F (placement, frame) pairs in placement-major order, run in
@@ -83,16 +84,31 @@ def evaluate_patch(model, transform, frames_u8, input_ids, attention_mask, patch
     two models' patched rates cannot be compared.
     resize="lanczos3": frames_u8 are a simulator's camera frames [F,H,W,3] of any size; each is resized to 224x224 once (K8,
     transform.eval_frames; rot180=True rotates it by 180 degrees first, as the LIBERO evaluation does), before the clean pass, and everything
-    above runs on the resized frames. Without it the frames must be 224x224 and are used as they are."""
+    above runs on the resized frames. Without it the frames must be 224x224 and are used as they are.
+    jpeg_quality (an integer 1..100, with resize="lanczos3" only: it is a step of the simulators' resize_image): every frame goes through a JPEG
+    encoder and decoder at that quality between the rotation and the resize (K12), as libero_utils.py:42-43 does at 95. jpeg_compare=True
+    (with a jpeg_quality): the clean pass runs once more on the frames resized WITHOUT the JPEG step, and the report gains "jpeg_agreement"
+    (clean_agreement of the two clean token sets of `model`): what the step is worth on these frames."""
     if bs < 1:
         raise ValueError("bs must be at least 1")
     if resize not in (None, "lanczos3"):
         raise ValueError(f"resize must be None or 'lanczos3', got {resize!r}")
     if resize is None and rot180:
         raise ValueError("rot180 is part of the frame resize: pass resize='lanczos3'")
+    if jpeg_quality is not None and resize is None:
+        raise ValueError("jpeg_quality is part of the frame resize: pass resize='lanczos3'")
+    if jpeg_quality is not None and (isinstance(jpeg_quality, bool) or not isinstance(jpeg_quality, (int, np.integer)) or not 1 <= jpeg_quality <= 100):
+        raise ValueError(f"jpeg_quality must be an integer in 1..100, got {jpeg_quality!r}")
+    if jpeg_compare and jpeg_quality is None:
+        raise ValueError("jpeg_compare compares with and without the JPEG step: pass a jpeg_quality")
     dev = transform.device
-    if resize is not None:
+    frames_nojpeg = None
+    if resize is not None and jpeg_quality is None:
         frames_u8 = transform.eval_frames(frames_u8, rot180)
+    elif resize is not None:
+        if jpeg_compare:
+            frames_nojpeg = transform.stage_images(transform.eval_frames(frames_u8, rot180))
+        frames_u8 = transform.eval_frames(frames_u8, rot180, jpeg_quality=int(jpeg_quality))
     frames = transform.stage_images(frames_u8 if isinstance(frames_u8, torch.Tensor) else torch.as_tensor(np.asarray(frames_u8)))
     ids, mask = input_ids.to(dev), attention_mask.to(dev)
     F, P = int(frames.shape[0]), len(placements)
@@ -118,6 +134,14 @@ def evaluate_patch(model, transform, frames_u8, input_ids, attention_mask, patch
         pasted = transform.simulation_patch_batch(frames[rows], patch, geo, ang, shx, shy, pos)
         patched.append(decode(transform.eval_pixel_values(pasted, mean, std, center_crop, crop_scale), rows))
     clean = torch.cat(clean).cpu()  # [F, models, A]
+    clean_nojpeg = None
+    if frames_nojpeg is not None:
+        clean_nojpeg = []
+        for i in range(0, F, bs):
+            rows = torch.arange(i, min(i + bs, F), device=dev)
+            pix = transform.eval_pixel_values(frames_nojpeg[rows], mean, std, center_crop, crop_scale)
+            clean_nojpeg.append(model.predict_action(ids[rows], mask[rows], pix, unnorm_stats=unnorm_stats, action_dim=action_dim)[0])
+        clean_nojpeg = torch.cat(clean_nojpeg).cpu()
     patched = torch.cat(patched).cpu() if patched else torch.empty((0, len(models), action_dim), dtype=torch.int64)
 
     def report(i):
@@ -128,6 +152,8 @@ def evaluate_patch(model, transform, frames_u8, input_ids, attention_mask, patch
     if quant_model is not None:
         out["quantised"] = dict(report(1), quant_type=getattr(quant_model, "quant_type", None))
         out["clean_agreement"] = clean_agreement(out["tokens_clean"], out["quantised"]["tokens_clean"])
+    if clean_nojpeg is not None:
+        out["jpeg_agreement"] = clean_agreement(out["tokens_clean"], clean_nojpeg)
     return out
 
 

@@ -290,6 +290,11 @@ def add_eval_frame_flags(parser: argparse.ArgumentParser):
                         help="resize the file's frames to 224x224 as the simulators' wrappers do (lanczos3 with antialias, round, clip)")
     parser.add_argument("--rotate180", type=str2bool, nargs="?", const=True, default=False,
                         help="rotate every frame by 180 degrees in front of the resize (the LIBERO evaluation does)")
+    parser.add_argument("--frame_jpeg", type=str2bool, nargs="?", const=True, default=False,
+                        help="JPEG-encode and decode every frame between the rotation and the resize, as LIBERO's resize_image does")
+    parser.add_argument("--frame_jpeg_quality", default=95, type=int, help="the quality of --frame_jpeg (1..100; tf.image.encode_jpeg's default: 95)")
+    parser.add_argument("--frame_jpeg_compare", type=str2bool, nargs="?", const=True, default=False,
+                        help="with --frame_jpeg: run the clean pass once more without the JPEG step and report how often the actions agree")
 
 
 def load_frames_file(path: str):
@@ -315,6 +320,12 @@ def check_eval_frames(parser: argparse.ArgumentParser, args):
     from .constants import IMG
 
     args.frames_data = None
+    if args.frame_jpeg_compare and not args.frame_jpeg:
+        parser.error("--frame_jpeg_compare compares with and without the JPEG step: pass --frame_jpeg true")
+    if args.frame_jpeg and (args.frames_file is None or args.frame_resize is None):
+        parser.error("--frame_jpeg is a step of the simulators' frame resize: it needs --frames_file and --frame_resize lanczos3")
+    if args.frame_jpeg and not 1 <= args.frame_jpeg_quality <= 100:
+        parser.error("--frame_jpeg_quality must be in 1..100")
     if args.frames_file is None:
         if args.frame_resize is not None or args.rotate180:
             parser.error("--frame_resize / --rotate180 act on the frames of --frames_file")

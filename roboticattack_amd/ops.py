@@ -1458,3 +1458,71 @@ def resize_frames(frames_u8, rot180: bool = False):
                                          sy.ctypes.data, wy.ctypes.data, int(wy.shape[1]), taps.data_ptr(), out.data_ptr(), _stream())
     _lib.check(rc, "vaa_frame_resize")
     return out
+
+
+# ------------------------------------------------------------------------------------------------------
+# K12: the JPEG round trip of camera frames in front of K8 (tf.io.encode_jpeg + decode_image in the simulators' resize_image)
+# ------------------------------------------------------------------------------------------------------
+JPEG_DEFAULT_QUALITY = 95  # tf.image.encode_jpeg's default, stated from memory (include/vaa.h)
+# Annex K of ITU-T T.81 (luminance, chrominance), natural order
+_JPEG_BASE = (
+    (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99),
+    (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99)
+    + (99,) * 32,
+)
+_jpeg_qtab_dev: dict = {}
+
+
+def jpeg_qtables(quality):
+    """libjpeg's quantisation tables of an integer quality 1..100, uint16 [2,64] {luminance, chrominance} in natural order: the Annex K tables
+    scaled by s = 5000 // q below 50, else 200 - 2q, each entry (base*s + 50) // 100 clamped to 1..255 (baseline)."""
+    import numpy as np
+
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= int(quality) <= 100:
+        raise ValueError(f"jpeg quality must be an integer in 1..100, got {quality!r}")
+    q = int(quality)
+    s = 5000 // q if q < 50 else 200 - 2 * q
+    return np.clip((np.asarray(_JPEG_BASE, dtype=np.int64) * s + 50) // 100, 1, 255).astype(np.uint16)
+
+
+def _jpeg_tables(qtables, device):
+    """qtables [2,64]: a host uint16 array or a (host array, device tensor) pair. The device copy of a host array is made once per table
+    contents and device. The host copy is what the library validates, the device copy what the kernels read (include/vaa.h)."""
+    import numpy as np
+
+    host, dev = qtables if isinstance(qtables, tuple) else (qtables, None)
+    host = np.asarray(host)
+    if host.shape != (2, 64) or host.dtype.kind not in "iu":
+        raise _lib.VaaError(f"qtables: expected an integer array of shape (2, 64), got {host.dtype} {host.shape}")
+    if host.min() < 0 or host.max() > 65535:
+        raise _lib.VaaError("qtables: entries must be in 1..255")
+    host = np.ascontiguousarray(host.astype(np.uint16))
+    if dev is None:
+        key = (device.index if device.index is not None else torch.cuda.current_device(), host.tobytes())
+        dev = _jpeg_qtab_dev.get(key)
+        if dev is None:
+            if len(_jpeg_qtab_dev) >= 64:
+                _jpeg_qtab_dev.clear()
+            dev = _jpeg_qtab_dev[key] = torch.from_numpy(host.view(np.int16).copy()).to(device)
+    return host, _need(dev, torch.int16, "qtables (device copy)", (2, 64))
+
+
+def jpeg_roundtrip(frames_u8, qtables, rot180: bool = False):
+    """K12. uint8 frames [B,H,W,3] (8 <= H, W <= 2048) -> uint8 [B,H,W,3]: the pixels after a baseline 4:2:0 JPEG encoder and decoder of the
+    libjpeg family with the quantisation tables `qtables` (`jpeg_qtables(quality)`), integer arithmetic throughout (include/vaa.h states every
+    step). rot180: the frames are read as frames[:, ::-1, ::-1] (LIBERO rotates before it encodes). Owns the workspace and the tables' device copy."""
+    if not isinstance(frames_u8, torch.Tensor) or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
+        raise _lib.VaaError("frames_u8: expected a uint8 tensor [B,H,W,3] on a ROCm device (there is no CPU fallback)")
+    _need(frames_u8, torch.uint8, "frames_u8")
+    B, H, W = (int(v) for v in frames_u8.shape[:3])
+    host, dev = _jpeg_tables(qtables, frames_u8.device)
+    L = _lib.lib()
+    out = torch.empty_like(frames_u8)
+    nbytes = int(L.vaa_jpeg_roundtrip_ws_bytes(B, H, W))
+    ws = _workspace(frames_u8.device, nbytes, "k12") if B > 0 and nbytes > 0 else None
+    with _timed("K12_jpeg_roundtrip", B=B, H=H, W=W):
+        rc = L.vaa_jpeg_roundtrip(frames_u8.data_ptr(), B, H, W, int(bool(rot180)), host.ctypes.data, dev.data_ptr(), out.data_ptr(),
+                                  ws.data_ptr() if ws is not None else None, nbytes if ws is not None else 0, _stream())
+    _lib.check(rc, "vaa_jpeg_roundtrip")
+    return out

@@ -463,14 +463,18 @@ class RandomPatchTransform:
         out = ops.eval_preprocess(img, float(crop_scale) if center_crop else 0.0, mean6, std6)
         return out if out_dtype == torch.bfloat16 else out.to(out_dtype)
 
-    def eval_frames(self, frames, rot180=False) -> torch.Tensor:
+    def eval_frames(self, frames, rot180=False, jpeg_quality=None) -> torch.Tensor:
         """A simulator's camera frames, uint8 [F,H,W,3] of any size from 8 to 2048 per side (numpy or a tensor) -> uint8 [F,224,224,3] on the
         device, as the reference's evaluations hand them on (experiments/robot/libero/libero_utils.py:44-58, bridgev2_utils.py:112): lanczos3
-        resize with antialias, round, clip; rot180=True reads the frames as frames[:, ::-1, ::-1] first (LIBERO). One launch (K8)."""
+        resize with antialias, round, clip; rot180=True reads the frames as frames[:, ::-1, ::-1] first (LIBERO). One launch (K8).
+        jpeg_quality (an integer 1..100; LIBERO's resize_image: 95): the frames go through a JPEG encoder and decoder at that quality first
+        (libero_utils.py:42-43), after the rotation and before the resize: K12 with rot180, then K8 without it."""
         t = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(frames)))
         if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[-1] != 3:
             raise ValueError("frames must be uint8 [F,H,W,3] (HWC)")
-        return ops.resize_frames(t.to(self.device).contiguous(), rot180)
+        if jpeg_quality is None:
+            return ops.resize_frames(t.to(self.device).contiguous(), rot180)
+        return ops.resize_frames(ops.jpeg_roundtrip(t.to(self.device).contiguous(), ops.jpeg_qtables(jpeg_quality), rot180), False)
 
     def im_process(self, images, mean, std, out_dtype=torch.bfloat16):
         """:190-197 — normalise the clean frames only (K1 with a 1x1 sentinel patch that is never kept)."""

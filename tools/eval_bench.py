@@ -27,7 +27,12 @@
             event-bracketed us, median, next to K11 bracketed the same way); and the share of 8 TB/s on the 2 x B x 6 x 224 x 224 x 2 bytes
             each launch must move; run it with --bs 8,64
 
-    python tools/eval_bench.py [--bs 1,8] [--iters 5] [--warmup 2] [--parts front,batch,k8,k9,k10,k11] [--out file.json]
+    k12     K12 (vaa_jpeg_roundtrip, the JPEG round trip of camera frames in front of K8) at quality 95 on 256x256 and 480x640 frames: per-dispatch
+            us of its two launches from vaa_prof_* (median of --reps after a warm-up; their sum, min and max reported), the event-bracketed us
+            of the call, the share of 8 TB/s on the 6*H*W bytes per frame it must move, and — where Pillow is installed — the wall time of
+            Pillow's save + load of the same frames on the host CPU (what a caller does without K12) and the bytes that differ from it
+
+    python tools/eval_bench.py [--bs 1,8] [--iters 5] [--warmup 2] [--parts front,batch,k8,k9,k10,k11,k12] [--out file.json]
 
 Each part runs in a fresh child process under `timeout`, one after the other; the first child that fails ends the run. One JSON line per result.
 """
@@ -507,6 +512,65 @@ def child_k11(batches, reps: int) -> int:
     return 0
 
 
+def child_k12(batches, reps: int) -> int:
+    import io
+
+    import numpy as np
+    import torch
+
+    from roboticattack_amd import ops
+
+    try:
+        from PIL import Image
+    except ImportError:
+        Image = None
+    dev = torch.device("cuda:0")
+    qt = ops.jpeg_qtables(ops.JPEG_DEFAULT_QUALITY)
+    for H, W in K8_SIZES:
+        for bs in batches:
+            rs = np.random.RandomState(1000 * H + bs)
+            ramp = np.linspace(0, 255, W)[None, None, :, None] * 0.7 + np.linspace(0, 255, H)[None, :, None, None] * 0.3
+            host = np.clip(ramp + rs.uniform(-30, 30, (bs, H, W, 3)), 0, 255).astype(np.uint8)
+            frames = torch.from_numpy(host).to(dev)
+            out = ops.jpeg_roundtrip(frames, qt)
+            for _ in range(5):
+                ops.jpeg_roundtrip(frames, qt)
+            torch.cuda.synchronize()
+            ops.async_error_check()
+            ops.prof_start(2 * reps)
+            for _ in range(reps):
+                ops.jpeg_roundtrip(frames, qt)
+            torch.cuda.synchronize()
+            disp = ops.prof_collect()
+            us = np.array([u for _, u in disp]).reshape(reps, 2)
+            tot = us.sum(axis=1)
+            ev = _event_us(lambda: ops.jpeg_roundtrip(frames, qt), reps)
+            nbytes = 6 * H * W * bs
+            row = dict(part="k12", H=H, W=W, bs=bs, quality=ops.JPEG_DEFAULT_QUALITY, reps=reps, launches=[n for n, _ in disp[:2]],
+                       launch_us_median=[round(float(v), 2) for v in np.median(us, axis=0)], us_median=round(float(np.median(tot)), 2),
+                       us_min=round(float(tot.min()), 2), us_max=round(float(tot.max()), 2), bytes=nbytes, us_at_8tb_s=round(nbytes / HBM_PEAK * 1e6, 3),
+                       share_of_8tb_s=round(nbytes / (float(np.median(tot)) * 1e-6) / HBM_PEAK, 4), event_us_median=round(_median(ev), 2))
+            if Image is not None:
+                def pillow():
+                    res = []
+                    for f in host:
+                        buf = io.BytesIO()
+                        Image.fromarray(f, "RGB").save(buf, format="JPEG", quality=ops.JPEG_DEFAULT_QUALITY, subsampling=2)
+                        res.append(np.asarray(Image.open(io.BytesIO(buf.getvalue())).convert("RGB")))
+                    return np.stack(res)
+
+                ref = pillow()
+                t = []
+                for _ in range(10):
+                    t0 = time.perf_counter()
+                    pillow()
+                    t.append((time.perf_counter() - t0) * 1e6)
+                row.update(pillow_host_us_median=round(_median(t), 1), pillow_host_us_min=round(min(t), 1), pillow_runs=10,
+                           bytes_differing_from_pillow=int((out.cpu().numpy() != ref).sum()))
+            print(json.dumps(row), flush=True)
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
@@ -531,6 +595,8 @@ def main() -> int:
         return child_k10(batches, a.reps, a.iters, a.warmup)
     if a.child == "k11":
         return child_k11(batches, a.reps)
+    if a.child == "k12":
+        return child_k12(batches, a.reps)
     results = []
     for part in a.parts.split(","):
         cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", part, "--iters", str(a.iters),

@@ -235,8 +235,7 @@ class AttackBase:
         K11: the planar K1 -> K11 -> K9 -> K10 path runs)."""
         t = self.randomPatchTransform
         return (os.environ.get("VAA_FUSED_EPILOGUE", "1") != "0" and self.use_rows and hasattr(self.vla, "hidden_rows")
-                and t.embed_with is not None and not t.resize_patch and not t.colorjitter and not t.train_crop and not t.scene_jitter
-                and not t.defocus_blur and not self.patch_reg_on)
+                and t.embed_with is not None and not t.resize_patch and not t.colorjitter and not t.frame_stages_on() and not self.patch_reg_on)
 
     @staticmethod
     def _fused_head(R, h, W) -> bool:
@@ -321,8 +320,8 @@ class AttackBase:
         L1 clip (UPA's clip needs the whole gradient's norm first). Works behind both boundaries: K2' (a model that exposes its patch-embed
         weights) and K2 on a black-box model's pixel gradient."""
         t = self.randomPatchTransform
-        ok = (os.environ.get("VAA_FUSED_EPILOGUE", "1") != "0" and not t.resize_patch and not t.colorjitter and not t.train_crop
-              and not t.scene_jitter and not t.defocus_blur and not optimizer.l1_clip and not self.patch_reg_on)  # (K6 adds to patch.grad, which the fused update never materialises)
+        ok = (os.environ.get("VAA_FUSED_EPILOGUE", "1") != "0" and not t.resize_patch and not t.colorjitter and not t.frame_stages_on()
+              and not optimizer.l1_clip and not self.patch_reg_on)  # (K6 adds to patch.grad, which the fused update never materialises)
         return {} if ok else None
 
     def fused_update(self, sink, patch, optimizer, scalars):

@@ -11,6 +11,7 @@ import torch
 
 from .. import ops
 from ..labels import mask_labels, tma_target_labels, tma_target_tokens
+from ..transform import frame_stage
 
 SWEEP_MAX_ROWS = 128    # labelled rows per rank K3s covers (vaa_head_slice_applies)
 SWEEP_MAX_IMAGES = 512  # images per rank K2' keeps one partial tile each (vaa_patch_grad_partials)
@@ -199,12 +200,9 @@ def check(attacker, kind: SweepKind, groups):
         refuse("resize_patch=True is not supported (one patch size per group only)")
     if attacker.randomPatchTransform.colorjitter:
         refuse("colorjitter is not supported (one shared patch per group only)")
-    if attacker.randomPatchTransform.train_crop:
-        refuse("train_crop is not supported (the sweeps' K2' cannot take the cropped pixel gradient)")
-    if attacker.randomPatchTransform.scene_jitter:
-        refuse("scene_jitter is not supported (the sweeps' K2' cannot take the pixel gradient behind K10)")
-    if attacker.randomPatchTransform.defocus_blur:
-        refuse("defocus_blur is not supported (the sweeps' K2' cannot take the pixel gradient behind K11)")
+    stages = attacker.randomPatchTransform.frame_stages_on()
+    if stages:
+        refuse(f"{stages[0]} is not supported ({frame_stage(stages[0]).why['sweep']})")
     if attacker.patch_reg_on:
         refuse("tv_weight / nps_weight are not supported (the sweeps' K4 lives inside the segmented epilogue: patch.grad is never materialised)")
     if not attacker.fused_ddp_available():

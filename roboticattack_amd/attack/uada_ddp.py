@@ -72,14 +72,8 @@ class OpenVLAAttacker(AttackBase):
         of the patch through the per-image forms of K1 / K2'; validation evaluates the patch as it is saved. Not available with a sweep.
         `tv_weight`, `nps_weight`, `nps_palette` are EXTENSIONS (AttackBase.set_patch_reg): the total-variation and non-printability terms of the
         patch; every rank adds their gradient before the exchange, so the rank mean carries it once. Not available with a sweep.
-        `train_crop` / `train_crop_scale` are EXTENSIONS (None | "center" | "random", the crop's share of the area): every training step sends the pasted
-        frames through the evaluation's crop (K9 on K1's pixel values: the un-fused step); validation uses the centre box. Not available with a sweep.
-        `scene_jitter` is an EXTENSION (True = OpenVLA's image_aug strengths (0.2, 0.2, 0.2, 0.05), or four strengths): every training step ends in a
-        per-image brightness / contrast / saturation / hue draw of the whole pasted frame (K10, behind K9: the un-fused step); validation gets none.
-        Not available with a sweep.
-        `defocus_blur` is an EXTENSION (True = a maximum sigma of 1.0 pixels, or a maximum sigma in (0, 2.0]): every training step blurs the pasted
-        frame with a per-image Gaussian of sigma ~ U(0, maximum) (K11, in front of K9 and K10: the un-fused step); validation sees the sharp frame.
-        Not available with a sweep."""
+        `train_crop` / `train_crop_scale`, `scene_jitter`, `defocus_blur` are EXTENSIONS: the frame stages K9 / K10 / K11 of every training step, as
+        RandomPatchTransform.set_frame_stages states them (the un-fused step). Not available with a sweep."""
         rank, world, local = vdist.env_rank_world()
         if device is None:
             device = vdist.local_device()
@@ -99,9 +93,7 @@ class OpenVLAAttacker(AttackBase):
             raise ValueError(f"attack_type must be UADA, UPA or TMA, got {attack_type!r}")
         self.attack_type, self.alpha, self.belta, self.target_action = attack_type, alpha, belta, target_action
         self.randomPatchTransform.colorjitter = colorjitter
-        self.randomPatchTransform.set_train_crop(train_crop, train_crop_scale)
-        self.randomPatchTransform.set_scene_jitter(scene_jitter)
-        self.randomPatchTransform.set_defocus_blur(defocus_blur)
+        self.randomPatchTransform.set_frame_stages(train_crop, train_crop_scale, scene_jitter, defocus_blur)
         if tv_weight or nps_weight or nps_palette is not None:
             self.set_patch_reg(tv_weight, nps_weight, nps_palette)
         # at most one kind of sweep; the parameters are checked in KINDS' order, so a refusal of an earlier one comes first

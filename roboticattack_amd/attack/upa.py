@@ -79,16 +79,10 @@ class OpenVLAAttacker(AttackBase):
                                   train_crop=None, train_crop_scale=0.9, scene_jitter=False, defocus_blur=False):
         """colorjitter (an EXTENSION: True or three strengths): every training step pastes a per-image brightness / contrast / saturation variant of
         the patch; validation evaluates the patch as it is saved.
-        train_crop (an EXTENSION: None | "center" | "random", with train_crop_scale the crop's share of the area): every training step sends the
-        pasted frames through the evaluation's crop (K9 on K1's pixel values); the validation passes use the centre box, as the evaluation will.
-        scene_jitter (an EXTENSION: True = OpenVLA's image_aug strengths (0.2, 0.2, 0.2, 0.05), or four strengths): every training step ends in a
-        per-image brightness / contrast / saturation / hue draw of the whole pasted frame (K10, behind K9); validation passes get none.
-        defocus_blur (an EXTENSION: True = a maximum sigma of 1.0 pixels, or a maximum sigma in (0, 2.0]): every training step blurs the pasted frame
-        with a per-image Gaussian of sigma ~ U(0, maximum) (K11, in front of K9 and K10); validation passes see the sharp frame."""
+        train_crop / train_crop_scale, scene_jitter, defocus_blur (EXTENSIONS): the frame stages K9 / K10 / K11 of every training step, as
+        RandomPatchTransform.set_frame_stages states them."""
         self.randomPatchTransform.colorjitter = colorjitter
-        self.randomPatchTransform.set_train_crop(train_crop, train_crop_scale)
-        self.randomPatchTransform.set_scene_jitter(scene_jitter)
-        self.randomPatchTransform.set_defocus_blur(defocus_blur)
+        self.randomPatchTransform.set_frame_stages(train_crop, train_crop_scale, scene_jitter, defocus_blur)
         self.val_CE_loss, self.val_L1_loss, self.val_ASR, self.train_CE_loss, self.val_relative_distance = [], [], [], [], []
         dev = self.device
         patch = torch.rand(patch_size).to(dev)

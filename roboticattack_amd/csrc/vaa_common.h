@@ -11,6 +11,9 @@
 #include <math.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
+#include <stdio.h>
+
+#include <initializer_list>
 
 #include "../../include/vaa.h"
 
@@ -54,6 +57,31 @@ inline int check_patch_call(const char* who, int B, int h, int w, int geometry, 
         // warp the all-background blend -100*(nw+ne+sw+se) is not exactly -100, so the rule would depend on rounding over the whole frame
         set_error("%s: VAA_MASK_NE_M100 is defined for geometry=0 only (appply_random_transform.py:153,179)", who);
         return VAA_E_UNSUPPORTED;
+    }
+    return VAA_OK;
+}
+
+// The checks that open every planar frame-stage entry point (K9 / K10 / K11; host), in the order a caller observes them: the batch range (B in
+// [0, max_B]; batch_note: what the stage adds behind "B=<B>", or ""), the empty batch (VAA_OK: the caller returns without a launch), a null
+// pointer among `dev` or `host`, a pointer of `dev` (the tensors and the rows' device copy, named `rows_dev` in the message) that is not 16-byte
+// aligned. The stage's own rules (its rows, an overlap, a workspace) follow in its own file.
+inline int check_stage_call(const char* who, int B, long max_B, const char* batch_note, std::initializer_list<const void*> dev,
+                            std::initializer_list<const void*> host, const char* rows_dev) {
+    if (B < 0 || (long)B > max_B) {
+        set_error("%s: bad batch size (B=%d%s)", who, B, batch_note);
+        return VAA_E_INVALID;
+    }
+    if (B == 0) return VAA_OK;  // empty batch: nothing to read or write (pointers may be null)
+    bool null = false, misaligned = false;
+    for (const void* p : host) null |= !p;
+    for (const void* p : dev) null |= !p, misaligned |= ((uintptr_t)p & 15u) != 0;
+    if (null) {
+        set_error("%s: null pointer argument", who);
+        return VAA_E_INVALID;
+    }
+    if (misaligned) {
+        set_error("%s: the tensors and %s must be 16-byte aligned", who, rows_dev);
+        return VAA_E_INVALID;
     }
     return VAA_OK;
 }

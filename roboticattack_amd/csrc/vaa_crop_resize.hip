@@ -223,19 +223,9 @@ __global__ __launch_bounds__(kCrThreads) void crop_resize_bwd_kernel(const CropA
 }
 
 static int check_crop_call(const char* who, const void* t_in, const float* boxes_host, const float* boxes_dev, int B, const void* t_out) {
-    if (B < 0 || (long)B * kCrItemsPerImg > 0x7fffffffL) {
-        set_error("%s: bad batch size (B=%d)", who, B);
-        return VAA_E_INVALID;
-    }
-    if (B == 0) return VAA_OK;  // empty batch: nothing to read or write (pointers may be null)
-    if (!t_in || !boxes_host || !boxes_dev || !t_out) {
-        set_error("%s: null pointer argument", who);
-        return VAA_E_INVALID;
-    }
-    if (((uintptr_t)t_in & 15u) || ((uintptr_t)t_out & 15u) || ((uintptr_t)boxes_dev & 15u)) {
-        set_error("%s: the tensors and boxes_dev must be 16-byte aligned", who);
-        return VAA_E_INVALID;
-    }
+    // at most 0x7fffffff work items (B * kCrItemsPerImg)
+    const int rc = check_stage_call(who, B, 0x7fffffffL / kCrItemsPerImg, "", {t_in, t_out, boxes_dev}, {boxes_host}, "boxes_dev");
+    if (rc != VAA_OK || B == 0) return rc;
     for (int b = 0; b < B; ++b)
         for (int ax = 0; ax < 2; ++ax) {
             const float lo = boxes_host[4 * b + ax], hi = boxes_host[4 * b + 2 + ax];
@@ -248,28 +238,26 @@ static int check_crop_call(const char* who, const void* t_in, const float* boxes
     return VAA_OK;
 }
 
+static int crop_call(const char* who, bool fwd, const uint16_t* t_in, const float* boxes_host, const float* boxes_dev, int B, uint16_t* t_out,
+                     void* stream) {
+    const int rc = check_crop_call(who, t_in, boxes_host, boxes_dev, B, t_out);
+    if (rc != VAA_OK || B == 0) return rc;
+    CropArgs a = {t_in, t_out, boxes_dev, B};
+    const long total = (long)B * kCrItemsPerImg;
+    const dim3 grid((unsigned)((total + kCrThreads - 1) / kCrThreads));
+    if (fwd) VAA_LAUNCH(crop_resize_fwd_kernel, grid, dim3(kCrThreads), 0, (hipStream_t)stream, a);
+    else VAA_LAUNCH(crop_resize_bwd_kernel, grid, dim3(kCrThreads), 0, (hipStream_t)stream, a);
+    return check_launch(who);
+}
+
 }  // namespace vaa
 
 extern "C" int vaa_crop_resize_fwd(const uint16_t* x_bf16, const float* boxes_host, const float* boxes_dev, int B, uint16_t* out_bf16,
                                    void* stream) {
-    using namespace vaa;
-    const char* who = "vaa_crop_resize_fwd";
-    const int rc = check_crop_call(who, x_bf16, boxes_host, boxes_dev, B, out_bf16);
-    if (rc != VAA_OK || B == 0) return rc;
-    CropArgs a = {x_bf16, out_bf16, boxes_dev, B};
-    const long total = (long)B * kCrItemsPerImg;
-    VAA_LAUNCH(crop_resize_fwd_kernel, dim3((unsigned)((total + kCrThreads - 1) / kCrThreads)), dim3(kCrThreads), 0, (hipStream_t)stream, a);
-    return check_launch(who);
+    return vaa::crop_call("vaa_crop_resize_fwd", true, x_bf16, boxes_host, boxes_dev, B, out_bf16, stream);
 }
 
 extern "C" int vaa_crop_resize_bwd(const uint16_t* gout_bf16, const float* boxes_host, const float* boxes_dev, int B, uint16_t* gx_bf16,
                                    void* stream) {
-    using namespace vaa;
-    const char* who = "vaa_crop_resize_bwd";
-    const int rc = check_crop_call(who, gout_bf16, boxes_host, boxes_dev, B, gx_bf16);
-    if (rc != VAA_OK || B == 0) return rc;
-    CropArgs a = {gout_bf16, gx_bf16, boxes_dev, B};
-    const long total = (long)B * kCrItemsPerImg;
-    VAA_LAUNCH(crop_resize_bwd_kernel, dim3((unsigned)((total + kCrThreads - 1) / kCrThreads)), dim3(kCrThreads), 0, (hipStream_t)stream, a);
-    return check_launch(who);
+    return vaa::crop_call("vaa_crop_resize_bwd", false, gout_bf16, boxes_host, boxes_dev, B, gx_bf16, stream);
 }

@@ -260,19 +260,10 @@ __global__ __launch_bounds__(kBlurThreads) void defocus_blur_bwd_kernel(const Bl
 }
 
 static int check_blur_call(const char* who, const void* t_in, const float* taps_host, const float* taps_dev, int B, const void* t_out) {
-    if (B < 0 || (long)B > kBlurMaxB) {
-        set_error("%s: bad batch size (B=%d; at most %ld: one workgroup per image, plane and band of %d rows)", who, B, kBlurMaxB, kBlurBand);
-        return VAA_E_INVALID;
-    }
-    if (B == 0) return VAA_OK;  // empty batch: nothing to read or write (pointers may be null)
-    if (!t_in || !taps_host || !taps_dev || !t_out) {
-        set_error("%s: null pointer argument", who);
-        return VAA_E_INVALID;
-    }
-    if (((uintptr_t)t_in & 15u) || ((uintptr_t)t_out & 15u) || ((uintptr_t)taps_dev & 15u)) {
-        set_error("%s: the tensors and taps_dev must be 16-byte aligned", who);
-        return VAA_E_INVALID;
-    }
+    char note[96];
+    snprintf(note, sizeof note, "; at most %ld: one workgroup per image, plane and band of %d rows", kBlurMaxB, kBlurBand);
+    const int rc = check_stage_call(who, B, kBlurMaxB, note, {t_in, t_out, taps_dev}, {taps_host}, "taps_dev");
+    if (rc != VAA_OK || B == 0) return rc;
     {   // a workgroup reads a halo that its neighbours write: no byte of the input may lie inside the output (K4's rule, by address ranges)
         const size_t nb = (size_t)B * 6 * VAA_NPIX * sizeof(uint16_t);
         const uintptr_t i0 = (uintptr_t)t_in, o0 = (uintptr_t)t_out;

@@ -276,19 +276,8 @@ __global__ __launch_bounds__(kSjThreads) void scene_jitter_bwd_kernel(const Scen
 
 static int check_scene_call(const char* who, const void* t0, const void* t1, const float* factors_host, const float* factors_dev, const float* mean6,
                             const float* std6, int B, const void* t_out, const void* ws, size_t ws_bytes) {
-    if (B < 0 || B > kSjMaxB) {
-        set_error("%s: bad batch size (B=%d)", who, B);
-        return VAA_E_INVALID;
-    }
-    if (B == 0) return VAA_OK;  // empty batch: nothing to read or write (pointers may be null)
-    if (!t0 || !t1 || !factors_host || !factors_dev || !mean6 || !std6 || !t_out) {
-        set_error("%s: null pointer argument", who);
-        return VAA_E_INVALID;
-    }
-    if (((uintptr_t)t0 & 15u) || ((uintptr_t)t1 & 15u) || ((uintptr_t)t_out & 15u) || ((uintptr_t)factors_dev & 15u)) {
-        set_error("%s: the tensors and factors_dev must be 16-byte aligned", who);
-        return VAA_E_INVALID;
-    }
+    const int rc = check_stage_call(who, B, kSjMaxB, "", {t0, t1, t_out, factors_dev}, {factors_host, mean6, std6}, "factors_dev");
+    if (rc != VAA_OK || B == 0) return rc;
     for (int q = 0; q < 6; ++q)
         if (!(isfinite(mean6[q]) && isfinite(std6[q]) && std6[q] > 0.0f)) {
             set_error("%s: channel %d has mean = %g, std = %g: need finite values and std > 0", who, q, (double)mean6[q], (double)std6[q]);

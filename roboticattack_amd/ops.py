@@ -1193,42 +1193,81 @@ def eval_preprocess(img_u8, crop_scale: float = 0.0, mean6=None, std6=None):
 
 
 # ------------------------------------------------------------------------------------------------------
-# K9: the evaluation's crop inside a training step (crop + bilinear resize of K1's pixel values, and the adjoint)
+# K9 / K10 / K11, the planar frame stages between K1 and the model: one host layer. Each stage has one row of host float32 values per image
+# (its rows spec: the noun of the messages and the width), a forward and an adjoint entry point, and a Function that names only what differs.
 # ------------------------------------------------------------------------------------------------------
-def _crop_boxes(boxes, B: int, device):
-    """boxes [B,4] {y1, x1, y2, x2}: a host float32 array (copied to the device here) or a (host array, device tensor) pair. The host copy is
-    what the library validates, the device copy what the kernels read (include/vaa.h)."""
-    import numpy as np
-
-    host, dev = boxes if isinstance(boxes, tuple) else (boxes, None)
-    host = np.ascontiguousarray(np.asarray(host, dtype=np.float32))
-    if host.shape != (B, 4):
-        raise _lib.VaaError(f"boxes: expected shape {(B, 4)}, got {host.shape}")
-    if dev is None:
-        dev = torch.from_numpy(host).to(device, non_blocking=True)
-    return host, _need(dev, torch.float32, "boxes (device copy)", (B, 4))
-
-
-def _crop_call(name, fn, t, boxes):
+def _planar_batch(t, name: str) -> int:
     B = t.shape[0] if isinstance(t, torch.Tensor) and t.dim() == 4 else 0
     _need(t, torch.bfloat16, name, (B, 6, IMG, IMG))
-    host, dev = _crop_boxes(boxes, B, t.device)
-    out = torch.empty_like(t)
+    return B
+
+
+def _host_rows(rows, B: int, width: int, what: str, device):
+    """rows [B,width]: a host float32 array (copied to the device here) or a (host array, device tensor) pair. The host copy is what the
+    library validates, the device copy what the kernels read (include/vaa.h)."""
+    import numpy as np
+
+    host, dev = rows if isinstance(rows, tuple) else (rows, None)
+    host = np.ascontiguousarray(np.asarray(host, dtype=np.float32))
+    if host.shape != (B, width):
+        raise _lib.VaaError(f"{what}: expected shape {(B, width)}, got {host.shape}")
+    if dev is None:
+        dev = torch.from_numpy(host).to(device, non_blocking=True)
+    return host, _need(dev, torch.float32, f"{what} (device copy)", (B, width))
+
+
+def _stage_call(fn: str, tensors, rows, norm=None, ws=None):
+    """One entry point of a frame stage, in the C argument order all of them share: the bf16 [B,6,224,224] `tensors` ((name, tensor), ...), the
+    rows pair of `rows` = (what, width, value), [norm = (mean6, std6),] B, the output, [the workspace of ws = (its *_ws_bytes function, its
+    _workspace kind),] the stream."""
+    B = _planar_batch(tensors[0][1], tensors[0][0])
+    for name, t in tensors[1:]:
+        _need(t, torch.bfloat16, name, (B, 6, IMG, IMG))
+    what, width, value = rows
+    host, dev = _host_rows(value, B, width, what, tensors[0][1].device)
+    L = _lib.lib()
+    args = [t.data_ptr() for _, t in tensors] + [host.ctypes.data, dev.data_ptr()]
+    if norm is not None:
+        args += [_MEAN if norm[0] is None else _lib.f32x(norm[0]), _STD if norm[1] is None else _lib.f32x(norm[1])]
+    out = torch.empty_like(tensors[0][1])
+    args += [B, out.data_ptr()]
+    if ws is not None:
+        buf = _workspace(out.device, getattr(L, ws[0])(B), ws[1])
+        args += [buf.data_ptr(), buf.numel()]
     with _timed(fn, B=B):
-        rc = getattr(_lib.lib(), fn)(t.data_ptr(), host.ctypes.data, dev.data_ptr(), B, out.data_ptr(), _stream())
+        rc = getattr(L, fn)(*args, _stream())
     _lib.check(rc, fn)
     return out
+
+
+def _stage_forward(ctx, fwd, spec, pixel_values, rows, *norm, save_input=False):
+    """Forward of every frame-stage Function: `fwd` (the stage's public wrapper) on the contiguous input with the rows pair of spec = (what,
+    width), which stays on ctx for the adjoint; save_input: the adjoint reads the forward's input too."""
+    x = pixel_values.contiguous() if isinstance(pixel_values, torch.Tensor) else pixel_values
+    ctx.rows, ctx.norm = _host_rows(rows, _planar_batch(x, "pixel_values"), spec[1], spec[0], x.device), norm
+    if save_input:
+        ctx.save_for_backward(x)
+    return fwd(x, ctx.rows, *norm)
+
+
+def _stage_backward(ctx, bwd, gout):
+    """Backward of every frame-stage Function: `bwd` on the bf16 gradient [and the saved input]; no gradient for the rows or mean / std."""
+    return (bwd(gout.to(torch.bfloat16).contiguous(), *ctx.saved_tensors, ctx.rows, *ctx.norm), None) + (None,) * len(ctx.norm)
+
+
+# K9: the evaluation's crop inside a training step (crop + bilinear resize of K1's pixel values, and the adjoint)
+_BOXES = ("boxes", 4)  # {y1, x1, y2, x2}
 
 
 def crop_resize_fwd(pixel_values, boxes):
     """K9. pixel_values bf16 [B,6,224,224] (K1's planar output) -> the same planes cropped to each image's box {y1, x1, y2, x2} (normalised
     coordinates, sides in [0.5, 1]) and resized back bilinearly: K7's geometry on the normalised values (include/vaa.h states the arithmetic)."""
-    return _crop_call("pixel_values", "vaa_crop_resize_fwd", pixel_values, boxes)
+    return _stage_call("vaa_crop_resize_fwd", (("pixel_values", pixel_values),), _BOXES + (boxes,))
 
 
 def crop_resize_bwd(gout, boxes):
     """K9's adjoint: the gradient of crop_resize_fwd's output -> the gradient of its input, the exact transpose of the forward's taps."""
-    return _crop_call("gout", "vaa_crop_resize_bwd", gout, boxes)
+    return _stage_call("vaa_crop_resize_bwd", (("gout", gout),), _BOXES + (boxes,))
 
 
 class CropResize(torch.autograd.Function):
@@ -1236,15 +1275,11 @@ class CropResize(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pixel_values, boxes):
-        x = pixel_values.contiguous() if isinstance(pixel_values, torch.Tensor) else pixel_values
-        B = x.shape[0] if isinstance(x, torch.Tensor) and x.dim() == 4 else 0
-        _need(x, torch.bfloat16, "pixel_values", (B, 6, IMG, IMG))
-        ctx.boxes = _crop_boxes(boxes, B, x.device)
-        return crop_resize_fwd(x, ctx.boxes)
+        return _stage_forward(ctx, crop_resize_fwd, _BOXES, pixel_values, boxes)
 
     @staticmethod
     def backward(ctx, gout):
-        return crop_resize_bwd(gout.to(torch.bfloat16).contiguous(), ctx.boxes), None
+        return _stage_backward(ctx, crop_resize_bwd, gout)
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -1274,48 +1309,20 @@ def scene_factors(delta, kappa, sigma, hue):
     return out
 
 
-def _scene_factors(factors, B: int, device):
-    """factors [B,12]: a host float32 array (copied to the device here) or a (host array, device tensor) pair. The host copy is what the
-    library validates, the device copy what the kernels read (include/vaa.h)."""
-    import numpy as np
-
-    host, dev = factors if isinstance(factors, tuple) else (factors, None)
-    host = np.ascontiguousarray(np.asarray(host, dtype=np.float32))
-    if host.shape != (B, 12):
-        raise _lib.VaaError(f"factors: expected shape {(B, 12)}, got {host.shape}")
-    if dev is None:
-        dev = torch.from_numpy(host).to(device, non_blocking=True)
-    return host, _need(dev, torch.float32, "factors (device copy)", (B, 12))
-
-
-def _scene_call(fn, tensors, names, factors, mean6, std6):
-    t = tensors[0]
-    B = t.shape[0] if isinstance(t, torch.Tensor) and t.dim() == 4 else 0
-    for v, name in zip(tensors, names):
-        _need(v, torch.bfloat16, name, (B, 6, IMG, IMG))
-    host, dev = _scene_factors(factors, B, t.device)
-    mean_c = _MEAN if mean6 is None else _lib.f32x(mean6)
-    std_c = _STD if std6 is None else _lib.f32x(std6)
-    L = _lib.lib()
-    ws = _workspace(t.device, L.vaa_scene_jitter_ws_bytes(B), "scene")
-    out = torch.empty_like(t)
-    with _timed(fn, B=B):
-        rc = getattr(L, fn)(*(v.data_ptr() for v in tensors), host.ctypes.data, dev.data_ptr(), mean_c, std_c, B, out.data_ptr(), ws.data_ptr(),
-                            ws.numel(), _stream())
-    _lib.check(rc, fn)
-    return out
+_FACTORS = ("factors", 12)  # {delta, kappa, sigma, R(hue) row-major}
+_SCENE_WS = ("vaa_scene_jitter_ws_bytes", "scene")
 
 
 def scene_jitter_fwd(pixel_values, factors, mean6=None, std6=None):
     """K10. pixel_values bf16 [B,6,224,224] (K1 / K9's planar output) -> the same frames under each image's brightness / contrast / saturation /
     hue factors (`scene_factors`), both towers alike (include/vaa.h states the arithmetic)."""
-    return _scene_call("vaa_scene_jitter_fwd", (pixel_values,), ("pixel_values",), factors, mean6, std6)
+    return _stage_call("vaa_scene_jitter_fwd", (("pixel_values", pixel_values),), _FACTORS + (factors,), (mean6, std6), _SCENE_WS)
 
 
 def scene_jitter_bwd(gout, pixel_values, factors, mean6=None, std6=None):
     """K10's adjoint: the gradient of scene_jitter_fwd's output -> the gradient of its input, the exact derivative with torch.clamp's gates
     (recomputed from `pixel_values` and the factors), the whole-image term of the contrast mean included."""
-    return _scene_call("vaa_scene_jitter_bwd", (gout, pixel_values), ("gout", "pixel_values"), factors, mean6, std6)
+    return _stage_call("vaa_scene_jitter_bwd", (("gout", gout), ("pixel_values", pixel_values)), _FACTORS + (factors,), (mean6, std6), _SCENE_WS)
 
 
 class SceneJitter(torch.autograd.Function):
@@ -1323,18 +1330,11 @@ class SceneJitter(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pixel_values, factors, mean6=None, std6=None):
-        x = pixel_values.contiguous() if isinstance(pixel_values, torch.Tensor) else pixel_values
-        B = x.shape[0] if isinstance(x, torch.Tensor) and x.dim() == 4 else 0
-        _need(x, torch.bfloat16, "pixel_values", (B, 6, IMG, IMG))
-        ctx.factors = _scene_factors(factors, B, x.device)
-        ctx.norm = (mean6, std6)
-        ctx.save_for_backward(x)
-        return scene_jitter_fwd(x, ctx.factors, mean6, std6)
+        return _stage_forward(ctx, scene_jitter_fwd, _FACTORS, pixel_values, factors, mean6, std6, save_input=True)
 
     @staticmethod
     def backward(ctx, gout):
-        (x,) = ctx.saved_tensors
-        return scene_jitter_bwd(gout.to(torch.bfloat16).contiguous(), x, ctx.factors, *ctx.norm), None, None, None
+        return _stage_backward(ctx, scene_jitter_bwd, gout)
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -1366,41 +1366,19 @@ def blur_taps(sigma):
     return out
 
 
-def _blur_taps(taps, B: int, device):
-    """taps [B,8]: a host float32 array (copied to the device here) or a (host array, device tensor) pair. The host copy is what the library
-    validates, the device copy what the kernels read (include/vaa.h)."""
-    import numpy as np
-
-    host, dev = taps if isinstance(taps, tuple) else (taps, None)
-    host = np.ascontiguousarray(np.asarray(host, dtype=np.float32))
-    if host.shape != (B, 8):
-        raise _lib.VaaError(f"taps: expected shape {(B, 8)}, got {host.shape}")
-    if dev is None:
-        dev = torch.from_numpy(host).to(device, non_blocking=True)
-    return host, _need(dev, torch.float32, "taps (device copy)", (B, 8))
-
-
-def _blur_call(name, fn, t, taps):
-    B = t.shape[0] if isinstance(t, torch.Tensor) and t.dim() == 4 else 0
-    _need(t, torch.bfloat16, name, (B, 6, IMG, IMG))
-    host, dev = _blur_taps(taps, B, t.device)
-    out = torch.empty_like(t)
-    with _timed(fn, B=B):
-        rc = getattr(_lib.lib(), fn)(t.data_ptr(), host.ctypes.data, dev.data_ptr(), B, out.data_ptr(), _stream())
-    _lib.check(rc, fn)
-    return out
+_TAPS = ("taps", 8)  # {w0, ..., w6, 0}
 
 
 def defocus_blur_fwd(x, taps):
     """K11. x bf16 [B,6,224,224] (K1's planar output) -> every plane under image b's separable 13-tap kernel `taps[b]` (`blur_taps`), rows then
     columns, edges replicated, the intermediate kept in fp32 (include/vaa.h states the arithmetic)."""
-    return _blur_call("x", "vaa_defocus_blur_fwd", x, taps)
+    return _stage_call("vaa_defocus_blur_fwd", (("x", x),), _TAPS + (taps,))
 
 
 def defocus_blur_bwd(gout, taps):
     """K11's adjoint: the gradient of defocus_blur_fwd's output -> the gradient of its input, the exact transpose (the edge rows and columns
     collect the taps the replication folded onto them)."""
-    return _blur_call("gout", "vaa_defocus_blur_bwd", gout, taps)
+    return _stage_call("vaa_defocus_blur_bwd", (("gout", gout),), _TAPS + (taps,))
 
 
 class DefocusBlur(torch.autograd.Function):
@@ -1408,15 +1386,11 @@ class DefocusBlur(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pixel_values, taps):
-        x = pixel_values.contiguous() if isinstance(pixel_values, torch.Tensor) else pixel_values
-        B = x.shape[0] if isinstance(x, torch.Tensor) and x.dim() == 4 else 0
-        _need(x, torch.bfloat16, "pixel_values", (B, 6, IMG, IMG))
-        ctx.taps = _blur_taps(taps, B, x.device)
-        return defocus_blur_fwd(x, ctx.taps)
+        return _stage_forward(ctx, defocus_blur_fwd, _TAPS, pixel_values, taps)
 
     @staticmethod
     def backward(ctx, gout):
-        return defocus_blur_bwd(gout.to(torch.bfloat16).contiguous(), ctx.taps), None
+        return _stage_backward(ctx, defocus_blur_bwd, gout)
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -13,18 +13,13 @@ Differences a caller can observe (all documented in DESIGN.md):
   * Appendix A defects: D1 (IndentationError) n/a; D2 (resize_patch UnboundLocalError) resolved as "scale the BASE
     patch per image"; D3 (`colorjitter=` kwarg, dead in the reference) given a meaning here: a per-image brightness / contrast /
     saturation draw on the patch (include/vaa.h states the arithmetic; `_draw_jitter` the draws). Off by default: zero extra RNG calls.
-  * `train_crop` (an EXTENSION, off by default: no extra RNG call, no extra launch): the pasted frames go through the evaluation's crop
-    (K7's geometry, `eval_pixel_values(center_crop=True)`) inside the training step — K9 on K1's pixel values, `_crop_boxes` the draws.
-  * `scene_jitter` (an EXTENSION, off by default: no extra RNG call, no extra launch): the pasted (and cropped) frames of a training step get a
-    per-image brightness / contrast / saturation / hue draw of the WHOLE frame — K10 behind K9, the photometric half of OpenVLA's `image_aug`
-    (include/vaa.h states the arithmetic; `_scene_draw` the draws).
-  * `defocus_blur` (an EXTENSION, off by default: no extra RNG call, no extra launch): the pasted frames of a training step are blurred by a
-    per-image Gaussian of random width — K11 in front of K9 and K10, because optics act before the crop (include/vaa.h states the arithmetic;
-    `_blur_draw` the draws).
+  * `train_crop`, `scene_jitter`, `defocus_blur` (EXTENSIONS, each off by default: no extra RNG call, no extra launch): the frame stages
+    K9 / K10 / K11 on K1's pixel values between the paste and the model — `FRAME_STAGES` the table, `set_frame_stages` what each one does.
 """
 from __future__ import annotations
 
 import random
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -120,6 +115,31 @@ def _six(mean, std):
     return m, s
 
 
+# The planar frame stages between the paste and the model, in kernel order. flag: the attribute that switches the stage on (None = off);
+# function: its ops Function; draw: the method that makes the call's rows, looked up on the instance when the stage runs; train_only: it runs in
+# differentiable calls only and its draw takes (batch) — a stage that runs in every call takes (batch, patch) and tells the calls apart itself;
+# norm: its Function takes (mean6, std6); why: the reason each refusing site gives (a stage's gradient is one K2' cannot take).
+FrameStage = namedtuple("FrameStage", "flag function draw train_only norm why")
+FRAME_STAGES = (
+    FrameStage("train_crop", ops.CropResize, "_crop_boxes", False, False,
+               dict(grad_sink="the pixel gradient goes through the crop adjoint first", apply_sweep_batch="K2' cannot take the cropped gradient",
+                    sweep="the sweeps' K2' cannot take the cropped pixel gradient")),
+    FrameStage("scene_jitter", ops.SceneJitter, "_scene_draw", True, True,
+               dict(grad_sink="the pixel gradient goes through the scene-jitter adjoint first",
+                    apply_sweep_batch="K2' cannot take the pixel gradient behind K10", sweep="the sweeps' K2' cannot take the pixel gradient behind K10")),
+    FrameStage("defocus_blur", ops.DefocusBlur, "_blur_draw", True, False,
+               dict(grad_sink="the pixel gradient goes through the blur adjoint first",
+                    apply_sweep_batch="K2' cannot take the pixel gradient behind K11", sweep="the sweeps' K2' cannot take the pixel gradient behind K11")),
+)
+FRAME_CHAIN = ("defocus_blur", "train_crop", "scene_jitter")  # the order they run (and draw) in: optics, then the crop, then the lighting
+assert sorted(FRAME_CHAIN) == sorted(s.flag for s in FRAME_STAGES), "every frame stage has one place in the chain"
+
+
+def frame_stage(flag):
+    """The row of FRAME_STAGES whose flag is `flag` (KeyError: no such stage)."""
+    return {s.flag: s for s in FRAME_STAGES}[flag]
+
+
 class RandomPatchTransform:
     def __init__(self, device, resize_patch: bool = False, train_crop=None, train_crop_scale: float = TRAIN_CROP_SCALE):
         self.device = torch.device(device)
@@ -188,17 +208,42 @@ class RandomPatchTransform:
         self.last_blur = np.array([random.uniform(0.0, self.defocus_blur) for _ in range(batch)], np.float32)
         return ops.blur_taps(self.last_blur)  # from the fp32 sigmas: ops.blur_taps(last_blur) reproduces the call's taps
 
+    def set_frame_stages(self, train_crop=None, train_crop_scale=TRAIN_CROP_SCALE, scene_jitter=False, defocus_blur=False):
+        """The three frame stages as the attackers' keywords name them (EXTENSIONS, all off by default); `_finish` chains the ones that are set.
+        train_crop (None | "center" | "random", with train_crop_scale the crop's share of the area): every training step sends the pasted frames
+        through the evaluation's crop (K9 on K1's pixel values); the validation passes use the centre box, as the evaluation will.
+        scene_jitter (True = OpenVLA's image_aug strengths (0.2, 0.2, 0.2, 0.05), or four strengths): every training step ends in a per-image
+        brightness / contrast / saturation / hue draw of the whole pasted frame (K10, behind K9); validation passes get none.
+        defocus_blur (True = a maximum sigma of 1.0 pixels, or a maximum sigma in (0, 2.0]): every training step blurs the pasted frame with a
+        per-image Gaussian of sigma ~ U(0, maximum) (K11, in front of K9 and K10); validation passes see the sharp frame.
+        A step with any of them takes the planar, un-fused path (K2' cannot take the gradient behind them); the sweeps refuse all three."""
+        self.set_train_crop(train_crop, train_crop_scale)
+        self.set_scene_jitter(scene_jitter)
+        self.set_defocus_blur(defocus_blur)
+
+    def frame_stages_on(self):
+        """The flags of the frame stages that are set, in FRAME_STAGES' order: what keeps a step off K2' (grad_sink, the sweeps, the fused paths)."""
+        return tuple(s.flag for s in FRAME_STAGES if getattr(self, s.flag) is not None)
+
+    def _refuse_frame_stages(self, site):
+        """`site` ("grad_sink" | "apply_sweep_batch") hands K2' the gradient: ValueError naming the first frame stage that is set, and why."""
+        on = self.frame_stages_on()
+        if on:
+            raise ValueError(f"{site} is not available with {on[0]} ({frame_stage(on[0]).why[site]})")
+
     def _finish(self, out, patch, out_dtype, mean6=None, std6=None):
-        """The tail of every paste that returns pixel values: [K11 with the call's taps ->] [K9 with the call's boxes ->] [K10 with the call's
-        factors ->] the caller's dtype. K11 and K10 run in a differentiable call only (a training step): the validation passes inside the loops
-        see the frame sharp and as it is lit. Draw order behind the paste's own draws: the blur's sigmas (one per image), then the crop's offsets
-        (two per image), then the scene's factors (four per image), each image-major."""
-        if self.defocus_blur is not None and patch.requires_grad and torch.is_grad_enabled():
-            out = ops.DefocusBlur.apply(out, self._blur_draw(int(out.shape[0])))
-        if self.train_crop is not None:
-            out = ops.CropResize.apply(out, self._crop_boxes(int(out.shape[0]), patch))
-        if self.scene_jitter is not None and patch.requires_grad and torch.is_grad_enabled():
-            out = ops.SceneJitter.apply(out, self._scene_draw(int(out.shape[0])), mean6, std6)
+        """The tail of every paste that returns pixel values: the frame stages that are set, in FRAME_CHAIN's order ([K11 with the call's taps
+        ->] [K9 with the call's boxes ->] [K10 with the call's factors]), then the caller's dtype. K11 and K10 run in a differentiable call only
+        (a training step): the validation passes inside the loops see the frame sharp and as it is lit. Draw order behind the paste's own
+        draws, the chain's: the blur's sigmas (one per image), then the crop's offsets (two per image), then the scene's factors (four per
+        image), each image-major."""
+        training = patch.requires_grad and torch.is_grad_enabled()
+        for stage in map(frame_stage, FRAME_CHAIN):
+            if getattr(self, stage.flag) is None or (stage.train_only and not training):
+                continue
+            draw, batch = getattr(self, stage.draw), int(out.shape[0])
+            rows = draw(batch) if stage.train_only else draw(batch, patch)
+            out = stage.function.apply(out, rows, mean6, std6) if stage.norm else stage.function.apply(out, rows)
         return out if out_dtype == torch.bfloat16 else out.to(out_dtype)
 
     # ---- small tensor helpers kept for API compatibility (:16-24) ----
@@ -296,15 +341,9 @@ class RandomPatchTransform:
         draws: (xy, theta) host arrays from `draw_params` to use instead of drawing (a maskidx sweep hands every group the same draws).
         colorjitter (True: strengths 0.2 each; or three strengths): every image pastes its own brightness / contrast / saturation variant of the
         patch (`_apply_jittered`); False makes no extra RNG call.
-        With `train_crop` set the result is ops.CropResize of K1's pixel values (the planar K1 -> K9 path; no grad_sink); with `scene_jitter`
-        set a training call ends in ops.SceneJitter (K10, behind K9; no grad_sink either); with `defocus_blur` set a training call puts
-        ops.DefocusBlur (K11) in front of both (no grad_sink either)."""
-        if self.train_crop is not None and grad_sink is not None:
-            raise ValueError("grad_sink is not available with train_crop (the pixel gradient goes through the crop adjoint first)")
-        if self.scene_jitter is not None and grad_sink is not None:
-            raise ValueError("grad_sink is not available with scene_jitter (the pixel gradient goes through the scene-jitter adjoint first)")
-        if self.defocus_blur is not None and grad_sink is not None:
-            raise ValueError("grad_sink is not available with defocus_blur (the pixel gradient goes through the blur adjoint first)")
+        With a frame stage set (`set_frame_stages`) the result is K1's pixel values behind `_finish`'s chain (the planar path; no grad_sink)."""
+        if grad_sink is not None:
+            self._refuse_frame_stages("grad_sink")
         mean6, std6 = _six(mean, std)
         img = self.stage_images(images)
         B = img.shape[0]
@@ -341,22 +380,16 @@ class RandomPatchTransform:
         Bp = int(img.shape[0]) // P
         if self.embed_with is None:
             raise ValueError("apply_sweep_batch needs a model that exposes its patch-embed weights")
-        if self.train_crop is not None:
-            raise ValueError("apply_sweep_batch is not available with train_crop (K2' cannot take the cropped gradient)")
-        if self.scene_jitter is not None:
-            raise ValueError("apply_sweep_batch is not available with scene_jitter (K2' cannot take the pixel gradient behind K10)")
-        if self.defocus_blur is not None:
-            raise ValueError("apply_sweep_batch is not available with defocus_blur (K2' cannot take the pixel gradient behind K11)")
+        self._refuse_frame_stages("apply_sweep_batch")
         xy_n, th_n = draws if draws is not None else self._draw(Bp, ph, pw, geometry)
         xy, theta = self._to_dev(np.tile(xy_n, (P, 1)), np.tile(th_n, (P, 1)))
         emb = self.embed_with.patch_embed_params()
         return ops.PatchEmbeds(ops.PatchApplySweepEmbed.apply(patches, img, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6, *emb, grad_sink))
 
     def _embed_params(self, patch, out_dtype):
-        """Patch-embed weights for the path that never materialises the pixel gradient — only for differentiable bf16 calls, and never with
-        train_crop, scene_jitter or defocus_blur: K2' evaluates only the tiles under the uncropped patch and cannot be fed the gradient behind
-        K9 / K10 / K11."""
-        if self.train_crop is not None or self.scene_jitter is not None or self.defocus_blur is not None or self.embed_with is None or not patch.requires_grad or out_dtype != torch.bfloat16 or not torch.is_grad_enabled():
+        """Patch-embed weights for the path that never materialises the pixel gradient — only for differentiable bf16 calls, and never with a
+        frame stage set: K2' evaluates only the tiles under the uncropped patch and cannot be fed the gradient behind K9 / K10 / K11."""
+        if self.frame_stages_on() or self.embed_with is None or not patch.requires_grad or out_dtype != torch.bfloat16 or not torch.is_grad_enabled():
             return None
         return self.embed_with.patch_embed_params()
 

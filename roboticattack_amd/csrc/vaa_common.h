@@ -159,28 +159,8 @@ struct Samp {
 
 // bx/by: base coords of output column j / row i; th: row-major 2x3 affine.
 // grid = base @ theta^T as torch's CPU GEMM evaluates it (product, one FMA, plain add), then
-// grid_sample's unnormalise contracted into one FMA, clamp to the border, floor, weights.
-__device__ __forceinline__ Samp sample_pos(float bx, float by, const float* th) {
-    Samp s;
-    float gx = __builtin_fmaf(by, th[1], bx * th[0]) + th[2];
-    float gy = __builtin_fmaf(by, th[4], bx * th[3]) + th[5];
-    float ix = __builtin_fmaf(gx + 1.0f, 112.0f, -0.5f);
-    float iy = __builtin_fmaf(gy + 1.0f, 112.0f, -0.5f);
-    ix = fminf(223.0f, fmaxf(ix, 0.0f));
-    iy = fminf(223.0f, fmaxf(iy, 0.0f));
-    float xw = floorf(ix), yn = floorf(iy);
-    float w = ix - xw, e = 1.0f - w, n = iy - yn, so = 1.0f - n;
-    s.x0 = (int)xw;
-    s.y0 = (int)yn;
-    s.nw = so * e;
-    s.ne = so * w;
-    s.sw = n * e;
-    s.se = n * w;
-    return s;
-}
-
-// The same coordinates with the fractional parts kept (K2 stores {x0, y0, w, n} per pixel and forms the four corner weights
-// when it scatters: so*e, so*w, n*e, n*w with e = 1-w, so = 1-n — the products of sample_pos above, bit for bit).
+// grid_sample's unnormalise contracted into one FMA, clamp to the border, floor; (x0, y0) and the fractional parts w, n.
+// (K2 stores {x0, y0, w, n} per pixel and forms the four corner weights when it scatters: the products of samp_from_frac.)
 __device__ __forceinline__ void sample_pos_frac(float bx, float by, const float* th, int& x0, int& y0, float& w, float& n) {
     float gx = __builtin_fmaf(by, th[1], bx * th[0]) + th[2];
     float gy = __builtin_fmaf(by, th[4], bx * th[3]) + th[5];
@@ -201,6 +181,24 @@ __device__ __forceinline__ Samp samp_from_frac(int x0, int y0, float w, float n)
     s.x0 = x0; s.y0 = y0;
     s.nw = so * e; s.ne = so * w; s.sw = n * e; s.se = n * w;
     return s;
+}
+
+// the sample position with its bilinear corner weights
+__device__ __forceinline__ Samp sample_pos(float bx, float by, const float* th) {
+    int x0, y0;
+    float w, n;
+    sample_pos_frac(bx, by, th, x0, y0, w, n);
+    return samp_from_frac(x0, y0, w, n);
+}
+
+// The patch image b pastes: the batch's one patch [3,ph,pw], or with pdesc ([B,4] = {h_b, w_b, offset_b, 0}; resize_patch=True,
+// appply_random_transform.py:113-118) its own resized patch at patch + offset_b.
+__device__ __forceinline__ void patch_of(const int32_t* pdesc, int ph, int pw, const float* patch, int b, int& ph_b, int& pw_b, const float*& p_b) {
+    if (pdesc) {
+        ph_b = pdesc[4 * b]; pw_b = pdesc[4 * b + 1]; p_b = patch + pdesc[4 * b + 2];
+    } else {
+        ph_b = ph; pw_b = pw; p_b = patch;
+    }
 }
 
 // canvas = -100 everywhere with the patch pasted at (px,py) (appply_random_transform.py:111,125);
@@ -253,6 +251,42 @@ __device__ __forceinline__ void solve_interval(float a, float base, float lo, fl
         jl = 1e30f;
         jh = -1e30f;
     }
+}
+
+// Conservative COLUMN span of output row i of an image whose ph x pw patch is pasted at (px, py): pixels [jlo, jhi] may have a source
+// point with a corner on patch rows [v_lo, v_hi) (the whole patch: v_lo = 0, v_hi = ph); [0, -1] when the row is clear. theta_b: the
+// image's 2x3 affine, read only when geometry != 0 (a flag and not a nullable pointer: a null test on theta + 6b does not fold away).
+// INVARIANT: every role of both K1 kernels, K5 and K2 derive ownership and coverage from this one function — K1's roles split the
+// frame by it, and K2 (a workgroup per band of patch rows) walks exactly the pixels K1's footprint role evaluated, so no kept pixel's
+// gradient is lost.
+__device__ __forceinline__ void row_span(int px, int py, int ph, int pw, int v_lo, int v_hi, int geometry, const float* theta_b, int i, int& jlo, int& jhi) {
+    jlo = 0; jhi = -1;
+    if (geometry) {
+        float th[6];
+#pragma unroll
+        for (int z = 0; z < 6; ++z) th[z] = theta_b[z];
+        const PixAffine pa = pix_affine(th);
+        // source x must fall in [px-1, px+pw) (corner x0 or x0+1 on the patch), source y in [py+v_lo-1, py+v_hi); a side of the patch
+        // that lies on the frame edge also receives every clamped out-of-frame sample (padding_mode='border'): open to infinity
+        const float xlo = (px == 0) ? -1e30f : (float)(px - 1);
+        const float xhi = (px + pw == VAA_IMG) ? 1e30f : (float)(px + pw);
+        const float ylo = (py == 0 && v_lo == 0) ? -1e30f : (float)(py + v_lo - 1);
+        const float yhi = (py + ph == VAA_IMG && v_hi == ph) ? 1e30f : (float)(py + v_hi);
+        float jl = -1e30f, jh = 1e30f;
+        solve_interval(pa.a00, pa.a01 * (float)i + pa.c0, xlo, xhi, jl, jh);
+        solve_interval(pa.a10, pa.a11 * (float)i + pa.c1, ylo, yhi, jl, jh);
+        if (jl <= jh && v_lo < v_hi) {
+            jlo = (int)fmaxf(0.0f, floorf(jl) - 1.0f);
+            jhi = (int)fminf((float)(VAA_IMG - 1), ceilf(jh) + 1.0f);
+        }
+    } else if (i >= py + v_lo && i < py + v_hi) {
+        jlo = px;
+        jhi = px + pw - 1;
+    }
+    // an interval that lies wholly beyond the frame (possible when a side is open to +-infinity) clamps to jhi < jlo with jlo > 0;
+    // normalise every empty row to [0, -1] so that ALL roles see "nothing" (the background role of the planar K1 packs the count into
+    // 8 bits and would otherwise skip items nobody writes)
+    if (jhi < jlo) { jlo = 0; jhi = -1; }
 }
 
 // K4's per-element arithmetic (vaa_update.hip; also applied by the step epilogue when the update is fused into it: one source, same bits)

@@ -43,24 +43,8 @@ __global__ __launch_bounds__(kEvThreads) void patch_apply_eval_kernel(const Eval
         int jlo = 0, jhi = -1;
         if (gr < (long)a.B * VAA_IMG) {
             const int b = (int)(gr / VAA_IMG), i = (int)(gr % VAA_IMG);
-            const int px = a.xy[2 * b], py = a.xy[2 * b + 1];
-            if (a.geometry[b]) {
-                float th[6];
-#pragma unroll
-                for (int z = 0; z < 6; ++z) th[z] = a.theta[6 * b + z];
-                const PixAffine pa = pix_affine(th);
-                const float xlo = (px == 0) ? -1e30f : (float)(px - 1), xhi = (px + a.pw == VAA_IMG) ? 1e30f : (float)(px + a.pw);
-                const float ylo = (py == 0) ? -1e30f : (float)(py - 1), yhi = (py + a.ph == VAA_IMG) ? 1e30f : (float)(py + a.ph);
-                float jl = -1e30f, jh = 1e30f;
-                solve_interval(pa.a00, pa.a01 * (float)i + pa.c0, xlo, xhi, jl, jh);
-                solve_interval(pa.a10, pa.a11 * (float)i + pa.c1, ylo, yhi, jl, jh);
-                if (jl <= jh) { jlo = (int)fmaxf(0.0f, floorf(jl) - 1.0f); jhi = (int)fminf((float)(VAA_IMG - 1), ceilf(jh) + 1.0f); }
-            } else if (i >= py && i < py + a.ph) {
-                jlo = px;
-                jhi = px + a.pw - 1;
-            }
+            row_span(a.xy[2 * b], a.xy[2 * b + 1], a.ph, a.pw, 0, a.ph, a.geometry[b], a.theta + 6 * b, i, jlo, jhi);
         }
-        if (jhi < jlo) { jlo = 0; jhi = -1; }  // an interval wholly beyond the frame (side open to infinity) is an empty row
         rb_lo[tid] = (short)jlo;
         rb_hi[tid] = (short)jhi;
     }

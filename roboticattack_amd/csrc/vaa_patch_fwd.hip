@@ -30,14 +30,6 @@ struct FwdArgs {
     Norm6 nrm;
 };
 
-__device__ __forceinline__ void patch_of(const FwdArgs& a, int b, int& ph, int& pw, const float*& p) {
-    if (a.pdesc) {  // resize_patch=True (appply_random_transform.py:113-118): every image has its own resized patch
-        ph = a.pdesc[4 * b]; pw = a.pdesc[4 * b + 1]; p = a.patch + a.pdesc[4 * b + 2];
-    } else {
-        ph = a.ph; pw = a.pw; p = a.patch;
-    }
-}
-
 constexpr int kPix = 16;                                  // pixels per item: 48 B in (3 x 16 B), 2 x 16 B out per plane
 constexpr int kItemsPerRow = VAA_IMG / kPix;              // 14
 constexpr int kItemsPerImg = VAA_IMG * kItemsPerRow;      // 3136
@@ -46,38 +38,12 @@ constexpr int kMaxRows = 20;                              // rows one workgroup'
 
 // (bf16_rne / norm_pack / fill_norm_lut, the arithmetic of the camera-pixel LUT, live in vaa_common.h: K7 normalises with the same table)
 
-// Conservative COLUMN span of output row i of image b: pixels [jlo, jhi] may have a source point that touches the patch; jhi < jlo
-// (normalised to [0, -1]) when the row is clear. Every role of both K1 kernels derives its ownership from this one function.
+// row_span (vaa_common.h) of output row i of image b over the whole patch: every role of both K1 kernels derives its ownership from it
 __device__ __forceinline__ void row_span(const FwdArgs a, int b, int i, int& jlo, int& jhi) {
-    const int px = a.xy[2 * b], py = a.xy[2 * b + 1];
     int ph, pw;
     const float* unused;
-    patch_of(a, b, ph, pw, unused);
-    jlo = 0; jhi = -1;
-    if (a.geometry) {
-        float th[6];
-#pragma unroll
-        for (int z = 0; z < 6; ++z) th[z] = a.theta[6 * b + z];
-        const PixAffine pa = pix_affine(th);
-        const float xlo = (px == 0) ? -1e30f : (float)(px - 1);
-        const float xhi = (px + pw == VAA_IMG) ? 1e30f : (float)(px + pw);
-        const float ylo = (py == 0) ? -1e30f : (float)(py - 1);
-        const float yhi = (py + ph == VAA_IMG) ? 1e30f : (float)(py + ph);
-        float jl = -1e30f, jh = 1e30f;
-        solve_interval(pa.a00, pa.a01 * (float)i + pa.c0, xlo, xhi, jl, jh);
-        solve_interval(pa.a10, pa.a11 * (float)i + pa.c1, ylo, yhi, jl, jh);
-        if (jl <= jh) {
-            jlo = (int)fmaxf(0.0f, floorf(jl) - 1.0f);
-            jhi = (int)fminf((float)(VAA_IMG - 1), ceilf(jh) + 1.0f);
-        }
-    } else if (i >= py && i < py + ph) {
-        jlo = px;
-        jhi = px + pw - 1;
-    }
-    // an interval that lies wholly beyond the frame (possible when a side is open to +-infinity: patch on the frame edge) clamps to
-    // jhi < jlo with jlo > 0; normalise every empty row to [0, -1] so that ALL roles see "nothing" (the background role of the planar
-    // kernel packs the count into 8 bits and would otherwise skip items nobody writes)
-    if (jhi < jlo) { jlo = 0; jhi = -1; }
+    patch_of(a.pdesc, a.ph, a.pw, a.patch, b, ph, pw, unused);
+    row_span(a.xy[2 * b], a.xy[2 * b + 1], ph, pw, 0, ph, a.geometry, a.theta + 6 * b, i, jlo, jhi);
 }
 
 // Conservative ITEM bounds of output row i of image b: items [it_lo, it_hi] (16-pixel groups) may contain a pixel whose
@@ -90,31 +56,73 @@ __device__ __forceinline__ void row_items(const FwdArgs a, int b, int i, int& it
     it_hi = (jhi < jlo) ? -1 : (jhi >> 4);
 }
 
+// Output pixel (i, j) of image b in the footprint role of both K1 kernels: L[c] = the packed {bf16 norm0, bf16 norm1} of channel c,
+// kept[c] = the channel shows the patch (else L[c] is the camera byte's LUT value). patch: image b's [3,ph,pw], pasted at (px, py); th:
+// its affine (read with geometry only); bgrid / lut: the workgroup's base_coord and fill_norm_lut tables.
+// Every load of the pixel (3 camera bytes, 12 patch texels, then the LUT) is issued before anything is consumed: texel addresses are
+// clamped into the patch so the gather is branch-free, the canvas rule (-100 outside the paste, 0 beyond the frame) is applied to the
+// loaded values afterwards -> one memory latency per pixel instead of two.
+__device__ __forceinline__ void footprint_pixel(const uint8_t* img, const float* patch, int ph, int pw, int px, int py, const float* th,
+                                                const float* bgrid, const uint32_t* lut, const Norm6& nrm, int mask_mode, int geometry,
+                                                int b, int i, int j, uint32_t (&L)[3], bool (&kept)[3]) {
+    const uint8_t* sp = img + ((size_t)(b * VAA_IMG + i) * VAA_IMG + j) * 3;
+    const uint32_t by0 = sp[0], by1 = sp[1], by2 = sp[2];
+    const int plane = ph * pw;
+    float cv[3];
+    bool inside;
+    if (geometry) {
+        const Samp s = sample_pos(bgrid[j], bgrid[i], th);
+        const int u0 = s.x0 - px, v0 = s.y0 - py;
+        inside = !(u0 < -1 || u0 >= pw || v0 < -1 || v0 >= ph);
+        const int uc0 = min(max(u0, 0), pw - 1), uc1 = min(max(u0 + 1, 0), pw - 1);
+        const int vc0 = min(max(v0, 0), ph - 1), vc1 = min(max(v0 + 1, 0), ph - 1);
+        float t[3][4];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float* pc = patch + c * plane;
+            t[c][0] = pc[vc0 * pw + uc0]; t[c][1] = pc[vc0 * pw + uc1];
+            t[c][2] = pc[vc1 * pw + uc0]; t[c][3] = pc[vc1 * pw + uc1];
+        }
+        const bool ux0 = (unsigned)u0 < (unsigned)pw, ux1 = (unsigned)(u0 + 1) < (unsigned)pw;
+        const bool vy0 = (unsigned)v0 < (unsigned)ph, vy1 = (unsigned)(v0 + 1) < (unsigned)ph;
+        const bool fx1 = s.x0 + 1 < VAA_IMG, fy1 = s.y0 + 1 < VAA_IMG;  // (x0, y0) itself is always inside the frame
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float vnw = (ux0 && vy0) ? t[c][0] : -100.0f;
+            const float vne = !fx1 ? 0.0f : ((ux1 && vy0) ? t[c][1] : -100.0f);
+            const float vsw = !fy1 ? 0.0f : ((ux0 && vy1) ? t[c][2] : -100.0f);
+            const float vse = !(fx1 && fy1) ? 0.0f : ((ux1 && vy1) ? t[c][3] : -100.0f);
+            cv[c] = __builtin_fmaf(vse, s.se, __builtin_fmaf(vsw, s.sw, __builtin_fmaf(vne, s.ne, vnw * s.nw)));
+        }
+    } else {
+        const int u = j - px, v = i - py;
+        inside = (unsigned)u < (unsigned)pw && (unsigned)v < (unsigned)ph;
+        const int uc = min(max(u, 0), pw - 1), vc = min(max(v, 0), ph - 1);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) cv[c] = patch[c * plane + vc * pw + uc];
+    }
+    L[0] = lut[by0]; L[1] = lut[256 + by1]; L[2] = lut[512 + by2];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) kept[c] = false;
+    if (inside) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            if (keep_rule(cv[c], mask_mode)) { L[c] = norm_pack(cv[c], nrm, c); kept[c] = true; }
+    }
+}
+
 // One launch, two workgroup roles:
 //   blockIdx.x >= n_fp : BACKGROUND — 256 items of 16 pixels, pure streaming through the LUT; items that may show the
 //                        patch are skipped entirely (not written).
 //   blockIdx.x <  n_fp : FOOTPRINT  — owns exactly the skipped items of one image (a 1/fsplit share of them), one LANE per
 //                        pixel: LUT value, exact warp sample, mask, normalise, 2-byte stores; keep bits by wave ballot.
 // The two roles never write the same byte, so no ordering between workgroups is needed.
-#ifdef VAA_K1_TIMING
-__device__ long long* vaa_k1_dbg = nullptr;
-#define K1_T0() long long k1_t = wall_clock64(); const long long k1_start = k1_t; long long k1_acc[6] = {0, 0, 0, 0, 0, 0};
-#define K1_STAMP(i) { const long long tn = wall_clock64(); k1_acc[i] += tn - k1_t; k1_t = tn; }
-#define K1_FLUSH(role) if ((threadIdx.x & 63) == 0 && vaa_k1_dbg) { long long* d = vaa_k1_dbg + ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8; \
-    for (int z = 0; z < 6; ++z) d[z] = k1_acc[z]; d[6] = role; d[7] = k1_start; }
-#else
-#define K1_T0()
-#define K1_STAMP(i)
-#define K1_FLUSH(role)
-#endif
-
 __global__ __launch_bounds__(kFwdThreads) void patch_apply_fwd_kernel(const FwdArgs a, int n_fp, int fsplit) {
     __shared__ uint32_t lut[3 * 256];
     __shared__ float bgrid[VAA_IMG];
     __shared__ uint32_t row_word[VAA_IMG];  // footprint role: (it_lo << 8) | n_items per row; background: first kMaxRows rows
     __shared__ int red_min, red_max, red_n;
     const int tid = threadIdx.x;
-    K1_T0()
     const bool bg = (int)blockIdx.x >= n_fp;
     // Background role: the input bytes of this lane's two half items depend on nothing but the item index, so their loads are
     // issued first and fly while the LUT is built and the placement (xy, theta -> row table) is fetched.
@@ -144,9 +152,7 @@ __global__ __launch_bounds__(kFwdThreads) void patch_apply_fwd_kernel(const FwdA
             if (gr < (long)a.B * VAA_IMG) row_items(a, (int)(gr / VAA_IMG), (int)(gr % VAA_IMG), lo, hi);
             row_word[tid] = ((uint32_t)(lo & 0xff) << 8) | (uint32_t)((hi - lo + 1) & 0xff);
         }
-        K1_STAMP(0)
         __syncthreads();
-        K1_STAMP(1)
         // A wave owns 64 consecutive items = 1024 pixels. Lane l handles two HALF items: pixels [8l, 8l+8) of the wave's first
         // 512 pixels and the same of its second 512, so that every store instruction writes 64 x 16 B = 1 KB CONTIGUOUS bytes
         // of a plane (a thread storing its own 16 pixels as two 16 B halves leaves every 128 B line to be completed by a
@@ -192,8 +198,6 @@ __global__ __launch_bounds__(kFwdThreads) void patch_apply_fwd_kernel(const FwdA
                 for (int c = 0; c < 3; ++c) a.keep[kbase + (size_t)c * (VAA_NPIX / 8)] = (uint8_t)0;
             }
         }
-        K1_STAMP(2)
-        K1_FLUSH(0)
         return;
     }
 
@@ -212,7 +216,6 @@ __global__ __launch_bounds__(kFwdThreads) void patch_apply_fwd_kernel(const FwdA
         if ((tid & 63) == 0) { atomicMin(&red_min, wmin); atomicMax(&red_max, wmax); atomicMax(&red_n, wn); }
     }
     __syncthreads();
-    K1_STAMP(0)
     const int rmin = red_min, nrows = red_max - rmin + 1;
     if (nrows <= 0) return;
     const int nseg = (red_n + 1) >> 1;                             // half-wave = 32 pixels = 2 items per slot
@@ -222,8 +225,7 @@ __global__ __launch_bounds__(kFwdThreads) void patch_apply_fwd_kernel(const FwdA
     const int px = a.xy[2 * b], py = a.xy[2 * b + 1];
     int ph, pw;
     const float* patch;
-    patch_of(a, b, ph, pw, patch);
-    const int plane = ph * pw;
+    patch_of(a.pdesc, a.ph, a.pw, a.patch, b, ph, pw, patch);
     float th[6] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f};
     if (a.geometry) {
 #pragma unroll
@@ -240,52 +242,7 @@ __global__ __launch_bounds__(kFwdThreads) void patch_apply_fwd_kernel(const FwdA
         uint32_t L[3] = {0u, 0u, 0u};
         bool kept[3] = {false, false, false};
         if (active) {
-            // every load of this pixel (3 camera bytes, 12 patch texels) is issued before anything is consumed: texel addresses
-            // are clamped into the patch so the gather is branch-free, the canvas rule (-100 outside the paste, 0 beyond the
-            // frame) is applied to the loaded values afterwards -> one memory latency per slot instead of two.
-            const uint8_t* sp = a.img + ((size_t)(b * VAA_IMG + i) * VAA_IMG + j) * 3;
-            const uint32_t by0 = sp[0], by1 = sp[1], by2 = sp[2];
-            float cv[3];
-            bool inside;
-            if (a.geometry) {
-                const Samp s = sample_pos(bgrid[j], bgrid[i], th);
-                const int u0 = s.x0 - px, v0 = s.y0 - py;
-                inside = !(u0 < -1 || u0 >= pw || v0 < -1 || v0 >= ph);
-                const int uc0 = min(max(u0, 0), pw - 1), uc1 = min(max(u0 + 1, 0), pw - 1);
-                const int vc0 = min(max(v0, 0), ph - 1), vc1 = min(max(v0 + 1, 0), ph - 1);
-                float t[3][4];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float* pc = patch + c * plane;
-                    t[c][0] = pc[vc0 * pw + uc0]; t[c][1] = pc[vc0 * pw + uc1];
-                    t[c][2] = pc[vc1 * pw + uc0]; t[c][3] = pc[vc1 * pw + uc1];
-                }
-                const bool ux0 = (unsigned)u0 < (unsigned)pw, ux1 = (unsigned)(u0 + 1) < (unsigned)pw;
-                const bool vy0 = (unsigned)v0 < (unsigned)ph, vy1 = (unsigned)(v0 + 1) < (unsigned)ph;
-                const bool fx1 = s.x0 + 1 < VAA_IMG, fy1 = s.y0 + 1 < VAA_IMG;  // (x0, y0) itself is always inside the frame
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float vnw = (ux0 && vy0) ? t[c][0] : -100.0f;
-                    const float vne = !fx1 ? 0.0f : ((ux1 && vy0) ? t[c][1] : -100.0f);
-                    const float vsw = !fy1 ? 0.0f : ((ux0 && vy1) ? t[c][2] : -100.0f);
-                    const float vse = !(fx1 && fy1) ? 0.0f : ((ux1 && vy1) ? t[c][3] : -100.0f);
-                    cv[c] = __builtin_fmaf(vse, s.se, __builtin_fmaf(vsw, s.sw, __builtin_fmaf(vne, s.ne, vnw * s.nw)));
-                }
-            } else {
-                const int u = j - px, v = i - py;
-                inside = (unsigned)u < (unsigned)pw && (unsigned)v < (unsigned)ph;
-                const int uc = min(max(u, 0), pw - 1), vc = min(max(v, 0), ph - 1);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) cv[c] = patch[c * plane + vc * pw + uc];
-            }
-            K1_STAMP(1)
-            L[0] = lut[by0]; L[1] = lut[256 + by1]; L[2] = lut[512 + by2];
-            K1_STAMP(2)
-            if (inside) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    if (keep_rule(cv[c], a.mask_mode)) { L[c] = norm_pack(cv[c], a.nrm, c); kept[c] = true; }
-            }
+            footprint_pixel(a.img, patch, ph, pw, px, py, th, bgrid, lut, a.nrm, a.mask_mode, a.geometry, b, i, j, L, kept);
             const size_t o = ((size_t)b * 6 * VAA_IMG + i) * VAA_IMG + j;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
@@ -304,9 +261,7 @@ __global__ __launch_bounds__(kFwdThreads) void patch_apply_fwd_kernel(const FwdA
                 }
             }
         }
-        K1_STAMP(3)
     }
-    K1_FLUSH(1)
 }
 
 
@@ -423,16 +378,14 @@ __global__ __launch_bounds__(kFwdThreads) void patch_apply_tiles_kernel(const Fw
     const int px = a.xy[2 * b], py = a.xy[2 * b + 1];
     int ph, pw;
     const float* patch;
-    patch_of(a, b, ph, pw, patch);
-    const int plane = ph * pw;
+    patch_of(a.pdesc, a.ph, a.pw, a.patch, b, ph, pw, patch);
     float th[6] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f};
     if (a.geometry) {
 #pragma unroll
         for (int z = 0; z < 6; ++z) th[z] = a.theta[6 * b + z];
     }
-    // One tile per iteration, one lane per pixel: wave w takes rows 4w..4w+3 (14 lanes = one row = one keep word). Every load of a pixel
-    // (3 camera bytes, 12 patch texels at addresses clamped into the patch) is issued before anything is consumed; the canvas rule (-100
-    // outside the paste, 0 beyond the frame) is applied to the loaded values. No barrier in the loop: byte w of a tile's flag word is wave w's.
+    // One tile per iteration, one lane per pixel (footprint_pixel): wave w takes rows 4w..4w+3 (14 lanes = one row = one keep word).
+    // No barrier in the loop: byte w of a tile's flag word is wave w's.
     const int yr = lane / kTS, x = lane - yr * kTS, y = 4 * wv + yr;
     const bool active = lane < 4 * kTS && y < kTS;
     for (int ti = chunk; ti < M; ti += fsplit) {
@@ -441,50 +394,7 @@ __global__ __launch_bounds__(kFwdThreads) void patch_apply_tiles_kernel(const Fw
         uint32_t L[3] = {0u, 0u, 0u};
         bool kept[3] = {false, false, false};
         if (active) {
-            const uint8_t* sp = a.img + ((size_t)(b * VAA_IMG + i) * VAA_IMG + j) * 3;
-            const uint32_t by0 = sp[0], by1 = sp[1], by2 = sp[2];
-            float cv[3];
-            bool inside;
-            int rx0 = j, ry0 = i;
-            float rwf = 0.0f, rnf = 0.0f;
-            if (a.geometry) {
-                sample_pos_frac(bgrid[j], bgrid[i], th, rx0, ry0, rwf, rnf);
-                const Samp s = samp_from_frac(rx0, ry0, rwf, rnf);  // the products of sample_pos, bit for bit
-                const int u0 = s.x0 - px, v0 = s.y0 - py;
-                inside = !(u0 < -1 || u0 >= pw || v0 < -1 || v0 >= ph);
-                const int uc0 = min(max(u0, 0), pw - 1), uc1 = min(max(u0 + 1, 0), pw - 1);
-                const int vc0 = min(max(v0, 0), ph - 1), vc1 = min(max(v0 + 1, 0), ph - 1);
-                float tx4[3][4];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float* pc = patch + c * plane;
-                    tx4[c][0] = pc[vc0 * pw + uc0]; tx4[c][1] = pc[vc0 * pw + uc1];
-                    tx4[c][2] = pc[vc1 * pw + uc0]; tx4[c][3] = pc[vc1 * pw + uc1];
-                }
-                const bool ux0 = (unsigned)u0 < (unsigned)pw, ux1 = (unsigned)(u0 + 1) < (unsigned)pw;
-                const bool vy0 = (unsigned)v0 < (unsigned)ph, vy1 = (unsigned)(v0 + 1) < (unsigned)ph;
-                const bool fx1 = s.x0 + 1 < VAA_IMG, fy1 = s.y0 + 1 < VAA_IMG;  // (x0, y0) itself is always inside the frame
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float vnw = (ux0 && vy0) ? tx4[c][0] : -100.0f;
-                    const float vne = !fx1 ? 0.0f : ((ux1 && vy0) ? tx4[c][1] : -100.0f);
-                    const float vsw = !fy1 ? 0.0f : ((ux0 && vy1) ? tx4[c][2] : -100.0f);
-                    const float vse = !(fx1 && fy1) ? 0.0f : ((ux1 && vy1) ? tx4[c][3] : -100.0f);
-                    cv[c] = __builtin_fmaf(vse, s.se, __builtin_fmaf(vsw, s.sw, __builtin_fmaf(vne, s.ne, vnw * s.nw)));
-                }
-            } else {
-                const int u = j - px, v = i - py;
-                inside = (unsigned)u < (unsigned)pw && (unsigned)v < (unsigned)ph;
-                const int uc = min(max(u, 0), pw - 1), vc = min(max(v, 0), ph - 1);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) cv[c] = patch[c * plane + vc * pw + uc];
-            }
-            L[0] = lut[by0]; L[1] = lut[256 + by1]; L[2] = lut[512 + by2];
-            if (inside) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    if (keep_rule(cv[c], a.mask_mode)) { L[c] = norm_pack(cv[c], a.nrm, c); kept[c] = true; }
-            }
+            footprint_pixel(a.img, patch, ph, pw, px, py, th, bgrid, lut, a.nrm, a.mask_mode, a.geometry, b, i, j, L, kept);
             const size_t e = ((size_t)b * 256 + t) * kTElems + y * kTS + x;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
@@ -544,10 +454,6 @@ static int launch_patch_apply(const char* who, const uint8_t* img_u8, const floa
 }
 
 }  // namespace vaa
-
-#ifdef VAA_K1_TIMING
-extern "C" int vaa_k1_set_debug(long long* p) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(vaa::vaa_k1_dbg), &p, sizeof(p)); }
-#endif
 
 extern "C" int vaa_patch_apply_fwd(const uint8_t* img_u8, const float* patch, const int32_t* xy, const float* theta, int B,
                                    int ph, int pw, int geometry, int mask_mode, const float* mean6, const float* std6,

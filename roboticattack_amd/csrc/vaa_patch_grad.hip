@@ -57,9 +57,6 @@ struct GradArgs {
 
 constexpr int kTilePx = 14, kTilesPerSide = 16, kTileElems = 3 * kTilePx * kTilePx;  // ViT patch-embed tiling of the 224x224 frame
 
-#ifdef VAA_K2_TIMING
-__device__ long long* vaa_k2_dbg = nullptr;
-#endif
 constexpr int kImgsPerPass = 8;   // images whose row tables are built together (one barrier set per pass)
 constexpr int kCBits = 30;        // a contribution fl(G*w) is rounded to an integer of < 2^30 relative to the workgroup's exponent
 constexpr int kExpUnset = -100000;
@@ -105,13 +102,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
     if (tid < VAA_IMG) bgrid[tid] = base_coord(tid);
     if (tid < 3) round_max[tid] = 0u;
     if (tid == 0) nonfinite = 0;
-#ifdef VAA_K2_TIMING
-    long long tacc[6] = {0, 0, 0, 0, 0, 0};
-    long long tlast = wall_clock64();
-#define K2_STAMP(i) { const long long tn = wall_clock64(); tacc[i] += tn - tlast; tlast = tn; }
-#else
-#define K2_STAMP(i)
-#endif
     int E = kExpUnset;  // exponent of the tile's fixed-point format (workgroup-uniform): quantum = 2^(E + 1 - kCBits)
     int rnd = 0;        // round counter (workgroup-uniform)
     long absorbed = 0;  // footprint pixels added into the tile since the last flush (workgroup-uniform)
@@ -178,34 +168,11 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
                 int len = 0;
                 if (q < nimg && i < VAA_IMG) {
                     const int b = b0 + q * gx;
-                    const int px = a.xy[2 * b], py = a.xy[2 * b + 1];
-                    const int ph = MULTI ? a.pdesc[4 * b] : a.ph, pw = MULTI ? a.pdesc[4 * b + 1] : a.pw;
-                    int jlo = 0, jhi = -1;
-                    if (a.geometry) {
-                        float th[6];
-    #pragma unroll
-                        for (int z = 0; z < 6; ++z) th[z] = a.theta[6 * b + z];
-                        const PixAffine pa = pix_affine(th);
-                        // source x must fall in [px-1, px+pw) (corner x0 or x0+1 on the patch); a side that lies on the
-                        // frame edge also receives every clamped out-of-frame sample (padding_mode='border').
-                        const float xlo = (px == 0) ? -1e30f : (float)(px - 1);
-                        const float xhi = (px + pw == VAA_IMG) ? 1e30f : (float)(px + pw);
-                        // ... restricted to this workgroup's band of patch rows [v_lo, vb_hi): source y in [py + v_lo - 1, py + vb_hi)
-                        const int vb_hi = min(ph, v_lo + a.band_rows);
-                        const float ylo = (py == 0 && v_lo == 0) ? -1e30f : (float)(py + v_lo - 1);
-                        const float yhi = (py + ph == VAA_IMG && vb_hi == ph) ? 1e30f : (float)(py + vb_hi);
-                        float jl = -1e30f, jh = 1e30f;
-                        solve_interval(pa.a00, pa.a01 * (float)i + pa.c0, xlo, xhi, jl, jh);
-                        solve_interval(pa.a10, pa.a11 * (float)i + pa.c1, ylo, yhi, jl, jh);
-                        if (jl <= jh && v_lo < ph) {
-                            jlo = (int)fmaxf(0.0f, floorf(jl) - 1.0f);
-                            jhi = (int)fminf((float)(VAA_IMG - 1), ceilf(jh) + 1.0f);
-                        }
-                    } else if (i >= py + v_lo && i < py + min(ph, v_lo + a.band_rows)) {
-                        jlo = px;
-                        jhi = px + pw - 1;
-                    }
-                    if (jhi < jlo) { jlo = 0; jhi = -1; }  // an interval wholly beyond the frame (side open to infinity) is an empty row
+                    int ph, pw, jlo, jhi;
+                    const float* unused;
+                    patch_of(MULTI ? a.pdesc : nullptr, a.ph, a.pw, a.patch, b, ph, pw, unused);
+                    // restricted to this workgroup's band of patch rows (empty when the band lies below this image's patch)
+                    row_span(a.xy[2 * b], a.xy[2 * b + 1], ph, pw, v_lo, min(ph, v_lo + a.band_rows), a.geometry, a.theta + 6 * b, i, jlo, jhi);
                     jlo &= ~1;  // a lane's pixel pair starts at an even column: one aligned 4-byte load per plane
                     len = max(0, jhi - jlo + 1);
                     row_word[q][i] = ((uint32_t)jlo << 16) | (uint32_t)len;
@@ -219,12 +186,13 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
             }
         }
         __syncthreads();
-        K2_STAMP(0)
 
         for (int q = 0; q < nimg; ++q) {
             const int b = b0 + q * gx;
             const int rmin = row_min[q], nrows = row_max[q] - rmin + 1;
-            const int ph = MULTI ? a.pdesc[4 * b] : a.ph, pw = MULTI ? a.pdesc[4 * b + 1] : a.pw;
+            int ph, pw;
+            const float* pimg;
+            patch_of(MULTI ? a.pdesc : nullptr, a.ph, a.pw, a.patch, b, ph, pw, pimg);
             const int plane = ph * pw;
             const int v_hi = min(ph, v_lo + a.band_rows);
             if (nrows > 0 && v_lo < ph) {
@@ -237,7 +205,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
 #pragma unroll
                     for (int z = 0; z < 6; ++z) th[z] = a.theta[6 * b + z];
                 }
-                const float* pimg = MULTI ? a.patch + a.pdesc[4 * b + 2] : a.patch;
                 const uint16_t* gimg = a.g + (size_t)b * 6 * VAA_NPIX;
                 const bool ktiled = TILED && HASK && a.keep_t != nullptr;  // workgroup-uniform
                 const uint8_t* kimg = (HASK && !ktiled) ? a.keep + (size_t)b * 3 * (VAA_NPIX / 8) : nullptr;  // HASK: K1's keep bits are given
@@ -352,7 +319,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
                             }
                         }
                     }
-                    K2_STAMP(1)
                     float lmax = 0.0f;
                     bool bad = false;
 #pragma unroll
@@ -388,9 +354,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
                     // slot (rnd+1)%3 was last read after the barrier of round rnd-2, i.e. before every thread arrived at the barrier
                     // of round rnd-1, and is next written after this round's barrier: resetting it here races with neither
                     if (tid == 0) round_max[(rnd + 1) % 3] = 0u;
-                    K2_STAMP(2)
                     __syncthreads();
-                    K2_STAMP(3)
                     const uint32_t mbits = round_max[rnd % 3];
                     if (mbits == 0u) continue;  // nothing kept in this round (workgroup-uniform)
                     int e = (int)(mbits >> 23) - 127;  // floor(log2(max |G|)) (denormals: -127)
@@ -441,7 +405,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
                                 }
                             }
                         }
-                    K2_STAMP(4)
                 }
             }
             if (MULTI) {  // per-image output: write this image's band of d L / d (its own patch), reset the tile
@@ -455,11 +418,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
     if (MULTI) return;
     __syncthreads();
     drain(a.partial + (size_t)blockIdx.x * 3 * a.ph * a.pw, a.ph, a.pw, flushed, false);
-#ifdef VAA_K2_TIMING
-    K2_STAMP(5)
-    if ((tid & 63) == 0 && a.geff == nullptr && vaa_k2_dbg)
-        for (int z = 0; z < 6; ++z) vaa_k2_dbg[((size_t)blockIdx.x * 16 + (tid >> 6)) * 6 + z] = tacc[z];
-#endif
 }
 
 // gpatch[e] = sum_p partial[p][e] in a fixed two-level order (16 interleaved slices, then slice 0..15), fp64.
@@ -599,10 +557,6 @@ static int launch_scatter_multi(GradArgs a, hipStream_t st, const char* who) {
 }
 
 }  // namespace vaa
-
-#ifdef VAA_K2_TIMING
-extern "C" int vaa_k2_set_debug(long long* p) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(vaa::vaa_k2_dbg), &p, sizeof(p)); }
-#endif
 
 extern "C" size_t vaa_patch_grad_ws_bytes(int B, int ph, int pw) {
     if (B <= 0 || ph <= 0 || pw <= 0) return 0;
@@ -936,10 +890,6 @@ __global__ __launch_bounds__(kEmbedFastThreads) void embed_dgrad_tiles_lds_kerne
     }
     const int b = unit % a.B, mg0 = (unit / a.B) % ny;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, g = lane >> 4;
-#ifdef VAA_K2_TIMING
-    long long tacc[6] = {0, 0, 0, 0, 0, 0};
-    long long tlast = wall_clock64();
-#endif
 
     bool flag = false;
     if (tid < 256) flag = a.flags ? a.flags[(size_t)b * 256 + tid] != 0 : tile_has_kept_pixel(a.keep + (size_t)b * 3 * (VAA_NPIX / 8), tid >> 4, tid & 15);
@@ -952,7 +902,6 @@ __global__ __launch_bounds__(kEmbedFastThreads) void embed_dgrad_tiles_lds_kerne
     if (flag) tiles[slot] = (int16_t)tid;
     __syncthreads();
 
-    K2_STAMP(0)
     // this wave's column blocks: [nb0, nb0 + nbw) of the workgroup's range [ch * per, min(37, (ch + 1) * per))
     const int per = (kNBlocks + nch - 1) / nch;
     const int wg_lo = ch * per, wg_n = max(0, min(kNBlocks, wg_lo + per) - wg_lo);
@@ -1032,7 +981,6 @@ __global__ __launch_bounds__(kEmbedFastThreads) void embed_dgrad_tiles_lds_kerne
                 }
             }
             __syncthreads();
-            K2_STAMP(1 + 2 * tower)
             // ---- barrier-free k-loop ----
             v4f_e acc[NB][4];
 #pragma unroll
@@ -1084,7 +1032,6 @@ __global__ __launch_bounds__(kEmbedFastThreads) void embed_dgrad_tiles_lds_kerne
                             res[j][q][r] = (tower != t_lo) ? res[j][q][r] + v : v;
                         }
                     }
-            K2_STAMP(2 + 2 * tower)
         }
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
@@ -1103,12 +1050,7 @@ __global__ __launch_bounds__(kEmbedFastThreads) void embed_dgrad_tiles_lds_kerne
                     }
                 }
         }
-        K2_STAMP(5)
     }
-#ifdef VAA_K2_TIMING  // tools/scratch/k2etiming.py: flags / stage 0 / k-loop 0 / stage 1 / k-loop 1 / store, per wave
-    if (lane == 0 && vaa_k2_dbg)
-        for (int z = 0; z < 6; ++z) vaa_k2_dbg[((size_t)blockIdx.x * 16 + wv) * 6 + z] = tacc[z];
-#endif
 }
 
 }  // namespace vaa

@@ -14,6 +14,7 @@
 #include <stdio.h>
 
 #include <initializer_list>
+#include <string>
 
 #include "../../include/vaa.h"
 
@@ -32,13 +33,14 @@ constexpr unsigned VAA_ASYNC_DECODE_POS = 4u;    // vaa_model_attention_decode: 
 int launch_partial_reduce(const float* partial, float* gpatch, int n, int nparts, hipStream_t st, const char* who);
 
 // Argument rules every patch entry point shares (host). check_patch_size: the batch / patch sizes and the frame (what vaa_patch_apply_eval,
-// which has no mask mode and takes its geometry per image, checks); check_patch_call adds the mask mode rules of K1 / K2 / K2'.
-inline int check_patch_size(const char* who, int B, int h, int w) {
+// which has no mask mode and takes its geometry per image, checks; frame_bound = false: the sizes alone); check_patch_call adds the mask mode
+// rules of K1 / K2 / K2'.
+inline int check_patch_size(const char* who, int B, int h, int w, bool frame_bound = true) {
     if (B < 0 || h <= 0 || w <= 0) {
         set_error("%s: bad sizes (B=%d ph=%d pw=%d)", who, B, h, w);
         return VAA_E_INVALID;
     }
-    if (h > VAA_IMG || w > VAA_IMG) {
+    if (frame_bound && (h > VAA_IMG || w > VAA_IMG)) {
         set_error("%s: patch %dx%d larger than the %dx%d frame", who, h, w, VAA_IMG, VAA_IMG);
         return VAA_E_UNSUPPORTED;
     }
@@ -84,6 +86,44 @@ inline int check_stage_call(const char* who, int B, long max_B, const char* batc
         return VAA_E_INVALID;
     }
     return VAA_OK;
+}
+
+// The argument rules of the per-image patch stages (K0 resize, K0c jitter; host): a null pointer among `ptrs`, then the sizes. The stages differ
+// in one rule, kept per stage (DESIGN.md lists them): K0c bounds the patch by the frame (check_patch_size), K0 only wants positive sizes.
+inline int check_patch_stage(const char* who, std::initializer_list<const void*> ptrs, int B, int ph, int pw, bool frame_bound) {
+    for (const void* p : ptrs)
+        if (!p) {
+            set_error("%s: null pointer argument", who);
+            return VAA_E_INVALID;
+        }
+    return check_patch_size(who, B, ph, pw, frame_bound);
+}
+
+// the `parts` partial gradients [3*ph*pw] an adjoint of these stages leaves to the fixed-order reduce; one part is written to gpatch itself
+inline size_t patch_stage_ws_bytes(int parts, int ph, int pw) { return parts > 1 ? (size_t)parts * 3 * ph * pw * sizeof(float) : 0; }
+
+// What both adjoint entry points of the per-image patch stages do around their kernel (host), in the order a caller observes it: an empty batch
+// zeroes gpatch (when there is one to zero) and, with empty_ok, is VAA_OK whatever else was passed (K0c; K0 goes on to the argument check, so
+// B == 0 with a null gpatch is its null-pointer error); the argument check; the workspace; launch(out) with out = the workspace when
+// parts > 1, else gpatch; check_launch; the fixed-order reduce of the parts.
+template <typename Launch>
+inline int patch_stage_bwd(const char* who, std::initializer_list<const void*> ptrs, int B, int ph, int pw, bool frame_bound, bool empty_ok, int parts,
+                           float* gpatch, void* ws, size_t ws_bytes, hipStream_t st, Launch launch) {
+    if (B == 0 && gpatch && ph > 0 && pw > 0)
+        return hipMemsetAsync(gpatch, 0, (size_t)3 * ph * pw * sizeof(float), st) == hipSuccess ? VAA_OK
+                                                                                                  : check_launch((std::string(who) + "(memset)").c_str());
+    if (B == 0 && empty_ok) return VAA_OK;
+    int rc = check_patch_stage(who, ptrs, B, ph, pw, frame_bound);
+    if (rc != VAA_OK) return rc;
+    const size_t need = patch_stage_ws_bytes(parts, ph, pw);
+    if (need > 0 && (!ws || ws_bytes < need)) {
+        set_error("%s: workspace %zu B < required %zu B", who, ws_bytes, need);
+        return VAA_E_WORKSPACE;
+    }
+    launch(parts > 1 ? (float*)ws : gpatch);
+    rc = check_launch(who);
+    if (rc != VAA_OK || parts == 1) return rc;
+    return launch_partial_reduce((const float*)ws, gpatch, 3 * ph * pw, parts, st, (std::string(who) + "(reduce)").c_str());
 }
 
 // 1/std of the six normalisation channels, rounded from double: the factor K2 / K2' apply to the incoming gradient

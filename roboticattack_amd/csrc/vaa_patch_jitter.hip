@@ -168,55 +168,30 @@ __global__ __launch_bounds__(kJitThreads) void patch_jitter_bwd_kernel(JitterArg
     }
 }
 
-static int check_jitter_args(const char* who, const void* p0, const void* p1, const void* p2, const void* p3, const void* p4, int B, int ph, int pw) {
-    if (!p0 || !p1 || !p2 || !p3 || !p4) {
-        set_error("%s: null pointer argument", who);
-        return VAA_E_INVALID;
-    }
-    return check_patch_size(who, B, ph, pw);
-}
-
 }  // namespace vaa
 
 extern "C" int vaa_patch_jitter_fwd(const float* patch, int ph, int pw, const float* factors, const int32_t* pdesc, int B, float* packed,
                                     void* stream) {
     using namespace vaa;
     if (B == 0) return VAA_OK;
-    int rc = check_jitter_args("vaa_patch_jitter_fwd", patch, factors, pdesc, packed, packed, B, ph, pw);
+    int rc = check_patch_stage("vaa_patch_jitter_fwd", {patch, factors, pdesc, packed}, B, ph, pw, /*frame_bound=*/true);
     if (rc != VAA_OK) return rc;
-    JitterArgs a;
-    a.patch = patch; a.factors = factors; a.pdesc = pdesc; a.gpacked = nullptr; a.out = packed; a.err_word = async_error_word();
-    a.B = B; a.ph = ph; a.pw = pw;
+    const JitterArgs a{patch, factors, pdesc, nullptr, packed, async_error_word(), B, ph, pw};
     VAA_LAUNCH(patch_jitter_fwd_kernel, dim3(B), dim3(kJitThreads), 0, (hipStream_t)stream, a);
     return check_launch("vaa_patch_jitter_fwd");
 }
 
 extern "C" size_t vaa_patch_jitter_ws_bytes(int B, int ph, int pw) {
-    if (B <= 1 || ph <= 0 || pw <= 0) return 0;  // one partial per image; a single image writes gpatch itself
-    return (size_t)B * 3 * ph * pw * sizeof(float);
+    return (B <= 0 || ph <= 0 || pw <= 0) ? 0 : vaa::patch_stage_ws_bytes(B, ph, pw);  // one partial per image; a single image writes gpatch itself
 }
 
 extern "C" int vaa_patch_jitter_bwd(const float* gpacked, const float* patch, int ph, int pw, const float* factors, const int32_t* pdesc, int B,
                                     float* gpatch, void* ws, size_t ws_bytes, void* stream) {
     using namespace vaa;
     hipStream_t st = (hipStream_t)stream;
-    if (B == 0) {
-        if (gpatch && ph > 0 && pw > 0 && hipMemsetAsync(gpatch, 0, (size_t)3 * ph * pw * sizeof(float), st) != hipSuccess)
-            return check_launch("vaa_patch_jitter_bwd(memset)");
-        return VAA_OK;
-    }
-    int rc = check_jitter_args("vaa_patch_jitter_bwd", gpacked, patch, factors, pdesc, gpatch, B, ph, pw);
-    if (rc != VAA_OK) return rc;
-    const size_t need = vaa_patch_jitter_ws_bytes(B, ph, pw);
-    if (need > 0 && (!ws || ws_bytes < need)) {
-        set_error("vaa_patch_jitter_bwd: workspace %zu B < required %zu B", ws_bytes, need);
-        return VAA_E_WORKSPACE;
-    }
-    JitterArgs a;
-    a.patch = patch; a.factors = factors; a.pdesc = pdesc; a.gpacked = gpacked; a.out = B > 1 ? (float*)ws : gpatch; a.err_word = async_error_word();
-    a.B = B; a.ph = ph; a.pw = pw;
-    VAA_LAUNCH(patch_jitter_bwd_kernel, dim3(B), dim3(kJitThreads), 0, st, a);
-    rc = check_launch("vaa_patch_jitter_bwd");
-    if (rc != VAA_OK || B == 1) return rc;
-    return launch_partial_reduce((const float*)ws, gpatch, 3 * ph * pw, B, st, "vaa_patch_jitter_bwd(reduce)");
+    return patch_stage_bwd("vaa_patch_jitter_bwd", {gpacked, patch, factors, pdesc, gpatch}, B, ph, pw, /*frame_bound=*/true, /*empty_ok=*/true,
+                           /*parts=*/B, gpatch, ws, ws_bytes, st, [&](float* out) {
+        const JitterArgs a{patch, factors, pdesc, gpacked, out, async_error_word(), B, ph, pw};
+        VAA_LAUNCH(patch_jitter_bwd_kernel, dim3(B), dim3(kJitThreads), 0, st, a);
+    });
 }

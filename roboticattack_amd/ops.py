@@ -287,62 +287,50 @@ def make_pdesc(sizes, align: int = 4):
     return pdesc, off
 
 
+def _patch_stage_call(fn: str, lead, hw, extra, pdesc, total=None, ws=None):
+    """One entry point of a per-image patch stage (K0 resize, K0c jitter), in the C argument order all four share: the float32 `lead` tensors
+    ((name, tensor), ...; the base patch last where there is one), its (ph, pw) = hw (None: the base patch's own), the stage's `extra` float32
+    [B,3] tensors, pdesc [B,4], B, the output (total given: the zero-filled packed [total] of a forward; None: an adjoint's [3,ph,pw]), [the
+    workspace of ws = the stage's word in its vaa_patch_<ws>_ws_bytes and its _workspace kind,] the stream."""
+    for name, t in lead:
+        _need(t, torch.float32, name)
+    B = int(pdesc.shape[0])
+    ph, pw = hw if hw is not None else (int(v) for v in lead[-1][1].shape[1:])
+    _need(pdesc, torch.int32, "pdesc", (B, 4))
+    for name, t in extra:
+        _need(t, torch.float32, name, (B, 3))
+    dev = lead[0][1].device
+    out = torch.empty((3, ph, pw), dtype=torch.float32, device=dev) if total is None else torch.zeros(int(total), dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    args = [t.data_ptr() for _, t in lead] + [ph, pw] + [t.data_ptr() for _, t in extra] + [pdesc.data_ptr(), B, out.data_ptr()]
+    if ws is not None:
+        buf = _workspace(dev, getattr(L, f"vaa_patch_{ws}_ws_bytes")(B, ph, pw), ws)
+        args += [buf.data_ptr(), buf.numel()]
+    with _timed("K0_" + fn[4:], B=B):
+        rc = getattr(L, fn)(*args, _stream())
+    _lib.check(rc, fn)
+    return out
+
+
 def patch_resize_fwd(patch, pdesc, total: int):
     """Base patch [3,ph,pw] f32 -> packed f32 [total]: image b's antialias-bilinear resized patch [3,h_b,w_b] at pdesc[b].offset."""
-    _need(patch, torch.float32, "patch")
-    B = int(pdesc.shape[0])
-    _need(pdesc, torch.int32, "pdesc", (B, 4))
-    packed = torch.zeros(int(total), dtype=torch.float32, device=patch.device)
-    with _timed("K0_patch_resize_fwd", B=B):
-        rc = _lib.lib().vaa_patch_resize_fwd(patch.data_ptr(), int(patch.shape[1]), int(patch.shape[2]), pdesc.data_ptr(), B, packed.data_ptr(), _stream())
-    _lib.check(rc, "vaa_patch_resize_fwd")
-    return packed
+    return _patch_stage_call("vaa_patch_resize_fwd", (("patch", patch),), None, (), pdesc, total)
 
 
 def patch_resize_bwd(gpacked, pdesc, ph: int, pw: int):
     """Adjoint of patch_resize_fwd summed over the images: gpacked f32 [total] -> d L / d base patch [3,ph,pw]."""
-    _need(gpacked, torch.float32, "gpacked")
-    B = int(pdesc.shape[0])
-    _need(pdesc, torch.int32, "pdesc", (B, 4))
-    L = _lib.lib()
-    ws = _workspace(gpacked.device, L.vaa_patch_resize_ws_bytes(B, ph, pw), "resize")
-    g = torch.empty((3, ph, pw), dtype=torch.float32, device=gpacked.device)
-    with _timed("K0_patch_resize_bwd", B=B):
-        rc = L.vaa_patch_resize_bwd(gpacked.data_ptr(), ph, pw, pdesc.data_ptr(), B, g.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
-    _lib.check(rc, "vaa_patch_resize_bwd")
-    return g
+    return _patch_stage_call("vaa_patch_resize_bwd", (("gpacked", gpacked),), (ph, pw), (), pdesc, ws="resize")
 
 
 def patch_jitter_fwd(patch, factors, pdesc, total: int):
     """colorjitter (K0c): base patch [3,ph,pw] f32, factors [B,3] f32 (brightness, contrast, saturation) -> packed f32 [total]: image b's
     jittered patch [3,ph,pw] at pdesc[b].offset (include/vaa.h states the arithmetic)."""
-    _need(patch, torch.float32, "patch")
-    B = int(pdesc.shape[0])
-    _need(pdesc, torch.int32, "pdesc", (B, 4))
-    _need(factors, torch.float32, "factors", (B, 3))
-    packed = torch.zeros(int(total), dtype=torch.float32, device=patch.device)
-    with _timed("K0_patch_jitter_fwd", B=B):
-        rc = _lib.lib().vaa_patch_jitter_fwd(patch.data_ptr(), int(patch.shape[1]), int(patch.shape[2]), factors.data_ptr(), pdesc.data_ptr(), B,
-                                             packed.data_ptr(), _stream())
-    _lib.check(rc, "vaa_patch_jitter_fwd")
-    return packed
+    return _patch_stage_call("vaa_patch_jitter_fwd", (("patch", patch),), None, (("factors", factors),), pdesc, total)
 
 
 def patch_jitter_bwd(gpacked, patch, factors, pdesc):
     """Adjoint of patch_jitter_fwd summed over the images: gpacked f32 [total] -> d L / d base patch [3,ph,pw] (gates recomputed from `patch`)."""
-    _need(gpacked, torch.float32, "gpacked")
-    _need(patch, torch.float32, "patch")
-    B, ph, pw = int(pdesc.shape[0]), int(patch.shape[1]), int(patch.shape[2])
-    _need(pdesc, torch.int32, "pdesc", (B, 4))
-    _need(factors, torch.float32, "factors", (B, 3))
-    L = _lib.lib()
-    ws = _workspace(gpacked.device, L.vaa_patch_jitter_ws_bytes(B, ph, pw), "jitter")
-    g = torch.empty((3, ph, pw), dtype=torch.float32, device=gpacked.device)
-    with _timed("K0_patch_jitter_bwd", B=B):
-        rc = L.vaa_patch_jitter_bwd(gpacked.data_ptr(), patch.data_ptr(), ph, pw, factors.data_ptr(), pdesc.data_ptr(), B, g.data_ptr(),
-                                    ws.data_ptr(), ws.numel(), _stream())
-    _lib.check(rc, "vaa_patch_jitter_bwd")
-    return g
+    return _patch_stage_call("vaa_patch_jitter_bwd", (("gpacked", gpacked), ("patch", patch)), None, (("factors", factors),), pdesc, ws="jitter")
 
 
 def patch_reg_grad(patch, palette, w_tv: float, w_nps: float, grad=None, accumulate: bool = False, part=None, want_grad: bool = True):
@@ -414,26 +402,24 @@ def sweep_pdesc(P: int, Bp: int, ph: int, pw: int, device) -> torch.Tensor:
     return d.contiguous().to(device, non_blocking=True)
 
 
-def _resized_pack(patch, sizes):
-    """The prologue of resize_patch=True: host sizes [B,2] (h,w) -> (every image's own resized patch, packed (K0); pdesc on the device; (max h, max w))."""
-    pdesc_np, total = make_pdesc(sizes)
-    pdesc = torch.from_numpy(pdesc_np).to(patch.device, non_blocking=True)
-    return patch_resize_fwd(patch, pdesc, total), pdesc, (int(pdesc_np[:, 0].max()), int(pdesc_np[:, 1].max()))
-
-
-def _jittered_pack(patch, factors):
-    """The prologue of colorjitter: factors [B,3] on the device -> (every image's own jittered patch, packed (K0c); pdesc on the device; (ph, pw))."""
+def _stage_pack(stage: str, patch, rows):
+    """The prologue of a per-image patch stage: the descriptor, its device copy and the stage's forward on the base patch -> (every image's own
+    patch, packed; pdesc on the device; (max h, max w)). "resize" (K0): rows = host sizes [B,2] (h,w); "jitter" (K0c): rows = factors [B,3] on
+    the device, every image's patch keeps the base size."""
     ph, pw = int(patch.shape[1]), int(patch.shape[2])
-    pdesc_np, total = make_pdesc([(ph, pw)] * int(factors.shape[0]))
+    pdesc_np, total = make_pdesc(rows if stage == "resize" else [(ph, pw)] * int(rows.shape[0]))
     pdesc = torch.from_numpy(pdesc_np).to(patch.device, non_blocking=True)
-    return patch_jitter_fwd(patch, factors, pdesc, total), pdesc, (ph, pw)
+    if stage == "resize":
+        return patch_resize_fwd(patch, pdesc, total), pdesc, (int(pdesc_np[:, 0].max()), int(pdesc_np[:, 1].max()))
+    return patch_jitter_fwd(patch, rows, pdesc, total), pdesc, (ph, pw)
 
 
-def _paste_forward(ctx, p, img_u8, xy, theta, geometry, mask_mode, mean6, std6, pdesc=None, max_hw=None, embed=None, sink=None, base=None, factors=None):
+def _paste_forward(ctx, p, img_u8, xy, theta, geometry, mask_mode, mean6, std6, pdesc=None, max_hw=None, embed=None, sink=None, stage=None, base=None,
+                   factors=None):
     """Forward of every PatchApply* Function. p: what K1 pastes — the patch, or with pdesc / max_hw the per-image patches. embed=None: K1 planar
     -> pixel values; embed=(w0, b0, wp0, w1, b1, wp1): K1 writes the two GEMM operands directly (tile-major: no [B,6,224,224] tensor, no im2col
-    copies) -> the two patch-embed outputs. base: the base patch p was resized from (the backward then ends in the resize adjoint) or, with
-    factors [B,3], jittered from (it ends in the jitter adjoint)."""
+    copies) -> the two patch-embed outputs. stage ("resize" | "jitter"): the per-image patch stage that made p from the base patch `base` [and
+    the factors [B,3]]; it stays on ctx and names the adjoint that ends the backward."""
     if embed is None:
         ret, keep = _k1(img_u8, p, xy, theta, geometry, mask_mode, mean6, std6, pdesc, max_hw)
         mask = (keep,)
@@ -442,23 +428,30 @@ def _paste_forward(ctx, p, img_u8, xy, theta, geometry, mask_mode, mean6, std6, 
         t0, t1, keep_t, flags = _k1(img_u8, p, xy, theta, geometry, mask_mode, mean6, std6, pdesc, max_hw, tiles=True)
         ret = torch.nn.functional.linear(t0, w0, b0), torch.nn.functional.linear(t1, w1, b1)
         mask = (keep_t, flags, wp0, wp1)
-    jit = (base, factors) if factors is not None else (xy, xy)
-    ctx.save_for_backward(p, xy, theta if geometry else xy, pdesc if base is not None else xy, *jit, *mask)
-    ctx.jittered = factors is not None
+    staged = (pdesc, base, factors if factors is not None else xy) if stage is not None else (xy, xy, xy)
+    ctx.save_for_backward(p, xy, theta if geometry else xy, *staged, *mask)
     ctx.geometry, ctx.mask_mode, ctx.std6, ctx.sink = bool(geometry), int(mask_mode), std6, sink
-    ctx.max_hw, ctx.base_hw = (max_hw, (int(base.shape[1]), int(base.shape[2]))) if base is not None else (None, None)
+    ctx.stage, ctx.max_hw = stage, (max_hw if stage is not None else None)
     return ret
+
+
+def _stage_paste_forward(ctx, stage, patch, img_u8, rows, xy, theta, geometry, mask_mode, mean6, std6, embed=None):
+    """Forward of the four per-image Functions, which name only their stage: its prologue on the base patch, then the paste of the packed patches."""
+    p = patch.detach().contiguous()
+    packed, pdesc, max_hw = _stage_pack(stage, p, rows)
+    return _paste_forward(ctx, packed, img_u8, xy, theta, geometry, mask_mode, mean6, std6, pdesc, max_hw, embed=embed, stage=stage, base=p,
+                          factors=rows if stage == "jitter" else None)
 
 
 def _paste_backward(ctx, *grads):
     """Backward of every PatchApply* Function: K2 on the pixel gradient, or K2' on the gradients of the two patch-embed outputs. With a sink the
-    partial tiles are left in sink["partials"] for the caller's step epilogue and there is no gradient; a resized patch ends in the resize adjoint,
-    a jittered one in the jitter adjoint."""
+    partial tiles are left in sink["partials"] for the caller's step epilogue and there is no gradient; per-image patches end in the adjoint of
+    the stage the forward stored (ctx.stage)."""
     p, xy, theta, pdesc, base, factors, *mask = ctx.saved_tensors
     g = [t.to(torch.bfloat16).contiguous() for t in grads]
     if p.dim() == 4:  # a sweep's patches [P,3,ph,pw]: the keep words are given, K2' never reads patch values, only the [3,ph,pw] shape
         p = p[0]
-    theta, resized, defer = theta if ctx.geometry else None, ctx.base_hw is not None, ctx.sink is not None
+    theta, resized, defer = theta if ctx.geometry else None, ctx.stage is not None, ctx.sink is not None
     rest = (ctx.geometry, ctx.mask_mode, ctx.std6)
     # through the public wrappers, looked up when called: they are where a caller counts or replaces the K2 / K2' of a step
     if len(g) == 1:
@@ -475,9 +468,9 @@ def _paste_backward(ctx, *grads):
     if defer:
         ctx.sink["partials"] = out
         return None
-    if ctx.base_hw is None:
+    if ctx.stage is None:
         return out
-    return patch_jitter_bwd(out, base, factors, pdesc) if ctx.jittered else patch_resize_bwd(out, pdesc, *ctx.base_hw)
+    return patch_jitter_bwd(out, base, factors, pdesc) if ctx.stage == "jitter" else patch_resize_bwd(out, pdesc, int(base.shape[1]), int(base.shape[2]))
 
 
 class PatchApply(torch.autograd.Function):
@@ -499,9 +492,7 @@ class PatchApplyResized(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, patch, img_u8, sizes, xy, theta, geometry, mask_mode, mean6=None, std6=None):
-        p = patch.detach().contiguous()
-        packed, pdesc, max_hw = _resized_pack(p, sizes)
-        return _paste_forward(ctx, packed, img_u8, xy, theta, geometry, mask_mode, mean6, std6, pdesc, max_hw, base=p)
+        return _stage_paste_forward(ctx, "resize", patch, img_u8, sizes, xy, theta, geometry, mask_mode, mean6, std6)
 
     @staticmethod
     def backward(ctx, gout):
@@ -514,9 +505,7 @@ class PatchApplyJittered(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, patch, img_u8, factors, xy, theta, geometry, mask_mode, mean6=None, std6=None):
-        p = patch.detach().contiguous()
-        packed, pdesc, max_hw = _jittered_pack(p, factors)
-        return _paste_forward(ctx, packed, img_u8, xy, theta, geometry, mask_mode, mean6, std6, pdesc, max_hw, base=p, factors=factors)
+        return _stage_paste_forward(ctx, "jitter", patch, img_u8, factors, xy, theta, geometry, mask_mode, mean6, std6)
 
     @staticmethod
     def backward(ctx, gout):
@@ -569,9 +558,7 @@ class PatchApplyResizedEmbed(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, patch, img_u8, sizes, xy, theta, geometry, mask_mode, mean6, std6, w0, b0, wp0, w1, b1, wp1):
-        p = patch.detach().contiguous()
-        packed, pdesc, max_hw = _resized_pack(p, sizes)
-        return _paste_forward(ctx, packed, img_u8, xy, theta, geometry, mask_mode, mean6, std6, pdesc, max_hw, embed=(w0, b0, wp0, w1, b1, wp1), base=p)
+        return _stage_paste_forward(ctx, "resize", patch, img_u8, sizes, xy, theta, geometry, mask_mode, mean6, std6, (w0, b0, wp0, w1, b1, wp1))
 
     @staticmethod
     def backward(ctx, d0, d1):
@@ -584,10 +571,7 @@ class PatchApplyJitteredEmbed(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, patch, img_u8, factors, xy, theta, geometry, mask_mode, mean6, std6, w0, b0, wp0, w1, b1, wp1):
-        p = patch.detach().contiguous()
-        packed, pdesc, max_hw = _jittered_pack(p, factors)
-        return _paste_forward(ctx, packed, img_u8, xy, theta, geometry, mask_mode, mean6, std6, pdesc, max_hw, embed=(w0, b0, wp0, w1, b1, wp1),
-                              base=p, factors=factors)
+        return _stage_paste_forward(ctx, "jitter", patch, img_u8, factors, xy, theta, geometry, mask_mode, mean6, std6, (w0, b0, wp0, w1, b1, wp1))
 
     @staticmethod
     def backward(ctx, d0, d1):

@@ -360,11 +360,8 @@ class RandomPatchTransform:
             return self._apply_resized(img, patch, mean6, std6, geometry, out_dtype)
         ph, pw = int(patch.shape[1]), int(patch.shape[2])
         xy, theta = self._to_dev(*(draws if draws is not None else self._draw(B, ph, pw, geometry)))
-        emb = self._embed_params(patch, out_dtype)
-        if emb is not None:
-            return ops.PatchEmbeds(ops.PatchApplyEmbed.apply(patch, img, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6, *emb, grad_sink))
-        out = ops.PatchApply.apply(patch, img, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6, grad_sink)
-        return self._finish(out, patch, out_dtype, mean6, std6)
+        return self._paste_tail((ops.PatchApply, ops.PatchApplyEmbed), (), patch, img, xy, theta, geometry, ops.MASK_LT_M20, mean6, std6, out_dtype,
+                                (grad_sink,))
 
     def draw_params(self, batch, ph, pw, geometry):
         """The host draws of one apply_random_patch_batch call on `batch` frames (the same RNG consumption), for `draws=` / apply_sweep_batch."""
@@ -393,6 +390,16 @@ class RandomPatchTransform:
             return None
         return self.embed_with.patch_embed_params()
 
+    def _paste_tail(self, functions, lead, patch, img, xy, theta, geometry, mask_mode, mean6, std6, out_dtype, sink=()):
+        """The tail of the four paste sites. functions: the site's (planar, embed) Function pair; lead: their arguments in front of xy (nothing,
+        the sizes, the factors); sink: (grad_sink,) at the one site whose pair takes it. With patch-embed weights (`_embed_params`) the embed
+        Function's outputs as ops.PatchEmbeds, else the planar Function's pixel values behind `_finish`."""
+        planar, embed = functions
+        emb = self._embed_params(patch, out_dtype)
+        if emb is not None:
+            return ops.PatchEmbeds(embed.apply(patch, img, *lead, xy, theta, bool(geometry), mask_mode, mean6, std6, *emb, *sink))
+        return self._finish(planar.apply(patch, img, *lead, xy, theta, bool(geometry), mask_mode, mean6, std6, *sink), patch, out_dtype, mean6, std6)
+
     def _draw_resized(self, batch, ph0, pw0, geometry):
         """Draw order per image with resize_patch=True (:114, :123-128): uniform (scale) BEFORE the position, the position against
         the resized size, then the transform matrix."""
@@ -414,11 +421,8 @@ class RandomPatchTransform:
         sizes, xy_n, theta_n = self._draw_resized(img.shape[0], int(patch.shape[1]), int(patch.shape[2]), geometry)
         self.last_sizes = sizes
         xy, theta = self._to_dev(xy_n, theta_n)
-        emb = self._embed_params(patch, out_dtype)
-        if emb is not None:
-            return ops.PatchEmbeds(ops.PatchApplyResizedEmbed.apply(patch, img, sizes, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6, *emb))
-        out = ops.PatchApplyResized.apply(patch, img, sizes, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6)
-        return self._finish(out, patch, out_dtype, mean6, std6)
+        return self._paste_tail((ops.PatchApplyResized, ops.PatchApplyResizedEmbed), (sizes,), patch, img, xy, theta, geometry, ops.MASK_LT_M20,
+                                mean6, std6, out_dtype)
 
     def _draw_jitter(self, batch, strength):
         """3 * batch calls random.uniform(1 - s_k, 1 + s_k): image-major, in order brightness, contrast, saturation."""
@@ -436,22 +440,15 @@ class RandomPatchTransform:
         self.last_jitter = self._draw_jitter(B, strength)
         xy, theta = self._to_dev(xy_n, theta_n)
         factors = torch.from_numpy(self.last_jitter).to(self.device, non_blocking=True)
-        emb = self._embed_params(patch, out_dtype)
-        if emb is not None:
-            return ops.PatchEmbeds(ops.PatchApplyJitteredEmbed.apply(patch, img, factors, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6, *emb))
-        out = ops.PatchApplyJittered.apply(patch, img, factors, xy, theta, bool(geometry), ops.MASK_LT_M20, mean6, std6)
-        return self._finish(out, patch, out_dtype, mean6, std6)
+        return self._paste_tail((ops.PatchApplyJittered, ops.PatchApplyJitteredEmbed), (factors,), patch, img, xy, theta, geometry, ops.MASK_LT_M20,
+                                mean6, std6, out_dtype)
 
     def _paste(self, images, patch, mean, std, out_dtype):
         mean6, std6 = _six(mean, std)
         img = self.stage_images(images)
         ph, pw = int(patch.shape[1]), int(patch.shape[2])
         xy, theta = self._to_dev(*self._draw(img.shape[0], ph, pw, False))
-        emb = self._embed_params(patch, out_dtype)
-        if emb is not None:
-            return ops.PatchEmbeds(ops.PatchApplyEmbed.apply(patch, img, xy, theta, False, ops.MASK_NE_M100, mean6, std6, *emb)), xy
-        out = ops.PatchApply.apply(patch, img, xy, theta, False, ops.MASK_NE_M100, mean6, std6)
-        return self._finish(out, patch, out_dtype, mean6, std6), xy
+        return self._paste_tail((ops.PatchApply, ops.PatchApplyEmbed), (), patch, img, xy, theta, False, ops.MASK_NE_M100, mean6, std6, out_dtype), xy
 
     def random_paste_patch(self, images, patch, mean, std, out_dtype=torch.bfloat16):
         """:138-158 — paste without warp, mask rule `canvas != -100`."""

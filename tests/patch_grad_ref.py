@@ -565,6 +565,10 @@ K0_CASES = {  # the size lists of test_patch_resize_kernel_vs_torch_cpu
     "r100": (100, 100, [(61, 61), (139, 139), (100, 100), (100, 61), (139, 100), (1, 1), (224, 224)]),
     "r50": (50, 50, [(30, 69), (50, 50), (19, 19), (69, 69)]),
     "r37x61": (37, 61, [(22, 84), (51, 37)]),
+    # scale 4 on an axis: 9 taps > kTapMax, the direct form (the workload's U(0.61, 1.39) never reaches it); one axis untouched in two of the
+    # sizes; (4, 7) is direct on both axes (5x and 2.86x), its weights through the ncx candidate logic
+    "r20": (20, 20, [(5, 5), (5, 20), (20, 5), (6, 40), (4, 7)]),
+    "r20mix": (20, 20, [(5, 5), (20, 20), (27, 13)]),  # a group walks a direct, an identity and a tabled image in sequence
 }
 CASES = {"k2": K2_CASES, "k2e": K2E_CASES, "k0": K0_CASES}
 

@@ -412,7 +412,9 @@ def test_resize_patch_config5_vs_reference_golden(ops, f):
 
 
 @pytest.mark.parametrize("ph,pw,sizes", [(100, 100, [(61, 61), (139, 139), (100, 100), (100, 61), (139, 100), (1, 1), (224, 224)]),
-                                         (50, 50, [(30, 69), (50, 50), (19, 19), (69, 69)]), (37, 61, [(22, 84), (51, 37)])])
+                                         (50, 50, [(30, 69), (50, 50), (19, 19), (69, 69)]), (37, 61, [(22, 84), (51, 37)]),
+                                         # K0_CASES "r20" / "r20mix" of patch_grad_ref.py: the direct form (more than kTapMax taps)
+                                         (20, 20, [(5, 5), (5, 20), (20, 5), (6, 40), (4, 7)]), (20, 20, [(5, 5), (20, 20), (27, 13)])])
 def test_patch_resize_kernel_vs_torch_cpu(ops, ph, pw, sizes):
     """The HIP resize equals torch's CPU antialias-bilinear kernel bit for bit (up- and down-scaling, unchanged axes, extremes);
     its adjoint equals torch autograd to fp32 summation order."""

@@ -166,3 +166,50 @@ def test_restatement_fp32_against_fp64_baseline(name):
     miss = float((no_mean - c["grad64"])[:, c["keep"]].abs().max()) / float(c["grad64"][:, c["keep"]].abs().max())
     print(f"{name}: adjoint without the mean term misses by {miss:.3e} of max|ref| ({miss / tol_g:.0f} x tol_g)")
     assert miss > 10 * tol_g
+
+
+class _Model:
+    """Stands in for a model that exposes its patch-embed weights: six distinguishable objects."""
+    emb = tuple(f"emb{k}" for k in range(6))
+
+    def patch_embed_params(self):
+        return self.emb
+
+
+@pytest.mark.parametrize("embed", [False, True], ids=["planar", "embed"])
+@pytest.mark.parametrize("site", ["plain", "plain_sink", "resized", "jittered", "paste"])
+def test_every_paste_site_hands_its_function_the_same_arguments(monkeypatch, site, embed):
+    """The one paste tail behind apply_random_patch_batch (plain, resize_patch, colorjitter) and _paste: each site's Function — the planar one,
+    or with `embed_with` the *Embed one — receives, behind (patch, frames), exactly [sizes | factors,] xy, theta, geometry, mask mode, mean6,
+    std6 [, the six patch-embed parameters] [, grad_sink]; _paste passes MASK_NE_M100 and geometry False, and only the plain site has a sink."""
+    from roboticattack_amd.transform import _six
+
+    name = {"plain": "PatchApply", "plain_sink": "PatchApply", "resized": "PatchApplyResized", "jittered": "PatchApplyJittered",
+            "paste": "PatchApply"}[site] + ("Embed" if embed else "")
+    calls = []
+    for n in ("PatchApply", "PatchApplyResized", "PatchApplyJittered"):
+        _stub(monkeypatch, n, calls)
+        _stub(monkeypatch, n + "Embed", calls)
+    t = RandomPatchTransform("cpu", resize_patch=(site == "resized"))
+    t.embed_with = _Model() if embed else None
+    patch = torch.rand(3, PH, PW, requires_grad=True)
+    sink = {} if site == "plain_sink" else None
+    _seed()
+    if site == "paste":
+        out = t.random_paste_patch(_frames(), patch, MEAN, STD)
+    else:
+        out = t.apply_random_patch_batch(_frames(), patch, MEAN, STD, True, colorjitter=(site == "jittered"), grad_sink=sink)
+    assert isinstance(out, ops.PatchEmbeds) == embed
+    assert [c[0] for c in calls] == [name]
+    rest = list(calls[0][1])
+    lead = {"resized": t.last_sizes, "jittered": t.last_jitter}.get(site)
+    if lead is not None:
+        got = rest.pop(0)
+        assert np.array_equal(got.numpy() if isinstance(got, torch.Tensor) else got, lead)
+    xy, theta = rest[:2]
+    assert np.array_equal(xy.numpy(), t.last_params[0]) and np.array_equal(theta.numpy(), t.last_params[1])
+    mean6, std6 = _six(MEAN, STD)
+    want = [site != "paste", ops.MASK_NE_M100 if site == "paste" else ops.MASK_LT_M20, mean6, std6] + (list(_Model.emb) if embed else [])
+    if site.startswith("plain"):
+        want.append(sink)
+    assert rest[2:] == want and rest[2] is want[0] and (sink is None or rest[-1] is sink)

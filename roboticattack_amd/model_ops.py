@@ -17,10 +17,14 @@ def enabled(x: torch.Tensor) -> bool:
     return x.is_cuda and x.dtype == torch.bfloat16 and not os.environ.get("VAA_NO_FUSED_MODEL_OPS")
 
 
+def attention_kernel_enabled(ops_on: bool, hd: int) -> bool:
+    """attention_enabled less its stride condition, from facts alone (ops_on = enabled(x)); openvla_model._route decides with it."""
+    return bool(ops_on) and not os.environ.get("VAA_NO_FUSED_ATTENTION") and hd % 8 == 0 and hd <= 128
+
+
 def attention_enabled(x_bthd: torch.Tensor) -> bool:
     """Matrix-core attention (vaa_attention.hip) applies: bf16 on ROCm, head dim % 8 == 0 and <= 128, 16-byte aligned strides."""
-    hd = x_bthd.shape[-1]
-    return (enabled(x_bthd) and not os.environ.get("VAA_NO_FUSED_ATTENTION") and hd % 8 == 0 and hd <= 128
+    return (attention_kernel_enabled(enabled(x_bthd), x_bthd.shape[-1])
             and all(s % 8 == 0 for s in x_bthd.stride()[:-1]) and x_bthd.stride(-1) == 1)
 
 
@@ -258,22 +262,49 @@ def attention_bwd(q, k, v, o, lse, dout, causal: bool, scale: float, packed_grad
     return buf if packed_grad else (dq, dk, dv)
 
 
+def rope_in_attention(hd: int) -> bool:
+    """The rotary adjoint of dq/dk runs in the attention backward's epilogues (a lane holds head-dim d and d + hd/2 of its row) at these head
+    widths only. Three decisions rest on it and have to agree, so all three ask here: LlamaLayer takes RopeAttentionFn / RopePackedAttentionFn
+    (else RopeFn x2 + AttentionFn), the one-GEMM qkv feeds RopePackedAttentionFn only, and hidden_states may hand a SeqPack to the layers —
+    cu_seqlens exist on the two rope Functions alone, so a pack given to any other route would be attended as ONE sequence."""
+    return hd in (64, 128)
+
+
+def _attention_forward(ctx, q, k, v, rope, causal, scale, cu_seqlens, max_len, packed_src):
+    """The forward of the four attention Functions. rope = (cos, sin) or None: q and k are rotated first, and only the rotated ones are kept.
+    packed_src = the [B,T,3,H,hd] buffer q/k/v are slices of, or None: it is saved in place of its slices and the gradient comes back packed."""
+    scale = float(q.shape[-1]) ** -0.5 if scale is None else float(scale)
+    if rope is not None:
+        q, k = _rope_launch(q, *rope, 1.0), _rope_launch(k, *rope, 1.0)
+    o, lse = attention_fwd(q, k, v, causal, scale, cu_seqlens, max_len)
+    operands = (q, k, v) if packed_src is None else (q, k, packed_src) if rope is not None else (packed_src,)
+    ctx.save_for_backward(o, lse, *operands, *(rope or ()), *([cu_seqlens] if cu_seqlens is not None else []))
+    ctx.attn = (bool(causal), scale, int(max_len), packed_src is not None, rope is not None, cu_seqlens is not None)
+    return o
+
+
+def _attention_backward(ctx, dout):
+    """The one backward: what to unpack, and how many inputs the calling Function had, follow from what the forward recorded."""
+    causal, scale, max_len, packed, roped, has_cu = ctx.attn
+    o, lse, *rest = ctx.saved_tensors
+    cu = rest.pop() if has_cu else None
+    rope = (rest.pop(-2), rest.pop()) if roped else None
+    if packed:  # the buffer was kept in place of its slices: v always, q and k unless rotated
+        src = rest.pop()
+        rest += [src[:, :, z] for z in range(len(rest), 3)]
+    g = attention_bwd(*rest, o, lse, dout, causal, scale, packed_grad=packed, rope=rope, cu_seqlens=cu, max_len=max_len)
+    # behind the operands' gradients (one buffer if packed, else three): causal, scale; the rope forms add cos, sin, cu_seqlens, max_len
+    return (*((g,) if packed else g), *(None,) * (2 + (4 if roped else 0)))
+
+
 class AttentionFn(torch.autograd.Function):
     """softmax(scale q k^T [causal]) v on [B,T,H,hd] bf16 views -> [B,T,H,hd] (vaa_attention.hip, fwd + 2-kernel bwd)."""
 
     @staticmethod
     def forward(ctx, q, k, v, causal, scale):
-        scale = float(q.shape[-1]) ** -0.5 if scale is None else float(scale)
-        o, lse = attention_fwd(q, k, v, causal, scale)
-        ctx.save_for_backward(q, k, v, o, lse)
-        ctx.causal, ctx.scale = bool(causal), scale
-        return o
+        return _attention_forward(ctx, q, k, v, None, causal, scale, None, 0, None)
 
-    @staticmethod
-    def backward(ctx, dout):
-        q, k, v, o, lse = ctx.saved_tensors
-        dq, dk, dv = attention_bwd(q, k, v, o, lse, dout, ctx.causal, ctx.scale)
-        return dq, dk, dv, None, None
+    backward = staticmethod(_attention_backward)
 
 
 class RopeAttentionFn(torch.autograd.Function):
@@ -283,19 +314,9 @@ class RopeAttentionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, cos, sin, causal, scale, cu_seqlens=None, max_len=0):
         """Packed form (cu_seqlens given): q/k/v are [1,sumT,H,hd] and cos/sin hold one row PER PACKED TOKEN (gathered by position id)."""
-        scale = float(q.shape[-1]) ** -0.5 if scale is None else float(scale)
-        qr, kr = _rope_launch(q, cos, sin, 1.0), _rope_launch(k, cos, sin, 1.0)
-        o, lse = attention_fwd(qr, kr, v, causal, scale, cu_seqlens, max_len)
-        ctx.save_for_backward(qr, kr, v, o, lse, cos, sin, *([cu_seqlens] if cu_seqlens is not None else []))
-        ctx.causal, ctx.scale, ctx.max_len = bool(causal), scale, int(max_len)
-        return o
+        return _attention_forward(ctx, q, k, v, (cos, sin), causal, scale, cu_seqlens, max_len, None)
 
-    @staticmethod
-    def backward(ctx, dout):
-        qr, kr, v, o, lse, cos, sin, *cu = ctx.saved_tensors
-        dq, dk, dv = attention_bwd(qr, kr, v, o, lse, dout, ctx.causal, ctx.scale, rope=(cos, sin), cu_seqlens=cu[0] if cu else None,
-                                   max_len=ctx.max_len)
-        return dq, dk, dv, None, None, None, None, None, None
+    backward = staticmethod(_attention_backward)
 
 
 class RopePackedAttentionFn(torch.autograd.Function):
@@ -305,20 +326,9 @@ class RopePackedAttentionFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, cos, sin, causal, scale, cu_seqlens=None, max_len=0):
-        scale = float(qkv.shape[-1]) ** -0.5 if scale is None else float(scale)
-        qr, kr = _rope_launch(qkv[:, :, 0], cos, sin, 1.0), _rope_launch(qkv[:, :, 1], cos, sin, 1.0)
-        v = qkv[:, :, 2]
-        o, lse = attention_fwd(qr, kr, v, causal, scale, cu_seqlens, max_len)
-        ctx.save_for_backward(qr, kr, qkv, o, lse, cos, sin, *([cu_seqlens] if cu_seqlens is not None else []))
-        ctx.causal, ctx.scale, ctx.max_len = bool(causal), scale, int(max_len)
-        return o
+        return _attention_forward(ctx, qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], (cos, sin), causal, scale, cu_seqlens, max_len, qkv)
 
-    @staticmethod
-    def backward(ctx, dout):
-        qr, kr, qkv, o, lse, cos, sin, *cu = ctx.saved_tensors
-        buf = attention_bwd(qr, kr, qkv[:, :, 2], o, lse, dout, ctx.causal, ctx.scale, packed_grad=True, rope=(cos, sin),
-                            cu_seqlens=cu[0] if cu else None, max_len=ctx.max_len)
-        return buf, None, None, None, None, None, None
+    backward = staticmethod(_attention_backward)
 
 
 class PackedAttentionFn(torch.autograd.Function):
@@ -326,16 +336,9 @@ class PackedAttentionFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, causal, scale):
-        scale = float(qkv.shape[-1]) ** -0.5 if scale is None else float(scale)
-        o, lse = attention_fwd(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], causal, scale)
-        ctx.save_for_backward(qkv, o, lse)
-        ctx.causal, ctx.scale = bool(causal), scale
-        return o
+        return _attention_forward(ctx, qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], None, causal, scale, None, 0, qkv)
 
-    @staticmethod
-    def backward(ctx, dout):
-        qkv, o, lse = ctx.saved_tensors
-        return attention_bwd(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], o, lse, dout, ctx.causal, ctx.scale, packed_grad=True), None, None
+    backward = staticmethod(_attention_backward)
 
 
 def _str2(x: torch.Tensor):

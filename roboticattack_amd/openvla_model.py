@@ -18,14 +18,16 @@ Random-init throughput runs use `init="random"`; a local HF checkpoint directory
 """
 from __future__ import annotations
 
-import math
+import os
 import types
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import model_ops
 from .constants import IGNORE_INDEX, MODEL_VOCAB, N_IMG_TOKENS, PAD_ID
 
 
@@ -77,6 +79,62 @@ def tiny_cfg() -> OpenVLACfg:
     )
 
 
+def _fused(ops_on: bool, D: int, hd: int | None = None, has_tab: bool = True) -> bool:
+    """The fused elementwise operators serve a block of width D. ops_on = model_ops.enabled(x). The Llama layers pass their head width (RoPE
+    kernel: hd % 16 == 0; the ViT blocks have no such condition) and LlamaLayer.forward whether it was handed a rotary table."""
+    return bool(ops_on) and has_tab and D % 8 == 0 and D <= 8192 and (hd is None or hd % 16 == 0)
+
+
+def _norm(norm, x, fused):
+    """(x, norm(x)). Fused: the pass-through Function of the module's kind — its ONE backward kernel also absorbs the residual-stream
+    gradient, so the caller continues with the x returned here; otherwise the stock module."""
+    if not fused:
+        return x, norm(x)
+    if isinstance(norm, nn.LayerNorm):
+        return model_ops.ResidualLayerNormFn.apply(x, norm.weight, norm.bias, norm.eps)
+    return model_ops.ResidualRMSNormFn.apply(x, norm.weight, norm.eps)
+
+
+class Route(NamedTuple):
+    """What one LlamaLayer.forward call goes through ("Model-side operators": the route table)."""
+    fused: bool      # fused norms, RoPE and SwiGLU kernels
+    tn: bool         # projections through FrozenLinearsFn (TN-layout dgrad, residual adds in the GEMM epilogues)
+    qkv_cat: bool    # q/k/v as ONE GEMM over the row-concatenated weights
+    attention: str   # rope_packed | rope | rope_fn_attention | rope_fn_sdpa | stock_sdpa
+    cu: object       # SeqPack.cu / .max_len where the attention takes them (the two rope Functions), else None / 0
+    max_len: int
+
+
+def _facts(x, heads: int, rope_tab) -> dict:
+    """What _route decides from, read off a layer's input [B,T,D] and the environment (the switches are read at call time). attn_on leaves
+    out attention_enabled's stride condition: every operand a fused layer forms is a view of a contiguous GEMM output with D % 8 == 0 and
+    hd % 16 == 0, whose strides are multiples of 8."""
+    hd, ops_on = x.shape[-1] // heads, model_ops.enabled(x)
+    return dict(ops_on=ops_on, attn_on=model_ops.attention_kernel_enabled(ops_on, hd), tn_on=model_ops.tn_dgrad_enabled(),
+                qkv_mode=os.environ.get("VAA_FUSED_QKV", "auto"), hd=hd, D=x.shape[-1], has_tab=rope_tab is not None)
+
+
+def _route(ops_on, attn_on, tn_on, qkv_mode, hd, D, rows, has_tab, pack=None) -> Route:
+    """The route of a layer call over rows = B*T positions, from facts alone (tests/test_model_route_host.py tabulates it).
+    qkv_mode is VAA_FUSED_QKV: at the per-rank batches of the strong-scaling configs (1,200 / 2,400 rows) three [M,4096]x[4096,4096]
+    products run at 0.8-1.05 PFLOP/s, the single [M,4096]x[4096,12288] at 1.3-1.36 (tools/gemm_overlap_probe.py); at 19,200 rows the two
+    forms are level, so the separate, tuned GEMMs stay. 1 / 0 forces it on / off."""
+    fused = _fused(ops_on, D, hd, has_tab)
+    tn = fused and bool(tn_on)
+    in_attn = model_ops.rope_in_attention(hd)
+    qkv_cat = tn and in_attn and (qkv_mode == "1" or (qkv_mode != "0" and rows < 8192))
+    if not fused:
+        attention = "stock_sdpa"
+    elif not attn_on:
+        attention = "rope_fn_sdpa"
+    elif not in_attn:
+        attention = "rope_fn_attention"
+    else:
+        attention = "rope_packed" if qkv_cat else "rope"
+    packed = pack is not None and attention in ("rope_packed", "rope")
+    return Route(fused, tn, qkv_cat, attention, pack.cu if packed else None, pack.max_len if packed else 0)
+
+
 class VitBlock(nn.Module):
     def __init__(self, c: VitCfg):
         super().__init__()
@@ -92,13 +150,8 @@ class VitBlock(nn.Module):
 
     def forward(self, x):
         B, T, D = x.shape
-        from . import model_ops
-
-        fused_ln = model_ops.enabled(x) and D % 8 == 0 and D <= 8192
-        if fused_ln:  # (x) -> (x, LN(x)): the backward kernel also absorbs the residual-stream gradient
-            x, h = model_ops.ResidualLayerNormFn.apply(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)
-        else:
-            h = self.norm1(x)
+        fused_ln = _fused(model_ops.enabled(x), D)
+        x, h = _norm(self.norm1, x, fused_ln)
         qkv = self.qkv(h).view(B, T, 3, self.heads, D // self.heads)
         if model_ops.attention_enabled(qkv):  # matrix-core attention on the packed projection; packed gradient, no permute copies
             a = model_ops.PackedAttentionFn.apply(qkv, False, None).reshape(B, T, D)
@@ -107,10 +160,7 @@ class VitBlock(nn.Module):
             a = F.scaled_dot_product_attention(qkv[0], qkv[1], qkv[2]).transpose(1, 2).reshape(B, T, D)
         a = self.proj(a)
         x = model_ops.scale_add(x, a, self.ls1) if self.ls1 is not None else x + a  # LayerScale + residual in one pass
-        if fused_ln:
-            x, h = model_ops.ResidualLayerNormFn.apply(x, self.norm2.weight, self.norm2.bias, self.norm2.eps)
-        else:
-            h = self.norm2(x)
+        x, h = _norm(self.norm2, x, fused_ln)
         h = self.fc2(F.gelu(self.fc1(h)))
         return model_ops.scale_add(x, h, self.ls2) if self.ls2 is not None else x + h
 
@@ -252,105 +302,66 @@ class LlamaLayer(nn.Module):
             self._wt_cache[key] = hit
         return hit[2], hit[3]
 
-    @staticmethod
-    def _fuse_qkv(rows: int) -> bool:
-        """q/k/v as ONE GEMM over the concatenated weights (and one data-gradient GEMM with K = 3D): at the per-rank batches of the
-        strong-scaling configs (M = B*T = 1,200 / 2,400 rows) three [M,4096]x[4096,4096] products run at 0.8-1.05 PFLOP/s, the single
-        [M,4096]x[4096,12288] at 1.3-1.36 (tools/gemm_overlap_probe.py); at M = 19,200 the two forms are level, so the separate, tuned GEMMs
-        stay. VAA_FUSED_QKV=1 / 0 forces it on / off."""
-        import os
-
-        mode = os.environ.get("VAA_FUSED_QKV", "auto")
-        return mode == "1" or (mode != "0" and rows < 8192)
-
     def _lin(self, x, names, res=None):
-        from . import model_ops
-
-        ws = []
-        for n in names:
-            ws += [getattr(self, n).weight, self._wt(n)]
+        ws = [w for n in names for w in (getattr(self, n).weight, self._wt(n))]
         return model_ops.FrozenLinearsFn.apply(x, res, *ws)
 
-    def forward(self, x, cos, sin, rope_tab=None, rows=None, pack=None):
-        """`rows` (flat indices into the B*T positions): everything after the attention — o_proj, residual, MLP — is evaluated
-        for those rows only and [R,D] is returned (last layer of `forward_rows`: no other position reaches the loss)."""
-        from . import model_ops
+    # ---- training: the stages of `forward`, each reading the Route (what the names mean and launch: DESIGN.md, the route table) ----
+    def _qkv(self, h, r):
+        """The q/k/v projections of h [B,T,D]: [B,T,3,H,hd] out of ONE GEMM on the cat route, else three [B,T,H,hd] views."""
+        B, T, _ = h.shape
+        if r.qkv_cat:
+            (qkv,) = model_ops.FrozenLinearsFn.apply(h, None, *self._wcat(("q_proj", "k_proj", "v_proj")))
+            return qkv.view(B, T, 3, self.heads, -1)
+        qkv = self._lin(h, ("q_proj", "k_proj", "v_proj")) if r.tn else (self.q_proj(h), self.k_proj(h), self.v_proj(h))
+        return tuple(t.view(B, T, self.heads, -1) for t in qkv)
 
+    def _attention(self, qkv, r, cos, sin, rope_tab):
+        """Rotary embedding and causal attention (right padding + causal == HF's mask on real tokens) by r.attention: [B,T,H,hd]."""
+        if r.attention == "rope_packed":
+            return model_ops.RopePackedAttentionFn.apply(qkv, *rope_tab, True, None, r.cu, r.max_len)
+        q, k, v = qkv if isinstance(qkv, tuple) else (qkv[:, :, z] for z in range(3))
+        if r.attention == "rope":
+            return model_ops.RopeAttentionFn.apply(q, k, v, *rope_tab, True, None, r.cu, r.max_len)
+        if r.attention != "stock_sdpa":  # one HBM pass per tensor instead of neg + cat + 2 mul + add (and their autograd chains)
+            q, k = model_ops.RopeFn.apply(q, *rope_tab), model_ops.RopeFn.apply(k, *rope_tab)
+        if r.attention == "rope_fn_attention":
+            return model_ops.AttentionFn.apply(q, k, v, True, None)
+        q, k, v = q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2)
+        if r.attention == "stock_sdpa":
+            q, k = _rope(q, k, cos, sin)
+        return F.scaled_dot_product_attention(q, k, v, is_causal=True).transpose(1, 2)
+
+    def _proj_res(self, name, a, x, r):
+        """x + a @ W^T for o_proj / down_proj, the residual in the GEMM's epilogue."""
+        if r.tn:
+            return self._lin(a, (name,), res=x)[0]
+        return torch.addmm(x.reshape(-1, x.shape[-1]), a.reshape(-1, a.shape[-1]), getattr(self, name).weight.t()).view(x.shape)
+
+    def _mlp(self, x, h, r):
+        """x + down_proj(silu(gate) * up). The SwiGLU kernel takes a multiple of 8 elements — of the rows it is GIVEN (after a row selection)."""
+        if not (r.fused and (h.shape[0] * h.shape[1] * self.gate_proj.out_features) % 8 == 0):
+            return x + self.down_proj(F.silu(self.gate_proj(h)) * self.up_proj(h))
+        g, u = self._lin(h, ("gate_proj", "up_proj")) if r.tn else (self.gate_proj(h), self.up_proj(h))
+        return self._proj_res("down_proj", model_ops.SwiGLUFn.apply(g, u), x, r)
+
+    def forward(self, x, cos, sin, rope_tab=None, rows=None, pack=None, route=None):
+        """`rows` (flat indices into the B*T positions): everything after the attention — o_proj, residual, MLP — is evaluated
+        for those rows only and [R,D] is returned (last layer of `forward_rows`: no other position reaches the loss). `route`: the
+        Route of this call where the caller has worked it out already (hidden_states: once for all layers)."""
         if self.quant_type:
             from . import quant
 
             quant.refuse_training("LlamaLayer.forward", self.quant_type)
         B, T, D = x.shape
-        hd = D // self.heads
-        fused = rope_tab is not None and model_ops.enabled(x) and hd % 16 == 0 and D % 8 == 0 and D <= 8192
-        tn = fused and model_ops.tn_dgrad_enabled()
-        if fused:
-            x, h = model_ops.ResidualRMSNormFn.apply(x, self.input_layernorm.weight, self.input_layernorm.eps)
-        else:
-            h = self.input_layernorm(x)
-        if tn and hd in (64, 128) and self._fuse_qkv(B * T):
-            wqkv, wqkv_t = self._wcat(("q_proj", "k_proj", "v_proj"))
-            (qkv,) = model_ops.FrozenLinearsFn.apply(h, None, wqkv, wqkv_t)
-            qkv = qkv.view(B, T, 3, self.heads, hd)
-            if model_ops.attention_enabled(qkv[:, :, 0]):
-                a = model_ops.RopePackedAttentionFn.apply(qkv, *rope_tab, True, None, pack.cu if pack is not None else None,
-                                                          pack.max_len if pack is not None else 0).view(B, T, D)
-                q = k = v = None
-            else:
-                q, k, v = (qkv[:, :, z].reshape(B, T, D) for z in range(3))
-                a = None
-        elif tn:
-            q, k, v = self._lin(h, ("q_proj", "k_proj", "v_proj"))
-            a = None
-        else:
-            q, k, v = self.q_proj(h), self.k_proj(h), self.v_proj(h)
-            a = None
-        if a is not None:
-            pass
-        elif fused and model_ops.attention_enabled(q.view(B, T, self.heads, hd)):
-            sh = (B, T, self.heads, hd)
-            if hd in (64, 128):  # rotary adjoint of dq/dk runs in the attention backward's epilogues
-                a = model_ops.RopeAttentionFn.apply(q.view(sh), k.view(sh), v.view(sh), *rope_tab, True, None,
-                                                    pack.cu if pack is not None else None, pack.max_len if pack is not None else 0).view(B, T, D)
-            else:
-                q = model_ops.RopeFn.apply(q.view(sh), *rope_tab)
-                k = model_ops.RopeFn.apply(k.view(sh), *rope_tab)
-                a = model_ops.AttentionFn.apply(q, k, v.view(sh), True, None).view(B, T, D)
-        elif fused:  # one HBM pass per tensor instead of neg + cat + 2 mul + add (and their autograd chains)
-            q = model_ops.RopeFn.apply(q.view(B, T, self.heads, hd), *rope_tab).transpose(1, 2)
-            k = model_ops.RopeFn.apply(k.view(B, T, self.heads, hd), *rope_tab).transpose(1, 2)
-            v = v.view(B, T, self.heads, hd).transpose(1, 2)
-            a = None
-        else:
-            q = q.view(B, T, self.heads, hd).transpose(1, 2)
-            k = k.view(B, T, self.heads, hd).transpose(1, 2)
-            v = v.view(B, T, self.heads, hd).transpose(1, 2)
-            q, k = _rope(q, k, cos, sin)
-            a = None
-        if a is None:
-            a = F.scaled_dot_product_attention(q, k, v, is_causal=True)  # right padding + causal == HF's mask on real tokens
-            a = a.transpose(1, 2).reshape(B, T, D)
+        r = route if route is not None else _route(rows=B * T, pack=pack, **_facts(x, self.heads, rope_tab))
+        x, h = _norm(self.input_layernorm, x, r.fused)
+        a = self._attention(self._qkv(h, r), r, cos, sin, rope_tab).reshape(B, T, D)
         if rows is not None:
-            a = a.reshape(-1, D).index_select(0, rows)[None]
-            x = x.reshape(-1, D).index_select(0, rows)[None]
-            B, T = 1, a.shape[1]
-        if tn:
-            (x,) = self._lin(a, ("o_proj",), res=x)  # residual in the GEMM epilogue
-        else:
-            x = torch.addmm(x.reshape(-1, D), a.reshape(-1, D), self.o_proj.weight.t()).view(B, T, D)
-        if fused:
-            x, h = model_ops.ResidualRMSNormFn.apply(x, self.post_attention_layernorm.weight, self.post_attention_layernorm.eps)
-        else:
-            h = self.post_attention_layernorm(x)
-        if fused and (h.shape[0] * h.shape[1] * self.gate_proj.out_features) % 8 == 0:
-            if tn:
-                g, u = self._lin(h, ("gate_proj", "up_proj"))
-                (x,) = self._lin(model_ops.SwiGLUFn.apply(g, u), ("down_proj",), res=x)
-                return x[0] if rows is not None else x
-            y = model_ops.SwiGLUFn.apply(self.gate_proj(h), self.up_proj(h))
-            x = torch.addmm(x.reshape(-1, D), y.reshape(-1, y.shape[-1]), self.down_proj.weight.t()).view(B, T, D)
-        else:
-            x = x + self.down_proj(F.silu(self.gate_proj(h)) * self.up_proj(h))
+            a, x = (t.reshape(-1, D).index_select(0, rows)[None] for t in (a, x))
+        x = self._proj_res("o_proj", a, x, r)
+        x, h = _norm(self.post_attention_layernorm, x, r.fused)
+        x = self._mlp(x, h, r)
         return x[0] if rows is not None else x
 
     # ---- inference only: KV-cached greedy decoding (predict.py). ONE graph for bf16, 4-bit and int8 weights: norm, qkv, attention (prefill:
@@ -358,30 +369,20 @@ class LlamaLayer(nn.Module):
     # projection is formed is all that differs, and sits behind self.projections (Bf16Projections above, quant.Q4Projections / Q8Projections);
     # `gemv` tells the 4-bit kind that the rows are a decode step's. `forward` is the training path and never materialises the rotated K. ----
     def _infer_fused(self, x) -> bool:
-        from . import model_ops
-
-        D = x.shape[-1]
-        return model_ops.enabled(x) and (D // self.heads) % 16 == 0 and D % 8 == 0 and D <= 8192
-
-    def _infer_norm(self, norm, x, fused):
-        from . import model_ops
-
-        return model_ops.ResidualRMSNormFn.apply(x, norm.weight, norm.eps)[1] if fused else norm(x)
+        return _fused(model_ops.enabled(x), x.shape[-1], x.shape[-1] // self.heads)
 
     def _infer_norm_qkv(self, x, fused, gemv):
         """RMSNorm and the q/k/v projections of x [B,T,D]: [B,T,3,H,hd]."""
         B, T, D = x.shape
-        h = self._infer_norm(self.input_layernorm, x, fused).reshape(-1, D)
+        h = _norm(self.input_layernorm, x, fused)[1].reshape(-1, D)
         return self.projections.qkv(h, fused, gemv).view(B, T, 3, self.heads, D // self.heads)
 
     def _infer_o_mlp(self, x, a, fused, gemv):
         """o_proj + residual, RMSNorm, SwiGLU MLP + residual on [B,T,D]; the residuals are the projections' `res`."""
-        from . import model_ops
-
         B, T, D = x.shape
         proj = self.projections
         x2 = proj.o(a.reshape(-1, D), x.reshape(-1, D), gemv)
-        h = self._infer_norm(self.post_attention_layernorm, x2.view(B, T, D), fused).reshape(-1, D)
+        h = _norm(self.post_attention_layernorm, x2.view(B, T, D), fused)[1].reshape(-1, D)
         g, u = proj.gate_up(h, fused, gemv)
         fused_mlp = fused and (B * T * g.shape[1]) % 8 == 0
         y = model_ops.SwiGLUFn.apply(g, u) if fused_mlp else F.silu(g) * u
@@ -392,8 +393,6 @@ class LlamaLayer(nn.Module):
         """The layer on the whole right-padded prompt x [B,T,D]; the rotated K and V of its T positions go into cache = (kcache, vcache), each
         [B,Tmax,H,hd]. rope_tab = (cos, sin) float32 [Tmax, hd/2]. Causal attention on right-padded rows is HF's mask on the real tokens; the
         pad slots hold garbage that the decode steps overwrite before any query sees it."""
-        from . import model_ops
-
         B, T, D = x.shape
         fused = self._infer_fused(x)
         qkv = self._infer_norm_qkv(x, fused, gemv=False)  # T is a whole prompt: a 4-bit layer takes dequant + GEMM
@@ -417,8 +416,6 @@ class LlamaLayer(nn.Module):
         """The layer on one new token per row: x [B,1,D], pos int32 [B] (row b's position; its cache holds keys 0 .. pos[b]-1). RMSNorm, the
         q/k/v projection of [B,1,D] (a 4-bit layer: ONE vaa_model_q4_gemv over the row-concatenated codes while B <= quant.GEMV_MAX_ROWS),
         model_ops.attention_decode (rotation, cache append and attention in one launch), o_proj, residual, MLP."""
-        from . import model_ops
-
         B, _, D = x.shape
         fused = self._infer_fused(x)
         qkv = self._infer_norm_qkv(x, fused, gemv=True)[:, 0]  # [B,3,H,hd]
@@ -521,8 +518,6 @@ class OpenVLAShaped(nn.Module):
         tower runs on a second HIP stream next to DINOv2 — forward, and backward too (autograd replays each node on its forward
         stream). Measured on one MI355X: bs=8 78.2 -> 74.7 ms/step, bs=64 473 -> 468 (the towers' tails overlap). VAA_TOWER_STREAMS=0
         turns it off."""
-        import os
-
         f = (lambda m, x: m(None, embedded=x)) if embedded else (lambda m, x: m(x))
         mode = os.environ.get("VAA_TOWER_STREAMS", "auto")
         if mode == "auto" and os.environ.get("VAA_DIST_BACKEND") == "gloo" and int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -566,8 +561,6 @@ class OpenVLAShaped(nn.Module):
 
     def seq_bucket(self, L: int) -> int:
         """Padded prompt length of the rows-only path (cfg.seq_floor / seq_multiple; VAA_SEQ_FLOOR overrides the floor, 0 = off)."""
-        import os
-
         floor = int(os.environ.get("VAA_SEQ_FLOOR", self.cfg.seq_floor))
         if floor <= 0 or os.environ.get("VAA_SEQ_PACK"):
             return L
@@ -602,20 +595,19 @@ class OpenVLAShaped(nn.Module):
         emb = self.embed_tokens(input_ids)
         x = torch.cat([emb[:, :1], proj.to(emb.dtype), emb[:, 1:]], dim=1)
         T = x.shape[1]
-        hd = self.cfg.llm_dim // self.cfg.llm_heads
         cos, sin, rope_tab = self._rope_tables(T, x.device, x.dtype)
-        from . import model_ops
-
-        if pack is not None and model_ops.enabled(x) and model_ops.attention_enabled(x.view(x.shape[0], T, self.cfg.llm_heads, hd)) and hd in (64, 128):
+        facts = _facts(x, self.cfg.llm_heads, rope_tab)
+        if pack is not None and _route(rows=x.shape[0] * T, pack=pack, **facts).cu is not None:  # the layers' route takes a pack
             # packed token axis [1, sum T_b, D]: no padding rows through the 32 layers (rows = packed indices, see SeqPack.rows)
             x = x.reshape(-1, x.shape[-1]).index_select(0, pack.gather)[None]
             rope_tab = pack.rope_tab(*rope_tab)
             rows = pack.rows(rows) if rows is not None else None
         else:
             pack = None
+        route = _route(rows=x.shape[0] * x.shape[1], pack=pack, **facts)  # once: the layers share shape, dtype and switches
         last = len(self.layers) - 1
         for i, layer in enumerate(self.layers):
-            x = layer(x, cos, sin, rope_tab, rows if i == last else None, pack)
+            x = layer(x, cos, sin, rope_tab, rows if i == last else None, pack, route)
         return self.norm(x)
 
     @staticmethod
@@ -623,8 +615,6 @@ class OpenVLAShaped(nn.Module):
         """SeqPack of a right-padded batch when packing is asked for (VAA_SEQ_PACK=1) and there is something to drop, else None.
         OPT-IN: the packed row count (e.g. 18 688 instead of 19 200 at bs=64) falls outside the shipped hipBLASLt selections, and the
         default heuristics cost more (476 -> 511 ms/step measured) than the 2.7 % of rows saved; it pays once those shapes are tuned."""
-        import os
-
         if not os.environ.get("VAA_SEQ_PACK") or attention_mask is None or not attention_mask.is_cuda:
             return None
         p = SeqPack(attention_mask)
@@ -682,8 +672,6 @@ def enable_tuned_gemms() -> bool:
     4 (config 5) with prompts bucketed to 44 tokens (cfg.seq_floor) — (roboticattack_amd/tunableop/*.csv, one identical copy per device ordinal; made by
     tools/tune_gemms.sh). Tuning itself stays off: unknown shapes fall back to the default hipBLASLt heuristic, a validator mismatch
     (different ROCm / hipBLASLt build) ignores the file. Worth ~3 % of the step; honours a user's own PYTORCH_TUNABLEOP_* env."""
-    import os
-
     if os.environ.get("PYTORCH_TUNABLEOP_ENABLED") is not None or os.environ.get("VAA_NO_TUNED_GEMMS"):
         return False
     try:
@@ -723,7 +711,6 @@ def check_hf_config(cfg: OpenVLACfg, ckpt_dir: str) -> list:
     numerical constants differ — RMSNorm epsilon, RoPE base, vocabulary / padding, image size, a single vision tower — must not be loaded
     into a model that silently computes with other values. A checkpoint directory without config.json is refused as well."""
     import json
-    import os
 
     path = os.path.join(ckpt_dir, "config.json")
     if not os.path.exists(path):
@@ -768,7 +755,6 @@ def load_hf_openvla(model: OpenVLAShaped, ckpt_dir: str) -> OpenVLAShaped:
     disagree with the model's OpenVLACfg is refused. The name mapping is exercised on a synthetic checkpoint written with the HF module names
     (tests/test_host_logic.py); the released weights themselves are not in this image (no network), so no numerical check against them exists."""
     import glob
-    import os
 
     from safetensors.torch import load_file
 

@@ -389,6 +389,43 @@ def test_rope_packed_attention_equals_separate_operands(hd):
         assert torch.equal(qkv.grad[:, :, z], t.grad)
 
 
+_FN_CASES = ([("AttentionFn", hd, causal, False) for hd in (64, 128, 80) for causal in (True, False)]
+             + [("PackedAttentionFn", hd, causal, False) for hd in (64, 128) for causal in (True, False)]  # causal off: the ViT blocks
+             + [(fn, hd, True, varlen) for fn in ("RopeAttentionFn", "RopePackedAttentionFn") for hd in (64, 128) for varlen in (False, True)])
+
+
+@pytest.mark.parametrize("fn,hd,causal,varlen", _FN_CASES)
+def test_attention_function_equals_raw_calls(fn, hd, causal, varlen):
+    """Each of the four attention Functions against the raw attention_fwd / attention_bwd calls on the same operands (_rope_launch in front
+    where the Function rotates), bit for bit: o and every returned gradient. T = 17 crosses the 16-row tile; varlen: two sequences of 5 and
+    17 tokens packed back to back with cu_seqlens. A backward that returns the wrong number of gradients is an autograd error here."""
+    from roboticattack_amd import model_ops
+
+    H, lens = 2, (5, 17)
+    B, T = (1, sum(lens)) if varlen else (2, 17)
+    packed, roped = "Packed" in fn, "Rope" in fn
+    g = torch.Generator(device=DEV).manual_seed(hd + len(fn))
+    ops = [torch.randn(*((B, T, 3, H, hd) if packed else (B, T, H, hd)), device=DEV, generator=g).to(torch.bfloat16) for _ in range(1 if packed else 3)]
+    go = torch.randn(B, T, H, hd, device=DEV, generator=g).to(torch.bfloat16)
+    pos = torch.cat([torch.arange(n, device=DEV) for n in lens]) if varlen else torch.arange(T, device=DEV)
+    ang = torch.outer(pos.float(), 1.0 / (10000 ** (torch.arange(0, hd, 2, device=DEV, dtype=torch.float32) / hd)))
+    rope = (ang.cos().contiguous(), ang.sin().contiguous()) if roped else None
+    cu, max_len = (torch.tensor([0, 5, 22], dtype=torch.int32, device=DEV), 17) if varlen else (None, 0)
+
+    q, k, v = (ops[0][:, :, z] for z in range(3)) if packed else ops
+    if roped:
+        q, k = model_ops._rope_launch(q, *rope, 1.0), model_ops._rope_launch(k, *rope, 1.0)
+    o_raw, lse = model_ops.attention_fwd(q, k, v, causal, hd ** -0.5, cu, max_len)
+    g_raw = model_ops.attention_bwd(q, k, v, o_raw, lse, go, causal, hd ** -0.5, packed_grad=packed, rope=rope, cu_seqlens=cu, max_len=max_len)
+
+    ins = [t.clone().requires_grad_(True) for t in ops]
+    o = getattr(model_ops, fn).apply(*ins, *(rope or ()), causal, None, *((cu, max_len) if varlen else ()))
+    o.backward(go)
+    assert torch.equal(o, o_raw)
+    for got, want in zip(ins, (g_raw,) if packed else g_raw, strict=True):
+        assert got.grad.shape == want.shape and torch.equal(got.grad, want)
+
+
 @pytest.mark.gpu
 def test_model_fused_qkv_matches_separate_projections(monkeypatch):
     """q/k/v as ONE GEMM over the concatenated weights (the default below 8,192 rows) against three GEMMs: same logits rows and pixel gradient up

@@ -16,6 +16,8 @@ import torch
 from .. import _lib, ops, palette as _palette
 from ..action_tokenizer import ActionTokenizer
 from ..constants import MEAN0, MEAN1, STD0, STD1
+from ..labels import mask_labels as _mask_labels
+from ..optim import CosineWarmupSchedule, PatchOptimizer
 from ..transform import RandomPatchTransform
 
 try:  # optional, exactly like a reference run with --wandb_project false
@@ -371,11 +373,7 @@ class AttackBase:
     # ---- metrics (host, once per outer iteration) ----
     def decode_pred_gt(self, pred: torch.Tensor, labels: torch.Tensor):
         """Continuous predicted / ground-truth actions of the action rows, (b,k) order (UADA.py:165-175)."""
-        p = pred.detach().cpu().numpy()
-        gt = labels[:, 1:].detach().cpu().numpy()
-        m = gt > self.action_tokenizer.action_token_begin_idx
-        return (torch.tensor(self.action_tokenizer.decode_token_ids_to_actions(p[m])),
-                torch.tensor(self.action_tokenizer.decode_token_ids_to_actions(gt[m])))
+        return self.decode_pred_gt_np(pred.detach().cpu().numpy(), labels[:, 1:].detach().cpu().numpy())
 
     def decode_pred_gt_np(self, p: np.ndarray, gt: np.ndarray):
         """decode_pred_gt on maps that are already on the host (ValReadback.read): p [B,L-1] predictions, gt = labels[:, 1:]."""
@@ -461,9 +459,99 @@ class AttackBase:
         torch.save(self.loss_buffer, "%s/loss" % (self.save_dir))
 
     def dump_lists(self, names):
-        for n in names:
-            with open(os.path.join(self.save_dir, f"{n}.pkl"), "wb") as f:
-                pickle.dump(getattr(self, n), f)
+        """`names`: attributes pickled under their own name, or (file name, attribute) pairs where the reference names the file differently."""
+        for fname, attr in ((n, n) if isinstance(n, str) else n for n in names):
+            with open(os.path.join(self.save_dir, f"{fname}.pkl"), "wb") as f:
+                pickle.dump(getattr(self, attr), f)
+
+    # ---- the single-GPU drivers (attack/uada.py, upa.py, tma.py): what they share; DESIGN.md §1 lists the hooks and what differs ----
+    accumulates = True  # the driver's inner step takes `do_step` (UADA's runs its optimiser on every step: False there)
+
+    def mask_labels(self, labels, maskidx):
+        return _mask_labels(labels, maskidx)
+
+    def begin_run(self, patch_size, lr, l1_clip, warmup, num_iter, accumulate_steps, innerLoop, colorjitter, train_crop, train_crop_scale, scene_jitter,
+                  defocus_blur):
+        """-> (patch, optimizer, scheduler | None, scalar buffer [max(innerLoop, 1), 10]). The patch is the FIRST draw a run takes from torch's CPU
+        generator (then H2D: same values as UADA.py:104); `l1_clip` applies with AdamW only (UPA.py:157).
+        The keywords of `patchattack_unconstrained` the reference does not have are EXTENSIONS, all off by default:
+        colorjitter (True or three strengths): every training step pastes a per-image brightness / contrast / saturation variant of the patch;
+        validation evaluates the patch as it is saved (in the reference's TMA the keyword exists and is dead, Appendix A-D3).
+        train_crop / train_crop_scale, scene_jitter, defocus_blur: the frame stages K9 / K10 / K11 of every training step, as
+        RandomPatchTransform.set_frame_stages states them."""
+        self.randomPatchTransform.colorjitter = colorjitter
+        self.randomPatchTransform.set_frame_stages(train_crop, train_crop_scale, scene_jitter, defocus_blur)
+        patch = torch.rand(patch_size).to(self.device)
+        patch.requires_grad_(True)
+        self.patch = patch
+        adam = self.optimizer == "adamW"
+        optimizer = PatchOptimizer(patch, lr, "adamW" if adam else "pgd", l1_clip=l1_clip if adam else 0.0)
+        scheduler = CosineWarmupSchedule(optimizer, warmup, int(num_iter / accumulate_steps), 0.5) if adam else None
+        return patch, optimizer, scheduler, torch.zeros((max(innerLoop, 1), 10), dtype=torch.float32, device=self.device)
+
+    def fetch_batch(self, data, maskidx, filterGripTrainTo1):
+        """-> (pixel_values, labels, attention_mask, input_ids) on the device; the gripper filter only for maskidx == [6] (UADA.py:120-127)."""
+        if gripper_only(maskidx) and filterGripTrainTo1:
+            labels, attention_mask, input_ids, pixel_values = self.filter_train(data)
+            return pixel_values, labels, attention_mask, input_ids
+        return to_dev(data, self.device)
+
+    def run_outer_loop(self, run, patch, optimizer, scheduler, scal, train_dataloader, val_dataloader, num_iter):
+        """UADA.py:117-292, UPA.py:118-275, TMA.py:110-383 around the driver's hooks. Nothing waits for the device inside the inner loop: the scalars
+        of an outer iteration's steps stay in `scal` and are read back ONCE (the reference syncs 4-5 times per inner step); nothing of an
+        iteration is logged or written before assert_finite_state has seen them. A step that ended in the fused update (fused_update) leaves
+        its row in `self._stats_row`: the gradient statistics of the last such step are folded from its block sums here, once (whether steps
+        end fused follows from the run's arguments, so the steps of an iteration all do or none does).
+        A driver that does not accumulate asks for the `do_step` rule, and so for the loader's length, only where a scheduler follows it."""
+        train_iterator, val_iterator = iter(train_dataloader), iter(val_dataloader)
+        for i in range(num_iter):
+            pixel_values, labels, attention_mask, input_ids = self.fetch_batch(next(train_iterator), run.maskidx, run.filterGripTrainTo1)
+            labels = self._train_labels(run, labels)
+            do_step = (scheduler is None and not self.accumulates) or (i + 1) % run.accumulate_steps == 0 or (i + 1) == len(train_dataloader)
+            self._stats_row = None
+            preds = [self._loop_step(run, patch, optimizer, pixel_values, input_ids, attention_mask, labels, scal, k, do_step) for k in range(run.innerLoop)]
+            if scheduler is not None and do_step:
+                scheduler.step()
+            if self._stats_row is not None:
+                scal[self._stats_row, 8:10] = optimizer.last_stats
+            host = scal[: run.innerLoop].cpu().numpy()
+            self.assert_finite_state(patch, optimizer, host[:, :8], f"{self.attack_name} outer iteration {i}")
+            self.last_train_log = self._train_log(run, host, preds, labels, optimizer, self.patch_reg_log("TRAIN"))
+            if wandb_enabled(run.args):
+                wandb.log(self.last_train_log, step=i)
+            if i % 100 == 0:
+                self.plot_loss()
+                val_iterator = self.validate(i, patch, val_dataloader, val_iterator, run)
+        return patch
+
+    def val_pass(self, val_batch, patch, val_dataloader, val_iterator):
+        """The no-grad sweep every `validate` starts with: `val_batches` batches, the iterator restarted when it runs out, nothing read back
+        inside the loop (the host enqueues batch after batch), ONE read-back behind the last batch.
+        `val_batch(rb, patch, pixel_values, labels, attention_mask, input_ids)` pastes, labels, calls the model and `rb.add`s; it returns
+        (pasted frames, the labels it used — their rows are the samples counted) or None for a batch it leaves out.
+        -> (val_iterator, samples, frames of the last batch kept, *ValReadback.read())."""
+        rb = ValReadback(self.val_batches, self.device)
+        samples, frames = 0, None
+        with torch.no_grad():
+            for _ in range(self.val_batches):
+                data, val_iterator = next_or_restart(val_iterator, val_dataloader)
+                kept = val_batch(rb, patch, *to_dev(data, self.device))
+                if kept is not None:
+                    frames, samples = kept[0], samples + kept[1].shape[0]
+        return (val_iterator, samples, frames) + rb.read()
+
+    def save_best_and_last(self, patch, i, best_attr: str, value):
+        """patch.pt into `<i>/` when `value` is below the attacker's best so far (`best_attr`, then updated), and into `last/` always
+        (UADA.py:257-275) -> the directories written, `last/` last."""
+        improved = value < getattr(self, best_attr)
+        if improved:
+            setattr(self, best_attr, value)
+        return ([self.save_patch(patch, f"{str(i)}")] if improved else []) + [self.save_patch(patch, "last")]
+
+
+def gripper_only(maskidx) -> bool:
+    """The attack is on the gripper DoF alone: what turns on the train filter (UADA.py:120) and TMA's validation filter (TMA.py:222)."""
+    return len(maskidx) == 1 and maskidx[0] == 6
 
 
 def to_dev(batch, device):

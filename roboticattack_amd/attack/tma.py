@@ -2,24 +2,26 @@
 
 Loss = HF mean CE against a fixed target-token vector on the `maskidx` DoFs, divided by accumulate_steps (TMA.py:148);
 AdamW (+cosine) or PGD sign step (TMA.py:164-175); without geometry the patch is pasted by `paste_patch_fix`
-(mask rule canvas != -100, TMA.py:133-135), with geometry or colorjitter by `apply_random_patch_batch` (the `colorjitter=` kwarg is dead in
-the reference, Appendix A-D3; here the training steps jitter the patch per image and validation evaluates it as it is saved). Validation: 100 batches, ASR / L1 metrics, best patch by L1 (TMA.py:202-383).
+(mask rule canvas != -100, TMA.py:133-135), with geometry or colorjitter by `apply_random_patch_batch`.
+Validation: 100 batches, ASR / L1 metrics, best patch by L1 (TMA.py:202-383). The outer loop and the validation sweep are AttackBase's (engine.py).
 """
 from __future__ import annotations
 
 import os
+from functools import partial
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from .. import ops
 from ..labels import tma_target_labels, tma_target_tokens
-from ..optim import CosineWarmupSchedule, PatchOptimizer
-from .engine import AttackBase, ValReadback, next_or_restart, to_dev, wandb, wandb_enabled
+from .engine import AttackBase, gripper_only, wandb, wandb_enabled
 
 
 class OpenVLAAttacker(AttackBase):
     val_batches = 100  # TMA.py:211
+    attack_name = "TMA"
 
     def __init__(self, vla, processor=None, save_dir="", optimizer="pgd", resize_patch=False):
         super().__init__(vla, processor, save_dir, optimizer, resize_patch)
@@ -70,6 +72,7 @@ class OpenVLAAttacker(AttackBase):
         fused = sink is not None and "partials" in sink
         if fused:
             self.fused_update(sink, patch, optimizer, scalars)
+            self._stats_row = k
             optimizer.zero_grad()
         elif do_step:
             scalars_out[k, 8:10] = optimizer.step()
@@ -81,105 +84,72 @@ class OpenVLAAttacker(AttackBase):
                                   patch_size=[3, 50, 50], alpha=1 / 255, accumulate_steps=1, maskidx=[], warmup=20,
                                   filterGripTrainTo1=False, geometry=False, colorjitter=False, innerLoop=1, args=None, train_crop=None,
                                   train_crop_scale=0.9, scene_jitter=False, defocus_blur=False):
-        """train_crop / train_crop_scale, scene_jitter, defocus_blur (EXTENSIONS): the frame stages K9 / K10 / K11 of every training step, as
-        RandomPatchTransform.set_frame_stages states them."""
-        self.randomPatchTransform.colorjitter = colorjitter
-        self.randomPatchTransform.set_frame_stages(train_crop, train_crop_scale, scene_jitter, defocus_blur)
+        """TMA.py:82-383 (`alpha` is the step size); `colorjitter` and the keywords behind `args` are the EXTENSIONS AttackBase.begin_run states."""
         self.val_CE_loss, self.val_L1_loss, self.val_ASR, self.val_inner_relatived_distance = [], [], [], []
         self.train_CE_loss, self.train_inner_avg_loss, self.train_inner_relatived_distance = [], [], []
-        dev = self.device
-        patch = torch.rand(patch_size).to(dev)
-        patch.requires_grad_(True)
-        self.patch = patch
-        target = tma_target_tokens(target_action, maskidx, self.action_tokenizer).to(dev)  # TMA.py:93-99
+        begun = self.begin_run(patch_size, alpha, 0.0, warmup, num_iter, accumulate_steps, innerLoop, colorjitter, train_crop, train_crop_scale,
+                               scene_jitter, defocus_blur)
+        target = tma_target_tokens(target_action, maskidx, self.action_tokenizer).to(self.device)  # TMA.py:93-99, behind the patch's draw
         print(f"target_action: {target}")
-        optimizer = PatchOptimizer(patch, alpha, "adamW" if self.optimizer == "adamW" else "pgd")
-        scheduler = CosineWarmupSchedule(optimizer, warmup, int(num_iter / accumulate_steps), 0.5) if self.optimizer == "adamW" else None
-        train_iterator, val_iterator = iter(train_dataloader), iter(val_dataloader)
-        scal = torch.zeros((max(innerLoop, 1), 10), dtype=torch.float32, device=dev)
+        run = SimpleNamespace(maskidx=maskidx, geometry=geometry, args=args, accumulate_steps=accumulate_steps, innerLoop=innerLoop,
+                              filterGripTrainTo1=filterGripTrainTo1, colorjitter=colorjitter, target=target, gripper=gripper_only(maskidx))
+        return self.run_outer_loop(run, *begun, train_dataloader, val_dataloader, num_iter)
 
-        for i in range(num_iter):
-            data = next(train_iterator)
-            if len(maskidx) == 1 and maskidx[0] == 6 and filterGripTrainTo1:
-                labels, attention_mask, input_ids, pixel_values = self.filter_train(data)
-            else:
-                pixel_values, labels, attention_mask, input_ids = to_dev(data, dev)
-            newlabels = tma_target_labels(labels, target)  # TMA.py:124-129
-            do_step = (i + 1) % accumulate_steps == 0 or (i + 1) == len(train_dataloader)
-            rel = []
-            fused_row = None
-            for inner_loop in range(innerLoop):
-                pred, fused = self.inner_step(patch, optimizer, pixel_values, input_ids, attention_mask, newlabels, geometry, colorjitter, scal, inner_loop,
-                                              accumulate_steps=accumulate_steps, do_step=do_step)
-                if fused:
-                    fused_row = inner_loop
-                rel.append(pred)
-            if scheduler is not None and do_step:
-                scheduler.step()
-            if fused_row is not None:
-                scal[fused_row, 8:10] = optimizer.last_stats
-            host = scal[:innerLoop].cpu().numpy()
-            self.assert_finite_state(patch, optimizer, host[:, :8], f"TMA outer iteration {i}")
-            inner_avg_loss = float(host[:, 0].mean())
-            inner_rel = 0.0
-            for p in rel:  # TMA.py:153-162
-                cp, cg = self.decode_pred_gt(p, newlabels)
-                inner_rel += float(self.calculate_relative_distance_target(cp, cg))
-            inner_rel /= innerLoop
-            loss = float(host[-1, 0])
-            self.loss_buffer.append(loss)
-            print(f"target_loss: {loss}")
-            self.last_train_log = {"TRAIN_attack_loss(CE)": loss, "TRAIN_patch_gradient": float(host[-1, 9]),
-                                   "TRAIN_LR": optimizer.param_groups[0]["lr"], "TRAIN_inner_avg_loss": inner_avg_loss,
-                                   "TRAIN_inner_relatived_distance": inner_rel}
-            self.last_train_log.update(self.patch_reg_log("TRAIN"))
-            if wandb_enabled(args):
-                wandb.log(self.last_train_log, step=i)
-            self.train_CE_loss.append(loss)
-            self.train_inner_avg_loss.append(inner_avg_loss)
-            self.train_inner_relatived_distance.append(inner_rel)
-            if i % 100 == 0:
-                self.plot_loss()
-                val_iterator = self.validate(i, patch, target, val_dataloader, val_iterator, maskidx, geometry, colorjitter, args)
-        return patch
+    def _train_labels(self, run, labels):
+        return tma_target_labels(labels, run.target)  # TMA.py:124-129
 
-    def validate(self, i, patch, target, val_dataloader, val_iterator, maskidx, geometry, colorjitter, args):
-        avg_CE = avg_L1 = 0.0
-        val_num_sample = success = 0
-        val_rel = 0.0
-        asr6 = [0] * 6
-        cont_pred = cont_gt = modified_images = None
-        gripper = len(maskidx) == 1 and maskidx[0] == 6
-        rb = ValReadback(self.val_batches, self.device)  # scalars + prediction maps stay on the device: ONE read-back behind the last batch
+    def _loop_step(self, run, patch, optimizer, pixel_values, input_ids, attention_mask, labels, scal, k, do_step):
+        return self.inner_step(patch, optimizer, pixel_values, input_ids, attention_mask, labels, run.geometry, run.colorjitter, scal, k,
+                               accumulate_steps=run.accumulate_steps, do_step=do_step)[0]
+
+    def _train_log(self, run, host, preds, labels, optimizer, reg):
+        inner_avg_loss = float(host[:, 0].mean())
+        inner_rel = 0.0
+        for p in preds:  # the predictions of EVERY inner step (TMA.py:153-162)
+            cp, cg = self.decode_pred_gt(p, labels)
+            inner_rel += float(self.calculate_relative_distance_target(cp, cg))
+        inner_rel /= run.innerLoop
+        loss = float(host[-1, 0])
+        self.loss_buffer.append(loss)
+        print(f"target_loss: {loss}")
+        self.train_CE_loss.append(loss)
+        self.train_inner_avg_loss.append(inner_avg_loss)
+        self.train_inner_relatived_distance.append(inner_rel)
+        return {"TRAIN_attack_loss(CE)": loss, "TRAIN_patch_gradient": float(host[-1, 9]), "TRAIN_LR": optimizer.param_groups[0]["lr"],
+                "TRAIN_inner_avg_loss": inner_avg_loss, "TRAIN_inner_relatived_distance": inner_rel, **reg}
+
+    def _val_batch(self, run, orig_gt, rb, patch, pixel_values, labels, attention_mask, input_ids):
+        if run.gripper:  # keep only samples whose clean gripper prediction is right (TMA.py:222-248): the NEXT forward's batch depends
+            # on this forward's predictions — the one read-back per batch that cannot be deferred
+            clean = self.randomPatchTransform.im_process(pixel_values, mean=self.mean, std=self.std)
+            _, _, pre = self.model_loss(input_ids, attention_mask, clean, labels, ops.LOSS_CE, need_grad=False)
+            pm = pre.cpu().numpy()
+            gt = labels[:, 1:].cpu().numpy()
+            ok = [b for b in range(gt.shape[0]) if pm[b][gt[b] > 31743][-1] == gt[b][gt[b] > 31743][-1]]
+            if not ok:
+                print("No Correct in Val!")
+                return None  # no read-back row, no samples
+            labels, attention_mask, input_ids = labels[ok], attention_mask[ok], input_ids[ok]
+            pixel_values = [pixel_values[b] for b in ok]
+            orig_gt.append(gt[ok])
+        frames = self._images(pixel_values, patch.detach(), run.geometry, run.colorjitter, jitter=False)
+        newlabels = tma_target_labels(labels, run.target)
+        _, scalars, pred = self.model_loss(input_ids, attention_mask, frames, newlabels, ops.LOSS_CE, need_grad=False)
+        rb.add(scalars, pred, newlabels)
+        return frames, newlabels
+
+    def validate(self, i, patch, val_dataloader, val_iterator, run):
         orig_gt = []  # gripper mode: the unmodified labels of the kept samples (already on the host there: the filter has to look at them)
-        with torch.no_grad():
-            for _ in range(self.val_batches):
-                data, val_iterator = next_or_restart(val_iterator, val_dataloader)
-                pixel_values, labels, attention_mask, input_ids = to_dev(data, self.device)
-                if gripper:  # keep only samples whose clean gripper prediction is right (TMA.py:222-248): the NEXT forward's batch depends
-                    # on this forward's predictions — the one read-back per batch that cannot be deferred
-                    clean = self.randomPatchTransform.im_process(pixel_values, mean=self.mean, std=self.std)
-                    _, _, pre = self.model_loss(input_ids, attention_mask, clean, labels, ops.LOSS_CE, need_grad=False)
-                    pm = pre.cpu().numpy()
-                    gt = labels[:, 1:].cpu().numpy()
-                    ok = [b for b in range(gt.shape[0]) if pm[b][gt[b] > 31743][-1] == gt[b][gt[b] > 31743][-1]]
-                    if not ok:
-                        print("No Correct in Val!")
-                        continue
-                    labels, attention_mask, input_ids = labels[ok], attention_mask[ok], input_ids[ok]
-                    pixel_values = [pixel_values[b] for b in ok]
-                    orig_gt.append(gt[ok])
-                val_num_sample += labels.shape[0]
-                modified_images = self._images(pixel_values, patch.detach(), geometry, colorjitter, jitter=False)
-                newlabels = tma_target_labels(labels, target)
-                _, scalars, pred = self.model_loss(input_ids, attention_mask, modified_images, newlabels, ops.LOSS_CE, need_grad=False)
-                rb.add(scalars, pred, newlabels)
-        host, maps = rb.read()
-        n = max(len(maskidx), 1)
+        val_iterator, val_num_sample, frames, host, maps = self.val_pass(partial(self._val_batch, run, orig_gt), patch, val_dataloader, val_iterator)
+        avg_CE = avg_L1 = val_rel = 0.0
+        success = 0
+        asr6 = [0] * 6
+        cont_pred = cont_gt = None
+        n = max(len(run.maskidx), 1)
         for k, (sc, (p_np, gt_np)) in enumerate(zip(host, maps)):  # the reference's per-batch bookkeeping (TMA.py:250-290), in batch order
             cont_pred, cont_gt = self.decode_pred_gt_np(p_np, gt_np)
             val_rel += float(self.calculate_relative_distance_target(cont_pred, cont_gt))
-            if gripper:
+            if run.gripper:
                 tm = gt_np > 31743
                 r = self.calculate_01_ASR(p_np[tm], orig_gt[k][tm])
                 asr6 = [a + b for a, b in zip(asr6, r)]
@@ -195,20 +165,16 @@ class OpenVLAAttacker(AttackBase):
         val_rel /= val_num_sample
         self.last_val_log = {"VAL_avg_CE_loss": avg_CE, "VAL_avg_L1_loss": avg_L1, "VAL_ASR": ASR, "VAL_inner_relatived_distance": val_rel}
         self.last_val_log.update(self.patch_reg_log("VAL", patch))
-        if len(maskidx) == 1 and maskidx[0] == 6:
+        if run.gripper:
             s02, n0, s12, n1, so2, no = asr6
             self.last_val_log.update({"ASR_02other": s02 / n0 if n0 else 0, "ASR_12other": s12 / n1 if n1 else 0,
                                       "ASR_other20": so2 / no if no else 0, "ALL_ASR_6": (s02 + s12) / (n0 + n1) if (n0 + n1) else 0})
-        if wandb_enabled(args):
+        if wandb_enabled(run.args):
             wandb.log(self.last_val_log, step=i)
-        dirs = []
-        if avg_L1 < self.min_val_avg_L1_loss:
-            self.min_val_avg_L1_loss = avg_L1
-            dirs.append(self.save_patch(patch, f"{str(i)}"))
-        dirs.append(self.save_patch(patch, "last"))
-        for k, d in enumerate(dirs):
-            if modified_images is not None and (k == 0 and len(dirs) == 2):
-                path, _ = self.save_val_images(modified_images, d)
+        dirs = self.save_best_and_last(patch, i, "min_val_avg_L1_loss", avg_L1)
+        for k, d in enumerate(dirs):  # frames only into the best directory when there are two; the last batch's actions into every one
+            if frames is not None and (k == 0 and len(dirs) == 2):
+                path, _ = self.save_val_images(frames, d)
             else:
                 path = os.path.join(d, "val_related_data")
                 os.makedirs(path, exist_ok=True)

@@ -20,7 +20,6 @@ import torch
 from .. import _lib
 from .. import dist as vdist
 from .. import ops
-from ..labels import mask_labels as _mask_labels
 from ..labels import tma_target_labels, tma_target_tokens
 from ..optim import CosineWarmupSchedule, PatchOptimizer, SweepPatchOptimizer
 from .engine import AttackBase, ValReadback, to_dev, wandb, wandb_enabled
@@ -116,9 +115,6 @@ class OpenVLAAttacker(AttackBase):
 
         if dist.is_initialized():
             dist.destroy_process_group()
-
-    def mask_labels(self, labels, maskidx):
-        return _mask_labels(labels, maskidx)
 
     def attack(self, rank, world_size):
         self.setup(rank, world_size)

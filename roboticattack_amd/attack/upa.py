@@ -5,22 +5,24 @@ reverse_direction=True (the CLI default): labels stay unmasked and the loss is
 over the soft-argmax of the first three action tokens (x, y, z). Other modes: `guide` (+CE against flipped targets,
 UPA.py:130-131,143-144,358-364) and plain -CE (UPA.py:149-150). Every step clips the patch gradient to L1 norm 1e-3
 before AdamW (UPA.py:157) — fused into K4. Validation: 100 batches, best patch by reverse-direction loss (UPA.py:193-275).
+The outer loop and the validation sweep are AttackBase's (engine.py).
 """
 from __future__ import annotations
 
 import os
+from functools import partial
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from .. import ops
-from ..labels import mask_labels as _mask_labels
-from ..optim import CosineWarmupSchedule, PatchOptimizer
-from .engine import AttackBase, ValReadback, next_or_restart, to_dev, wandb, wandb_enabled
+from .engine import AttackBase, wandb, wandb_enabled
 
 
 class OpenVLAAttacker(AttackBase):
     val_batches = 100  # UPA.py:205
+    attack_name = "UPA"
 
     def __init__(self, vla, processor=None, save_dir="", optimizer="pgd", resize_patch=False, alpha=0.8, belta=0.2):
         super().__init__(vla, processor, save_dir, optimizer, resize_patch)
@@ -28,9 +30,6 @@ class OpenVLAAttacker(AttackBase):
         self.avg_angle_loss, self.avg_distance_loss, self.avg_reserve_loss = [], [], []
         self.reverse_direction_loss = 100000
         self.min_val_avg_L1_loss = 1000000
-
-    def mask_labels(self, labels, maskidx):
-        return _mask_labels(labels, maskidx)
 
     def change_target(self, gt):
         """UPA.py:358-364, reproduced statement by statement. The reference assigns SEQUENTIALLY on the tensor it is rewriting: ties at
@@ -77,75 +76,44 @@ class OpenVLAAttacker(AttackBase):
                                   patch_size=[3, 50, 50], lr=1 / 255, accumulate_steps=1, maskidx=[], warmup=20,
                                   filterGripTrainTo1=False, geometry=False, innerLoop=1, guide=False, reverse_direction=False, args=None, colorjitter=False,
                                   train_crop=None, train_crop_scale=0.9, scene_jitter=False, defocus_blur=False):
-        """colorjitter (an EXTENSION: True or three strengths): every training step pastes a per-image brightness / contrast / saturation variant of
-        the patch; validation evaluates the patch as it is saved.
-        train_crop / train_crop_scale, scene_jitter, defocus_blur (EXTENSIONS): the frame stages K9 / K10 / K11 of every training step, as
-        RandomPatchTransform.set_frame_stages states them."""
-        self.randomPatchTransform.colorjitter = colorjitter
-        self.randomPatchTransform.set_frame_stages(train_crop, train_crop_scale, scene_jitter, defocus_blur)
+        """UPA.py:93-275; the keywords behind `args` are the EXTENSIONS AttackBase.begin_run states."""
         self.val_CE_loss, self.val_L1_loss, self.val_ASR, self.train_CE_loss, self.val_relative_distance = [], [], [], [], []
-        dev = self.device
-        patch = torch.rand(patch_size).to(dev)
-        patch.requires_grad_(True)
-        self.patch = patch
-        adam = self.optimizer == "adamW"
-        optimizer = PatchOptimizer(patch, lr, "adamW" if adam else "pgd", l1_clip=1e-3 if adam else 0.0)
-        scheduler = CosineWarmupSchedule(optimizer, warmup, int(num_iter / accumulate_steps), 0.5) if adam else None
-        train_iterator, val_iterator = iter(train_dataloader), iter(val_dataloader)
-        scal = torch.zeros((max(innerLoop, 1), 10), dtype=torch.float32, device=dev)
         mode, scale = self._mode(guide, reverse_direction)
+        run = SimpleNamespace(maskidx=maskidx, geometry=geometry, args=args, accumulate_steps=accumulate_steps, innerLoop=innerLoop,
+                              filterGripTrainTo1=filterGripTrainTo1, guide=guide, reverse_direction=reverse_direction, mode=mode, scale=scale)
+        begun = self.begin_run(patch_size, lr, 1e-3, warmup, num_iter, accumulate_steps, innerLoop, colorjitter, train_crop, train_crop_scale,
+                               scene_jitter, defocus_blur)
+        return self.run_outer_loop(run, *begun, train_dataloader, val_dataloader, num_iter)
 
-        for i in range(num_iter):
-            data = next(train_iterator)
-            if len(maskidx) == 1 and maskidx[0] == 6 and filterGripTrainTo1:
-                labels, attention_mask, input_ids, pixel_values = self.filter_train(data)
-            else:
-                pixel_values, labels, attention_mask, input_ids = to_dev(data, dev)
-            if not reverse_direction:
-                labels = self.mask_labels(labels, maskidx)
-            if guide:
-                labels = self.change_target(labels)
-            do_step = (i + 1) % accumulate_steps == 0 or (i + 1) == len(train_dataloader)
-            every = os.environ.get("VAA_FULL_CE_EVERY_STEP", "0") == "1"  # (=1: every step folds its scalars; same patch bits)
-            for inner_loop in range(innerLoop):
-                self.inner_step(patch, optimizer, pixel_values, input_ids, attention_mask, labels, geometry, mode, scale, scal, inner_loop, do_step=do_step,
-                                read_scalars=every or inner_loop == innerLoop - 1)
-            if scheduler is not None and do_step:
-                scheduler.step()
-            host = scal[:innerLoop].cpu().numpy()
-            self.assert_finite_state(patch, optimizer, host[:, :8], f"UPA outer iteration {i}")
-            loss, angle_loss, distance_loss = float(host[-1, 0]), float(host[-1, 3]), float(host[-1, 4])
-            print(f"loss: {loss}, " if reverse_direction else f"target_loss: {loss}")
-            self.last_train_log = {"TRAIN_attack_loss(CE)": loss, "TRAIN_patch_gradient": float(host[-1, 9]),
-                                   "TRAIN_LR": optimizer.param_groups[0]["lr"], "TRAIN_ANGLE_LOSS": angle_loss,
-                                   "TRAIN_DISTANCE_LOSS": distance_loss}
-            self.last_train_log.update(self.patch_reg_log("TRAIN"))
-            if wandb_enabled(args):
-                wandb.log(self.last_train_log, step=i)
-            self.train_CE_loss.append(loss)
-            if i % 100 == 0:
-                self.plot_loss()
-                val_iterator = self.validate(i, patch, val_dataloader, val_iterator, maskidx, geometry, reverse_direction, mode, scale, args)
-        return patch
+    def _train_labels(self, run, labels):
+        if not run.reverse_direction:
+            labels = self.mask_labels(labels, run.maskidx)
+        return self.change_target(labels) if run.guide else labels
 
-    def validate(self, i, patch, val_dataloader, val_iterator, maskidx, geometry, reverse_direction, mode, scale, args):
+    def _loop_step(self, run, patch, optimizer, pixel_values, input_ids, attention_mask, labels, scal, k, do_step):
+        every = os.environ.get("VAA_FULL_CE_EVERY_STEP", "0") == "1"  # (=1: every step folds its scalars; same patch bits)
+        return self.inner_step(patch, optimizer, pixel_values, input_ids, attention_mask, labels, run.geometry, run.mode, run.scale, scal, k, do_step=do_step,
+                               read_scalars=every or k == run.innerLoop - 1)
+
+    def _train_log(self, run, host, preds, labels, optimizer, reg):
+        loss = float(host[-1, 0])
+        print(f"loss: {loss}, " if run.reverse_direction else f"target_loss: {loss}")
+        self.train_CE_loss.append(loss)
+        return {"TRAIN_attack_loss(CE)": loss, "TRAIN_patch_gradient": float(host[-1, 9]), "TRAIN_LR": optimizer.param_groups[0]["lr"],
+                "TRAIN_ANGLE_LOSS": float(host[-1, 3]), "TRAIN_DISTANCE_LOSS": float(host[-1, 4]), **reg}
+
+    def _val_batch(self, run, rb, patch, pixel_values, labels, attention_mask, input_ids):
+        frames = self.randomPatchTransform.apply_random_patch_batch(pixel_values, patch.detach(), mean=self.mean, std=self.std, geometry=run.geometry)
+        if not run.reverse_direction:
+            labels = self.mask_labels(labels, run.maskidx)
+        _, scalars, _ = self.model_loss(input_ids, attention_mask, frames, labels, run.mode, alpha=self.alpha, beta=self.belta, scale=run.scale,
+                                        need_grad=False, full_ce=False)
+        rb.add(scalars)
+        return frames, labels
+
+    def validate(self, i, patch, val_dataloader, val_iterator, run):
+        val_iterator, val_num_sample, frames, host, _ = self.val_pass(partial(self._val_batch, run), patch, val_dataloader, val_iterator)
         avg_angle = avg_dist = avg_res = 0.0
-        val_num_sample = 0
-        modified_images = None
-        rb = ValReadback(self.val_batches, self.device)  # one read-back behind the last batch instead of one per batch
-        with torch.no_grad():
-            for _ in range(self.val_batches):
-                data, val_iterator = next_or_restart(val_iterator, val_dataloader)
-                pixel_values, labels, attention_mask, input_ids = to_dev(data, self.device)
-                val_num_sample += labels.shape[0]
-                modified_images = self.randomPatchTransform.apply_random_patch_batch(pixel_values, patch.detach(), mean=self.mean,
-                                                                                      std=self.std, geometry=geometry)
-                if not reverse_direction:
-                    labels = self.mask_labels(labels, maskidx)
-                _, scalars, _ = self.model_loss(input_ids, attention_mask, modified_images, labels, mode, alpha=self.alpha,
-                                                beta=self.belta, scale=scale, need_grad=False, full_ce=False)
-                rb.add(scalars)
-        host, _ = rb.read()
         for s in host:
             avg_angle += float(np.float32(s[3]))
             avg_dist += float(np.float32(s[4]))
@@ -155,16 +123,12 @@ class OpenVLAAttacker(AttackBase):
         avg_res /= val_num_sample
         self.last_val_log = {"reverse_direction_loss": avg_res, "avg_angle_loss": avg_angle, "avg_distance_loss": avg_dist}
         self.last_val_log.update(self.patch_reg_log("VAL", patch))
-        if wandb_enabled(args):
+        if wandb_enabled(run.args):
             wandb.log(self.last_val_log, step=i)
-        if avg_res < self.reverse_direction_loss:
-            self.reverse_direction_loss = avg_res
-            d = self.save_patch(patch, f"{str(i)}")
-            self.save_val_images(modified_images, d)
-        import os
-
-        d = self.save_patch(patch, "last")
-        os.makedirs(os.path.join(d, "val_related_data"), exist_ok=True)
+        dirs = self.save_best_and_last(patch, i, "reverse_direction_loss", avg_res)
+        if len(dirs) == 2:  # frames into the best directory only; last/ gets the empty folder (UPA.py:247-265)
+            self.save_val_images(frames, dirs[0])
+        os.makedirs(os.path.join(dirs[-1], "val_related_data"), exist_ok=True)
         self.val_CE_loss.append(0)
         self.val_L1_loss.append(0)
         self.val_ASR.append(0 / val_num_sample)
@@ -175,12 +139,6 @@ class OpenVLAAttacker(AttackBase):
         return val_iterator
 
     def save_info(self, path):
-        """UPA.py:309-325 (file names differ from attribute names there)."""
-        import os
-        import pickle
-
-        for fname, attr in (("val_relative_distance", "val_relative_distance"), ("val_CE_loss", "val_CE_loss"), ("val_L1_loss", "val_L1_loss"),
-                            ("val_ASR", "val_ASR"), ("train_CE_loss", "train_CE_loss"), ("val_avg_angle_loss", "avg_angle_loss"),
-                            ("val_avg_distance_loss", "avg_distance_loss"), ("val_avg_reserve_loss", "avg_reserve_loss")):
-            with open(os.path.join(self.save_dir, f"{fname}.pkl"), "wb") as f:
-                pickle.dump(getattr(self, attr), f)
+        """UPA.py:309-325 (three file names differ from the attribute names there)."""
+        self.dump_lists(["val_relative_distance", "val_CE_loss", "val_L1_loss", "val_ASR", "train_CE_loss", ("val_avg_angle_loss", "avg_angle_loss"),
+                         ("val_avg_distance_loss", "avg_distance_loss"), ("val_avg_reserve_loss", "avg_reserve_loss")])

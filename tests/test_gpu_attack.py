@@ -1162,6 +1162,153 @@ def test_attack_loops_fail_loudly_on_non_finite_state(tmp_path, which):
     assert not os.path.exists(os.path.join(str(tmp_path), "never", "patch.pt"))
 
 
+def _tiny_openvla():
+    from roboticattack_amd.openvla_model import OpenVLACfg, VitCfg, build_openvla
+
+    cfg = OpenVLACfg(dino=VitCfg(128, 3, 2, 256, 5, False, True), siglip=VitCfg(192, 3, 2, 384, 0, False, False),
+                     llm_dim=256, llm_layers=2, llm_heads=2, llm_mlp=512)
+    return build_openvla(cfg, device=DEV, dtype=torch.bfloat16, seed=9)
+
+
+def _written(root):
+    """(relative paths of the files, relative paths of the directories) under `root`."""
+    files = sorted(os.path.relpath(os.path.join(b, f), root) for b, _, fs in os.walk(root) for f in fs)
+    dirs = sorted(os.path.relpath(os.path.join(b, d), root) for b, ds, _ in os.walk(root) for d in ds)
+    return files, dirs
+
+
+def test_tma_gripper_validation_filters_batches_and_counts_kept_samples(tmp_path, monkeypatch):
+    """TMA.py:222-290 with maskidx=[6]: a validation batch keeps the samples whose CLEAN gripper prediction is right; a batch with none is
+    skipped and counts for nothing. The clean predictions are handed in (rows 1 and 2 of the first batch right, none of the second), the
+    patched forward is the model's: one read-back row, two samples, VAL_ASR = successes / 2, the four gripper rates in the log, images only
+    in the best directory, the continuous actions of the last kept batch in both."""
+    import types
+
+    from roboticattack_amd.attack import engine
+    from roboticattack_amd.attack.tma import OpenVLAAttacker
+
+    att = OpenVLAAttacker(_tiny_openvla(), None, str(tmp_path), optimizer="adamW")
+    att.val_batches = 2
+    orig, nograd, added = att.model_loss, [], []
+
+    def model_loss(input_ids, attention_mask, pix, labels, *a, **k):
+        total, scalars, pred = orig(input_ids, attention_mask, pix, labels, *a, **k)
+        if not k.get("need_grad", True):
+            nograd.append(int(labels.shape[0]))
+            if len(nograd) in (1, 3):  # the clean forward of validation batch 1 / batch 2
+                pred = torch.zeros_like(pred)
+                if len(nograd) == 1:
+                    pred[1:] = labels[1:, 1:].to(pred.dtype)
+        return total, scalars, pred
+
+    orig_add = engine.ValReadback.add
+
+    def add(self, scalars, pred=None, labels=None):
+        added.append((pred.cpu().numpy(), labels[:, 1:].cpu().numpy()))
+        return orig_add(self, scalars, pred, labels)
+
+    att.model_loss = model_loss
+    monkeypatch.setattr(engine.ValReadback, "add", add)
+    _seed()
+    att.patchattack_unconstrained(_Fresh([31], 3), _Fresh([41, 42], 3), num_iter=1, target_action=np.ones(7), patch_size=[3, 50, 50], alpha=0.02,
+                                  accumulate_steps=1, maskidx=[6], warmup=1, geometry=True, innerLoop=2, args=types.SimpleNamespace(wandb_project="false"))
+    assert nograd == [3, 2, 3] and len(added) == 1 and added[0][0].shape[0] == 2  # clean 1, patched 1 on the two kept rows, clean 2 (skipped)
+    cp, cg = att.decode_pred_gt_np(*added[0])
+    success, n = int((cp.view(-1, 1) == cg.view(-1, 1)).all(dim=1).sum()), 2
+    assert att.val_ASR == [success / max(n, 1)] and att.last_val_log["VAL_ASR"] == success / max(n, 1)
+    assert list(att.last_val_log) == ["VAL_avg_CE_loss", "VAL_avg_L1_loss", "VAL_ASR", "VAL_inner_relatived_distance", "ASR_02other", "ASR_12other",
+                                      "ASR_other20", "ALL_ASR_6"]
+    assert att.val_L1_loss == [float(torch.nn.functional.l1_loss(cp, cg)) / n] and att.last_val_log["VAL_avg_L1_loss"] == att.val_L1_loss[0]
+    for name in ("val_CE_loss", "val_L1_loss", "val_ASR", "val_inner_relatived_distance", "train_CE_loss", "train_inner_avg_loss",
+                 "train_inner_relatived_distance", "loss_buffer"):
+        assert len(getattr(att, name)) == 1, name
+    files, dirs = _written(str(tmp_path))
+    pkl = sorted(f"{n}.pkl" for n in ("val_CE_loss", "val_L1_loss", "val_ASR", "val_inner_relatived_distance", "train_CE_loss", "train_inner_avg_loss",
+                                      "train_inner_relatived_distance"))
+    acts = ["continuous_actions_gt.pt", "continuous_actions_pred.pt"]
+    assert dirs == ["0", "0/val_related_data", "last", "last/val_related_data"]
+    assert sorted(set(files) - {"loss_curve.png"}) == sorted(["0/patch.pt", "last/patch.pt", "loss"] + pkl + [f"0/val_related_data/{f}" for f in ["0.png", "1.png"] + acts]
+                                                             + [f"last/val_related_data/{f}" for f in acts])  # (the curve is best effort)
+    assert torch.equal(torch.load(os.path.join(str(tmp_path), "last", "val_related_data", "continuous_actions_pred.pt")), cp)
+
+
+def test_upa_guide_loop_flips_the_targets_and_divides_its_lists_twice(tmp_path):
+    """UPA.py:130-131,143-144 (guide=True: masked labels, then change_target: every kept label -> 31999; loss = +CE) and UPA.py:254-275: images in
+    the best directory only, an empty last/val_related_data, val_CE_loss / val_L1_loss / val_ASR take a 0, and the three averages are divided by
+    the sample count a SECOND time before they are appended (UPA.py:269-271); the pickles' names differ from the attributes'."""
+    import types
+
+    from roboticattack_amd import ops
+    from roboticattack_amd.attack.upa import OpenVLAAttacker
+
+    att = OpenVLAAttacker(_tiny_openvla(), None, str(tmp_path), optimizer="adamW", alpha=0.8, belta=0.2)
+    att.val_batches = 2
+    orig, seen = att.model_loss, []
+
+    def model_loss(input_ids, attention_mask, pix, labels, mode, *a, **k):
+        seen.append((bool(k.get("need_grad", True)), labels.clone(), mode, k.get("scale")))
+        return orig(input_ids, attention_mask, pix, labels, mode, *a, **k)
+
+    att.model_loss = model_loss
+    _seed()
+    att.patchattack_unconstrained(_Fresh([31], 3), _Fresh([41, 42], 2), num_iter=1, patch_size=[3, 50, 50], lr=0.02, accumulate_steps=1, maskidx=[0, 1, 2],
+                                  warmup=1, geometry=True, innerLoop=2, guide=True, args=types.SimpleNamespace(wandb_project="false"))
+    assert [s[0] for s in seen] == [True, True, False, False] and all(s[2] == ops.LOSS_CE and s[3] == 1.0 for s in seen)
+    for grad, labels, _, _ in seen:  # three DoFs kept per row (the EOS is no action token and stays -> it is flipped too); validation keeps the true labels
+        kept = labels[labels != -100]
+        assert kept.numel() == 4 * labels.shape[0] and bool((kept == 31999).all()) == grad
+    n = 4  # two validation batches of two
+    assert list(att.last_val_log) == ["reverse_direction_loss", "avg_angle_loss", "avg_distance_loss"]
+    assert att.val_CE_loss == [0] and att.val_L1_loss == [0] and att.val_ASR == [0.0] and att.val_relative_distance == [] and len(att.train_CE_loss) == 1
+    assert att.avg_angle_loss == [att.last_val_log["avg_angle_loss"] / n] and att.avg_distance_loss == [att.last_val_log["avg_distance_loss"] / n]
+    assert att.avg_reserve_loss == [att.last_val_log["reverse_direction_loss"] / n] and att.reverse_direction_loss == att.last_val_log["reverse_direction_loss"]
+    files, dirs = _written(str(tmp_path))
+    pkl = [f"{n}.pkl" for n in ("val_relative_distance", "val_CE_loss", "val_L1_loss", "val_ASR", "train_CE_loss", "val_avg_angle_loss",
+                                "val_avg_distance_loss", "val_avg_reserve_loss")]
+    assert dirs == ["0", "0/val_related_data", "last", "last/val_related_data"]
+    assert sorted(set(files) - {"loss_curve.png"}) == sorted(["0/patch.pt", "last/patch.pt", "loss", "0/val_related_data/0.png", "0/val_related_data/1.png"] + pkl)
+
+
+def test_uada_gripper_filter_trains_on_the_closed_gripper_rows(tmp_path):
+    """UADA.py:308-339 with maskidx=[6], filterGripTrainTo1=True: a training batch with between two and seven rows whose gripper token is 31744
+    is cut down to those rows; validation takes its batches whole, and writes patch and frames into the best AND the last directory."""
+    import types
+
+    from roboticattack_amd.attack.uada import OpenVLAAttacker
+
+    class _Grip(_Fresh):
+        def __iter__(self):
+            for b in super().__iter__():
+                act = b["labels"] > 31743
+                last = act.int().cumsum(dim=1).eq(7) & act  # the seventh action token of every row
+                b["labels"][last] = torch.tensor([31744, 31872, 31744, 31872][: self.b])
+                yield b
+
+    att = OpenVLAAttacker(_tiny_openvla(), None, str(tmp_path), optimizer="adamW")
+    att.val_batches = 2
+    orig, steps = att.inner_step, []
+
+    def inner_step(patch, optimizer, pixel_values, input_ids, attention_mask, labels, *a, **k):
+        steps.append((len(pixel_values), tuple(input_ids.shape[:1]), tuple(attention_mask.shape[:1]), labels.clone()))
+        return orig(patch, optimizer, pixel_values, input_ids, attention_mask, labels, *a, **k)
+
+    att.inner_step = inner_step
+    _seed()
+    att.patchattack_unconstrained(_Grip([31], 4), _Fresh([41, 42], 2), num_iter=1, patch_size=[3, 50, 50], lr=0.02, accumulate_steps=1, maskidx=[6],
+                                  warmup=1, filterGripTrainTo1=True, geometry=True, innerLoop=2, args=types.SimpleNamespace(wandb_project="false"))
+    assert len(steps) == 2
+    for n_img, n_ids, n_mask, labels in steps:
+        assert n_img == 2 and n_ids == (2,) and n_mask == (2,) and labels.shape[0] == 2
+        assert labels[labels > 31743].tolist() == [31744, 31744]  # masked to the gripper DoF of the two closed-gripper rows
+    assert list(att.last_val_log) == ["VAL_MSE_Distance", "VAL_UAD", "val_rd_6"] and "train_rd_6" in att.last_train_log
+    assert [len(getattr(att, n)) for n in ("train_CE_loss", "train_MSE_distance_loss", "train_UAD", "val_CE_loss", "val_MSE_Distance", "val_UAD")] == [2, 2, 2, 1, 1, 1]
+    assert att.MSE_Distance_best == att.val_MSE_Distance[0] == att.last_val_log["VAL_MSE_Distance"]
+    files, dirs = _written(str(tmp_path))
+    pkl = [f"{n}.pkl" for n in ("train_CE_loss", "train_MSE_distance_loss", "train_UAD", "val_CE_loss", "val_MSE_Distance", "val_UAD")]
+    assert dirs == ["0", "0/val_related_data", "last", "last/val_related_data"]
+    assert sorted(set(files) - {"loss_curve.png"}) == sorted(["0/patch.pt", "last/patch.pt", "loss"] + pkl + [f"{d}/val_related_data/{o}.png" for d in ("0", "last") for o in (0, 1)])
+
+
 def test_uada_trajectory_k2e_vs_reference_loop(tmp_path, monkeypatch):
     """The PRODUCTION backward on a reference-loop trajectory: tools/gen_golden.py:gen_trajectory_k2e drove the reference's
     own `UADA.patchattack_unconstrained` over SurrogateEmbedVLA (two bf16 patch-embed towers + fp32 body) on the CPU — bf16 pixel_values, the
